@@ -8,7 +8,13 @@ this rank's batch of frames.  Frames are independent, so N GPUs = N disjoint fra
 data-path collective (weak scaling: frames per GPU fixed); torch.distributed (RCCL) is used only
 for the barrier and the max-over-ranks of the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--workload mtm|fft|fft1k|mtm16k|mtm75|hparma] [--no-secondary]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--workload mtm|fft|fft1k|mtm16k|mtm75|hparma]
+                  [--dump-outputs DIR] [--full [--no-secondary] [--no-cpu-baseline]]
+
+A plain run times the chosen workload alone and prints its line.  --full adds everything else the line can carry: the
+secondary rows (the other BASELINE.json configs, mean removal, pitch, averages, LMP, F-test), the parity object, the
+host-memory rows (end_to_end, c4_as_worded; host_side when N > 1) and the CPU baseline.  --dump-outputs DIR writes a
+fixed, seeded sample of the rows the last timed step computed (float32) to DIR/psd_rows.npy, for output comparison.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks
 itself (one child process per GPU, started before anything in this process touches the GPU) and
@@ -273,9 +279,26 @@ def pmc_summary(pmc_name):
     return None, None
 
 
-def measure(torch, G, dist, workload, frames, steps, warmup, world, rank, local, rehearse, params_kw=None, avg_depth=0, dc=0.0, avg_form="two"):
+DUMP_BYTES = 48 << 20        # --dump-outputs: all ranks' sampled rows together, inside the 64 MB a dump may take
+
+
+def dump_rows(torch, psd, bins, out_dir, rank, world):
+    """--dump-outputs: frame 0, the last frame and a fixed, seeded sample of the others from the rows the last timed step
+    wrote (float32, `bins` wide), one file per rank.  The same arguments give the same frames and the same input stream."""
+    import numpy as np
+    count = psd.shape[0]
+    k = max(1, min(count, DUMP_BYTES // (4 * bins * world)))
+    idx = np.unique(np.concatenate([[0, count - 1], np.random.default_rng(20260101).choice(count, k, replace=False)]))
+    rows = psd[torch.from_numpy(idx).to(psd.device)][:, :bins].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "psd_rows.npy" if world == 1 else "psd_rows_rank%d.npy" % rank), rows)
+
+
+def measure(torch, G, dist, workload, frames, steps, warmup, world, rank, local, rehearse, params_kw=None, avg_depth=0, dc=0.0, avg_form="two",
+            dump=None):
     """W untimed + K timed passes of one workload over this rank's frame range; the timed region is
-    bracketed by barrier + synchronize on both sides and the MAX over ranks is taken.  Returns a dict
+    bracketed by barrier + synchronize on both sides and the MAX over ranks is taken.  With `dump` (a
+    directory) the rows of the last timed pass are sampled into it (dump_rows).  Returns a dict
     (every rank; only rank 0 uses it)."""
     name, n, overlap, nw, kmax, default_frames, _ = WORKLOADS[workload]
     dev = torch.device("cuda", local)
@@ -350,6 +373,8 @@ def measure(torch, G, dist, workload, frames, steps, warmup, world, rank, local,
            "ms_per_step": dt / steps * 1e3, "b_alg": 4 * hop + 4 * bins,
            "kernel_ms_first": each[0], "kernel_ms_min": min(each), "kernel_ms_max": max(each)}
     res["achieved_gbs"] = frames * res["b_alg"] / (kernel_ms * 1e-3) / 1e9
+    if dump:
+        dump_rows(torch, psd, bins, dump, rank, world)
     del shard, psd, avg_out
     sp.close()
     torch.cuda.empty_cache()
@@ -668,7 +693,7 @@ def c4_as_worded(torch, G, local, devices=None):
             pass
 
 
-# the default run's secondary rows (BASELINE.json configs other than the headline): workload -> timed steps
+# the --full run's secondary rows (BASELINE.json configs other than the headline): workload -> timed steps
 SECONDARY = (("fft1k", 5), ("fft", 5), ("mtm75", 5), ("mtm16k", 5), ("hparma", 5))
 SECONDARY_WARMUP = 3    # untimed passes per secondary row: the first pass over a freshly allocated 8 GB of rows runs 10 % slow on a fresh box
 
@@ -680,9 +705,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=0, help="frames per GPU per step (0 = the workload's default)")
     ap.add_argument("--workload", default="mtm", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary rows, the parity object, the host-memory rows and the CPU baseline (a plain run times the workload alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed, seeded sample of the last timed step's rows to DIR/psd_rows.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary rows (C1, C2, C3 at 75 %% overlap, C4, C5) and the parity object")
+                    help="with --full: skip the secondary rows (C1, C2, C3 at 75 %% overlap, C4, C5), the parity object and the host-memory rows")
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -716,7 +745,7 @@ def main():
                                     device_id=torch.device("cuda", local))
     torch.cuda.set_device(local)
 
-    res = measure(torch, G, dist, args.workload, args.frames, args.steps, args.warmup, world, rank, local, rehearse)
+    res = measure(torch, G, dist, args.workload, args.frames, args.steps, args.warmup, world, rank, local, rehearse, dump=args.dump_outputs)
 
     if rank == 0:
         frames, n, hop, b_alg, kernel_ms = res["frames"], res["n"], res["hop"], res["b_alg"], res["kernel_ms"]
@@ -755,7 +784,7 @@ def main():
 
     # ---- the other BASELINE.json configs, each timed the same way for a few steps (N = 1 only: they are
     # single-GPU rows; every rank would have to take part in their barriers otherwise)
-    if world == 1 and not args.no_secondary and args.workload == "mtm":
+    if world == 1 and args.full and not args.no_secondary and args.workload == "mtm":
         rows = []
         for wl, k in SECONDARY:
             r = measure(torch, G, dist, wl, 0, k, SECONDARY_WARMUP, world, rank, local, rehearse)
@@ -808,7 +837,7 @@ def main():
         line["end_to_end"] = end_to_end(torch, G, local)
         line["c4_as_worded"] = c4_as_worded(torch, G, local)
     # ---- N > 1: the host-side rows (rank 0 drives every GPU of the job from one process; the other ranks wait on the CPU)
-    if world > 1 and not args.no_secondary and args.workload == "mtm":
+    if world > 1 and args.full and not args.no_secondary and args.workload == "mtm":
         try:
             cpu_group = None if rehearse else dist.new_group(backend="gloo")
         except Exception:                            # no gloo beside RCCL on this stack: the default group's barrier (the waiting ranks' GPUs spin)
@@ -822,7 +851,7 @@ def main():
                                          "multi-GPU scaling can be lost (SURVEY 8(e)); never part of `value`" % world)
     if rank == 0:
         line["per_rank_ms_per_step"] = res["per_rank_ms"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             _, n, overlap, nw, kmax, _, cpu_frames = WORKLOADS[args.workload]
             line["cpu_baseline"] = cpu_baseline(args.workload, n, overlap, nw, kmax, cpu_frames)
             line["cpu_baseline"]["cpu_model"] = cpu_model()

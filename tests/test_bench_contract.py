@@ -92,3 +92,24 @@ def test_bench_parent_gives_up_when_a_rank_dies():
     r = _run_bench("--gpus", "2", "--dry-run", env={"GLFER_BENCH_FAIL_RANK": "1"})
     assert r.returncode == 3 and time.time() - t0 < 120
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_dumps_its_rows(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` times the headline alone (the rows behind --full stay out of the line), and
+    --dump-outputs DIR writes the last timed step's rows (float32, within 64 MB): here every frame of a small launch."""
+    import numpy as np
+    r = _run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "4096", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    for key, typ in (("metric", str), ("value", float), ("unit", str), ("higher_is_better", bool), ("dtype", str), ("ms_per_step", float)):
+        assert isinstance(line[key], typ), key
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f32"
+    for key in ("secondary", "parity", "end_to_end", "c4_as_worded", "cpu_baseline"):
+        assert key not in line, key
+    assert abs(line["value"] - 4096 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    rows = np.load(tmp_path / "psd_rows.npy")
+    assert rows.dtype == np.float32 and rows.shape == (4096, 2049) and rows.nbytes <= 64 << 20
+    assert np.isfinite(rows).all() and (rows > 0).any()

@@ -8,6 +8,8 @@ import re
 import numpy as np
 import pytest
 
+import _refpins as P
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -63,53 +65,24 @@ def test_kept_objects_link_against_the_library(tmp_path):
                     "-lglfer_compat", "-Wl,-rpath," + libdir, "-Wl,-rpath-link," + libdir], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip() == "1", (r.returncode, r.stdout, r.stderr)
-    # and the list itself: where the reference tree is mounted, every non-static function or object the dropped files define
-    # that a kept file names must be in the library
-    ref = "/root/reference"
-    if os.path.isdir(ref):
-        dropped = ["fft.c", "fft_radix2.c", "mtm.c", "g-l_dpss.c", "avg.c", "hparma.c", "lmp.c", "wav_fmt.c"]
-        kept = [f for f in os.listdir(ref) if f.endswith(".c") and f not in dropped and f != "bell-p-w.c"]
-        defined = set()
-        for f in dropped:
-            for line in open(os.path.join(ref, f), errors="replace"):
-                m = re.match(r"^(?!static)[A-Za-z_][\w \*]*?\**\b(\w+)\s*(\(|\[\]\s*=|=)", line)
-                if m and not line.rstrip().endswith(";") or (m and "=" in line):
-                    defined.add(m.group(1))
-        kept_text = " ".join(open(os.path.join(ref, f), errors="replace").read() for f in kept)
-        needed = sorted(s for s in defined if re.search(r"\b" + s + r"\b", kept_text) and s not in ("main", "opt", "glfer"))
-        assert "fft_windows" in needed and "num_fft_windows" in needed and "fft_do" in needed
-        import torch  # noqa: F401
-        L = ctypes.CDLL(os.path.join(libdir, "libglfer_compat.so"))
-        missing = [s for s in needed if not hasattr(L, s)]
-        assert not missing, missing
+    # and the list itself: every non-static function or object the dropped files define that a kept file names must be in
+    # the library (the list read from the reference's sources by tests/_refpins.py)
+    needed = P.load()["kept_files_need"]
+    assert "fft_windows" in needed and "num_fft_windows" in needed and "fft_do" in needed
+    import torch  # noqa: F401
+    L = ctypes.CDLL(os.path.join(libdir, "libglfer_compat.so"))
+    missing = [s for s in needed if not hasattr(L, s)]
+    assert not missing, missing
 
 
 def test_compat_struct_fields_follow_the_reference_header():
     """opt_t / glfer_t in include/glfer_compat.h list the fields of glfer.h:62-139 in the same
-    order with the same scalar types (GTK pointers as void *).  Reads the reference header as text
-    where the reference tree is mounted (build container); skipped elsewhere."""
-    ref = "/root/reference/glfer.h"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not mounted")
-
-    def fields(text, name):
-        body = re.search(r"typedef struct\s*\{([^}]*)\}\s*" + name + r"\s*;", re.sub(r"/\*.*?\*/", "", text, flags=re.S), re.S).group(1)
-        out = []
-        for decl in body.split(";"):
-            decl = " ".join(decl.split())
-            if not decl:
-                continue
-            m = re.match(r"(.*?)(\**)\s*(\w+)$", decl)
-            typ, ptr, ident = m.group(1).strip(), m.group(2), m.group(3)
-            if ptr and typ in ("GtkWidget", "GtkTooltips", "void"):
-                typ = "void"
-            out.append((typ + ptr, ident))
-        return out
-
+    order with the same scalar types (GTK pointers as void *); the reference header's lists were
+    read by tests/_refpins.py."""
     ours = open(os.path.join(ROOT, "include", "glfer_compat.h")).read()
-    theirs = open(ref).read()
+    theirs = P.load()["glfer_h"]
     for name in ("opt_t", "glfer_t"):
-        assert fields(ours, name) == fields(theirs, name), name
+        assert P.struct_fields(ours, name) == [tuple(f) for f in theirs[name]], name
 
 
 @pytest.mark.parametrize("n", [256, 1024, 4096, 16384])

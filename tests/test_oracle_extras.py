@@ -1,72 +1,44 @@
 """CPU tests for the oracle rows added in round 2: the file source (wav_read with its trailing
 partial block), the LMP estimator and the MTM harmonic F-test.
 
-Pins: wav_read is checked BIT-EXACT against the reference's own wav_fmt.c object (oracle/_ref).
+Pins: wav_read is checked BIT-EXACT against the reference's own wav_fmt.c object (oracle/_ref), through
+what it returned on the same bytes (tests/golden/ref_pins.json, made by tests/_refpins.py).
 lmp.c and mtm.c need <gtk/gtk.h> (unbuildable here, no stand-in written), so the LMP statistic and
 the F-test are pinned by independent float64 restatements of their formulas in numpy, by their
 degenerate cases, and by the committed golden vectors (tests/golden/l_*.npz, f_*.npz)."""
 import glob
 import os
-import struct
 
 import numpy as np
 import pytest
 
+import _refpins as P
 from _signals import rel_err, synth
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 @pytest.fixture(scope="module")
-def ref(oracle):
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    r = oracle.Ref()
-    if not hasattr(r.r, "wav_read"):
-        pytest.skip("oracle/_ref predates wav_fmt.c")
-    return r
+def pins():
+    return P.load()
 
 
-def _lp64_wav(path, pcm_bytes, bits, rate):
-    """A header the reference's open_wav_file() parses correctly on THIS (LP64) host: its struct
-    uses u_long, so it is 88 bytes with format at 40, sample_fq at 48 and bit_p_spl at 66
-    (wav_fmt.h:34-52).  Only the reference reads this layout; the product and the
-    oracle honour the canonical 44-byte one."""
-    hd = bytearray(88)
-    hd[0:4] = b"RIFF"
-    struct.pack_into("<H", hd, 40, 1)          # format = PCM
-    struct.pack_into("<H", hd, 42, 1)          # modus = mono
-    struct.pack_into("<Q", hd, 48, rate)       # sample_fq
-    struct.pack_into("<H", hd, 64, bits // 8)  # byte_p_spl
-    struct.pack_into("<H", hd, 66, bits)       # bit_p_spl
-    with open(path, "wb") as f:
-        f.write(bytes(hd))
-        f.write(pcm_bytes)
-
-
-@pytest.mark.parametrize("bits,extra_bytes,hop", [(16, 2 * 300, 512), (16, 2 * 300 + 1, 512), (8, 77, 512),
-                                                  (16, 0, 256), (8, 1, 102), (16, 2 * 5, 1024)])
-def test_wav_read_bitexact_vs_reference(oracle, ref, tmp_path, bits, extra_bytes, hop):
+@pytest.mark.parametrize("bits,extra_bytes,hop", P.WAV_CASES)
+def test_wav_read_bitexact_vs_reference(oracle, pins, bits, extra_bytes, hop):
     """Whole blocks, then a short last read: the new samples land on the stale tail of the previous
     block -- as the ESTIMATOR left it (here: mean removed in place, like fft.c:93-95) -- and the block
     still counts; an odd trailing byte of a 16-bit file is dropped; a file of whole blocks ends
-    without an extra one."""
-    rng = np.random.default_rng(bits + extra_bytes)
-    nbytes = 7 * hop * (bits // 8) + extra_bytes
-    pcm = rng.integers(0, 256, nbytes, dtype=np.uint8)
-    path = tmp_path / "lp64.wav"
-    _lp64_wav(path, pcm.tobytes(), bits, 8000)
-
-    def remove_mean(blk):
-        blk -= np.float32(blk.sum(dtype=np.float32) / np.float32(blk.size))
-
-    for mutate in (None, remove_mean):
-        want, speed = ref.wav_blocks(str(path), hop, mutate)
+    without an extra one.  The reference's side: its open_wav_file() + wav_read() over the same bytes
+    behind an LP64 header, the file at 8000 Hz (tests/_refpins.py)."""
+    pcm = P.wav_pcm(bits, extra_bytes, hop)
+    case = pins["wav"][P.wav_key(bits, extra_bytes, hop)]
+    assert P.sha(pcm) == case["in"], "the seeded input is not the one the pins were made from"
+    for label, mutate in (("as_read", None), ("mean_removed", P.remove_mean)):
+        want = case[label]
         got = oracle.wav_blocks(pcm, bits, hop, mutate)
-        assert speed == 8000
-        assert len(got) == len(want) == 7 + (1 if extra_bytes else 0)
-        for a, b in zip(got, want):
-            assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+        assert want["speed"] == 8000
+        assert len(got) == len(want["blocks"]) == 7 + (1 if extra_bytes else 0)
+        assert [P.sha(blk) for blk in got] == want["blocks"]
     if extra_bytes:
         fresh = extra_bytes if bits == 8 else extra_bytes // 2
         last, prev = got[-1], got[-2]
@@ -76,7 +48,7 @@ def test_wav_read_bitexact_vs_reference(oracle, ref, tmp_path, bits, extra_bytes
         assert np.array_equal(last[:fresh], tail)
         # stale part: the previous block after the estimator's mean removal
         stale = prev.copy()
-        remove_mean(stale)
+        P.remove_mean(stale)
         assert np.array_equal(last[fresh:], stale[fresh:])
 
 

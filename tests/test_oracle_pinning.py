@@ -1,5 +1,6 @@
-"""CPU tests: the oracle is pinned (a) bit-exact against the reference's own objects where they
-build (oracle/_ref: fft_radix2.c, g-l_dpss.c, avg.c, util.c), (b) against independent known
+"""CPU tests: the oracle is pinned (a) bit-exact against the reference's own objects (oracle/_ref:
+fft_radix2.c, g-l_dpss.c, avg.c, util.c), through what they returned on the same seeded inputs
+(tests/golden/ref_pins.json, made by tests/_refpins.py), (b) against independent known
 answers (numpy rfft in float64, scipy DPSS, Parseval) for the parts restating fft.c/mtm.c, and
 (c) against the committed golden vectors."""
 import glob
@@ -8,57 +9,49 @@ import os
 import numpy as np
 import pytest
 
+import _refpins as P
 from _signals import rel_err, synth
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 @pytest.fixture(scope="module")
-def ref(oracle):
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    return oracle.Ref()
+def pins():
+    return P.load()
 
 
-@pytest.mark.parametrize("n", [2, 4, 8, 16, 64, 512, 1024, 4096, 16384])
-def test_fft_bitexact_vs_reference(oracle, ref, n):
-    rng = np.random.default_rng(n)
-    for _ in range(3):
-        x = rng.standard_normal(n).astype(np.float32)
-        a, b = oracle.rfft_halfcomplex(x), ref.rfft_halfcomplex(x)
-        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+@pytest.mark.parametrize("n", P.FFT_NS)
+def test_fft_bitexact_vs_reference(oracle, pins, n):
+    for x, want in zip(P.fft_inputs(n), pins["fft"][str(n)]):
+        assert P.sha(x) == want["in"], "the seeded input is not the one the pins were made from"
+        assert P.sha(oracle.rfft_halfcomplex(x)) == want["out"]
 
 
-@pytest.mark.parametrize("n,kmax,nw", [(256, 2, 1.5), (1024, 4, 2.5), (4096, 4, 2.5), (4096, 7, 4.0),
-                                        (16384, 8, 4.5)])
-def test_dpss_bitexact_vs_reference(oracle, ref, n, kmax, nw):
+@pytest.mark.parametrize("n,kmax,nw", P.DPSS_CASES)
+def test_dpss_bitexact_vs_reference(oracle, pins, n, kmax, nw):
     v, s = oracle.dpss(n, kmax, nw)
-    err, v2, s2 = ref.dpss(n, kmax, nw)
-    assert err == 0
-    assert np.array_equal(v, v2) and np.array_equal(s, s2)
+    want = pins["dpss"]["%d-%d-%s" % (n, kmax, nw)]
+    assert want["err"] == 0
+    assert P.sha(v) == want["v"] and P.sha(s) == want["s"]
 
 
-def test_bessel_and_svd_bitexact_vs_reference(oracle, ref):
-    for x in np.linspace(0, 12, 97):
-        assert oracle.bessel_i0(x) == ref.bessel_i0(x)
-    A = np.random.default_rng(1).standard_normal((128, 33)).astype(np.float32)
+def test_bessel_and_svd_bitexact_vs_reference(oracle, pins):
+    assert [P.num(oracle.bessel_i0(x)) for x in P.bessel_inputs()] == pins["bessel_i0"]
+    A = P.svd_input()
+    want = pins["svd"]
+    assert P.sha(A) == want["in"], "the seeded input is not the one the pins were made from"
     rc, U, S, Q = oracle.svd(A)
-    rc2, U2, S2, Q2 = ref.svd(A)
-    assert rc == rc2 == 0
-    assert np.array_equal(U, U2) and np.array_equal(S, S2) and np.array_equal(Q, Q2)
+    assert rc == want["rc"] == 0
+    assert P.sha(U) == want["u"] and P.sha(S) == want["s"] and P.sha(Q) == want["q"]
 
 
-@pytest.mark.parametrize("mode", ["plain", "sumextreme", "sumavg"])
-def test_avg_bitexact_vs_reference(oracle, ref, mode):
-    rng = np.random.default_rng(5)
-    a1, a2 = oracle.Averager(1024, 4), ref.averager(1024, 4)
-    for f in range(14):
-        psd = (rng.random(513) ** 4).astype(np.float32)
-        r1 = a1.update(mode, psd, 10, 400, max0=f % 2, n=513)
-        r2 = a2.update(mode, psd, 10, 400, max0=f % 2, n=513)
-        assert r1[0] == r2[0] and r1[2] == r2[2]
-        assert np.array_equal(r1[1], r2[1])
-        assert r1[3] == r2[3] or (np.isnan(r1[3]) and np.isnan(r2[3]))
+@pytest.mark.parametrize("mode", P.AVG_MODES)
+def test_avg_bitexact_vs_reference(oracle, pins, mode):
+    rows = P.avg_inputs()
+    assert P.sha(np.stack(rows)) == pins["avg_in"], "the seeded input is not the one the pins were made from"
+    a1 = oracle.Averager(1024, 4)
+    for f, (psd, want) in enumerate(zip(rows, pins["avg"][mode])):
+        assert P.avg_step(a1.update(mode, psd, 10, 400, max0=f % 2, n=513)) == want, f
 
 
 def test_fft_known_answer_numpy(oracle):
