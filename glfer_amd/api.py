@@ -50,6 +50,8 @@ EXPORTS = [
     # round 5
     "glfer_hip_abi_version", "glfer_hip_spectrogram_avg_device", "glfer_hip_workers_create", "glfer_hip_workers_destroy",
     "glfer_hip_workers_spectrogram_wav", "glfer_hip_workers_spectrogram_host",
+    # many streams per call
+    "glfer_hip_spectrogram_batch_device",
 ]
 
 
@@ -132,6 +134,7 @@ def lib():
     L.glfer_hip_make_window.argtypes = [C.c_int, C.c_int, vp]
     L.glfer_hip_make_dpss.argtypes = [C.c_int, C.c_int, C.c_double, vp, vp]
     L.glfer_hip_spectrogram_device.argtypes = [vp, vp, sz, sz, sz, vp, vp]
+    L.glfer_hip_spectrogram_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp]
     L.glfer_hip_spectrum_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp]
     L.glfer_hip_spectrogram_host.argtypes = [vp, vp, sz, vp, C.POINTER(sz)]
     L.glfer_hip_wav_probe.argtypes = [C.c_char_p, C.POINTER(WavInfo)]
@@ -353,6 +356,25 @@ class Spectrogram:
                                                   first_frame, nframes, out.data_ptr(), st),
                "glfer_hip_spectrogram_device")
         return out                                       # (with cfg.psd_pitch: [nframes][pitch], a row's first `bins` floats are its bins)
+
+    def run_batch(self, streams, first_frame=0, nframes=None, out=None):
+        """streams: 2-D torch tensor [B, T] on this GPU, of the plan's sample dtype, stride(1) == 1 (stride(0) is the
+        distance between streams, in samples).  Returns psd [B][nframes][pitch] -- out[b] is what run(streams[b]) gives --
+        launched on torch's current stream (glfer_hip_spectrogram_batch_device)."""
+        torch = _torch()
+        assert streams.is_cuda and streams.dim() == 2 and (streams.stride(1) == 1 or streams.size(1) <= 1)
+        assert streams.dtype == self._sample_dtype(), (streams.dtype, self._sample_dtype())
+        nb, total = streams.size(0), streams.size(1)
+        if nframes is None:
+            nframes = self.num_frames(total) - first_frame
+        if out is None:
+            out = torch.empty((nb, nframes, self.pitch), dtype=torch.float32, device=streams.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= nb * nframes * self.pitch
+        st = C.c_void_p(torch.cuda.current_stream(streams.device).cuda_stream)
+        _check(lib().glfer_hip_spectrogram_batch_device(self._h, C.c_void_p(streams.data_ptr()), nb, streams.stride(0), total,
+                                                        first_frame, nframes, C.c_void_p(out.data_ptr()), st),
+               "glfer_hip_spectrogram_batch_device")
+        return out
 
     def run_avg(self, stream, avg_mode, depth, minbin, maxbin, max0=0, n_out=None, want_psd=False, want_ret=True,
                 first_frame=0, nframes=None):

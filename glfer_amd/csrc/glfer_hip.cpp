@@ -41,6 +41,8 @@ extern "C" hipError_t glfer_launch_ftest(const float *spec, size_t nframes, int 
 extern "C" hipError_t glfer_launch_submean_tail_ex(const void *raw_last, const float *prev, float *out, int H, int fresh, int exact,
                                                    int fmt, hipStream_t st);
 extern "C" hipError_t glfer_launch_hop_means_seq(const void *in, float *means, int H, long long nhops, int fmt, hipStream_t st);
+extern "C" hipError_t glfer_launch_hop_means_seq_batch(const void *in, float *means, int H, long long nhops, int fmt, unsigned nb,
+                                                       long long in_bstride, long long means_bstride, hipStream_t st);
 extern "C" hipError_t glfer_launch_hop_means_tiled(const void *in, float *means, int H, long long nhops, int fmt, int hpw, unsigned blocks,
                                                    hipStream_t st);
 extern "C" hipError_t glfer_launch_prepare(const SpectroParams *p, int n, const float *window, float *out,
@@ -1697,6 +1699,156 @@ extern "C" {
 int glfer_hip_spectrogram_device(glfer_hip_plan *p, const void *d_stream, size_t nsamples, size_t first,
                                  size_t nframes, float *d_psd, void *hip_stream) {
   return glfer_run_device(p, d_stream, nsamples, first, nframes, d_psd, nullptr, (hipStream_t)hip_stream);
+}
+
+// Many streams of one plan in one call (glfer_hip.h).  The estimator kernels at N = 256 .. 16384, the hop-means kernel and the
+// corrected copy carry a stream dimension (blockIdx.y; SpectroParams::nbatch / batch_stride / psd_batch_stride /
+// means_batch_stride): the routing, the cuts into head / body / tail frames and the hops each piece needs are those of ONE
+// stream (launch_by_n, launch_mean_inkernel, submean_scratch), and every launch they produce covers the whole batch, so the
+// rows are those of the single-stream entry and the launch count does not grow with the batch.
+
+// submean_scratch over nb streams (sp: the raw stream 0 with its batch_stride): one corrected copy per stream, nhops hops
+// each, side by side in one scratch block; sp leaves with the copy of stream 0 (virtual base) and the copies' stride.
+static int batch_submean_scratch(const glfer_hip_plan *p, SpectroParams &sp, size_t first, size_t nframes, unsigned nb,
+                                 hipStream_t st, float **scratch_out) {
+  const size_t hops_back = sp.history_mode ? 0 : (size_t)((p->keep + p->hop - 1) / p->hop);
+  const size_t hop_lo = (first > hops_back) ? first - hops_back : 0;
+  const size_t nhops = first + nframes - hop_lo, per = nhops * (size_t)p->hop;
+  float *scratch = nullptr, *means = nullptr;
+  HIP_TRY(glfer::scratch_malloc((void **)&scratch, (size_t)nb * per * sizeof(float), st));
+  const size_t esz = sp.fmt == GLFER_FMT_F32 ? 4 : (sp.fmt == GLFER_FMT_S16 ? 2 : 1);
+  const char *src = (const char *)sp.stream + hop_lo * (size_t)p->hop * esz;
+  hipError_t e = hipSuccess;
+  if (reference_means(p)) {
+    e = glfer::scratch_malloc((void **)&means, (size_t)nb * nhops * sizeof(float), st);
+    if (e == hipSuccess)
+      e = glfer_launch_hop_means_seq_batch(src, means, p->hop, (long long)nhops, sp.fmt, nb, sp.batch_stride, (long long)nhops, st);
+  }
+  if (e == hipSuccess)
+    e = glfer_launch_submean_batch(src, scratch, p->hop, (long long)nhops, sp.fmt, st, means, nb, sp.batch_stride, (long long)per,
+                                   (long long)nhops);
+  if (means) glfer::scratch_free(means, st);
+  if (e != hipSuccess) {
+    glfer::scratch_free(scratch, st);
+    return hip_fail(e, "glfer_launch_submean_batch");
+  }
+  sp.stream = reinterpret_cast<const char *>(scratch) - hop_lo * (size_t)p->hop * sizeof(float);
+  sp.fmt = GLFER_FMT_F32;
+  sp.batch_stride = (long long)(per * sizeof(float));
+  *scratch_out = scratch;
+  return GLFER_OK;
+}
+
+// launch_mean_inkernel over nb streams: the head / tail frames through the batch's corrected copies, the body from the raw
+// streams with the hop means summed by the kernel, or (the reference's order) given -- one table per stream, nhops apart.
+static int batch_mean_inkernel(glfer_hip_plan *p, const SpectroParams &sp, size_t first, size_t nframes, unsigned nb,
+                               hipStream_t st) {
+  const size_t first_inside = (size_t)((p->keep + p->hop - 1) / p->hop);
+  const size_t lanes = (size_t)p->n / 16;
+  const size_t G = body_route(sp, p->n) == ROUTE_SHARED_ODD ? 2 * (lanes >= 256 ? 1 : 256 / lanes) : 1;
+  const size_t end = first + nframes;
+  size_t b0 = std::max(first, first_inside);
+  b0 = (b0 + G - 1) / G * G;
+  size_t b1 = end / G * G;
+  if (b0 >= b1) b0 = b1 = end;
+  int rc = GLFER_OK;
+  auto by_copy = [&](size_t from, size_t to) {
+    if (rc != GLFER_OK || from >= to) return;
+    SpectroParams hs = sp;
+    hs.frame0 = (long long)from;
+    hs.nframes = (int)(to - from);
+    hs.psd = sp.psd + (from - first) * (size_t)p->pitch;
+    float *scratch = nullptr;
+    rc = batch_submean_scratch(p, hs, from, to - from, nb, st, &scratch);
+    if (rc == GLFER_OK) {
+      hipError_t e = launch_by_n(hs, p->n, st);
+      if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch, frames through the corrected copies)");
+    }
+    if (scratch) glfer::scratch_free(scratch, st);
+  };
+  by_copy(first, std::min(b0, end));
+  if (rc == GLFER_OK && b1 > b0) {
+    SpectroParams bs = sp;
+    bs.frame0 = (long long)b0;
+    bs.nframes = (int)(b1 - b0);
+    bs.psd = sp.psd + (b0 - first) * (size_t)p->pitch;
+    bs.mean_inkernel = 1;
+    float *means = nullptr;
+    hipError_t e = hipSuccess;
+    if (reference_means(p)) {
+      const size_t hop_lo = b0 - first_inside, nhops = b1 - hop_lo;      // (b0 >= first_inside)
+      const size_t esz = sp.fmt == GLFER_FMT_F32 ? 4 : (sp.fmt == GLFER_FMT_S16 ? 2 : 1);
+      e = glfer::scratch_malloc((void **)&means, (size_t)nb * nhops * sizeof(float), st);
+      if (e == hipSuccess)
+        e = glfer_launch_hop_means_seq_batch((const char *)sp.stream + hop_lo * (size_t)p->hop * esz, means, p->hop, (long long)nhops,
+                                             sp.fmt, nb, sp.batch_stride, (long long)nhops, st);
+      bs.means = means - hop_lo;                                         // indexed by the stream's own hop (= frame) index
+      bs.means_batch_stride = (long long)nhops;
+    }
+    if (e == hipSuccess) e = launch_by_n(bs, p->n, st);
+    if (means) glfer::scratch_free(means, st);
+    if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch, mean removal in the kernel)");
+  }
+  by_copy(std::max(b1, std::min(b0, end)), end);
+  return rc;
+}
+
+int glfer_hip_spectrogram_batch_device(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch,
+                                       size_t nsamples, size_t first, size_t nframes, float *d_psd, void *hip_stream) {
+  if (!p) return GLFER_E_ARG;
+  if (nstreams == 0 || nframes == 0) return GLFER_OK;
+  if (!d_streams || !d_psd) return GLFER_E_ARG;
+  if ((first + nframes) > nsamples / (size_t)p->hop) return GLFER_E_ARG;   // frame past the stream
+  if (nframes > 0x7fffffffu) return GLFER_E_ARG;
+  const int fmt = p->cfg.sample_format;
+  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
+  // body_route (and spectro16w's launcher) read the stream's alignment for integer samples: every stream must see the
+  // same kernels, so an odd pitch -- every other stream off the pair alignment -- is refused rather than routed per stream
+  if (fmt != GLFER_FMT_F32 && (stream_pitch & 1)) return GLFER_E_ARG;
+  const size_t rows = (size_t)p->pitch;
+  if (stream_pitch > (SIZE_MAX / esz) / nstreams || nframes > (SIZE_MAX / sizeof(float) / rows) / nstreams) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  const char *base = static_cast<const char *>(d_streams);
+  const bool one_launch = (p->cfg.mode == GLFER_MODE_FFT || p->cfg.mode == GLFER_MODE_MTM) && p->n >= 256 && p->n <= 16384;
+  if (!one_launch || nstreams == 1) {
+    for (size_t b = 0; b < nstreams; b++) {
+      const int rc = glfer_run_device(p, base + b * stream_pitch * esz, nsamples, first, nframes, d_psd + b * nframes * rows, nullptr, st);
+      if (rc != GLFER_OK) return rc;
+    }
+    return GLFER_OK;
+  }
+  DeviceGuard guard(p->cfg.device);
+  HIP_TRY(guard.error());
+  int dev = 0, ymax = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  HIP_TRY(hipDeviceGetAttribute(&ymax, hipDeviceAttributeMaxGridDimY, dev));
+  ymax = std::max(1, std::min(ymax, 65535));
+  for (size_t c0 = 0; c0 < nstreams; c0 += (size_t)ymax) {      // batches above the grid's y limit: chunks of it
+    const unsigned nb = (unsigned)std::min(nstreams - c0, (size_t)ymax);
+    SpectroParams sp;
+    fill_params(p, sp);
+    sp.stream = base + c0 * stream_pitch * esz;
+    sp.frame0 = (long long)first;
+    sp.nframes = (int)nframes;
+    sp.psd = d_psd + c0 * nframes * rows;
+    sp.nbatch = (int)nb;
+    sp.batch_stride = (long long)(stream_pitch * esz);
+    sp.psd_batch_stride = (long long)(nframes * rows);
+    int rc = GLFER_OK;
+    if (p->cfg.sub_mean && mean_inkernel_ok(p, sp, nullptr, -1)) {
+      rc = batch_mean_inkernel(p, sp, first, nframes, nb, st);
+    } else {
+      float *scratch = nullptr;
+      if (p->cfg.sub_mean) rc = batch_submean_scratch(p, sp, first, nframes, nb, st, &scratch);
+      if (rc == GLFER_OK) {
+        const hipError_t e = launch_by_n(sp, p->n, st);
+        if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch)");
+      }
+      if (scratch) glfer::scratch_free(scratch, st);
+    }
+    if (rc != GLFER_OK) return rc;
+  }
+  return GLFER_OK;
 }
 
 int glfer_hip_spectrum_device(glfer_hip_plan *p, const void *d_stream, size_t nsamples, size_t first,

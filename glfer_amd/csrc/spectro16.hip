@@ -66,8 +66,11 @@ namespace glfer {
 // go through three packed transforms, two sequences each (re / im), and every pair is separated through the mirror bins in LDS:
 // with Z = FFT(a + i b), X_a[k] = (Z[k] + conj Z[N-k]) / 2 and X_b[k] = (Z[k] - conj Z[N-k]) / (2 i) (the halves ride in the tables).
 // The accumulation per taper, its order and its statement types are those of FT = 1.
-template <int LOGN, int FMT, bool GEN, int WPS = GLFER16_WAVES_PER_SIMD, int STG = GLFER16_STAGGER, int KM = 0, int FT = 0>
+template <int LOGN, int FMT, bool GEN, int WPS = GLFER16_WAVES_PER_SIMD, int STG = GLFER16_STAGGER, int KM = 0, int FT = 0, int BAT = 0>
 __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(SpectroParams p) {
+  // BAT: the instantiations a batch launches (nbatch > 1) -- blockIdx.y is the stream; the single-stream ones are the code as it was
+  static_assert(BAT == 0 || FT == 0, "the F statistic is never batched");
+  if constexpr (BAT != 0) glfer_batch_select(p);
   static_assert(KM == 0 || (!GEN && (KM == 16 || KM == 8 || KM == 4)), "in-kernel mean removal: the plain path");
   static_assert(FT == 0 || !GEN, "F statistic: the plain path");
   constexpr int NH = KM > 0 ? 16 / KM : 1;
@@ -425,7 +428,11 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(S
 // K0: per-hop mean removal (fft.c:86-96).  One block per hop; writes a float copy of the
 // stream (the reference mutates the caller's hop buffer in place).
 template <int FMT>
-__global__ __launch_bounds__(256) void submean_kernel(const void *in, float *out, int H, long long nhops, const float *means) {
+__global__ __launch_bounds__(256) void submean_kernel(const void *in, float *out, int H, long long nhops, const float *means,
+                                                      long long in_bstride, long long out_bstride, long long means_bstride) {
+  in = reinterpret_cast<const char *>(in) + (long long)blockIdx.y * in_bstride;   // the stream of a batch (blockIdx.y; 0 otherwise)
+  out += (long long)blockIdx.y * out_bstride;
+  if (means) means += (long long)blockIdx.y * means_bstride;
   __shared__ float part[256];
   const long long hop = blockIdx.x;
   if (hop >= nhops) return;
@@ -466,7 +473,11 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
 }
 
 template <int FMT, int GROUP, int EPL>
-__global__ __launch_bounds__(256) void submean_reg_kernel(const void *in, float *out, int H, long long nhops, const float *means) {
+__global__ __launch_bounds__(256) void submean_reg_kernel(const void *in, float *out, int H, long long nhops, const float *means,
+                                                          long long in_bstride, long long out_bstride, long long means_bstride) {
+  in = reinterpret_cast<const char *>(in) + (long long)blockIdx.y * in_bstride;   // the stream of a batch (blockIdx.y; 0 otherwise)
+  out += (long long)blockIdx.y * out_bstride;
+  if (means) means += (long long)blockIdx.y * means_bstride;
   constexpr unsigned esz = FMT == GLFER_FMT_F32 ? 4 : (FMT == GLFER_FMT_S16 ? 2 : 1);
   __shared__ float part[4];
   const unsigned l = GROUP == 64 ? (threadIdx.x & 63u) : threadIdx.x;
@@ -545,7 +556,7 @@ using namespace glfer;
 #define GLFER_CAT2(a, b) a##b
 #define GLFER_CAT(a, b) GLFER_CAT2(a, b)
 
-template <int FMT>
+template <int FMT, int BAT>
 static hipError_t launch16_fmt(const SpectroParams &p, hipStream_t st) {
   constexpr int L = GLFER_LOGN;
   using LC = Launch16<L>;
@@ -556,54 +567,58 @@ static hipError_t launch16_fmt(const SpectroParams &p, hipStream_t st) {
   // (N = 4096) and runs at 30-36 M frames/s against 50 (N = 512: 328 against 425) -- tools/packed_rate.py, round 4
   const int wps = (p.nonlin || p.spec) && !p.ftest && !p.mean_inkernel ? 2 : GLFER16_WAVES_PER_SIMD;
   const long long resident = 256LL * ((wps * 256) / LC::BLOCK > 0 ? (wps * 256) / LC::BLOCK : 1);
-  unsigned grid = (unsigned)(work < 4 * resident ? work : 4 * resident);
+  const long long cap = glfer_batch_cap(4 * resident, p.nbatch);   // (a batch shares it among its streams)
+  unsigned grid = (unsigned)(work < cap ? work : cap);
   if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
   if (p.ftest) {
+    if (BAT) return hipErrorInvalidValue;           // (never batched)
     // the F statistic: one taper per round (two spill-free wavefronts per SIMD: mu and the sums are 48 more registers)
     if (p.nonlin || p.spec || p.mean_inkernel || !p.ft_U0) return hipErrorInvalidValue;
     // (the paired form keeps mu and the sums for the bins k <= N/2 only -- 27 registers, not 48: three wavefronts per SIMD)
-    if (p.ft_nseq > 0) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 3, GLFER16_STAGGER, 0, 2>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+    if (p.ft_nseq > 0) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 3, GLFER16_STAGGER, 0, 2, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     return hipGetLastError();
   }
   if (p.mean_inkernel) {
     // frames inside the stream only, history from the stream, a hop of 4, 8 or 16 sixteenths of the block
     if (p.nonlin || p.spec || p.history_mode || p.frame0 * (long long)p.H < (long long)p.R) return hipErrorInvalidValue;
     const int km = (16 * p.H) % (1 << L) == 0 ? (16 * p.H) >> L : 0;
-    if (km == 16) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 16>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-    else if (km == 8) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 8>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-    else if (km == 4) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 4>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+    if (km == 16) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 16, 0, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else if (km == 8) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 8, 0, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else if (km == 4) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 4, 0, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     else return hipErrorInvalidValue;
     return hipGetLastError();
   }
   if (p.nonlin || p.spec)
-    hipLaunchKernelGGL((spectro16_kernel<L, FMT, true, 2>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+    hipLaunchKernelGGL((spectro16_kernel<L, FMT, true, 2, GLFER16_STAGGER, 0, 0, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
   else
-    hipLaunchKernelGGL((spectro16_kernel<L, FMT, false>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+    hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 0, 0, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
   return hipGetLastError();
 }
 
 extern "C" hipError_t GLFER_CAT(glfer_launch_spectro16_n, GLFER_LOGN)(const SpectroParams *p, hipStream_t st) {
   switch (p->fmt) {
-    case GLFER_FMT_F32: return launch16_fmt<GLFER_FMT_F32>(*p, st);
-    case GLFER_FMT_S16: return launch16_fmt<GLFER_FMT_S16>(*p, st);
-    case GLFER_FMT_U8: return launch16_fmt<GLFER_FMT_U8>(*p, st);
+    case GLFER_FMT_F32: return p->nbatch > 1 ? launch16_fmt<GLFER_FMT_F32, 1>(*p, st) : launch16_fmt<GLFER_FMT_F32, 0>(*p, st);
+    case GLFER_FMT_S16: return p->nbatch > 1 ? launch16_fmt<GLFER_FMT_S16, 1>(*p, st) : launch16_fmt<GLFER_FMT_S16, 0>(*p, st);
+    case GLFER_FMT_U8: return p->nbatch > 1 ? launch16_fmt<GLFER_FMT_U8, 1>(*p, st) : launch16_fmt<GLFER_FMT_U8, 0>(*p, st);
   }
   return hipErrorInvalidValue;
 }
 
 #if GLFER_LOGN == 12
-extern "C" hipError_t glfer_launch_submean(const void *in, float *out, int H, long long nhops, int fmt,
-                                           hipStream_t st, const float *means) {
-  if (nhops <= 0) return hipSuccess;
+extern "C" hipError_t glfer_launch_submean_batch(const void *in, float *out, int H, long long nhops, int fmt, hipStream_t st,
+                                                 const float *means, unsigned nb, long long in_bstride, long long out_bstride,
+                                                 long long means_bstride) {
+  if (nhops <= 0 || nb == 0) return hipSuccess;
+  if (nb > 65535) return hipErrorInvalidValue;
   if (fmt != GLFER_FMT_F32 && fmt != GLFER_FMT_S16 && fmt != GLFER_FMT_U8) return hipErrorInvalidValue;
   // hops up to 16384 samples: held in registers (a wavefront per hop up to 1024 samples, a workgroup above)
 #define GLFER_SUBMEAN_REG(G, E)                                                                                     \
   do {                                                                                                              \
     const unsigned grid = G == 64 ? (unsigned)((nhops + 3) / 4) : (unsigned)nhops;                                  \
-    if (fmt == GLFER_FMT_F32) hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_F32, G, E>), dim3(grid), dim3(256), 0, st, in, out, H, nhops, means); \
-    else if (fmt == GLFER_FMT_S16) hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_S16, G, E>), dim3(grid), dim3(256), 0, st, in, out, H, nhops, means); \
-    else hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_U8, G, E>), dim3(grid), dim3(256), 0, st, in, out, H, nhops, means); \
+    if (fmt == GLFER_FMT_F32) hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_F32, G, E>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); \
+    else if (fmt == GLFER_FMT_S16) hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_S16, G, E>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); \
+    else hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_U8, G, E>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); \
     return hipGetLastError();                                                                                       \
   } while (0)
   if (H <= 64 * 2) GLFER_SUBMEAN_REG(64, 2);
@@ -616,12 +631,17 @@ extern "C" hipError_t glfer_launch_submean(const void *in, float *out, int H, lo
   if (H <= 256 * 64) GLFER_SUBMEAN_REG(256, 64);
 #undef GLFER_SUBMEAN_REG
   switch (fmt) {
-    case GLFER_FMT_F32: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_F32>), dim3((unsigned)nhops), dim3(256), 0, st, in, out, H, nhops, means); break;
-    case GLFER_FMT_S16: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_S16>), dim3((unsigned)nhops), dim3(256), 0, st, in, out, H, nhops, means); break;
-    case GLFER_FMT_U8: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_U8>), dim3((unsigned)nhops), dim3(256), 0, st, in, out, H, nhops, means); break;
+    case GLFER_FMT_F32: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_F32>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); break;
+    case GLFER_FMT_S16: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_S16>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); break;
+    case GLFER_FMT_U8: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_U8>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
+}
+
+extern "C" hipError_t glfer_launch_submean(const void *in, float *out, int H, long long nhops, int fmt,
+                                           hipStream_t st, const float *means) {
+  return glfer_launch_submean_batch(in, out, H, nhops, fmt, st, means, 1, 0, 0, 0);
 }
 
 extern "C" hipError_t glfer_launch_submean_tail_ex(const void *raw_last, const float *prev, float *out, int H, int fresh, int exact,

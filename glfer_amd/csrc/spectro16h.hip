@@ -237,6 +237,7 @@ __device__ __forceinline__ void produce_hop_means(const SpectroParams &p, float 
 // themselves are stored only if p.psd is given.  Two wavefronts per SIMD (the rings and the double sums do not fit 168 VGPRs).
 template <int LOGN, int FMT, int WPS = GLFER16H_WAVES_PER_SIMD, int VAR = GLFER16H_VAR, int MT = 0, int HIST = 0, int SHIFT = 0, int MEAN = 0, int MTAB = 0, int AVG = 0>
 __global__ __launch_bounds__(LaunchH<LOGN>::BLOCK, WPS) void spectro16h_kernel(SpectroParams p) {
+  if constexpr (AVG == 0) glfer_batch_select(p);  // the stream of the batch (blockIdx.y; 0 outside a batch); the average forms are never batched
   static_assert(AVG == 0 || (MT == 0 && HIST == 0 && ((MEAN == 0 && MTAB == 0) || (MEAN == 1 && MTAB == 1))),
                 "the average inside the kernel: the periodogram, plain or with GIVEN hop means (the reference's default, sub_mean = opt.autoscale), history from the stream");
   constexpr bool CONSEC = SHIFT > 0 || AVG != 0;         // every frame slot walks consecutive frames
@@ -1018,9 +1019,11 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
   using LC = LaunchH<L>;
   const long long work = ((long long)p.nframes + LC::FPB - 1) / LC::FPB;
   if (work == 0) return hipSuccess;
+  if (p.nbatch > 1 && (p.avg || p.nprod)) return hipErrorInvalidValue;   // the average and the in-launch producers: one stream only
   const long long per_cu = (GLFER16H_WAVES_PER_SIMD * 256) / LC::BLOCK > 0 ? (GLFER16H_WAVES_PER_SIMD * 256) / LC::BLOCK : 1;
   const long long resident = 256LL * per_cu;
-  unsigned grid = (unsigned)(work < 8 * resident ? work : 8 * resident);   // tools/hbench: 8x beats 4x by ~2 % with contiguous ranges
+  const long long cap = glfer_batch_cap(8 * resident, p.nbatch);   // (a batch shares it among its streams)
+  unsigned grid = (unsigned)(work < cap ? work : cap);   // tools/hbench: 8x beats 4x by ~2 % with contiguous ranges
   if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
 #if GLFER_LOGN >= 13
   if (p.htapers > 1) {
@@ -1029,14 +1032,14 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
       if (p.history_mode) return hipErrorInvalidValue;
       // (two wavefronts per SIMD: at three the hop means push the multitaper loop into spills, 152 B of scratch per lane)
       constexpr int W2 = GLFER16H_WAVES_PER_SIMD > 2 ? 2 : GLFER16H_WAVES_PER_SIMD;
-      if (km == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W2, 1, 1, 0, 0, 1>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W2, 1, 1, 0, 0, 8>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W2, 1, 1, 0, 0, 4>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+      if (km == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W2, 1, 1, 0, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (km == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W2, 1, 1, 0, 0, 8>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (km == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W2, 1, 1, 0, 0, 4>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
       else return hipErrorInvalidValue;
       return hipGetLastError();
     }
-    if (p.history_mode) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, 1, 1, 1>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, 1, 1, 0>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+    if (p.history_mode) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, 1, 1, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, 1, 1, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     return hipGetLastError();
   }
 #endif
@@ -1055,17 +1058,17 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
     if (p.mean_inkernel) {
       // the reference's default (sub_mean = opt.autoscale) with the means GIVEN (taken in its own order by hop_means_seq_kernel): the
       // table form's in-place correction in front of the same averaging block
-      if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 2, 1, 1, 1>), dim3(ga), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 4, 1, 1, 1>), dim3(ga), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 8, 1, 1, 1>), dim3(ga), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 0, 1, 1, 1>), dim3(ga), dim3(LC::BLOCK), 0, st, p);
+      if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 2, 1, 1, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 4, 1, 1, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 8, 1, 1, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 0, 1, 1, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
       else return hipErrorInvalidValue;
       return hipGetLastError();
     }
-    if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 2, 0, 0, 1>), dim3(ga), dim3(LC::BLOCK), 0, st, p);
-    else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 4, 0, 0, 1>), dim3(ga), dim3(LC::BLOCK), 0, st, p);
-    else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 8, 0, 0, 1>), dim3(ga), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 0, 0, 0, 1>), dim3(ga), dim3(LC::BLOCK), 0, st, p);   // any other hop: every frame loaded whole
+    if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 2, 0, 0, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 4, 0, 0, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 8, 0, 0, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 0, 0, 0, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);   // any other hop: every frame loaded whole
     return hipGetLastError();
 #else
     return hipErrorInvalidValue;
@@ -1076,7 +1079,7 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
 #else
   if (p.history_mode) {
     if (p.mean_inkernel) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 1>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+    hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     return hipGetLastError();
   }
 #if GLFER16H_SHIFT_BUILDS
@@ -1104,10 +1107,10 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
         q.prod_look = 96 * q.prod_block_frames + p.prod_look;       // what a front's resident consumers span (3 workgroups x 32 CUs an XCD) + the margin asked for
         const unsigned gl = (unsigned)(gc + p.nprod);
         constexpr int WL = GLFER16H_WAVES_PER_SIMD;
-        if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 0, 1, 1>), dim3(gl), dim3(LC::BLOCK), 0, st, q);
-        else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 2, 1, 1>), dim3(gl), dim3(LC::BLOCK), 0, st, q);
-        else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 4, 1, 1>), dim3(gl), dim3(LC::BLOCK), 0, st, q);
-        else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 8, 1, 1>), dim3(gl), dim3(LC::BLOCK), 0, st, q);
+        if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 0, 1, 1>), dim3(gl, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, q);
+        else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 2, 1, 1>), dim3(gl, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, q);
+        else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 4, 1, 1>), dim3(gl, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, q);
+        else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 8, 1, 1>), dim3(gl, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, q);
         else return hipErrorInvalidValue;
         return hipGetLastError();
       }
@@ -1120,24 +1123,24 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
       // NEXT piece (side stream) finds registers and LDS beside this one
       static const bool two = [] { const char *e = getenv("GLFER_MTAB_WPS"); return e && *e == '2'; }();
       if (two && W > 2) {
-        if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 0, 1, 1>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-        else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 2, 1, 1>), dim3(g), dim3(LC::BLOCK), 0, st, p);
-        else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 4, 1, 1>), dim3(g), dim3(LC::BLOCK), 0, st, p);
-        else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 8, 1, 1>), dim3(g), dim3(LC::BLOCK), 0, st, p);
+        if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 0, 1, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+        else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 2, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+        else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 4, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+        else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 8, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
         else return hipErrorInvalidValue;
         return hipGetLastError();
       }
-      if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 0, 1, 1>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 2, 1, 1>), dim3(g), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 4, 1, 1>), dim3(g), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 8, 1, 1>), dim3(g), dim3(LC::BLOCK), 0, st, p);
+      if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 0, 1, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 2, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 4, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 8, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
       else return hipErrorInvalidValue;
       return hipGetLastError();
     }
-    if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 0, 1>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-    else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 2, 1>), dim3(g), dim3(LC::BLOCK), 0, st, p);
-    else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 4, 1>), dim3(g), dim3(LC::BLOCK), 0, st, p);
-    else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 8, 1>), dim3(g), dim3(LC::BLOCK), 0, st, p);
+    if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 2, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 4, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 8, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     else return hipErrorInvalidValue;
     return hipGetLastError();
   }
@@ -1150,14 +1153,15 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
   // launch still fills the chip.
   const int shift = (16 * p.H) % (1 << L) == 0 ? (16 * p.H) >> L : 0;
   if ((shift == 2 || shift == 4 || shift == 8) && work >= 4 * resident) {
-    unsigned g = (unsigned)(work / 4 < 8 * resident ? work / 4 : 8 * resident) & ~7u;
-    if (shift == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0, 2>), dim3(g), dim3(LC::BLOCK), 0, st, p);
-    else if (shift == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0, 4>), dim3(g), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0, 8>), dim3(g), dim3(LC::BLOCK), 0, st, p);
+    unsigned g = (unsigned)(work / 4 < cap ? work / 4 : cap);
+    if (g >= 64) g &= ~7u;
+    if (shift == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0, 2>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else if (shift == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0, 4>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0, 8>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     return hipGetLastError();
   }
 #endif
-  hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+  hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
   return hipGetLastError();
 #endif
 }

@@ -98,6 +98,7 @@ struct LaunchW {
 // (a power of two) sits in the taper tables as before.
 template <int LOGN, int FMT, int MT, int VAR, int SETS, int WPS, int GEN = 0, int HIST = 0, int KM = 0>
 __global__ __launch_bounds__(LaunchW<LOGN>::BLOCK, WPS) void spectro16w_kernel(SpectroParams p) {
+  if constexpr (LOGN <= 14) glfer_batch_select(p);   // the stream of the batch (blockIdx.y; 0 outside a batch); N = 32768 is never batched
   static_assert(KM == 0 || ((KM == 16 || KM == 8 || KM == 4) && MT != 0 && GEN == 0 && HIST == 0),
                 "in-kernel mean removal: the multitaper form, hop = 16, 8 or 4 of a lane's 16 sample registers");
   constexpr int NH = KM ? 16 / KM : 1;                     // hops per frame
@@ -653,11 +654,15 @@ static hipError_t launch16w_fmt(const SpectroParams &p, hipStream_t st) {
   constexpr int L = GLFER_LOGN;
   using LC = LaunchW<L>;
   const long long work = ((long long)p.nframes + LC::FPB - 1) / LC::FPB;
+#if GLFER_LOGN >= 15
+  if (p.nbatch > 1) return hipErrorInvalidValue;     // N = 32768 is never batched (glfer_hip_spectrogram_batch_device goes stream by stream)
+#endif
   if (work == 0) return hipSuccess;
   constexpr int WPS = GLFER16W_WAVES_PER_SIMD;
   const long long per_cu = (WPS * 256) / LC::BLOCK > 0 ? (WPS * 256) / LC::BLOCK : 1;
   const long long resident = 256LL * per_cu;
-  unsigned grid = (unsigned)(work < 8 * resident ? work : 8 * resident);
+  const long long cap = glfer_batch_cap(8 * resident, p.nbatch);   // (a batch shares it among its streams)
+  unsigned grid = (unsigned)(work < cap ? work : cap);
   if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
 #if GLFER_LOGN >= 15
   // N = 32768: the only kernel for this size, so also its general form (zero history, unaligned
@@ -665,8 +670,8 @@ static hipError_t launch16w_fmt(const SpectroParams &p, hipStream_t st) {
   const bool general = p.nonlin || p.spec || p.frame0 * (long long)p.H < (long long)p.R ||
                        (p.fmt != GLFER_FMT_F32 && ((p.H & 1) || (reinterpret_cast<uintptr_t>(p.stream) & (p.fmt == GLFER_FMT_S16 ? 3u : 1u))));
   if (general) {
-    if (p.wtapers > 1) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS, 1>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 0, 1, GLFER16W_SETS, WPS, 1>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+    if (p.wtapers > 1) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 0, 1, GLFER16W_SETS, WPS, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     return hipGetLastError();
   }
 #endif
@@ -675,17 +680,17 @@ static hipError_t launch16w_fmt(const SpectroParams &p, hipStream_t st) {
     if (p.mean_inkernel) {
       const int km = (16 * p.H) % (1 << L) == 0 ? 16 * p.H / (1 << L) : 0;
       if (p.history_mode) return hipErrorInvalidValue;
-      if (km == 16) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0, 16>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 8) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0, 8>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 4) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0, 4>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+      if (km == 16) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0, 16>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (km == 8) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0, 8>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (km == 4) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0, 4>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
       else return hipErrorInvalidValue;
-    } else if (p.history_mode) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 1>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+    } else if (p.history_mode) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
   } else {
     if (p.mean_inkernel) return hipErrorInvalidValue;
     constexpr int VAR = (L <= 12) ? 2 : 1;         // the window in LDS where it costs no resident workgroup
-    if (p.history_mode) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 0, VAR, GLFER16W_SETS, WPS, 0, 1>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 0, VAR, GLFER16W_SETS, WPS, 0, 0>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+    if (p.history_mode) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 0, VAR, GLFER16W_SETS, WPS, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 0, VAR, GLFER16W_SETS, WPS, 0, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
   }
   return hipGetLastError();
 }

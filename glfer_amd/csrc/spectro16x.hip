@@ -47,6 +47,7 @@ struct LaunchX {
 // KM > 0: per-hop mean removal inside the kernel (load_frame16_mean, odd_taper.hpp)
 template <int LOGN, int FMT, int WPS = GLFER16X_WAVES_PER_SIMD, int KM = 0>
 __global__ __launch_bounds__(LaunchX<LOGN>::BLOCK, WPS) void spectro16x_kernel(SpectroParams p) {
+  glfer_batch_select(p);                          // the stream of the batch (blockIdx.y; 0 outside a batch)
   using C = Plan16<LOGN>;
   using L = LaunchX<LOGN>;
   constexpr int N = C::N, T = C::T, NPASS = C::NPASS, FPB = L::FPB, PADN = L::PADN, WPF = L::WPF;
@@ -254,22 +255,23 @@ static hipError_t launch16x_fmt(const SpectroParams &p, hipStream_t st) {
   if (work == 0) return hipSuccess;
   const long long per_cu = (GLFER16X_WAVES_PER_SIMD * 256) / LC::BLOCK > 0 ? (GLFER16X_WAVES_PER_SIMD * 256) / LC::BLOCK : 1;
   const long long resident = 256LL * per_cu;
-  unsigned grid = (unsigned)(work < 4 * resident ? work : 4 * resident);
+  const long long cap = glfer_batch_cap(4 * resident, p.nbatch);   // (a batch shares it among its streams)
+  unsigned grid = (unsigned)(work < cap ? work : cap);
   if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
   if (p.mean_inkernel) {
     if constexpr (Plan16<L>::T <= 64) {
       if (p.history_mode) return hipErrorInvalidValue;
       const int km = (16 * p.H) % (1 << L) == 0 ? (16 * p.H) >> L : 0;
-      if (km == 16) hipLaunchKernelGGL((spectro16x_kernel<L, FMT, GLFER16X_WAVES_PER_SIMD, 16>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 8) hipLaunchKernelGGL((spectro16x_kernel<L, FMT, GLFER16X_WAVES_PER_SIMD, 8>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 4) hipLaunchKernelGGL((spectro16x_kernel<L, FMT, GLFER16X_WAVES_PER_SIMD, 4>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+      if (km == 16) hipLaunchKernelGGL((spectro16x_kernel<L, FMT, GLFER16X_WAVES_PER_SIMD, 16>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (km == 8) hipLaunchKernelGGL((spectro16x_kernel<L, FMT, GLFER16X_WAVES_PER_SIMD, 8>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else if (km == 4) hipLaunchKernelGGL((spectro16x_kernel<L, FMT, GLFER16X_WAVES_PER_SIMD, 4>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
       else return hipErrorInvalidValue;
       return hipGetLastError();
     } else {
       return hipErrorInvalidValue;
     }
   }
-  hipLaunchKernelGGL((spectro16x_kernel<L, FMT>), dim3(grid), dim3(LC::BLOCK), 0, st, p);
+  hipLaunchKernelGGL((spectro16x_kernel<L, FMT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
   return hipGetLastError();
 }
 

@@ -45,6 +45,7 @@ struct LaunchXL {
 // KM > 0: per-hop mean removal inside the kernel (load_frame16_mean, odd_taper.hpp)
 template <int LOGN, int FMT, int KM = 0>
 __global__ __launch_bounds__(256, 2) void spectro16xl_kernel(SpectroParams p) {
+  glfer_batch_select(p);                          // the stream of the batch (blockIdx.y; 0 outside a batch)
   using C = Plan16<LOGN>;
   using L = LaunchXL<LOGN>;
   constexpr int N = C::N, T = C::T, NPASS = C::NPASS, FPB = L::FPB, PADN = L::PADN, WPF = L::WPF;
@@ -255,7 +256,8 @@ static hipError_t launch16xl_fmt(const SpectroParams &p, hipStream_t st) {
   const long long work = ((long long)p.nframes + 2 * LC::FPB - 1) / (2 * LC::FPB);
   if (work == 0) return hipSuccess;
   const long long resident = 256LL * 2;
-  unsigned grid = (unsigned)(work < 4 * resident ? work : 4 * resident);
+  const long long cap = glfer_batch_cap(4 * resident, p.nbatch);   // (a batch shares it among its streams)
+  unsigned grid = (unsigned)(work < cap ? work : cap);
   if (grid >= 64) grid &= ~7u;                       // whole XCD slices: see xcd_block_index()
   auto kern = spectro16xl_kernel<L, FMT>;
   if (p.mean_inkernel) {
@@ -272,7 +274,7 @@ static hipError_t launch16xl_fmt(const SpectroParams &p, hipStream_t st) {
   }
   hipError_t e = glfer::allow_dynamic_lds(reinterpret_cast<const void *>(kern), shmem);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, st, p);
+  hipLaunchKernelGGL(kern, dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p);
   return hipGetLastError();
 }
 

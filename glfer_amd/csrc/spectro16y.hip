@@ -46,8 +46,11 @@ struct LaunchY {
 // butterfly over the wavefront, the four wavefronts through LDS across the barriers that end the
 // shared round), and x - mu is formed once, before the frames' first round.  A hop's mean comes from
 // the same lanes' same registers in the same order whichever frame it is seen in.
-template <int FMT, int ABL = 0, int HIST = 0, int KM = 0>
+template <int FMT, int ABL = 0, int HIST = 0, int KM = 0, int BAT = 0>
 __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
+  // the stream of the batch (blockIdx.y; 0 outside a batch); the mean forms only in their batch instantiations (BAT), so that the
+  // single-stream ones keep their registers
+  if constexpr (KM == 0 || BAT != 0) glfer_batch_select(p);
   static_assert(KM == 0 || (HIST == 0 && (KM == 16 || KM == 8 || KM == 4)), "in-kernel mean removal: history from the stream");
   constexpr int NH = KM > 0 ? 16 / KM : 1;
   __shared__ float mred[KM > 0 ? 4 * (NH + 1) : 1];
@@ -355,7 +358,8 @@ static hipError_t launch16y_fmt(const SpectroParams &p, hipStream_t st) {
   const long long work = ((long long)p.nframes + 1) / 2;
   if (work == 0) return hipSuccess;
   const long long resident = 256LL * 2;
-  unsigned grid = (unsigned)(work < 16 * resident ? work : 16 * resident);   // tools/xbench: 16x beats 4x by ~2 %
+  const long long cap = glfer_batch_cap(16 * resident, p.nbatch);   // (a batch shares it among its streams)
+  unsigned grid = (unsigned)(work < cap ? work : cap);   // tools/xbench: 16x beats 4x by ~2 %
   if (grid >= 64) grid &= ~7u;                       // whole XCD slices: see xcd_block_index()
   constexpr size_t shmem = (size_t)LaunchY::LDS_WORDS * 8;
   {
@@ -367,9 +371,12 @@ static hipError_t launch16y_fmt(const SpectroParams &p, hipStream_t st) {
     const int km = p.H % 256 == 0 ? p.H / 256 : 0;
 #define GLFER_Y_MEAN(K)                                                                                              \
   do {                                                                                                               \
-    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, 0, K>), shmem);       \
+    const void *k_ = p.nbatch > 1 ? reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, 0, K, 1>)                 \
+                                  : reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, 0, K, 0>);                \
+    hipError_t e = allow_dynamic_lds(k_, shmem);                                                                     \
     if (e != hipSuccess) return e;                                                                                   \
-    hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0, K>), dim3(grid), dim3(256), shmem, st, p);                     \
+    if (p.nbatch > 1) hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0, K, 1>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p); \
+    else hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0, K, 0>), dim3(grid, 1), dim3(256), shmem, st, p);          \
     return hipGetLastError();                                                                                        \
   } while (0)
     if (km == 16) GLFER_Y_MEAN(16);
@@ -378,8 +385,8 @@ static hipError_t launch16y_fmt(const SpectroParams &p, hipStream_t st) {
 #undef GLFER_Y_MEAN
     return hipErrorInvalidValue;
   }
-  if (p.history_mode) hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 1>), dim3(grid), dim3(256), shmem, st, p);
-  else hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0>), dim3(grid), dim3(256), shmem, st, p);
+  if (p.history_mode) hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p);
+  else hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p);
   return hipGetLastError();
 }
 

@@ -82,7 +82,32 @@ struct SpectroParams {
   double *avg_ret;         /* device, optional: [nframes][4] = {band mean (avg.c:147), peak bin or -1, 0, effdepth}        */
   int avg_depth;           /* 1..4                                                                                           */
   int avg_minbin, avg_maxbin, avg_nout;
+  /* the stream dimension (glfer_hip_spectrogram_batch_device): blockIdx.y is the stream of the batch; a kernel moves stream and
+     psd on by blockIdx.y times these strides at entry (glfer_batch_select) and walks its frames inside that stream as before.
+     nbatch <= 1 with zero strides: one stream, the grid and the rows of the single-stream entry.                            */
+  int nbatch;              /* streams in this launch (gridDim.y); 0 or 1: one                                              */
+  long long batch_stride;  /* bytes from one stream's sample 0 (virtual base) to the next one's                             */
+  long long psd_batch_stride;   /* floats from one stream's first row to the next one's                                     */
+  long long means_batch_stride; /* floats from one stream's given hop-means table (means) to the next one's                  */
 };
+
+/* A launcher's persistent grid for a batch: `cap` workgroups for the whole launch, shared among its streams, so that
+   gridDim.x x nbatch stays near the single-stream cap.  The caller keeps gridDim.x a multiple of 8 once it is >= 64
+   (xcd_block_index: with gridDim.x a multiple of 8 the linear workgroup id of (x, y) is x modulo 8 as well). */
+static inline long long glfer_batch_cap(long long cap, int nbatch) {
+  return nbatch > 1 ? (cap + nbatch - 1) / nbatch : cap;
+}
+static inline unsigned glfer_batch_y(const SpectroParams &p) { return p.nbatch > 1 ? (unsigned)p.nbatch : 1u; }
+
+#ifdef __HIPCC__
+/* kernel entry: this workgroup's stream of the batch */
+__device__ __forceinline__ void glfer_batch_select(SpectroParams &p) {
+  const long long b = (long long)blockIdx.y;
+  p.stream = reinterpret_cast<const char *>(p.stream) + b * p.batch_stride;
+  p.psd = p.psd + b * p.psd_batch_stride;
+  if (p.means) p.means = p.means + b * p.means_batch_stride;
+}
+#endif
 
 #ifdef __cplusplus
 extern "C" {
@@ -124,6 +149,12 @@ hipError_t glfer_launch_map(const float *psd, const double *avg, size_t nframes,
                             hipStream_t st);
 hipError_t glfer_launch_submean(const void *in, float *out, int H, long long nhops, int fmt,
                                 hipStream_t st, const float *means /* NULL: summed by the kernel */);
+/* the same over nb streams (blockIdx.y): stream b reads in + b * in_bstride bytes, writes out + b * out_bstride floats and
+   takes means + b * means_bstride; nb <= 65535 */
+hipError_t glfer_launch_submean_batch(const void *in, float *out, int H, long long nhops, int fmt, hipStream_t st, const float *means,
+                                      unsigned nb, long long in_bstride, long long out_bstride, long long means_bstride);
+hipError_t glfer_launch_hop_means_seq_batch(const void *in, float *means, int H, long long nhops, int fmt, unsigned nb,
+                                            long long in_bstride, long long means_bstride, hipStream_t st);
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,10 @@
 namespace glfer {
 
 template <int FMT, int TILE>
-__global__ __launch_bounds__(256) void hop_means_seq_kernel(const void *in, float *means, int H, long long nhops) {
+__global__ __launch_bounds__(256) void hop_means_seq_kernel(const void *in, float *means, int H, long long nhops, long long in_bstride,
+                                                             long long means_bstride) {
+  in = reinterpret_cast<const char *>(in) + (long long)blockIdx.y * in_bstride;   // the stream of a batch (blockIdx.y; 0 otherwise)
+  means += (long long)blockIdx.y * means_bstride;
   constexpr unsigned esz = FMT == GLFER_FMT_F32 ? 4 : (FMT == GLFER_FMT_S16 ? 2 : 1);
   __shared__ float tile_all[4][64 * (TILE + 1)];
   const unsigned l = threadIdx.x & 63u;
@@ -184,15 +187,21 @@ extern "C" hipError_t glfer_launch_hop_means_tiled(const void *in, float *means,
   return hipGetLastError();
 }
 
-extern "C" hipError_t glfer_launch_hop_means_seq(const void *in, float *means, int H, long long nhops, int fmt, hipStream_t st) {
-  if (nhops <= 0) return hipSuccess;
-  const unsigned grid = (unsigned)((nhops + 255) / 256);
+extern "C" hipError_t glfer_launch_hop_means_seq_batch(const void *in, float *means, int H, long long nhops, int fmt, unsigned nb,
+                                                       long long in_bstride, long long means_bstride, hipStream_t st) {
+  if (nhops <= 0 || nb == 0) return hipSuccess;
+  if (nb > 65535) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((nhops + 255) / 256), nb);
   switch (fmt) {
-    case GLFER_FMT_F32: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_F32, 64>), dim3(grid), dim3(256), 0, st, in, means, H, nhops); break;
-    case GLFER_FMT_S16: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_S16, 64>), dim3(grid), dim3(256), 0, st, in, means, H, nhops); break;
-    case GLFER_FMT_U8: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_U8, 64>), dim3(grid), dim3(256), 0, st, in, means, H, nhops); break;
+    case GLFER_FMT_F32: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_F32, 64>), grid, dim3(256), 0, st, in, means, H, nhops, in_bstride, means_bstride); break;
+    case GLFER_FMT_S16: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_S16, 64>), grid, dim3(256), 0, st, in, means, H, nhops, in_bstride, means_bstride); break;
+    case GLFER_FMT_U8: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_U8, 64>), grid, dim3(256), 0, st, in, means, H, nhops, in_bstride, means_bstride); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
+}
+
+extern "C" hipError_t glfer_launch_hop_means_seq(const void *in, float *means, int H, long long nhops, int fmt, hipStream_t st) {
+  return glfer_launch_hop_means_seq_batch(in, means, H, nhops, fmt, 1, 0, 0, st);
 }
 

@@ -198,6 +198,32 @@ int glfer_hip_spectrogram_device(glfer_hip_plan *plan, const void *d_stream, siz
                                  size_t first_frame, size_t nframes, float *d_psd,
                                  void *hip_stream);
 
+/* Many independent streams of one plan in one call: the same frames [first_frame, first_frame+nframes) of each.
+ *   d_streams    : stream b is d_streams + b * stream_pitch samples -- exactly what glfer_hip_spectrogram_device would
+ *                  be given as d_stream (the virtual-base convention and the "Cutting a stream" rules included);
+ *                  every stream has nsamples samples
+ *   stream_pitch : in samples of cfg.sample_format; any value, overlapping streams included.  With s16 / u8 samples it
+ *                  must be even (GLFER_E_ARG otherwise): the kernel choice reads the stream's alignment (the real-input
+ *                  forms fetch integer samples in aligned pairs), and it must not differ between the streams of a batch
+ *   d_psd        : device, [nstreams][nframes][pitch] floats; row i of stream b at d_psd + (b * nframes + i) * pitch
+ * Every row is float for float the row glfer_hip_spectrogram_device writes for that stream on the same plan.
+ * nstreams == 0 or nframes == 0: GLFER_OK, nothing launched; every other argument error is the single-stream entry's.
+ * Asynchronous on hip_stream.
+ * FFT and MTM modes at N = 256 .. 16384 -- mean removal, RA9MB / limiter and ZERO_ALWAYS included -- run the whole batch
+ * in the launches one stream takes (the estimator, hop-means and corrected-copy kernels' stream dimension: blockIdx.y), so
+ * the launch count does not grow with nstreams; a batch above the device's grid y limit (65 535) is cut into chunks of that
+ * many streams.  Scratch: the corrected copies and hop-means tables of all streams at once, what the single-stream entry
+ * takes for a stream of nstreams times the hops.  HP-ARMA, LMP and N outside 256 .. 16384 go stream by stream inside the
+ * call.  The opt-in in-launch hop-means producers and the piecewise means (GLFER_MEANS_PRODUCERS, GLFER_EXACT_PIECE_MB)
+ * are never taken by this entry.
+ * Not covered: ragged batches (one length per stream), batched host / WAV / workers entries, a batched
+ * glfer_hip_spectrogram_avg_device (run glfer_hip_avg_device per stream: its averaging state restarts per stream), the
+ * F-test and halfcomplex-spectrum outputs, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as
+ * they are. */
+int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams,
+                                       size_t stream_pitch, size_t nsamples, size_t first_frame,
+                                       size_t nframes, float *d_psd, void *hip_stream);
+
 /* In LMP mode (GLFER_MODE_LMP, lmp.c:101-181) the same entry writes the detection statistic:
  * per frame the rectangular-window periodogram of the assembled frame (lmp.c:114-125), then per
  * bin mean and variance over the ring of the last lmp_av periodograms (zeros before the stream,
