@@ -51,7 +51,7 @@ EXPORTS = [
     "glfer_hip_abi_version", "glfer_hip_spectrogram_avg_device", "glfer_hip_workers_create", "glfer_hip_workers_destroy",
     "glfer_hip_workers_spectrogram_wav", "glfer_hip_workers_spectrogram_host",
     # many streams per call
-    "glfer_hip_spectrogram_batch_device",
+    "glfer_hip_spectrogram_batch_device", "glfer_hip_avg_batch_device", "glfer_hip_spectrogram_avg_batch_device",
 ]
 
 
@@ -193,6 +193,9 @@ def lib():
     L.glfer_hip_workers_spectrogram_wav.argtypes = [vp, C.c_char_p, vp, sz, C.POINTER(sz), C.c_uint, C.POINTER(Phases)]
     L.glfer_hip_workers_spectrogram_host.argtypes = [vp, vp, sz, vp, C.POINTER(sz), C.POINTER(Phases)]
     L.glfer_hip_spectrogram_avg_device.argtypes = [vp, vp, sz, sz, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.glfer_hip_avg_batch_device.argtypes = [C.c_int, vp, sz, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.glfer_hip_spectrogram_avg_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                         C.c_int, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -394,6 +397,32 @@ class Spectrogram:
                                                       C.c_void_p(psd.data_ptr() if want_psd else None), C.c_void_p(avg.data_ptr()),
                                                       C.c_void_p(ret.data_ptr() if want_ret else None), st),
                "glfer_hip_spectrogram_avg_device")
+        return avg, ret, psd
+
+    def run_avg_batch(self, streams, avg_mode, depth, minbin, maxbin, max0=0, n_out=None, want_psd=False, want_ret=True,
+                      first_frame=0, nframes=None):
+        """run_avg for many streams in one call (glfer_hip_spectrogram_avg_batch_device).  streams as run_batch takes them: 2-D
+        [B, T] on this GPU, of the plan's sample dtype, stride(1) == 1.  Returns (avg [B][nframes][n_out] float64, ret
+        [B][nframes][4] float64 or None, psd [B][nframes][bins] float32 or None); stream b's outputs are run_avg(streams[b])'s,
+        launched on torch's current stream."""
+        torch = _torch()
+        assert streams.is_cuda and streams.dim() == 2 and (streams.stride(1) == 1 or streams.size(1) <= 1)
+        assert streams.dtype == self._sample_dtype(), (streams.dtype, self._sample_dtype())
+        nb, total = streams.size(0), streams.size(1)
+        if nframes is None:
+            nframes = self.num_frames(total) - first_frame
+        n_out = n_out or self.bins
+        dev = streams.device
+        avg = torch.empty((nb, nframes, n_out), dtype=torch.float64, device=dev)
+        ret = torch.empty((nb, nframes, 4), dtype=torch.float64, device=dev) if want_ret else None
+        psd = torch.empty((nb, nframes, self.bins), dtype=torch.float32, device=dev) if want_psd else None
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(lib().glfer_hip_spectrogram_avg_batch_device(self._h, C.c_void_p(streams.data_ptr()), nb, streams.stride(0), total,
+                                                            first_frame, nframes, int(avg_mode), int(depth), int(minbin), int(maxbin),
+                                                            int(max0), int(n_out), C.c_void_p(psd.data_ptr() if want_psd else None),
+                                                            C.c_void_p(avg.data_ptr()), C.c_void_p(ret.data_ptr() if want_ret else None),
+                                                            st),
+               "glfer_hip_spectrogram_avg_batch_device")
         return avg, ret, psd
 
     def run_wav(self, path, chunk_frames=0, max_frames=None, partial_tail=False):
@@ -718,4 +747,21 @@ def update_avg(mode, psd, depth, minbin, maxbin, max0=0, n_out=None):
     _check(lib().glfer_hip_avg_device(int(mode), psd.data_ptr(), frames, bins, n_out, depth, minbin,
                                       maxbin, int(max0), avg.data_ptr(), ret.data_ptr(), st),
            "glfer_hip_avg_device")
+    return avg, ret
+
+
+def update_avg_batch(mode, psd, depth, minbin, maxbin, max0=0, n_out=None):
+    """update_avg over the rows of B independent streams (glfer_hip_avg_batch_device): psd [B][frames][bins] float32 on the
+    GPU, the averaging state empty at row 0 of each stream.  Returns (avg [B][frames][n_out] float64, ret [B][frames][4]
+    float64); stream b's are update_avg(mode, psd[b], ...)'s."""
+    torch = _torch()
+    assert psd.is_cuda and psd.dtype == torch.float32 and psd.is_contiguous() and psd.dim() == 3
+    nb, frames, bins = psd.shape
+    n_out = bins if n_out is None else n_out
+    avg = torch.empty((nb, frames, n_out), dtype=torch.float64, device=psd.device)
+    ret = torch.empty((nb, frames, 4), dtype=torch.float64, device=psd.device)
+    st = C.c_void_p(torch.cuda.current_stream(psd.device).cuda_stream)
+    _check(lib().glfer_hip_avg_batch_device(int(mode), psd.data_ptr(), nb, frames, bins, n_out, depth, minbin, maxbin, int(max0),
+                                            avg.data_ptr(), ret.data_ptr(), st),
+           "glfer_hip_avg_batch_device")
     return avg, ret

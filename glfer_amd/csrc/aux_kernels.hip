@@ -395,10 +395,18 @@ __global__ __launch_bounds__(256) void floor_wave_kernel(const float *__restrict
 // unless a bin's values within depth frames span more than ~2^26 (78 dB); beyond that the two differ
 // in the last bits of a double (the recurrence carries its own rounding history, the restart does
 // not).  131 072 rows: 2.1 M rows/s as one chain per bin, HBM-bound in chunks.
+// BAT (glfer_launch_avg_batch): blockIdx.z is the stream, its rows and sums psd_bs / avg_bs apart; the frames and the
+// chunks are the stream's own, so every stream's sums are those of a launch over it alone.
 constexpr int AVG_CHUNK = 128;
+struct AvgBatchStrides { long long psd, avg, ret; };   // per stream of a batch: floats of rows, doubles of averages, doubles of return values
+template <bool BAT = false>
 __global__ __launch_bounds__(256) void avg_cum_kernel(const float *__restrict__ psd, long long nframes,
                                                       int bins, int n_out, int depth, int minbin,
-                                                      int maxbin, double *__restrict__ avg) {
+                                                      int maxbin, double *__restrict__ avg, AvgBatchStrides bst) {
+  if constexpr (BAT) {
+    psd += (long long)blockIdx.z * bst.psd;
+    avg += (long long)blockIdx.z * bst.avg;
+  }
   const int b = minbin + blockIdx.x * 256 + threadIdx.x;
   if (b >= maxbin) return;
   const long long f0 = (long long)blockIdx.y * AVG_CHUNK;
@@ -430,11 +438,17 @@ __global__ __launch_bounds__(256) void avg_cum_kernel(const float *__restrict__ 
 
 // K5b.  Per-frame reductions over the band and the output normalisation of the three
 // modes (avg.c:129-156, 185-215, 248-294).  One block per frame, in place on the avg row.
-// mode: 1 sumavg, 2 plain, 3 sumextreme (glfer.h:56-58).
+// mode: 1 sumavg, 2 plain, 3 sumextreme (glfer.h:56-58).  BAT: blockIdx.y is the stream of a batch.
+template <bool BAT = false>
 __global__ __launch_bounds__(256) void avg_norm_kernel(const float *__restrict__ psd, int bins, int n_out,
                                                        int depth, int minbin, int maxbin, int mode,
                                                        int max0, double *__restrict__ avg,
-                                                       double *__restrict__ ret) {
+                                                       double *__restrict__ ret, AvgBatchStrides bst) {
+  if constexpr (BAT) {
+    psd += (long long)blockIdx.y * bst.psd;
+    avg += (long long)blockIdx.y * bst.avg;
+    ret += (long long)blockIdx.y * bst.ret;
+  }
   __shared__ double r_sum[256], r_max[256], r_min[256], r_var[256];
   __shared__ int r_idx[256], r_cnt[256];
   const long long f = blockIdx.x;
@@ -573,10 +587,20 @@ struct AvgMapArgs {
   long long fbeg;
 };
 
-template <int BPT, bool RING, bool MAP, int NT = 256>
+// BAT (glfer_launch_avg_batch): blockIdx.y is the stream of a batch -- psd, avg and ret move on by its strides, and nframes,
+// the chunks and their lead-in rows are the stream's own: a chunk never reaches back into the stream before it, and effdepth
+// counts from the stream's row 0.
+template <int BPT, bool RING, bool MAP, int NT = 256, bool BAT = false>
 __global__ __launch_bounds__(NT) void avg_fused_kernel(const float *__restrict__ psd, long long nframes, int chunk, int bins,
                                                         int n_out, int depth, int minbin, int maxbin, int mode, int max0,
-                                                        double *__restrict__ avg, double *__restrict__ ret, AvgMapArgs ma) {
+                                                        double *__restrict__ avg, double *__restrict__ ret, AvgMapArgs ma,
+                                                        AvgBatchStrides bst) {
+  static_assert(!(BAT && MAP), "the waterfall's columns are never batched");
+  if constexpr (BAT) {
+    psd += (long long)blockIdx.y * bst.psd;
+    avg += (long long)blockIdx.y * bst.avg;
+    ret += (long long)blockIdx.y * bst.ret;
+  }
   constexpr int NW = NT / 64;                     // wavefronts of the block
   constexpr bool RET = !MAP;                      // update_avg's return values (band mean, peak bin, variance): not for columns that are only mapped
   __shared__ double p_sum[2][NW], p_max[2][NW], p_min[2][NW], p_var[2][NW];
@@ -946,12 +970,15 @@ extern "C" hipError_t glfer_launch_floor(const float *psd, size_t nframes, int b
 
 static int bpt_of(int bpt) { return bpt <= 3 ? bpt : (bpt <= 5 ? 5 : (bpt <= 9 ? 9 : (bpt <= 17 ? 17 : 33))); }   // the BPT the fused kernel is built for
 
-extern "C" hipError_t glfer_launch_avg(int mode, const float *psd, size_t nframes, int bins, int n_out,
-                                       int depth, int minbin, int maxbin, int max0, double *avg,
-                                       double *ret, hipStream_t st) {
-  if (nframes == 0) return hipSuccess;
+// BAT: nb streams (blockIdx.y of the fused form, z of the cum kernel, y of the norm kernel), nframes rows each, bst apart.  The
+// shape -- chunk, BPT, ring, fused or two-pass -- is chosen from ONE stream's frame count, as a launch over that stream alone
+// would choose it, so that every stream's outputs are those of that launch chunk for chunk.
+template <bool BAT>
+static hipError_t launch_avg(int mode, const float *psd, size_t nframes, int bins, int n_out, int depth, int minbin, int maxbin,
+                             int max0, double *avg, double *ret, unsigned nb, AvgBatchStrides bst, hipStream_t st) {
+  if (nframes == 0 || nb == 0) return hipSuccess;
   const int band = maxbin - minbin;
-  if (band < 1 || minbin < 0 || maxbin > bins || maxbin > n_out || depth < 1) return hipErrorInvalidValue;
+  if (band < 1 || minbin < 0 || maxbin > bins || maxbin > n_out || depth < 1 || nb > 65535 || (!BAT && nb != 1)) return hipErrorInvalidValue;
   const long long nf = (long long)nframes;
   // A fused block walks `chunk` frames in order, so the launch has nframes/chunk blocks: 128-frame
   // chunks for long batches, shorter ones (down to 8) to keep ~1000 blocks in flight for short ones.
@@ -966,8 +993,8 @@ extern "C" hipError_t glfer_launch_avg(int mode, const float *psd, size_t nframe
     const bool ring = ring_bytes <= 60 * 1024;                 // beside the kernel's static words, under the 64 KB limit
 #define GLFER_AVG_FUSED(B)                                                                                              \
   do {                                                                                                                  \
-    if (ring) hipLaunchKernelGGL((avg_fused_kernel<B, true, false>), dim3(blocks), dim3(256), ring_bytes, st, psd, nf, chunk, bins, n_out, depth, minbin, maxbin, mode, max0, avg, ret, AvgMapArgs{}); \
-    else hipLaunchKernelGGL((avg_fused_kernel<B, false, false>), dim3(blocks), dim3(256), 0, st, psd, nf, chunk, bins, n_out, depth, minbin, maxbin, mode, max0, avg, ret, AvgMapArgs{}); \
+    if (ring) hipLaunchKernelGGL((avg_fused_kernel<B, true, false, 256, BAT>), dim3(blocks, nb), dim3(256), ring_bytes, st, psd, nf, chunk, bins, n_out, depth, minbin, maxbin, mode, max0, avg, ret, AvgMapArgs{}, bst); \
+    else hipLaunchKernelGGL((avg_fused_kernel<B, false, false, 256, BAT>), dim3(blocks, nb), dim3(256), 0, st, psd, nf, chunk, bins, n_out, depth, minbin, maxbin, mode, max0, avg, ret, AvgMapArgs{}, bst); \
   } while (0)
     if (bpt <= 1) GLFER_AVG_FUSED(1);
     else if (bpt <= 2) GLFER_AVG_FUSED(2);
@@ -978,15 +1005,29 @@ extern "C" hipError_t glfer_launch_avg(int mode, const float *psd, size_t nframe
     else GLFER_AVG_FUSED(33);
   } else {
     const unsigned chunks = (unsigned)((nframes + AVG_CHUNK - 1) / AVG_CHUNK);
-    hipLaunchKernelGGL(avg_cum_kernel, dim3((unsigned)((band + 255) / 256), chunks), dim3(256), 0, st, psd, nf, bins, n_out,
-                       depth, minbin, maxbin, avg);
+    hipLaunchKernelGGL(avg_cum_kernel<BAT>, dim3((unsigned)((band + 255) / 256), chunks, nb), dim3(256), 0, st, psd, nf, bins, n_out,
+                       depth, minbin, maxbin, avg, bst);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(avg_norm_kernel, dim3((unsigned)nframes), dim3(256), 0, st, psd, bins, n_out, depth, minbin, maxbin,
-                       mode, max0, avg, ret);
+    hipLaunchKernelGGL(avg_norm_kernel<BAT>, dim3((unsigned)nframes, nb), dim3(256), 0, st, psd, bins, n_out, depth, minbin, maxbin,
+                       mode, max0, avg, ret, bst);
   }
 #undef GLFER_AVG_FUSED
   return hipGetLastError();
+}
+
+extern "C" hipError_t glfer_launch_avg(int mode, const float *psd, size_t nframes, int bins, int n_out,
+                                       int depth, int minbin, int maxbin, int max0, double *avg,
+                                       double *ret, hipStream_t st) {
+  return launch_avg<false>(mode, psd, nframes, bins, n_out, depth, minbin, maxbin, max0, avg, ret, 1, AvgBatchStrides{}, st);
+}
+
+// update_avg_* over nb streams of nframes rows each (nb <= 65535): stream b's rows at psd + b * psd_bs floats, its averages at
+// avg + b * avg_bs and its return values at ret + b * ret_bs doubles; every stream's state starts empty at its row 0
+extern "C" hipError_t glfer_launch_avg_batch(int mode, const float *psd, size_t nframes, int bins, int n_out, int depth, int minbin,
+                                             int maxbin, int max0, double *avg, double *ret, unsigned nb, long long psd_bs,
+                                             long long avg_bs, long long ret_bs, hipStream_t st) {
+  return launch_avg<true>(mode, psd, nframes, bins, n_out, depth, minbin, maxbin, max0, avg, ret, nb, AvgBatchStrides{psd_bs, avg_bs, ret_bs}, st);
 }
 
 // update_avg_* and the column mapping in one kernel (avg_fused_kernel<.., MAP>): frames [fbeg, nframes)
@@ -1040,8 +1081,8 @@ extern "C" hipError_t glfer_launch_avgmap(int mode, const float *psd, size_t fbe
                           : reinterpret_cast<const void *>(avg_fused_kernel<B, false, true, NT>);                       \
     hipError_t e = allow_dynamic_lds(fn, shmem);                                                                        \
     if (e != hipSuccess) return e;                                                                                      \
-    if (ring) hipLaunchKernelGGL((avg_fused_kernel<B, true, true, NT>), dim3(blocks), dim3(NT), shmem, st, psd, nf, chunk, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma); \
-    else hipLaunchKernelGGL((avg_fused_kernel<B, false, true, NT>), dim3(blocks), dim3(NT), shmem, st, psd, nf, chunk, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma); \
+    if (ring) hipLaunchKernelGGL((avg_fused_kernel<B, true, true, NT>), dim3(blocks), dim3(NT), shmem, st, psd, nf, chunk, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma, AvgBatchStrides{}); \
+    else hipLaunchKernelGGL((avg_fused_kernel<B, false, true, NT>), dim3(blocks), dim3(NT), shmem, st, psd, nf, chunk, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma, AvgBatchStrides{}); \
   } while (0)
 #if GLFER_AVGMAP_WIDE
 #define GLFER_AVGMAP(B)                                                                                                 \
@@ -1071,7 +1112,7 @@ extern "C" hipError_t glfer_launch_avg_cum(const float *psd, size_t nframes, int
   const int band = maxbin - minbin;
   if (band < 1 || minbin < 0 || maxbin > bins || maxbin > n_out || depth < 1) return hipErrorInvalidValue;
   const unsigned chunks = (unsigned)((nframes + AVG_CHUNK - 1) / AVG_CHUNK);
-  hipLaunchKernelGGL(avg_cum_kernel, dim3((unsigned)((band + 255) / 256), chunks), dim3(256), 0, st, psd, (long long)nframes,
-                     bins, n_out, depth, minbin, maxbin, cum);
+  hipLaunchKernelGGL(avg_cum_kernel<false>, dim3((unsigned)((band + 255) / 256), chunks), dim3(256), 0, st, psd, (long long)nframes,
+                     bins, n_out, depth, minbin, maxbin, cum, AvgBatchStrides{});
   return hipGetLastError();
 }

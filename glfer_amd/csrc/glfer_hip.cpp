@@ -27,6 +27,9 @@ extern "C" hipError_t glfer_launch_floor(const float *psd, size_t nframes, int b
 extern "C" hipError_t glfer_launch_avg(int mode, const float *psd, size_t nframes, int bins, int n_out,
                                        int depth, int minbin, int maxbin, int max0, double *avg,
                                        double *ret, hipStream_t st);
+extern "C" hipError_t glfer_launch_avg_batch(int mode, const float *psd, size_t nframes, int bins, int n_out, int depth, int minbin,
+                                             int maxbin, int max0, double *avg, double *ret, unsigned nb, long long psd_bs,
+                                             long long avg_bs, long long ret_bs, hipStream_t st);
 extern "C" int glfer_avgmap_applies(size_t walk, int bins, int depth, int minbin, int maxbin);
 extern "C" hipError_t glfer_launch_avgmap(int mode, const float *psd, size_t fbeg, size_t nframes, int bins, int depth,
                                           int minbin, int maxbin, int max0, int scale_log, double thr255,
@@ -1793,6 +1796,13 @@ static int batch_mean_inkernel(glfer_hip_plan *p, const SpectroParams &sp, size_
   return rc;
 }
 
+// the plans whose rows a batch computes in the launches of one stream (the others go stream by stream)
+static bool batch_one_launch(const glfer_hip_plan *p) {
+  return (p->cfg.mode == GLFER_MODE_FFT || p->cfg.mode == GLFER_MODE_MTM) && p->n >= 256 && p->n <= 16384;
+}
+static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch, size_t nsamples, size_t first,
+                      size_t nframes, float *d_psd, size_t psd_bs, hipStream_t st);
+
 int glfer_hip_spectrogram_batch_device(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch,
                                        size_t nsamples, size_t first, size_t nframes, float *d_psd, void *hip_stream) {
   if (!p) return GLFER_E_ARG;
@@ -1807,12 +1817,18 @@ int glfer_hip_spectrogram_batch_device(glfer_hip_plan *p, const void *d_streams,
   if (fmt != GLFER_FMT_F32 && (stream_pitch & 1)) return GLFER_E_ARG;
   const size_t rows = (size_t)p->pitch;
   if (stream_pitch > (SIZE_MAX / esz) / nstreams || nframes > (SIZE_MAX / sizeof(float) / rows) / nstreams) return GLFER_E_ARG;
-  hipStream_t st = (hipStream_t)hip_stream;
+  return batch_rows(p, d_streams, nstreams, stream_pitch, nsamples, first, nframes, d_psd, nframes * rows, (hipStream_t)hip_stream);
+}
+
+// the body of glfer_hip_spectrogram_batch_device, arguments checked: stream b's rows at d_psd + b * psd_bs floats
+static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch, size_t nsamples, size_t first,
+                      size_t nframes, float *d_psd, size_t psd_bs, hipStream_t st) {
+  const int fmt = p->cfg.sample_format;
+  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
   const char *base = static_cast<const char *>(d_streams);
-  const bool one_launch = (p->cfg.mode == GLFER_MODE_FFT || p->cfg.mode == GLFER_MODE_MTM) && p->n >= 256 && p->n <= 16384;
-  if (!one_launch || nstreams == 1) {
+  if (!batch_one_launch(p) || nstreams == 1) {
     for (size_t b = 0; b < nstreams; b++) {
-      const int rc = glfer_run_device(p, base + b * stream_pitch * esz, nsamples, first, nframes, d_psd + b * nframes * rows, nullptr, st);
+      const int rc = glfer_run_device(p, base + b * stream_pitch * esz, nsamples, first, nframes, d_psd + b * psd_bs, nullptr, st);
       if (rc != GLFER_OK) return rc;
     }
     return GLFER_OK;
@@ -1830,10 +1846,10 @@ int glfer_hip_spectrogram_batch_device(glfer_hip_plan *p, const void *d_streams,
     sp.stream = base + c0 * stream_pitch * esz;
     sp.frame0 = (long long)first;
     sp.nframes = (int)nframes;
-    sp.psd = d_psd + c0 * nframes * rows;
+    sp.psd = d_psd + c0 * psd_bs;
     sp.nbatch = (int)nb;
     sp.batch_stride = (long long)(stream_pitch * esz);
-    sp.psd_batch_stride = (long long)(nframes * rows);
+    sp.psd_batch_stride = (long long)psd_bs;
     int rc = GLFER_OK;
     if (p->cfg.sub_mean && mean_inkernel_ok(p, sp, nullptr, -1)) {
       rc = batch_mean_inkernel(p, sp, first, nframes, nb, st);
@@ -2076,6 +2092,24 @@ int glfer_hip_avg_device(int avg_mode, const float *d_psd, size_t nframes, int b
   return GLFER_OK;
 }
 
+// The route of glfer_hip_spectrogram_avg_device (and of every stream of glfer_hip_spectrogram_avg_batch_device): true where the
+// average is taken inside the estimator launch for frames [*b0, first + nframes) -- the frames before *b0 then take the two
+// launches --, false where the whole call takes them.  sp: the call's parameters (the stream's alignment picks the form).
+static bool avg_in_launch(const glfer_hip_plan *p, const SpectroParams &sp, int avg_mode, int depth, int n_out, size_t first,
+                          size_t nframes, size_t *b0) {
+  static const bool fused_off = [] { const char *e = getenv("GLFER_AVG_FUSED"); return e && *e == '0'; }();   // (A/B runs and the tests that compare the two)
+  // mean removal: off, or the reference's own (cfg.sub_mean = 1: the means are taken first, in its summation order, and given to the kernel)
+  // where the hop is 2, 4, 8 or 16 sixteenths of the block; the in-kernel sums (GLFER_SUBMEAN_FAST) take the two launches
+  const bool with_means = p->cfg.sub_mean != 0;
+  const bool fused = !fused_off && avg_mode == GLFER_AVG_PLAIN && depth <= 4 && p->cfg.mode == GLFER_MODE_FFT && !p->nonlin &&
+                     !p->cfg.history_mode && p->n >= 512 && p->n <= 4096 && n_out <= 2 * p->n && body_route(sp, p->n) == ROUTE_REAL_INPUT &&
+                     (!with_means || (reference_means(p) && route_takes_mean(ROUTE_REAL_INPUT, sp, p->n) && !getenv("GLFER_MEAN_PREPASS")));
+  // the first frame every one of whose depth-1 predecessors lies inside the stream AND inside this call's averaging state
+  const size_t first_inside = (size_t)((p->keep + p->hop - 1) / p->hop), end = first + nframes;
+  *b0 = std::max(first, first_inside) + (size_t)(depth - 1);
+  return fused && *b0 + 256 <= end;                       // (short calls: the lead frames of every slot would outweigh the rest)
+}
+
 // fft_do + fft_psd + update_avg_* for a batch of frames in ONE call (source.c:141-158 followed by g_main.c:1153-1183).  Where the
 // periodogram's real-input kernel applies -- FFT mode, N = 512 .. 4096, no RA9MB / limiter, no mean removal, history from the
 // stream, dense rows -- and the average is the plain one over a window of at most four frames (glfer.c:295-296: the default
@@ -2119,17 +2153,10 @@ int glfer_hip_spectrogram_avg_device(glfer_hip_plan *p, const void *d_stream, si
   sp.stream = d_stream;
   sp.frame0 = (long long)first;
   sp.nframes = (int)nframes;
-  static const bool fused_off = [] { const char *e = getenv("GLFER_AVG_FUSED"); return e && *e == '0'; }();   // (A/B runs and the tests that compare the two)
-  // mean removal: off, or the reference's own (cfg.sub_mean = 1: the means are taken first, in its summation order, and given to the kernel)
-  // where the hop is 2, 4, 8 or 16 sixteenths of the block; the in-kernel sums (GLFER_SUBMEAN_FAST) take the two launches
   const bool with_means = p->cfg.sub_mean != 0;
-  const bool fused = !fused_off && avg_mode == GLFER_AVG_PLAIN && depth <= 4 && p->cfg.mode == GLFER_MODE_FFT && !p->nonlin &&
-                     !p->cfg.history_mode && p->n >= 512 && p->n <= 4096 && n_out <= 2 * p->n && body_route(sp, p->n) == ROUTE_REAL_INPUT &&
-                     (!with_means || (reference_means(p) && route_takes_mean(ROUTE_REAL_INPUT, sp, p->n) && !getenv("GLFER_MEAN_PREPASS")));
-  // the first frame every one of whose depth-1 predecessors lies inside the stream AND inside this call's averaging state
-  const size_t first_inside = (size_t)((p->keep + p->hop - 1) / p->hop), end = first + nframes;
-  const size_t b0 = std::max(first, first_inside) + (size_t)(depth - 1);
-  if (!fused || b0 + 256 > end) {                         // (short calls: the lead frames of every slot would outweigh the rest)
+  const size_t end = first + nframes;
+  size_t b0 = end;
+  if (!avg_in_launch(p, sp, avg_mode, depth, n_out, first, nframes, &b0)) {
     two_launches(first, end);
     return rc;
   }
@@ -2176,6 +2203,154 @@ int glfer_hip_spectrogram_avg_device(glfer_hip_plan *p, const void *d_stream, si
   }
   if (means) glfer::scratch_free(means, st);
   if (ret_scratch) glfer::scratch_free(ret_scratch, st);
+  return rc;
+}
+
+int glfer_hip_avg_batch_device(int avg_mode, const float *d_psd, size_t nstreams, size_t nframes, int bins, int n_out, int depth,
+                               int minbin, int maxbin, int max0, double *d_avg, double *d_ret, void *hip_stream) {
+  if (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME) return GLFER_E_ARG;
+  if (depth < 1 || minbin < 0 || maxbin <= minbin || maxbin > bins || maxbin > n_out || n_out < 1) return GLFER_E_ARG;
+  if (nstreams == 0 || nframes == 0) return GLFER_OK;
+  if (!d_psd || !d_avg || !d_ret) return GLFER_E_ARG;
+  if (nframes > (SIZE_MAX / sizeof(double) / (size_t)std::max(bins, n_out)) / nstreams) return GLFER_E_ARG;
+  DeviceGuard guard(data_device(d_psd));
+  HIP_TRY(guard.error());
+  const size_t chunk = 65535;                                    // streams per launch: the grid's y (z) limit
+  for (size_t c0 = 0; c0 < nstreams; c0 += chunk) {
+    const unsigned nb = (unsigned)std::min(nstreams - c0, chunk);
+    HIP_TRY(glfer_launch_avg_batch(avg_mode, d_psd + c0 * nframes * (size_t)bins, nframes, bins, n_out, depth, minbin, maxbin,
+                                   max0 ? 1 : 0, d_avg + c0 * nframes * (size_t)n_out, d_ret + c0 * nframes * 4, nb,
+                                   (long long)(nframes * (size_t)bins), (long long)(nframes * (size_t)n_out), (long long)(nframes * 4),
+                                   (hipStream_t)hip_stream));
+  }
+  return GLFER_OK;
+}
+
+// glfer_hip_spectrogram_avg_device over many streams (glfer_hip.h).  The route is that entry's for one stream (avg_in_launch: the
+// streams differ only by a multiple of an even pitch, so every stream would get the same one); each launch it produces -- the
+// rows (batch_rows), the average over them (glfer_launch_avg_batch), the estimator with the average inside it -- covers the
+// whole batch (blockIdx.y), with the frames of each stream cut exactly as the single-stream entry cuts them.
+int glfer_hip_spectrogram_avg_batch_device(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch,
+                                           size_t nsamples, size_t first, size_t nframes, int avg_mode, int depth, int minbin,
+                                           int maxbin, int max0, int n_out, float *d_psd, double *d_avg, double *d_ret,
+                                           void *hip_stream) {
+  if (!p) return GLFER_E_ARG;
+  if (p->cfg.mode == GLFER_MODE_HPARMA || p->pitch != p->bins) return GLFER_E_ARG;
+  if (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME) return GLFER_E_ARG;
+  if (depth < 1 || minbin < 0 || maxbin <= minbin || maxbin > p->bins || n_out < p->bins) return GLFER_E_ARG;
+  const int fmt = p->cfg.sample_format;
+  if (fmt != GLFER_FMT_F32 && (stream_pitch & 1)) return GLFER_E_ARG;      // (glfer_hip_spectrogram_batch_device's rule)
+  if (nstreams == 0 || nframes == 0) return GLFER_OK;
+  if (!d_streams || !d_avg) return GLFER_E_ARG;
+  if ((first + nframes) > nsamples / (size_t)p->hop || nframes > 0x7fffffffu) return GLFER_E_ARG;
+  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
+  const size_t bins = (size_t)p->bins;
+  if (stream_pitch > (SIZE_MAX / esz) / nstreams || nframes > (SIZE_MAX / sizeof(double) / (size_t)n_out) / nstreams) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  DeviceGuard guard(p->cfg.device);
+  HIP_TRY(guard.error());
+  const char *base = static_cast<const char *>(d_streams);
+  const size_t end = first + nframes;
+  SpectroParams sp;
+  fill_params(p, sp);
+  sp.stream = base;
+  sp.frame0 = (long long)first;
+  sp.nframes = (int)nframes;
+  size_t b0 = end;
+  const bool in_launch = avg_in_launch(p, sp, avg_mode, depth, n_out, first, nframes, &b0);
+  const bool with_means = p->cfg.sub_mean != 0;
+  // streams per group: the grid's y limit, and rows that go to scratch (no d_psd) kept under 8 GiB a group (4 096 one-second
+  // C2 streams take 1.5 GiB: one group)
+  const size_t scratch_frames = in_launch ? b0 - first : nframes;
+  size_t group = 65535;
+  if (!d_psd && scratch_frames > 0)
+    group = std::max<size_t>(1, std::min(group, ((size_t)8 << 30) / (scratch_frames * bins * sizeof(float))));
+  int rc = GLFER_OK;
+  for (size_t c0 = 0; rc == GLFER_OK && c0 < nstreams; c0 += group) {
+    const unsigned nb = (unsigned)std::min(nstreams - c0, group);
+    const char *sbase = base + c0 * stream_pitch * esz;
+    float *psd_c = d_psd ? d_psd + c0 * nframes * bins : nullptr;
+    double *avg_c = d_avg + c0 * nframes * (size_t)n_out, *ret_c = d_ret ? d_ret + c0 * nframes * 4 : nullptr;
+    // frames [from, to) of every stream of the group: the rows (to d_psd, or scratch), then update_avg over them with the state
+    // empty at `from`
+    auto two_launches = [&](size_t from, size_t to) {
+      if (rc != GLFER_OK || from >= to) return;
+      const size_t nf = to - from;
+      float *rows = psd_c ? psd_c + (from - first) * bins : nullptr;
+      double *ret = ret_c ? ret_c + (from - first) * 4 : nullptr;
+      const size_t rows_bs = psd_c ? nframes * bins : nf * bins, ret_bs = ret_c ? nframes * 4 : nf * 4;
+      hipError_t e = hipSuccess;
+      if (!psd_c) e = glfer::scratch_malloc((void **)&rows, (size_t)nb * nf * bins * sizeof(float), st);
+      if (e == hipSuccess && !ret_c) e = glfer::scratch_malloc((void **)&ret, (size_t)nb * nf * 4 * sizeof(double), st);
+      if (e != hipSuccess) rc = hip_fail(e, "scratch (rows to average, batch)");
+      if (rc == GLFER_OK) rc = batch_rows(p, sbase, nb, stream_pitch, nsamples, from, nf, rows, rows_bs, st);
+      if (rc == GLFER_OK) {
+        e = glfer_launch_avg_batch(avg_mode, rows, nf, (int)bins, n_out, depth, minbin, maxbin, max0 ? 1 : 0,
+                                   avg_c + (from - first) * (size_t)n_out, ret, nb, (long long)rows_bs,
+                                   (long long)(nframes * (size_t)n_out), (long long)ret_bs, st);
+        if (e != hipSuccess) rc = hip_fail(e, "update_avg launch (batch)");
+      }
+      if (!psd_c && rows) glfer::scratch_free(rows, st);
+      if (!ret_c && ret) glfer::scratch_free(ret, st);
+    };
+    if (!in_launch) {
+      two_launches(first, end);
+      continue;
+    }
+    two_launches(first, b0);
+    if (rc != GLFER_OK) break;
+    const size_t piece = (size_t)1 << 24;                   // frames per launch, as the single-stream entry cuts them
+    const size_t ret_rows = std::min(piece, end - b0);
+    double *ret_scratch = nullptr;
+    if (!ret_c) {
+      hipError_t e = glfer::scratch_malloc((void **)&ret_scratch, (size_t)nb * ret_rows * 4 * sizeof(double), st);
+      if (e != hipSuccess) return hip_fail(e, "scratch (return values, batch)");
+    }
+    // the hop means of everything the body touches, one table per stream: its frames, the depth-1 frames a slot recomputes in
+    // front of them, their history
+    float *means = nullptr;
+    const size_t hops_back = (size_t)((p->keep + p->hop - 1) / p->hop), hop_lo = b0 - (size_t)(depth - 1) - hops_back;
+    const size_t nhops = end - hop_lo;
+    if (with_means) {
+      hipError_t e = glfer::scratch_malloc((void **)&means, (size_t)nb * nhops * sizeof(float), st);
+      if (e == hipSuccess)
+        e = glfer_launch_hop_means_seq_batch(sbase + hop_lo * (size_t)p->hop * esz, means, p->hop, (long long)nhops, fmt, nb,
+                                             (long long)(stream_pitch * esz), (long long)nhops, st);
+      if (e != hipSuccess) {
+        if (means) glfer::scratch_free(means, st);
+        if (ret_scratch) glfer::scratch_free(ret_scratch, st);
+        return hip_fail(e, "hop means (average inside the kernel, batch)");
+      }
+    }
+    for (size_t f0 = b0; rc == GLFER_OK && f0 < end; f0 += piece) {
+      const size_t nf = std::min(piece, end - f0);
+      SpectroParams q = sp;
+      q.stream = sbase;
+      q.nbatch = (int)nb;
+      q.batch_stride = (long long)(stream_pitch * esz);
+      if (with_means) {
+        q.mean_inkernel = 1;
+        q.means = means - hop_lo;                              // indexed by the stream's own hop (= frame) index
+        q.means_batch_stride = (long long)nhops;
+      }
+      q.frame0 = (long long)f0;
+      q.nframes = (int)nf;
+      q.psd = psd_c ? psd_c + (f0 - first) * bins : nullptr;
+      q.psd_batch_stride = psd_c ? (long long)(nframes * bins) : 0;    // (0: psd stays NULL in every stream)
+      q.avg = avg_c + (f0 - first) * (size_t)n_out;
+      q.avg_batch_stride = (long long)(nframes * (size_t)n_out);
+      q.avg_ret = ret_c ? ret_c + (f0 - first) * 4 : ret_scratch;
+      q.avg_ret_batch_stride = (long long)(ret_c ? nframes * 4 : ret_rows * 4);
+      q.avg_depth = depth;
+      q.avg_minbin = minbin;
+      q.avg_maxbin = maxbin;
+      q.avg_nout = n_out;
+      hipError_t e = launch_real_input(q, p->n, st);
+      if (e != hipSuccess) rc = hip_fail(e, "estimator launch (average inside the kernel, batch)");
+    }
+    if (means) glfer::scratch_free(means, st);
+    if (ret_scratch) glfer::scratch_free(ret_scratch, st);
+  }
   return rc;
 }
 

@@ -237,7 +237,10 @@ __device__ __forceinline__ void produce_hop_means(const SpectroParams &p, float 
 // themselves are stored only if p.psd is given.  Two wavefronts per SIMD (the rings and the double sums do not fit 168 VGPRs).
 template <int LOGN, int FMT, int WPS = GLFER16H_WAVES_PER_SIMD, int VAR = GLFER16H_VAR, int MT = 0, int HIST = 0, int SHIFT = 0, int MEAN = 0, int MTAB = 0, int AVG = 0>
 __global__ __launch_bounds__(LaunchH<LOGN>::BLOCK, WPS) void spectro16h_kernel(SpectroParams p) {
-  if constexpr (AVG == 0) glfer_batch_select(p);  // the stream of the batch (blockIdx.y; 0 outside a batch); the average forms are never batched
+  // the stream of the batch (blockIdx.y; 0 outside a batch); the average forms select it only in their batch instantiations
+  // (AVG = 2), so that the single-stream ones (AVG = 1) keep their registers
+  if constexpr (AVG == 0) glfer_batch_select(p);
+  if constexpr (AVG == 2) glfer_batch_select_avg(p);
   static_assert(AVG == 0 || (MT == 0 && HIST == 0 && ((MEAN == 0 && MTAB == 0) || (MEAN == 1 && MTAB == 1))),
                 "the average inside the kernel: the periodogram, plain or with GIVEN hop means (the reference's default, sub_mean = opt.autoscale), history from the stream");
   constexpr bool CONSEC = SHIFT > 0 || AVG != 0;         // every frame slot walks consecutive frames
@@ -1019,7 +1022,7 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
   using LC = LaunchH<L>;
   const long long work = ((long long)p.nframes + LC::FPB - 1) / LC::FPB;
   if (work == 0) return hipSuccess;
-  if (p.nbatch > 1 && (p.avg || p.nprod)) return hipErrorInvalidValue;   // the average and the in-launch producers: one stream only
+  if (p.nbatch > 1 && p.nprod) return hipErrorInvalidValue;   // the in-launch producers: one stream only
   const long long per_cu = (GLFER16H_WAVES_PER_SIMD * 256) / LC::BLOCK > 0 ? (GLFER16H_WAVES_PER_SIMD * 256) / LC::BLOCK : 1;
   const long long resident = 256LL * per_cu;
   const long long cap = glfer_batch_cap(8 * resident, p.nbatch);   // (a batch shares it among its streams)
@@ -1051,10 +1054,30 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
     if (p.history_mode || (p.mean_inkernel && !p.means) || p.nprod || p.avg_depth < 1 || p.avg_depth > 4 || p.avg_nout < (1 << (L - 1)) + 1) return hipErrorInvalidValue;
     const long long per_cu2 = (2 * 256) / LC::BLOCK > 0 ? (2 * 256) / LC::BLOCK : 1;
     static const long long mult = [] { const char *e = getenv("GLFER_AVG_GRID_MULT"); const long v = e && *e ? atol(e) : 4; return (long long)(v < 1 ? 1 : v); }();
-    const long long cap = mult * 256LL * per_cu2, want = work / 32 > 0 ? work / 32 : 1;
+    const long long cap = glfer_batch_cap(mult * 256LL * per_cu2, p.nbatch), want = work / 32 > 0 ? work / 32 : 1;   // (a batch shares the cap)
     unsigned ga = (unsigned)(want < cap ? want : cap);
     if (ga >= 64) ga &= ~7u;
     const int k16 = (16 * p.H) % (1 << L) == 0 ? (16 * p.H) >> L : 0;
+    if (p.nbatch > 1) {                              // a batch (glfer_hip_spectrogram_avg_batch_device): the AVG = 2 instantiations
+      const int mt = p.mean_inkernel ? 1 : 0;
+      if (mt && k16 != 2 && k16 != 4 && k16 != 8 && k16 != 16) return hipErrorInvalidValue;
+      const int sh = (k16 == 2 || k16 == 4 || k16 == 8) ? k16 : 0;
+#define GLFER16H_AVG_BATCH(SH, M)                                                                                              \
+  hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, SH, M, M, 2>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p)
+      if (mt) {
+        if (sh == 2) GLFER16H_AVG_BATCH(2, 1);
+        else if (sh == 4) GLFER16H_AVG_BATCH(4, 1);
+        else if (sh == 8) GLFER16H_AVG_BATCH(8, 1);
+        else GLFER16H_AVG_BATCH(0, 1);
+      } else {
+        if (sh == 2) GLFER16H_AVG_BATCH(2, 0);
+        else if (sh == 4) GLFER16H_AVG_BATCH(4, 0);
+        else if (sh == 8) GLFER16H_AVG_BATCH(8, 0);
+        else GLFER16H_AVG_BATCH(0, 0);
+      }
+#undef GLFER16H_AVG_BATCH
+      return hipGetLastError();
+    }
     if (p.mean_inkernel) {
       // the reference's default (sub_mean = opt.autoscale) with the means GIVEN (taken in its own order by hop_means_seq_kernel): the
       // table form's in-place correction in front of the same averaging block

@@ -89,6 +89,8 @@ struct SpectroParams {
   long long batch_stride;  /* bytes from one stream's sample 0 (virtual base) to the next one's                             */
   long long psd_batch_stride;   /* floats from one stream's first row to the next one's                                     */
   long long means_batch_stride; /* floats from one stream's given hop-means table (means) to the next one's                  */
+  long long avg_batch_stride;   /* doubles from one stream's first averaged row (avg) to the next one's                        */
+  long long avg_ret_batch_stride;   /* doubles from one stream's first return values (avg_ret) to the next one's               */
 };
 
 /* A launcher's persistent grid for a batch: `cap` workgroups for the whole launch, shared among its streams, so that
@@ -106,6 +108,14 @@ __device__ __forceinline__ void glfer_batch_select(SpectroParams &p) {
   p.stream = reinterpret_cast<const char *>(p.stream) + b * p.batch_stride;
   p.psd = p.psd + b * p.psd_batch_stride;
   if (p.means) p.means = p.means + b * p.means_batch_stride;
+}
+/* the same for the average taken inside the launch (glfer_hip_spectrogram_avg_batch_device; psd_batch_stride 0 when no PSD rows are
+   asked for, so that psd stays NULL) */
+__device__ __forceinline__ void glfer_batch_select_avg(SpectroParams &p) {
+  glfer_batch_select(p);
+  const long long b = (long long)blockIdx.y;
+  p.avg = p.avg + b * p.avg_batch_stride;
+  p.avg_ret = p.avg_ret + b * p.avg_ret_batch_stride;
 }
 #endif
 

@@ -216,10 +216,9 @@ int glfer_hip_spectrogram_device(glfer_hip_plan *plan, const void *d_stream, siz
  * takes for a stream of nstreams times the hops.  HP-ARMA, LMP and N outside 256 .. 16384 go stream by stream inside the
  * call.  The opt-in in-launch hop-means producers and the piecewise means (GLFER_MEANS_PRODUCERS, GLFER_EXACT_PIECE_MB)
  * are never taken by this entry.
- * Not covered: ragged batches (one length per stream), batched host / WAV / workers entries, a batched
- * glfer_hip_spectrogram_avg_device (run glfer_hip_avg_device per stream: its averaging state restarts per stream), the
- * F-test and halfcomplex-spectrum outputs, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as
- * they are. */
+ * The moving average of many streams: glfer_hip_spectrogram_avg_batch_device and glfer_hip_avg_batch_device below.
+ * Not covered: ragged batches (one length per stream), batched host / WAV / workers entries, the F-test and
+ * halfcomplex-spectrum outputs, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as they are. */
 int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams,
                                        size_t stream_pitch, size_t nsamples, size_t first_frame,
                                        size_t nframes, float *d_psd, void *hip_stream);
@@ -422,6 +421,31 @@ int glfer_hip_avg_device(int avg_mode, const float *d_psd, size_t nframes, int b
 int glfer_hip_spectrogram_avg_device(glfer_hip_plan *plan, const void *d_stream, size_t nsamples, size_t first_frame,
                                      size_t nframes, int avg_mode, int depth, int minbin, int maxbin, int max0, int n_out,
                                      float *d_psd, double *d_avg, double *d_ret, void *hip_stream);
+
+/* update_avg_* over the rows of nstreams independent streams, the state empty at row 0 of EACH stream.
+ *   d_psd [nstreams][nframes][bins] floats, d_avg [nstreams][nframes][n_out] doubles, d_ret [nstreams][nframes][4] doubles.
+ * Stream b's outputs equal glfer_hip_avg_device over d_psd + b*nframes*bins, double for double: the kernels' stream
+ * dimension chooses chunks, window lead-ins and the fused or two-pass form from one stream's frame count, as that call
+ * does.  The argument rules are glfer_hip_avg_device's; nstreams == 0 or nframes == 0: GLFER_OK, nothing launched.
+ * One launch (two on the two-pass form) per 65 535 streams.  Asynchronous on hip_stream. */
+int glfer_hip_avg_batch_device(int avg_mode, const float *d_psd, size_t nstreams, size_t nframes, int bins, int n_out,
+                               int depth, int minbin, int maxbin, int max0, double *d_avg, double *d_ret, void *hip_stream);
+
+/* glfer_hip_spectrogram_avg_device for nstreams streams laid out as glfer_hip_spectrogram_batch_device takes them
+ * (d_streams, stream_pitch, nsamples, first_frame, nframes: same meaning and the same argument rules).
+ *   d_psd [nstreams][nframes][bins] or NULL, d_avg [nstreams][nframes][n_out], d_ret [nstreams][nframes][4] or NULL.
+ * Every output of stream b is bit for bit what glfer_hip_spectrogram_avg_device gives for that stream alone: the call
+ * routes one stream's frames as that entry does (the average inside the estimator launch, its head frames and 2^24-frame
+ * pieces, or the two launches) and makes every resulting launch cover the whole batch, so the launch count does not grow
+ * with nstreams.  Where the rows themselves are not batched (LMP; N outside 256 .. 16384) they are computed stream by
+ * stream, then averaged in one batched launch.  The argument rules of both entries apply (HP-ARMA refused, dense rows,
+ * the band, n_out >= bins, an even pitch for s16 / u8); nstreams == 0 or nframes == 0: GLFER_OK, nothing launched.
+ * Scratch: rows (without d_psd) and return values (without d_ret) of all streams at once on the two-launch route, cut into
+ * groups of streams of at most 8 GiB of rows each.  Asynchronous on hip_stream. */
+int glfer_hip_spectrogram_avg_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams, size_t stream_pitch,
+                                           size_t nsamples, size_t first_frame, size_t nframes, int avg_mode, int depth,
+                                           int minbin, int maxbin, int max0, int n_out, float *d_psd, double *d_avg,
+                                           double *d_ret, void *hip_stream);
 
 /* The sliding sums alone: d_cum [nframes][n_out] = avgdata->cum after each frame (avg.c:114-127);
  * columns outside [minbin, maxbin) are left untouched. */
