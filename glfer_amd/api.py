@@ -52,6 +52,7 @@ EXPORTS = [
     "glfer_hip_workers_spectrogram_wav", "glfer_hip_workers_spectrogram_host",
     # many streams per call
     "glfer_hip_spectrogram_batch_device", "glfer_hip_avg_batch_device", "glfer_hip_spectrogram_avg_batch_device",
+    "glfer_hip_waterfall_batch_device",
 ]
 
 
@@ -193,6 +194,8 @@ def lib():
     L.glfer_hip_workers_spectrogram_wav.argtypes = [vp, C.c_char_p, vp, sz, C.POINTER(sz), C.c_uint, C.POINTER(Phases)]
     L.glfer_hip_workers_spectrogram_host.argtypes = [vp, vp, sz, vp, C.POINTER(sz), C.POINTER(Phases)]
     L.glfer_hip_spectrogram_avg_device.argtypes = [vp, vp, sz, sz, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.glfer_hip_waterfall_batch_device.argtypes = [dispp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, sz, C.c_int, vp, vp,
+                                                   vp, vp]
     L.glfer_hip_avg_batch_device.argtypes = [C.c_int, vp, sz, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.glfer_hip_spectrogram_avg_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                          C.c_int, vp, vp, vp, vp]
@@ -716,6 +719,28 @@ def waterfall(disp, psd, avg_mode=0, depth=1, minbin=0, maxbin=1, max0=0, want_l
     _check(lib().glfer_hip_waterfall_device(C.byref(disp), int(avg_mode), depth, minbin, maxbin, int(max0), psd.data_ptr(), frames,
                                             bins, rgb.data_ptr(), lev.data_ptr() if want_lev else None,
                                             stats.data_ptr() if want_stats else None, st), "glfer_hip_waterfall_device")
+    return rgb, lev, stats
+
+
+def waterfall_batch(disps, psd, avg_mode=0, depth=1, minbin=0, maxbin=1, max0=0, want_lev=True, want_stats=False):
+    """glfer_hip_waterfall_batch_device: waterfall() over B independent streams in one call.  psd [B][frames][bins] float32 on
+    the GPU (Spectrogram.run_batch's rows), disps a sequence of B Display objects with the same options, each carrying its
+    stream's state in and out (updated in place).  Returns (rgb [B][frames][bins][3], lev [B][frames][bins] | None,
+    stats [B][frames][4] | None); stream b's are waterfall(disps[b], psd[b], ...)'s."""
+    torch = _torch()
+    assert psd.is_cuda and psd.dtype == torch.float32 and psd.is_contiguous() and psd.dim() == 3
+    nb, frames, bins = psd.shape
+    assert len(disps) == nb
+    arr = (Display * nb)(*disps)
+    rgb = torch.empty((nb, frames, bins, 3), dtype=torch.uint8, device=psd.device)
+    lev = torch.empty((nb, frames, bins), dtype=torch.int16, device=psd.device) if want_lev else None
+    stats = torch.empty((nb, frames, 4), dtype=torch.float32, device=psd.device) if want_stats else None
+    st = C.c_void_p(torch.cuda.current_stream(psd.device).cuda_stream)
+    _check(lib().glfer_hip_waterfall_batch_device(arr, nb, int(avg_mode), depth, minbin, maxbin, int(max0), psd.data_ptr(), frames,
+                                                  bins, rgb.data_ptr(), lev.data_ptr() if want_lev else None,
+                                                  stats.data_ptr() if want_stats else None, st), "glfer_hip_waterfall_batch_device")
+    for d, out in zip(disps, arr):
+        C.memmove(C.addressof(d), C.addressof(out), C.sizeof(Display))
     return rgb, lev, stats
 
 

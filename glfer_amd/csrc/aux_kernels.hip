@@ -589,17 +589,26 @@ struct AvgMapArgs {
 
 // BAT (glfer_launch_avg_batch): blockIdx.y is the stream of a batch -- psd, avg and ret move on by its strides, and nframes,
 // the chunks and their lead-in rows are the stream's own: a chunk never reaches back into the stream before it, and effdepth
-// counts from the stream's row 0.
+// counts from the stream's row 0.  MAP and BAT (glfer_launch_avgmap_batch, the waterfall of many streams): nothing goes to avg
+// or ret, so their strides say where the stream's columns are instead -- bst.avg columns from one stream's rgb / lev to the
+// next's, bst.ret rows from one stream's levels to the next's; fbeg and nframes are the stream's own too (a tile's lead-in
+// reads back into the stream's own rows only).
 template <int BPT, bool RING, bool MAP, int NT = 256, bool BAT = false>
 __global__ __launch_bounds__(NT) void avg_fused_kernel(const float *__restrict__ psd, long long nframes, int chunk, int bins,
                                                         int n_out, int depth, int minbin, int maxbin, int mode, int max0,
                                                         double *__restrict__ avg, double *__restrict__ ret, AvgMapArgs ma,
                                                         AvgBatchStrides bst) {
-  static_assert(!(BAT && MAP), "the waterfall's columns are never batched");
   if constexpr (BAT) {
-    psd += (long long)blockIdx.y * bst.psd;
-    avg += (long long)blockIdx.y * bst.avg;
-    ret += (long long)blockIdx.y * bst.ret;
+    const long long sb = blockIdx.y;
+    psd += sb * bst.psd;
+    if constexpr (MAP) {
+      ma.levels += sb * bst.ret * 4;
+      ma.rgb += sb * bst.avg * n_out * 3;
+      if (ma.lev) ma.lev += sb * bst.avg * n_out;
+    } else {
+      avg += sb * bst.avg;
+      ret += sb * bst.ret;
+    }
   }
   constexpr int NW = NT / 64;                     // wavefronts of the block
   constexpr bool RET = !MAP;                      // update_avg's return values (band mean, peak bin, variance): not for columns that are only mapped
@@ -1060,13 +1069,17 @@ extern "C" int glfer_avgmap_applies(size_t walk, int bins, int depth, int minbin
   return avgmap_shape((long long)walk, bins, depth, minbin, maxbin).ok ? 1 : 0;
 }
 
-extern "C" hipError_t glfer_launch_avgmap(int mode, const float *psd, size_t fbeg, size_t nframes, int bins, int depth,
-                                          int minbin, int maxbin, int max0, int scale_log, double thr255,
-                                          double one_m_thr, const float *levels, const unsigned char *colortab,
-                                          const double *log_thr, unsigned char *rgb, short *lev, hipStream_t st) {
-  if (nframes <= fbeg) return hipSuccess;
+// BAT: nb streams (blockIdx.y, nb <= 65535), frames [fbeg, nframes) of each -- stream b's rows at psd + b * psd_bs floats, its
+// levels lv_bs rows and its columns col_bs columns after stream b-1's; the shape comes from ONE stream's walk, as a launch over
+// that stream alone would take it.
+template <bool BAT>
+static hipError_t launch_avgmap(int mode, const float *psd, size_t fbeg, size_t nframes, int bins, int depth, int minbin, int maxbin,
+                                int max0, int scale_log, double thr255, double one_m_thr, const float *levels,
+                                const unsigned char *colortab, const double *log_thr, unsigned char *rgb, short *lev, unsigned nb,
+                                AvgBatchStrides bst, hipStream_t st) {
+  if (nframes <= fbeg || nb == 0) return hipSuccess;
   const int band = maxbin - minbin;
-  if (band < 1 || minbin < 0 || maxbin > bins || depth < 1) return hipErrorInvalidValue;
+  if (band < 1 || minbin < 0 || maxbin > bins || depth < 1 || nb > 65535 || (!BAT && nb != 1)) return hipErrorInvalidValue;
   const long long nf = (long long)nframes, walk = nf - (long long)fbeg;
   const AvgMapShape shape = avgmap_shape(walk, bins, depth, minbin, maxbin);
   if (!shape.ok) return hipErrorNotSupported;
@@ -1077,12 +1090,12 @@ extern "C" hipError_t glfer_launch_avgmap(int mode, const float *psd, size_t fbe
   const AvgMapArgs ma{levels, colortab, log_thr, rgb, lev, scale_log, thr255, one_m_thr, (long long)fbeg};
 #define GLFER_AVGMAP_NT(B, NT)                                                                                          \
   do {                                                                                                                  \
-    const void *fn = ring ? reinterpret_cast<const void *>(avg_fused_kernel<B, true, true, NT>)                         \
-                          : reinterpret_cast<const void *>(avg_fused_kernel<B, false, true, NT>);                       \
+    const void *fn = ring ? reinterpret_cast<const void *>(avg_fused_kernel<B, true, true, NT, BAT>)                    \
+                          : reinterpret_cast<const void *>(avg_fused_kernel<B, false, true, NT, BAT>);                  \
     hipError_t e = allow_dynamic_lds(fn, shmem);                                                                        \
     if (e != hipSuccess) return e;                                                                                      \
-    if (ring) hipLaunchKernelGGL((avg_fused_kernel<B, true, true, NT>), dim3(blocks), dim3(NT), shmem, st, psd, nf, chunk, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma, AvgBatchStrides{}); \
-    else hipLaunchKernelGGL((avg_fused_kernel<B, false, true, NT>), dim3(blocks), dim3(NT), shmem, st, psd, nf, chunk, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma, AvgBatchStrides{}); \
+    if (ring) hipLaunchKernelGGL((avg_fused_kernel<B, true, true, NT, BAT>), dim3(blocks, nb), dim3(NT), shmem, st, psd, nf, chunk, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma, bst); \
+    else hipLaunchKernelGGL((avg_fused_kernel<B, false, true, NT, BAT>), dim3(blocks, nb), dim3(NT), shmem, st, psd, nf, chunk, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma, bst); \
   } while (0)
 #if GLFER_AVGMAP_WIDE
 #define GLFER_AVGMAP(B)                                                                                                 \
@@ -1103,6 +1116,25 @@ extern "C" hipError_t glfer_launch_avgmap(int mode, const float *psd, size_t fbe
 #undef GLFER_AVGMAP_NT
 #undef GLFER_AVGMAP
   return hipGetLastError();
+}
+
+extern "C" hipError_t glfer_launch_avgmap(int mode, const float *psd, size_t fbeg, size_t nframes, int bins, int depth,
+                                          int minbin, int maxbin, int max0, int scale_log, double thr255,
+                                          double one_m_thr, const float *levels, const unsigned char *colortab,
+                                          const double *log_thr, unsigned char *rgb, short *lev, hipStream_t st) {
+  return launch_avgmap<false>(mode, psd, fbeg, nframes, bins, depth, minbin, maxbin, max0, scale_log, thr255, one_m_thr, levels,
+                              colortab, log_thr, rgb, lev, 1, AvgBatchStrides{}, st);
+}
+
+// glfer_launch_avgmap over nb streams (the waterfall of many streams): psd_bs floats from one stream's rows to the next's,
+// lv_bs rows from one stream's levels to the next's, col_bs columns from one stream's rgb / lev to the next's
+extern "C" hipError_t glfer_launch_avgmap_batch(int mode, const float *psd, size_t fbeg, size_t nframes, int bins, int depth,
+                                                int minbin, int maxbin, int max0, int scale_log, double thr255, double one_m_thr,
+                                                const float *levels, const unsigned char *colortab, const double *log_thr,
+                                                unsigned char *rgb, short *lev, unsigned nb, long long psd_bs, long long lv_bs,
+                                                long long col_bs, hipStream_t st) {
+  return launch_avgmap<true>(mode, psd, fbeg, nframes, bins, depth, minbin, maxbin, max0, scale_log, thr255, one_m_thr, levels,
+                             colortab, log_thr, rgb, lev, nb, AvgBatchStrides{psd_bs, col_bs, lv_bs}, st);
 }
 
 // avgdata->cum alone (the shims hand it back to the caller's avg_data_t)

@@ -21,6 +21,13 @@ struct LevelsParams {
   float overlap;
   float max_lvl0, min_lvl0;      // state carried in (autoscale) or the fixed levels (not autoscale)
 };
+// BAT (glfer_launch_levels_batch): the stream of a batch -- its statistics, levels and chunk states move on by its strides,
+// and the state carried into its walk is its row of `state` ([stream][3] = {first_buffer, display_max_lvl, display_min_lvl}),
+// not LevelsParams'.  levels_fixup_kernel writes the state after the stream's last column back into that row.
+struct LevelsBatch {
+  long long stats_bs, levels_bs;       // floats from one stream's statistics / levels to the next's
+  float *state;
+};
 
 // levels: [nframes][4] = {display_max, display_min, display_max_lvl, display_min_lvl}
 //
@@ -127,12 +134,24 @@ __device__ __forceinline__ void levels_walk(const float *__restrict__ stats, lon
 }
 
 // chunk state: [chunk][4] = {warm-up end max, min, final max, min}
+// BAT: blockIdx.y is the stream; its chunks are its own (a warm-up never reads another stream's columns)
+template <bool BAT = false>
 __global__ __launch_bounds__(64) void levels_kernel(const float *__restrict__ stats, long long nframes,
                                                     LevelsParams p, float *__restrict__ levels,
-                                                    float *__restrict__ chunk_state) {
+                                                    float *__restrict__ chunk_state, LevelsBatch lb) {
   __shared__ float sx[2][64];
   __shared__ float sy[2][64];
   const int lane = threadIdx.x;
+  if constexpr (BAT) {
+    const long long b = blockIdx.y;
+    stats += b * lb.stats_bs;
+    levels += b * lb.levels_bs;
+    chunk_state += b * (long long)gridDim.x * 4;
+    const float *s = lb.state + b * 3;
+    p.first_buffer = s[0] != 0.0f;
+    p.max_lvl0 = s[1];
+    p.min_lvl0 = s[2];
+  }
   const long long c = blockIdx.x, begin = c * LEV_CHUNK;
   const long long end = begin + LEV_CHUNK < nframes ? begin + LEV_CHUNK : nframes;
   const long long ws = begin - LEV_WARM_SEEDED;
@@ -192,12 +211,21 @@ __global__ __launch_bounds__(64) void levels_kernel(const float *__restrict__ st
 // chunks of 131 072 columns, a fifth of the whole level tracking); the chunks that differ -- a few
 // per thousand -- are then walked in order.  A re-walk that changes its chunk's final state makes
 // the successor's comparison stale: the successor is walked again too (always correct, and rarer still).
+// BAT: one block per stream (blockIdx.x), its chunks compared with its own only; the block then carries the stream's
+// final state into its row of lb.state (first_buffer 0, g_main.c:1120).
+template <bool BAT = false>
 __global__ __launch_bounds__(64) void levels_fixup_kernel(const float *__restrict__ stats, long long nframes,
                                                           LevelsParams p, float *__restrict__ levels,
-                                                          float *__restrict__ chunk_state, int nchunks) {
+                                                          float *__restrict__ chunk_state, int nchunks, LevelsBatch lb) {
   __shared__ float sx[2][64];
   __shared__ float sy[2][64];
   const int lane = threadIdx.x;
+  if constexpr (BAT) {
+    const long long b = blockIdx.x;
+    stats += b * lb.stats_bs;
+    levels += b * lb.levels_bs;
+    chunk_state += b * (long long)nchunks * 4;
+  }
   bool carry = false;                                      // the chunk before this batch changed its final state
   for (int c0 = 1; c0 < nchunks; c0 += 64) {
     const int c = c0 + lane;
@@ -227,6 +255,11 @@ __global__ __launch_bounds__(64) void levels_fixup_kernel(const float *__restric
       }
     }
   }
+  if constexpr (BAT) {
+    float *s = lb.state + (long long)blockIdx.x * 3;
+    if (lane < 2) s[1 + lane] = chunk_state[(long long)(nchunks - 1) * 4 + 2 + lane];
+    if (lane == 0) s[0] = 0.0f;
+  }
 }
 
 // autoscale off: the levels are the same for every frame (g_main.c:1125-1139, evaluated on the host)
@@ -243,13 +276,23 @@ __global__ __launch_bounds__(256) void levels_fixed_kernel(long long nframes, fl
 // out as one 12-byte and one 8-byte store (byte-aligned: rows of 3n bytes start anywhere; gfx950 runs
 // with unaligned global access enabled and the compiler emits dwordx3/dwordx2 for it), instead of
 // twelve byte stores and four short stores; the palette sits in LDS as one dword per colour.
-template <typename SRC>
+// BAT (glfer_launch_map_batch): blockIdx.y is the stream, its rows, levels and columns mb apart -- a frame tile of a batch of
+// streams is not one run of rows, so the flattened launch does not serve there.
+struct MapBatch { long long src, levels, rgb, lev; };   // per stream: SRC values, floats of levels, bytes of rgb, shorts of lev
+template <typename SRC, bool BAT = false>
 __global__ __launch_bounds__(256) void map_kernel(const SRC *__restrict__ src, int n, int src_pitch, int scale_log,
                                                   double thr255, double one_m_thr,
                                                   const float *__restrict__ levels,
                                                   const unsigned char *__restrict__ colortab,
                                                   const double *__restrict__ log_thr,
-                                                  unsigned char *__restrict__ rgb, short *__restrict__ lev) {
+                                                  unsigned char *__restrict__ rgb, short *__restrict__ lev, MapBatch mb) {
+  if constexpr (BAT) {
+    const long long b = blockIdx.y;
+    src += b * mb.src;
+    levels += b * mb.levels;
+    rgb += b * mb.rgb;
+    if (lev) lev += b * mb.lev;
+  }
   __shared__ unsigned tab[256];      // palette: colour index -> RGB dword
   __shared__ unsigned ctab[256];     // logarithmic scales: dB short l0 + i -> RGB dword (display_map.hpp, DbTable)
   __shared__ int table_ok;
@@ -326,10 +369,31 @@ extern "C" hipError_t glfer_launch_levels(const float *stats, size_t nframes, in
   if (nframes == 0) return hipSuccess;
   LevelsParams p{scale_log, autoscale, first_buffer, overlap, max_lvl0, min_lvl0};
   const int nchunks = (int)((nframes + LEV_CHUNK - 1) / LEV_CHUNK);
-  hipLaunchKernelGGL(levels_kernel, dim3(nchunks), dim3(64), 0, st, stats, (long long)nframes, p, levels, chunk_state);
+  hipLaunchKernelGGL(levels_kernel<false>, dim3(nchunks), dim3(64), 0, st, stats, (long long)nframes, p, levels, chunk_state,
+                     LevelsBatch{});
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || nchunks == 1) return e;
-  hipLaunchKernelGGL(levels_fixup_kernel, dim3(1), dim3(64), 0, st, stats, (long long)nframes, p, levels, chunk_state, nchunks);
+  hipLaunchKernelGGL(levels_fixup_kernel<false>, dim3(1), dim3(64), 0, st, stats, (long long)nframes, p, levels, chunk_state, nchunks,
+                     LevelsBatch{});
+  return hipGetLastError();
+}
+
+// The autoscale walk of nb streams (nb <= 65535), nframes columns each: stream b's statistics at stats + b * stats_bs, its
+// levels at levels + b * levels_bs floats, its chunk states the next glfer_levels_scratch_floats(nframes) floats of
+// chunk_state; state [nb][3] = {first_buffer, display_max_lvl, display_min_lvl} in, the state after the last column out.
+// The fix-up always runs (one block per stream): it is what carries the state.
+extern "C" hipError_t glfer_launch_levels_batch(const float *stats, size_t nframes, int scale_log, float overlap, float *state,
+                                                long long stats_bs, long long levels_bs, float *levels, float *chunk_state,
+                                                unsigned nb, hipStream_t st) {
+  if (nframes == 0 || nb == 0) return hipSuccess;
+  if (nb > 65535) return hipErrorInvalidValue;
+  LevelsParams p{scale_log, 1, 0, overlap, 0.0f, 0.0f};
+  const LevelsBatch lb{stats_bs, levels_bs, state};
+  const int nchunks = (int)((nframes + LEV_CHUNK - 1) / LEV_CHUNK);
+  hipLaunchKernelGGL(levels_kernel<true>, dim3(nchunks, nb), dim3(64), 0, st, stats, (long long)nframes, p, levels, chunk_state, lb);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(levels_fixup_kernel<true>, dim3(nb), dim3(64), 0, st, stats, (long long)nframes, p, levels, chunk_state, nchunks, lb);
   return hipGetLastError();
 }
 
@@ -350,9 +414,37 @@ extern "C" hipError_t glfer_launch_map(const float *psd, const double *avg, size
   if (nframes == 0) return hipSuccess;
   if (avg)
     hipLaunchKernelGGL(map_kernel<double>, dim3((unsigned)nframes), dim3(256), 0, st, avg, n, n, scale_log,
-                       thr255, one_m_thr, levels, colortab, log_thr, rgb, lev);
+                       thr255, one_m_thr, levels, colortab, log_thr, rgb, lev, MapBatch{});
   else
     hipLaunchKernelGGL(map_kernel<float>, dim3((unsigned)nframes), dim3(256), 0, st, psd, n, psd_pitch, scale_log,
-                       thr255, one_m_thr, levels, colortab, log_thr, rgb, lev);
+                       thr255, one_m_thr, levels, colortab, log_thr, rgb, lev, MapBatch{});
   return hipGetLastError();
+}
+
+// The same for nb streams (nb <= 65535) of nframes columns each: stream b's rows at psd / avg + b * src_bs values (rows
+// psd_pitch floats apart, averaged rows n doubles apart), its levels at levels + b * levels_bs floats, its columns at
+// rgb + b * rgb_bs bytes and lev + b * lev_bs shorts.  Launches of at most 2^22 columns per stream (gridDim.x x 256 threads).
+extern "C" hipError_t glfer_launch_map_batch(const float *psd, const double *avg, size_t nframes, int n, int psd_pitch, int scale_log,
+                                             double thr255, double one_m_thr, const float *levels, const unsigned char *colortab,
+                                             const double *log_thr, unsigned char *rgb, short *lev, unsigned nb, long long src_bs,
+                                             long long levels_bs, long long rgb_bs, long long lev_bs, hipStream_t st) {
+  if (nframes == 0 || nb == 0) return hipSuccess;
+  if (nb > 65535) return hipErrorInvalidValue;
+  const MapBatch mb{src_bs, levels_bs, rgb_bs, lev_bs};
+  const size_t piece = (size_t)1 << 22;
+  for (size_t f0 = 0; f0 < nframes; f0 += piece) {
+    const unsigned nf = (unsigned)(nframes - f0 < piece ? nframes - f0 : piece);
+    const float *lv = levels + f0 * 4;
+    unsigned char *o = rgb + f0 * (size_t)n * 3;
+    short *l = lev ? lev + f0 * (size_t)n : nullptr;
+    if (avg)
+      hipLaunchKernelGGL((map_kernel<double, true>), dim3(nf, nb), dim3(256), 0, st, avg + f0 * (size_t)n, n, n, scale_log,
+                         thr255, one_m_thr, lv, colortab, log_thr, o, l, mb);
+    else
+      hipLaunchKernelGGL((map_kernel<float, true>), dim3(nf, nb), dim3(256), 0, st, psd + f0 * (size_t)psd_pitch, n, psd_pitch,
+                         scale_log, thr255, one_m_thr, lv, colortab, log_thr, o, l, mb);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }

@@ -35,6 +35,18 @@ extern "C" hipError_t glfer_launch_avgmap(int mode, const float *psd, size_t fbe
                                           int minbin, int maxbin, int max0, int scale_log, double thr255,
                                           double one_m_thr, const float *levels, const unsigned char *colortab,
                                           const double *log_thr, unsigned char *rgb, short *lev, hipStream_t st);
+extern "C" hipError_t glfer_launch_avgmap_batch(int mode, const float *psd, size_t fbeg, size_t nframes, int bins, int depth,
+                                                int minbin, int maxbin, int max0, int scale_log, double thr255, double one_m_thr,
+                                                const float *levels, const unsigned char *colortab, const double *log_thr,
+                                                unsigned char *rgb, short *lev, unsigned nb, long long psd_bs, long long lv_bs,
+                                                long long col_bs, hipStream_t st);
+extern "C" hipError_t glfer_launch_levels_batch(const float *stats, size_t nframes, int scale_log, float overlap, float *state,
+                                                long long stats_bs, long long levels_bs, float *levels, float *chunk_state,
+                                                unsigned nb, hipStream_t st);
+extern "C" hipError_t glfer_launch_map_batch(const float *psd, const double *avg, size_t nframes, int n, int psd_pitch, int scale_log,
+                                             double thr255, double one_m_thr, const float *levels, const unsigned char *colortab,
+                                             const double *log_thr, unsigned char *rgb, short *lev, unsigned nb, long long src_bs,
+                                             long long levels_bs, long long rgb_bs, long long lev_bs, hipStream_t st);
 extern "C" hipError_t glfer_launch_avg_cum(const float *psd, size_t nframes, int bins, int n_out, int depth,
                                            int minbin, int maxbin, double *cum, hipStream_t st);
 extern "C" hipError_t glfer_launch_lmp(const float *rows, long long row0, long long first, size_t nframes, int bins,
@@ -486,6 +498,35 @@ int glfer_hip_display_device(glfer_hip_display *d, const float *d_psd, const dou
 // stages run over tiles that only bound the scratch (averaged rows: 8 B/bin, 4 GiB per tile).
 }  // extern "C"
 
+// The route of a waterfall over `nframes` rows (glfer_hip_waterfall_device, and every stream of
+// glfer_hip_waterfall_batch_device): averages inside the mapping kernel (*fused) or staged, and the rows per tile.
+// Tiles only bound the scratch: the level walk costs its ~0.13 ms of latency per display call
+// however few columns it gets, so fewer, larger tiles are faster (two 65536-row tiles: 116 M rows/s
+// against 147 M stage by stage).  The averages are taken inside the mapping kernel where that form
+// applies (no averaged rows in memory at all: GLFER_WATERFALL_FUSED=0 forces the staged form, for
+// A/B runs and tests); staged, averaged rows are 8 B per bin: 4 GiB of them per tile.  Otherwise
+// only the 16 B of statistics per row are scratch.
+static void waterfall_route(int avg_mode, int depth, int minbin, int maxbin, int bins, int pitch, size_t nframes, bool *fused_out,
+                            size_t *tile_out) {
+  const bool averaging = avg_mode != 0;
+  bool fused = averaging && pitch == bins;               // (the average-in-the-map kernel walks dense rows)
+  if (const char *e = getenv("GLFER_WATERFALL_FUSED")) fused = fused && atoi(e) != 0;
+  size_t tile = (averaging && !fused) ? std::max<size_t>(16384, ((size_t)4 << 30) / ((size_t)bins * sizeof(double))) : (size_t)1 << 22;
+  if (const char *e = getenv("GLFER_WATERFALL_TILE")) {    // rows per tile, for tests of the tile seams and for tuning
+    const long v = atol(e);
+    if (v >= 64) tile = (size_t)v;
+  }
+  tile = std::min(tile, nframes);
+  tile = (nframes + (nframes + tile - 1) / tile - 1) / ((nframes + tile - 1) / tile);   // equal tiles: no short last one
+  // the form's chunking depends on the number of rows it walks, and the last tile may be a few rows
+  // shorter than the others: the fused form is taken only if it applies to BOTH lengths (ADVICE r2)
+  const size_t last_tile = nframes - (nframes - 1) / tile * tile;
+  if (fused) fused = glfer_avgmap_applies(tile, bins, depth, minbin, maxbin) != 0 &&
+                     glfer_avgmap_applies(last_tile, bins, depth, minbin, maxbin) != 0;
+  *fused_out = fused;
+  *tile_out = tile;
+}
+
 // Rows [row0, row0 + nframes) of the batch d_psd.  row0 > 0 / d_levels_in: the second phase of a
 // waterfall whose columns are spread over several GPUs (glfer_hip_waterfall_map_device) -- the moving
 // sums of the first rows reach back into the batch's rows before row0, the levels are given.
@@ -503,26 +544,9 @@ static int waterfall_columns(glfer_hip_display *d, int avg_mode, int depth, int 
   hipStream_t st = (hipStream_t)hip_stream;
   DeviceGuard guard(data_device(d_psd));
   HIP_TRY(guard.error());
-  // Tiles only bound the scratch: the level walk costs its ~0.13 ms of latency per display call
-  // however few columns it gets, so fewer, larger tiles are faster (two 65536-row tiles: 116 M rows/s
-  // against 147 M stage by stage).  The averages are taken inside the mapping kernel where that form
-  // applies (no averaged rows in memory at all: GLFER_WATERFALL_FUSED=0 forces the staged form, for
-  // A/B runs and tests); staged, averaged rows are 8 B per bin: 4 GiB of them per tile.  Otherwise
-  // only the 16 B of statistics per row are scratch.
-  bool fused = averaging && pitch == bins;               // (the average-in-the-map kernel walks dense rows)
-  if (const char *e = getenv("GLFER_WATERFALL_FUSED")) fused = fused && atoi(e) != 0;
-  size_t tile = (averaging && !fused) ? std::max<size_t>(16384, ((size_t)4 << 30) / ((size_t)bins * sizeof(double))) : (size_t)1 << 22;
-  if (const char *e = getenv("GLFER_WATERFALL_TILE")) {    // rows per tile, for tests of the tile seams and for tuning
-    const long v = atol(e);
-    if (v >= 64) tile = (size_t)v;
-  }
-  tile = std::min(tile, nframes);
-  tile = (nframes + (nframes + tile - 1) / tile - 1) / ((nframes + tile - 1) / tile);   // equal tiles: no short last one
-  // the form's chunking depends on the number of rows it walks, and the last tile may be a few rows
-  // shorter than the others: the fused form is taken only if it applies to BOTH lengths (ADVICE r2)
-  const size_t last_tile = nframes - (nframes - 1) / tile * tile;
-  if (fused) fused = glfer_avgmap_applies(tile, bins, depth, minbin, maxbin) != 0 &&
-                     glfer_avgmap_applies(last_tile, bins, depth, minbin, maxbin) != 0;
+  bool fused = false;
+  size_t tile = 0;
+  waterfall_route(avg_mode, depth, minbin, maxbin, bins, pitch, nframes, &fused, &tile);
   const size_t back = averaging ? (size_t)depth : 0;       // rows re-read in front of a tile to restart the sliding sums
   float *stats = d_stats;
   double *avg = nullptr, *ret = nullptr;
@@ -627,6 +651,196 @@ int glfer_hip_waterfall_map_device(const glfer_hip_display *d, int avg_mode, int
   glfer_hip_display copy = *d;               // the carried state is not touched: the walk was glfer_hip_levels_host's
   return waterfall_columns(&copy, avg_mode, depth, minbin, maxbin, max0, d_batch, first, nframes, bins, d_rgb, d_lev, nullptr,
                            hip_stream, d_levels, d->psd_pitch);
+}
+
+// glfer_hip_waterfall_device over many streams of one display plan (glfer_hip.h).  The route -- fused or staged average, the
+// frame tiles, the avgmap shape -- is that entry's for ONE stream's frames (waterfall_route); every launch it leads to covers
+// the batch: the floor statistics of all rows at once (the rows of all streams are one run), then per tile the autoscale walk
+// (blockIdx.y the stream, its carried state in a device table that stays there from tile to tile), and the map with a stream
+// dimension (fused: avg_fused_kernel<.., MAP, .., BAT>; staged: glfer_launch_avg_batch, then the map of the averaged rows).
+// One upload (palette, dB table, states), one download of the states and one synchronisation per call.
+static bool same_display_options(const glfer_hip_display &a, const glfer_hip_display &b) {
+  return a.scale_type == b.scale_type && a.autoscale == b.autoscale && a.overlap == b.overlap && a.max_level_db == b.max_level_db &&
+         a.min_level_db == b.min_level_db && a.thr_level == b.thr_level && a.palette == b.palette && a.psd_pitch == b.psd_pitch;
+}
+
+int glfer_hip_waterfall_batch_device(glfer_hip_display *disps, size_t nstreams, int avg_mode, int depth, int minbin, int maxbin,
+                                     int max0, const float *d_psd, size_t nframes, int bins, unsigned char *d_rgb, short *d_lev,
+                                     float *d_stats, void *hip_stream) {
+  if (nstreams == 0) return GLFER_OK;
+  if (!disps) return GLFER_E_ARG;
+  for (size_t b = 1; b < nstreams; b++)                  // one plan, many streams
+    if (!same_display_options(disps[0], disps[b])) return GLFER_E_ARG;
+  const glfer_hip_display &d0 = disps[0];
+  const int pitch = d0.psd_pitch == 0 ? bins : d0.psd_pitch;
+  if (bins < 1 || bins > 32769 || pitch < bins) return GLFER_E_ARG;     // (waterfall_columns' rules)
+  const bool averaging = avg_mode != 0;
+  if (averaging && (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME || depth < 1 || minbin < 0 ||
+                    maxbin <= minbin || maxbin > bins))
+    return GLFER_E_ARG;
+  if (nframes == 0) return GLFER_OK;
+  if (!d_psd || !d_rgb) return GLFER_E_ARG;
+  if (d0.scale_type < GLFER_SCALE_LIN || d0.scale_type > GLFER_SCALE_LOG_MAX0) return GLFER_E_ARG;   // (display_columns')
+  if (nframes > (SIZE_MAX / sizeof(double) / (size_t)pitch) / nstreams) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  DeviceGuard guard(data_device(d_psd));
+  HIP_TRY(guard.error());
+  bool fused = false;
+  size_t tile = 0;
+  waterfall_route(avg_mode, depth, minbin, maxbin, bins, pitch, nframes, &fused, &tile);
+  const bool staged = averaging && !fused;
+  const bool autoscale = d0.autoscale != 0;
+  const int scale_log = d0.scale_type == GLFER_SCALE_LOG || d0.scale_type == GLFER_SCALE_LOG_MAX0;
+  const size_t back = averaging ? (size_t)depth : 0;
+  const size_t bins_z = (size_t)bins, rows_bs = nframes * (size_t)pitch, cols = nframes * bins_z;
+  const size_t chunk = 65535;                            // streams per launch: the grid's y limit
+  // staged: streams per group, the averaged rows of a group within the single-stream entry's 4 GiB per tile
+  size_t group = chunk;
+  if (staged) group = std::max<size_t>(1, std::min(group, ((size_t)4 << 30) / ((tile + back) * bins_z * sizeof(double))));
+
+  // one small allocation: palette, dB table, the carried states [nstreams][3]; one upload
+  const size_t thr_bytes = (2 * glfer::kLogThrK + 1) * sizeof(double);
+  const size_t small_bytes = 768 + thr_bytes + nstreams * 3 * sizeof(float);
+  std::vector<unsigned char> host(small_bytes);
+  glfer::make_palette(d0.palette, host.data());
+  memcpy(host.data() + 768, glfer::log_thresholds(), thr_bytes);
+  float *h_state = reinterpret_cast<float *>(host.data() + 768 + thr_bytes);
+  for (size_t b = 0; b < nstreams; b++) {
+    h_state[b * 3 + 0] = disps[b].first_buffer != 0 ? 1.0f : 0.0f;
+    h_state[b * 3 + 1] = disps[b].display_max_lvl;
+    h_state[b * 3 + 2] = disps[b].display_min_lvl;
+  }
+  unsigned char *small = nullptr;
+  HIP_TRY(glfer::scratch_malloc((void **)&small, small_bytes, st));
+  const unsigned char *d_tab = small;
+  const double *d_thr = reinterpret_cast<const double *>(small + 768);
+  float *d_state = reinterpret_cast<float *>(small + 768 + thr_bytes);
+  int rc = GLFER_OK;
+  auto fail = [&](hipError_t err, const char *what) {
+    if (rc == GLFER_OK) rc = hip_fail(err, what);
+  };
+  // pageable source: hipMemcpyAsync stages it before returning
+  hipError_t e = hipMemcpyAsync(small, host.data(), small_bytes, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) fail(e, "glfer_hip_waterfall_batch_device (upload)");
+
+  // scratch: statistics of all rows (without d_stats), a tile's levels and chunk states, a group's averaged rows (staged)
+  const size_t st_floats = autoscale ? glfer_levels_scratch_floats(tile) : 0;
+  float *stats = d_stats, *levels = nullptr;
+  double *avg = nullptr, *ret = nullptr;
+  if (rc == GLFER_OK && !d_stats) {
+    e = glfer::scratch_malloc((void **)&stats, nstreams * nframes * 4 * sizeof(float), st);
+    if (e != hipSuccess) { stats = nullptr; fail(e, "scratch (waterfall statistics, batch)"); }
+  }
+  if (rc == GLFER_OK) {
+    e = glfer::scratch_malloc((void **)&levels, nstreams * (tile * 4 + st_floats) * sizeof(float), st);
+    if (e != hipSuccess) { levels = nullptr; fail(e, "scratch (waterfall levels, batch)"); }
+  }
+  float *chunk_state = levels ? levels + nstreams * tile * 4 : nullptr;
+  if (rc == GLFER_OK && staged) {
+    const size_t gb = std::min(group, nstreams);
+    e = glfer::scratch_malloc((void **)&avg, gb * (tile + back) * bins_z * sizeof(double), st);
+    if (e == hipSuccess) e = glfer::scratch_malloc((void **)&ret, gb * (tile + back) * 4 * sizeof(double), st);
+    if (e != hipSuccess) fail(e, "hipMallocAsync(waterfall tile, batch)");
+  }
+
+  // compute_floor of every row: the streams' rows are one run of nstreams x nframes rows (pieces: the grid's x limit)
+  const int m = bins - (int)(bins * 0.95);                           // fft.c:271 (glfer_hip_floor_device_pitched)
+  const size_t all_rows = nstreams * nframes, piece = (size_t)1 << 22;
+  for (size_t r0 = 0; rc == GLFER_OK && r0 < all_rows; r0 += piece) {
+    e = glfer_launch_floor(d_psd + r0 * (size_t)pitch, std::min(piece, all_rows - r0), bins, pitch, m, stats + r0 * 4, st);
+    if (e != hipSuccess) fail(e, "compute_floor launch (batch)");
+  }
+
+  const float thr_level = d0.thr_level / 100.0;                                // g_main.c:1099
+  const double thr255 = 255.0 * thr_level, one_m_thr = 1.0 - thr_level;
+  float mx = 0.0f, mn = 0.0f;
+  if (!autoscale) {                                                            // g_main.c:1125-1139
+    mx = pow(10.0, d0.max_level_db / 10.0);
+    mn = pow(10.0, d0.min_level_db / 10.0);
+    mn = (mx > mn ? mn : mx / 10.0);
+  }
+  for (size_t f0 = 0; rc == GLFER_OK && f0 < nframes; f0 += tile) {
+    const size_t nf = std::min(tile, nframes - f0);
+    // the tile's levels, [nstreams][nf][4]
+    if (autoscale) {
+      for (size_t c0 = 0; rc == GLFER_OK && c0 < nstreams; c0 += chunk) {
+        const unsigned nb = (unsigned)std::min(nstreams - c0, chunk);
+        e = glfer_launch_levels_batch(stats + (c0 * nframes + f0) * 4, nf, scale_log, d0.overlap, d_state + c0 * 3,
+                                      (long long)(nframes * 4), (long long)(nf * 4), levels + c0 * nf * 4,
+                                      chunk_state + c0 * glfer_levels_scratch_floats(nf), nb, st);
+        if (e != hipSuccess) fail(e, "level tracking launch (batch)");
+      }
+    } else {
+      const float dmax = scale_log ? (float)(10.0 * log10(mx)) : mx;
+      const float dmin = scale_log ? (float)(10.0 * log10(mn)) : mn;
+      e = glfer_launch_levels_fixed(nstreams * nf, dmax, dmin, mx, mn, levels, st);
+      if (e != hipSuccess) fail(e, "levels launch (batch)");
+    }
+    if (rc != GLFER_OK) break;
+    if (fused) {
+      // the sliding sums of the tile's first rows reach back into the stream's rows before it by themselves
+      for (size_t c0 = 0; rc == GLFER_OK && c0 < nstreams; c0 += chunk) {
+        const unsigned nb = (unsigned)std::min(nstreams - c0, chunk);
+        e = glfer_launch_avgmap_batch(avg_mode, d_psd + c0 * rows_bs, f0, f0 + nf, bins, depth, minbin, maxbin, max0 ? 1 : 0, scale_log,
+                                      thr255, one_m_thr, levels + c0 * nf * 4, d_tab, d_thr, d_rgb + (c0 * cols + f0 * bins_z) * 3,
+                                      d_lev ? d_lev + c0 * cols + f0 * bins_z : nullptr, nb, (long long)rows_bs, (long long)nf,
+                                      (long long)nframes, st);
+        if (e != hipSuccess) fail(e, "average-and-map launch (batch)");
+      }
+      continue;
+    }
+    if (!averaging) {
+      for (size_t c0 = 0; rc == GLFER_OK && c0 < nstreams; c0 += chunk) {
+        const unsigned nb = (unsigned)std::min(nstreams - c0, chunk);
+        e = glfer_launch_map_batch(d_psd + c0 * rows_bs + f0 * (size_t)pitch, nullptr, nf, bins, pitch, scale_log, thr255, one_m_thr,
+                                   levels + c0 * nf * 4, d_tab, d_thr, d_rgb + (c0 * cols + f0 * bins_z) * 3,
+                                   d_lev ? d_lev + c0 * cols + f0 * bins_z : nullptr, nb, (long long)rows_bs, (long long)(nf * 4),
+                                   (long long)(cols * 3), (long long)cols, st);
+        if (e != hipSuccess) fail(e, "map launch (batch)");
+      }
+      continue;
+    }
+    // staged: the sums of the tile's first rows reach `depth` rows back -- run from there (from an empty state at the stream's
+    // row 0, as update_avg does after alloc_avg) and map the tile's rows
+    const size_t lead = std::min(back, f0), arows = nf + lead;
+    for (size_t c0 = 0; rc == GLFER_OK && c0 < nstreams; c0 += group) {
+      const unsigned nb = (unsigned)std::min(nstreams - c0, group);
+      e = glfer_launch_avg_batch(avg_mode, d_psd + c0 * rows_bs + (f0 - lead) * (size_t)pitch, arows, pitch, bins, depth, minbin, maxbin,
+                                 max0 ? 1 : 0, avg, ret, nb, (long long)rows_bs, (long long)(arows * bins_z), (long long)(arows * 4), st);
+      if (e != hipSuccess) fail(e, "update_avg launch (waterfall, batch)");
+      if (rc == GLFER_OK) {
+        e = glfer_launch_map_batch(nullptr, avg + lead * bins_z, nf, bins, bins, scale_log, thr255, one_m_thr, levels + c0 * nf * 4,
+                                   d_tab, d_thr, d_rgb + (c0 * cols + f0 * bins_z) * 3, d_lev ? d_lev + c0 * cols + f0 * bins_z : nullptr,
+                                   nb, (long long)(arows * bins_z), (long long)(nf * 4), (long long)(cols * 3), (long long)cols, st);
+        if (e != hipSuccess) fail(e, "map launch (waterfall, batch)");
+      }
+    }
+  }
+  std::vector<float> back_state(autoscale ? nstreams * 3 : 0);
+  if (rc == GLFER_OK && autoscale) {
+    e = hipMemcpyAsync(back_state.data(), d_state, nstreams * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) fail(e, "glfer_hip_waterfall_batch_device (state download)");
+  }
+  if (avg) glfer::scratch_free(avg, st);
+  if (ret) glfer::scratch_free(ret, st);
+  if (levels) glfer::scratch_free(levels, st);
+  if (!d_stats && stats) glfer::scratch_free(stats, st);
+  glfer::scratch_free(small, st);
+  e = hipStreamSynchronize(st);              // the carried states come back to the host
+  if (e != hipSuccess) fail(e, "glfer_hip_waterfall_batch_device");
+  if (rc == GLFER_OK) {
+    for (size_t b = 0; b < nstreams; b++) {
+      if (autoscale) {
+        disps[b].display_max_lvl = back_state[b * 3 + 1];
+        disps[b].display_min_lvl = back_state[b * 3 + 2];
+        disps[b].first_buffer = 0;                                             // g_main.c:1120
+      } else {
+        disps[b].display_max_lvl = mx;
+        disps[b].display_min_lvl = mn;
+      }
+    }
+  }
+  return rc;
 }
 
 size_t glfer_hip_scratch_trim(int device, size_t keep_bytes) {

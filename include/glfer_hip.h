@@ -216,7 +216,8 @@ int glfer_hip_spectrogram_device(glfer_hip_plan *plan, const void *d_stream, siz
  * takes for a stream of nstreams times the hops.  HP-ARMA, LMP and N outside 256 .. 16384 go stream by stream inside the
  * call.  The opt-in in-launch hop-means producers and the piecewise means (GLFER_MEANS_PRODUCERS, GLFER_EXACT_PIECE_MB)
  * are never taken by this entry.
- * The moving average of many streams: glfer_hip_spectrogram_avg_batch_device and glfer_hip_avg_batch_device below.
+ * The moving average of many streams: glfer_hip_spectrogram_avg_batch_device and glfer_hip_avg_batch_device below; their
+ * waterfalls: glfer_hip_waterfall_batch_device.
  * Not covered: ragged batches (one length per stream), batched host / WAV / workers entries, the F-test and
  * halfcomplex-spectrum outputs, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as they are. */
 int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams,
@@ -506,6 +507,26 @@ int glfer_hip_display_device(glfer_hip_display *disp, const float *d_psd, const 
 int glfer_hip_waterfall_device(glfer_hip_display *disp, int avg_mode, int depth, int minbin, int maxbin,
                                int max0, const float *d_psd, size_t nframes, int bins,
                                unsigned char *d_rgb, short *d_lev, float *d_stats, void *hip_stream);
+
+/* The waterfall of many independent streams in one call (a receiver per band or antenna, one display plan):
+ *   d_psd   : [nstreams][nframes][pitch] floats, pitch = disps[0].psd_pitch (0: bins) -- what
+ *             glfer_hip_spectrogram_batch_device writes
+ *   d_rgb   : [nstreams][nframes][bins][3];  d_lev: [nstreams][nframes][bins] or NULL;  d_stats: [nstreams][nframes][4] or NULL
+ *   disps   : [nstreams], stream b's carried state (first_buffer, display_max_lvl, display_min_lvl) in and out.  The options
+ *             (scale_type, autoscale, overlap, max_level_db, min_level_db, thr_level, palette, psd_pitch) must be the same in
+ *             every entry: GLFER_E_ARG otherwise, nothing launched, no state changed.
+ * Stream b's rgb, lev, stats and state are byte for byte what glfer_hip_waterfall_device gives over d_psd + b*nframes*pitch
+ * with a copy of disps[b] -- every avg_mode and max0, fused or staged average (GLFER_WATERFALL_FUSED and
+ * GLFER_WATERFALL_TILE apply as there): the route, the frame tiles and the average-in-the-map shape are chosen from ONE
+ * stream's frame count, and every launch covers the batch (the level walk, one wavefront chain per stream, blockIdx.y).  The
+ * launch count does not grow with nstreams, save chunks of 65 535 streams and, staged, groups of streams whose averaged rows
+ * stay within 4 GiB per tile.  One upload, one download of the states and one synchronisation per call.
+ * Argument rules are glfer_hip_waterfall_device's; disps NULL with nstreams > 0: GLFER_E_ARG; nstreams == 0 or
+ * nframes == 0: GLFER_OK, nothing launched.  On any error no entry of disps is modified.
+ * Not covered: per-stream options (palettes, scales), ragged batches, batched host / WAV / workers waterfalls, several GPUs. */
+int glfer_hip_waterfall_batch_device(glfer_hip_display *disps, size_t nstreams, int avg_mode, int depth, int minbin, int maxbin,
+                                     int max0, const float *d_psd, size_t nframes, int bins, unsigned char *d_rgb, short *d_lev,
+                                     float *d_stats, void *hip_stream);
 
 /* The two halves of glfer_hip_waterfall_device for a waterfall whose columns live on several GPUs
  * (or are computed piece by piece).  The level tracking of main_window_draw (g_main.c:1111-1124) is
