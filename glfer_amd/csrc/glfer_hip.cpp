@@ -2155,12 +2155,20 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t n
     p->d_ftaps = d + (size_t)2 * n;
     p->d_U0 = du;
     // the paired form's tables: two real sequences per N-point transform (re / im), each halved (X_a = (Z[k] + conj Z[N-k]) / 2)
+    // hn = sum_j U0_j v_j / sum(U0^2) has the 2-norm 1 / sqrt(sum(U0^2)) against a taper's 1: sharing a transform with taper 0 as it is,
+    // mu would come out of the separation with the rounding of a spectrum ~ sqrt(sum(U0^2)) times its size (up to 128 at N = 16384),
+    // and mu U0_j carries that into every residual.  A power of two brings hn to a taper's size; the kernel takes it out of mu again.
+    {
+      int ex = 0;
+      (void)frexpf(sqrtf(p->sum_U0_sqr), &ex);                     // sqrt(sum U0^2) = m 2^ex, 1/2 <= m < 1
+      p->hn_scale = p->sum_U0_sqr > 0.0f && ex > 0 && ex < 64 ? ldexpf(1.0f, ex - 1) : 1.0f;
+    }
     const int r_mu = (T + 2) / 2, r_nomu = (T + 1) / 2;
     std::vector<float> pt((size_t)(r_mu + r_nomu) * 2 * n, 0.0f);
     auto seq = [&](int s_, int i, bool with_mu) -> float {          // sequence s_ of the call: hn first when mu is live, then the tapers
       const int j = with_mu ? s_ - 1 : s_;
       if (j >= T) return 0.0f;
-      return 0.5f * (j < 0 ? p->hn[i] : (float)p->tapers[(size_t)j * n + i]);
+      return 0.5f * (j < 0 ? p->hn_scale * p->hn[i] : (float)p->tapers[(size_t)j * n + i]);
     };
     for (int r = 0; r < r_mu + r_nomu; r++) {
       const bool with_mu = r < r_mu;
@@ -2217,6 +2225,7 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t n
       q.ft_nseq = mu_live ? T + 1 : T;
       q.npairs = (q.ft_nseq + 1) / 2;
       q.taps = mu_live ? p->d_ftaps2 : p->d_ftaps2_nomu;
+      q.ft_mu_unscale = 1.0f / p->hn_scale;
     }
     hipError_t e = launch_packed(q, n, st);
     if (e != hipSuccess) rc = hip_fail(e, "ftest launch");

@@ -116,12 +116,13 @@ struct glfer_hip_plan {
   // harmonic F-test (mtm.c:124-136): built on first use
   float *d_ftaps_mu_first = nullptr;   // the allocation: [hn][taper 0..ntapers-1][hn], each [2n] alone in slot 0 of the packed layout
   float *d_ftaps = nullptr;         // = d_ftaps_mu_first + 2n: [ntapers+1][2n], taper j, then hn
-  float *d_ftaps2 = nullptr;        // the paired form (round 5): [ceil((ntapers+1)/2)][2n] with (hn, taper 0), (taper 1, taper 2) ... as (re, im), halved;
+  float *d_ftaps2 = nullptr;        // the paired form (round 5): [ceil((ntapers+1)/2)][2n] with (hn_scale hn, taper 0), (taper 1, taper 2) ... as (re, im), halved;
   float *d_ftaps2_nomu = nullptr;   //   then [ceil(ntapers/2)][2n] with (taper 0, taper 1) ... (mu_live = 0); one allocation
   double *d_U0 = nullptr;           // [ntapers]
   std::vector<double> U0;           // [ntapers]
   std::vector<float> hn;            // [n]
   float sum_U0_sqr = 0.0f;
+  float hn_scale = 1.0f;            // the power of two hn is multiplied by in d_ftaps2 (see SpectroParams::ft_mu_unscale)
   float spec_unscale = 1.0f;
   bool nonlin = false;
   glfer::IngestRing *ring = nullptr;   // the host entries' chunk ring, kept between calls (ingest.cpp)

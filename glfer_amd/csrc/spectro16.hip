@@ -284,9 +284,9 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(S
         constexpr int rho = decltype(rc)::value;
         if (seq >= p.ft_nseq) return;                              // (an odd number of sequences: the last table's second half is zero)
         const int jt = p.ft_mu_live ? seq - 1 : seq;               // taper of this sequence (-1: hn)
-        if (jt < 0) {
-          ftmur[rho] = xr;
-          ftmui[rho] = xi;
+        if (jt < 0) {                                              // (hn rides scaled by a power of two: SpectroParams::ft_mu_unscale)
+          ftmur[rho] = xr * p.ft_mu_unscale;
+          ftmui[rho] = xi * p.ft_mu_unscale;
           ftsum[rho] = 0.0f;
           return;
         }

@@ -50,6 +50,9 @@ struct SpectroParams {
                               (re: sequence 2r, im: sequence 2r+1, both scaled by 1/2; the sequences are hn -- when ft_mu_live --
                               then tapers 0..ntap-1), one N-point transform per pair, the two spectra separated through the
                               mirror bins (X_a = Z[k] + conj Z[N-k], X_b = (Z[k] - conj Z[N-k]) / i)                 */
+  float ft_mu_unscale;     /* the paired form: hn rides in its table times a power of two that brings it to a taper's size (hn is
+                              ~ 1/sqrt(sum U0^2) of one, and a sequence comes out of the separation with an error of an ulp of the
+                              LARGER of the pair); mu = its spectrum times this, the inverse power: exact                */
   int mean_inkernel;       /* per-hop mean removal (fft.c:86-96) inside spectro16h.hip: the stream is the RAW one;
                               only where the hop is 2, 4, 8 or 16 sixteenths of N               */
   const float *means;      /* device, optional (with mean_inkernel): means[h] = the mean of hop h of the whole stream (virtual

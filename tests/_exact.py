@@ -46,6 +46,27 @@ def periodogram64(x, n, overlap, window32, sub_mean=0, history_mode=0):
     return np.abs(np.fft.rfft(fr * np.asarray(window32, np.float64), axis=1)) ** 2 / n      # fft.c:203-226
 
 
+def ftest64(x, n, overlap, tapers, kmax, sub_mean=0, history_mode=0):
+    """The harmonic F statistic's parts as mtm.c:165-233 defines them, per frame and bin in float64:
+    (num, den, tot), each [frames][n/2+1].  num = kmax |mu|^2 sum(U0^2) with mu the spectrum of the frame under
+    hn = sum_j U0_j v_j / sum(U0^2) (mtm.c:76-83, 124-136, 165-174), den = sum_j |y_j - mu U0_j|^2 (mtm.c:203-210; the
+    reference never accumulates it at Nyquist, here it is the plain sum there too), tot = sum_j |y_j|^2."""
+    fr = frames64(x, n, overlap, sub_mean, history_mode)
+    v = np.asarray(tapers, np.float64)[:kmax + 1]
+    U0 = v.sum(axis=1)
+    s2 = (U0 * U0).sum()
+    hn = (U0[:, None] * v).sum(axis=0) / s2
+    mu = np.fft.rfft(fr * hn, axis=1)
+    num = kmax * np.abs(mu) ** 2 * s2
+    den = np.zeros_like(num)
+    tot = np.zeros_like(num)
+    for j in range(kmax + 1):
+        y = np.fft.rfft(fr * v[j], axis=1)
+        den += np.abs(y - mu * U0[j]) ** 2
+        tot += np.abs(y) ** 2
+    return num, den, tot
+
+
 def multitaper64(x, n, overlap, tapers, sig, sub_mean=0, history_mode=0):
     fr = frames64(x, n, overlap, sub_mean, history_mode)
     out = np.zeros((fr.shape[0], n // 2 + 1))
