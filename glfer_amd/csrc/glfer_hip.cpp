@@ -375,6 +375,53 @@ static size_t tap_slot(int n, int pair, int i, int which) {
   return (size_t)pair * n * 2 + ((size_t)(m / 2) * T + t) * 4 + (size_t)(m & 1) * 2 + which;
 }
 
+// spectro16y.hip's half-table form (five tapers at N = 4096): what a lane keeps in registers, from the tables the plan
+// builds for the full-table form -- taps (the two pairs, tap_slot layout) and xtaps (the last taper, [4][n/16][4]).
+// DPSS tapers are symmetric (even order) or antisymmetric (odd order) about the frame centre; the half table is built only
+// if the SCALED FLOATS have that symmetry exactly (a == b, a == -b as float comparisons: a zero of either sign gives a
+// product that is a zero either way, and no sum or power can tell them apart), because rows from half tables must be the
+// full-table form's rows bit for bit.  Layout: spectro_params.h, glfer_yhalf_residue().  false: `half` is left alone.
+static bool build_y_half_table(int n, const float *taps, const float *xtaps, float *half) {
+  if (n != 4096) return false;
+  const int T = n / 16;
+  auto last = [&](int i) { return xtaps[((size_t)((i / T) / 4) * T + (size_t)(i % T)) * 4 + (size_t)((i / T) & 3)]; };
+  for (int i = 0; i < n / 2; i++) {
+    for (int j = 0; j < 4; j++) {
+      const float a = taps[tap_slot(n, j / 2, i, j & 1)], b = taps[tap_slot(n, j / 2, n - 1 - i, j & 1)];
+      if (!((j & 1) ? b == -a : b == a)) return false;
+    }
+    if (!(last(n - 1 - i) == last(i))) return false;
+  }
+  for (int t = 0; t < T; t++) {
+    const int r = (int)glfer_yhalf_residue((unsigned)t);
+    float *row = half + (size_t)t * GLFER_YHALF_FLOATS;
+    for (int m = 0; m < 8; m++) {
+      for (int j = 0; j < 4; j++) row[16 * (j / 2) + 2 * m + (j & 1)] = taps[tap_slot(n, j / 2, r + T * m, j & 1)];
+      row[32 + m] = last(r + T * m);
+    }
+  }
+  return true;
+}
+
+// The scaled float tables of a multitaper plan with an odd taper count: the pairs (taps, tap_slot layout:
+// psd += |FFT(v_j x)|^2 / N / (1+sig_j), mtm.c:212-219, and the 1/2 of the packing) and the last taper alone (xtaps,
+// [4][n/16][4]; |Y|^2 = |E|^2/4 in the shared transform, so its scale carries 1/4 instead of 1/2).
+static void mtm_pair_tables(int n, int ntapers, const double *tapers, const double *sig, float *taps) {
+  for (int j = 0; j < ntapers; j++) {
+    const double scale = std::sqrt(1.0 / (2.0 * n * (1.0 + sig[j])));
+    for (int i = 0; i < n; i++)
+      taps[tap_slot(n, j / 2, i, j & 1)] = (float)(tapers[(size_t)j * n + i] * scale);
+  }
+}
+static void mtm_last_table(int n, int ntapers, const double *tapers, const double *sig, float *xtaps) {
+  const int T = n / 16, j = ntapers - 1;
+  const double scale = std::sqrt(1.0 / (4.0 * n * (1.0 + sig[j])));
+  for (int i = 0; i < n; i++) {
+    const int t = i % T, m = i / T;
+    xtaps[((size_t)(m / 4) * T + t) * 4 + (size_t)(m & 3)] = (float)(tapers[(size_t)j * n + i] * scale);
+  }
+}
+
 extern "C" {
 
 const char *glfer_hip_version(void) { return "glfer_hip 0.9 (gfx950; 16 points/lane Stockham radix-16 with LDS exchange, inter-pass twiddles folded into the butterflies: packed pairs, real-input and wavefront-private forms, shared odd taper, register reuse across overlapped frames, mean removal in the reference's summation order (cfg.sub_mean = 1) or inside the kernels; N = 8..1048576; periodogram, multitaper + F-test, HP-ARMA with column-disjoint Jacobi rotations side by side and frames from a queue, LMP; rows at a caller's pitch; wavefront floor, fused average, display map with the average taken inside it; chunk ring for ingest with uploads and downloads at once, WAV files and waterfalls over several GPUs, read-ahead behind the per-hop shim, kept scratch blocks with a cap, workers bound to their GPU's NUMA node)"; }
@@ -992,12 +1039,7 @@ int glfer_hip_plan_create(const glfer_hip_config *cfg, glfer_hip_plan **out) {
       }
     }
     taps.assign((size_t)2 * p->npairs * n, 0.0f);
-    for (int j = 0; j < p->ntapers && !huge; j++) {
-      // psd += |FFT(v_j x)|^2 / N / (1+sig_j)   (mtm.c:212-219), and the 1/2 of the packing
-      const double scale = std::sqrt(1.0 / (2.0 * n * (1.0 + p->sig[j])));
-      for (int i = 0; i < n; i++)
-        taps[tap_slot(n, j / 2, i, j & 1)] = (float)(p->tapers[(size_t)j * n + i] * scale);
-    }
+    if (!huge) mtm_pair_tables(n, p->ntapers, p->tapers.data(), p->sig.data(), taps.data());
     p->spec_unscale = 1.0f;
   }
   int logn = 0;
@@ -1086,13 +1128,16 @@ int glfer_hip_plan_create(const glfer_hip_config *cfg, glfer_hip_plan **out) {
   // |Y|^2 = |E|^2/4 there (no mirror-sum doubling), so its scale carries 1/4 instead of 1/2
   std::vector<float> xtaps;
   if (cfg->mode == GLFER_MODE_MTM && (p->ntapers & 1) && p->ntapers >= 3 && !small && !huge) {
-    const int T = n / 16, j = p->ntapers - 1;
-    const double scale = std::sqrt(1.0 / (4.0 * n * (1.0 + p->sig[j])));
     xtaps.resize((size_t)n);
-    for (int i = 0; i < n; i++) {
-      const int t = i % T, m = i / T;
-      xtaps[((size_t)(m / 4) * T + t) * 4 + (size_t)(m & 3)] = (float)(p->tapers[(size_t)j * n + i] * scale);
-    }
+    mtm_last_table(n, p->ntapers, p->tapers.data(), p->sig.data(), xtaps.data());
+  }
+
+  // --- five tapers at N = 4096 (spectro16y.hip): the half tables a lane keeps in registers, where the float tables are
+  // exactly (anti)symmetric; otherwise (and for every other taper count) the plan keeps the full-table form
+  std::vector<float> ytaps;
+  if (!xtaps.empty() && n == 4096 && p->ntapers == 5) {
+    ytaps.resize((size_t)(n / 16) * GLFER_YHALF_FLOATS);
+    if (!build_y_half_table(n, taps.data(), xtaps.data(), ytaps.data())) ytaps.clear();
   }
 
   // --- the same, with half tables that stay in LDS (spectro16xl.hip): DPSS tapers are symmetric
@@ -1243,6 +1288,10 @@ int glfer_hip_plan_create(const glfer_hip_config *cfg, glfer_hip_plan **out) {
     e = hipMalloc((void **)&p->d_xtaps, xtaps.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(p->d_xtaps, xtaps.data(), xtaps.size() * sizeof(float), hipMemcpyHostToDevice);
   }
+  if (e == hipSuccess && !ytaps.empty()) {
+    e = hipMalloc((void **)&p->d_ytaps, ytaps.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(p->d_ytaps, ytaps.data(), ytaps.size() * sizeof(float), hipMemcpyHostToDevice);
+  }
   if (e == hipSuccess && !ltaps.empty()) {
     e = hipMalloc((void **)&p->d_ltaps, ltaps.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(p->d_ltaps, ltaps.data(), ltaps.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -1285,6 +1334,7 @@ void glfer_hip_plan_destroy(glfer_hip_plan *p) {
   if (p->d_wcomb) (void)hipFree(p->d_wcomb);
   if (p->d_bigtw) (void)hipFree(p->d_bigtw);
   if (p->d_ltaps) (void)hipFree(p->d_ltaps);
+  if (p->d_ytaps) (void)hipFree(p->d_ytaps);
   if (p->d_lagmap) (void)hipFree(p->d_lagmap);
   if (p->d_rot_sched) (void)hipFree(p->d_rot_sched);
   if (p->d_unit) (void)hipFree(p->d_unit);
@@ -1319,6 +1369,19 @@ int glfer_hip_make_window(int window_type, int n, float *window) {
   if (!window || n < 2 || window_type < 0 || window_type > 7) return GLFER_E_ARG;
   glfer::make_window(window_type, n, window);
   return GLFER_OK;
+}
+
+int glfer_hip_y_half_tables(int n, int kmax, double nw, float *half, float *pairs, float *last) {
+  if (!half || n != 4096 || kmax != 4 || !(nw > 0.0)) return GLFER_E_ARG;
+  const int nt = kmax + 1;
+  std::vector<double> tapers((size_t)nt * n), sig(nt);
+  if (!glfer::make_dpss(n, kmax, nw, tapers.data(), sig.data())) return GLFER_E_NUMERIC;
+  std::vector<float> taps((size_t)2 * ((nt + 1) / 2) * n, 0.0f), xtaps((size_t)n);
+  mtm_pair_tables(n, nt, tapers.data(), sig.data(), taps.data());
+  mtm_last_table(n, nt, tapers.data(), sig.data(), xtaps.data());
+  if (pairs) memcpy(pairs, taps.data(), (size_t)4 * n * sizeof(float));
+  if (last) memcpy(last, xtaps.data(), (size_t)n * sizeof(float));
+  return build_y_half_table(n, taps.data(), xtaps.data(), half) ? 1 : 0;
 }
 
 int glfer_hip_make_dpss(int n, int kmax, double nw, double *tapers, double *sig) {
@@ -1388,8 +1451,22 @@ static int form_override() {
   return e && *e ? (int)*e : 0;
 }
 
+// GLFER_Y_TAPERS=full in the environment: spectro16y.hip keeps its full-table form where the plan has half tables (same-box
+// A/B runs and the tests that compare the two forms' rows; read per launch like GLFER_FORM)
+static bool y_full_tables_forced() {
+  const char *e = getenv("GLFER_Y_TAPERS");
+  return e && !strcmp(e, "full");
+}
+
 static hipError_t launch_shared_odd(const SpectroParams &sp, int n, hipStream_t st) {
-  if (n == 4096) return glfer_launch_spectro16y_n12(&sp, st);   // two frames interleaved per wavefront
+  if (n == 4096) {                     // two frames interleaved per wavefront
+    if (sp.ytaps && y_full_tables_forced()) {
+      SpectroParams q = sp;
+      q.ytaps = nullptr;
+      return glfer_launch_spectro16y_n12(&q, st);
+    }
+    return glfer_launch_spectro16y_n12(&sp, st);
+  }
   if (sp.ltaps) {                      // taper half tables resident in LDS
     switch (n) {
       case 256: return glfer_launch_spectro16xl_n8(&sp, st);
@@ -1537,6 +1614,7 @@ static void fill_params(const glfer_hip_plan *p, SpectroParams &sp) {
   sp.hrot = p->d_hrot;
   sp.xtaps = p->d_xtaps;
   sp.ltaps = p->d_ltaps;
+  sp.ytaps = p->d_ytaps;
   sp.wtaps = p->d_wtaps;
   sp.wtapers = p->wtapers;
   sp.wtw = p->d_wtw;
@@ -2196,7 +2274,7 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t n
   sp.nonlin = 0;
   sp.post_scale = sp.spec_unscale = 1.0f;
   sp.htaps = nullptr;                    // the packed kernel: it is the one with the spectrum output
-  sp.xtaps = sp.ltaps = nullptr;
+  sp.xtaps = sp.ltaps = sp.ytaps = nullptr;
   float *scratch = nullptr;
   int rc = GLFER_OK;
   if (p->cfg.sub_mean) {

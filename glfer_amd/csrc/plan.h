@@ -109,6 +109,7 @@ struct glfer_hip_plan {
   float2 *d_bigtw = nullptr;        // spectro_big.hip (N >= 32768): [W][16] the register part of the sub-transforms' twiddles
   float *d_xtaps = nullptr;         // odd taper counts (spectro16x.hip): the last taper alone, [4][n/16][4]
   float *d_ltaps = nullptr;         // odd taper counts, LDS-resident half tables (spectro16xl.hip)
+  float *d_ytaps = nullptr;         // five tapers at N = 4096, register-resident half tables (spectro16y.hip); NULL: not exactly symmetric
   uint16_t *d_lagmap = nullptr;     // HP-ARMA: [t][p_e+1] lag held by each matrix cell
   int *d_rot_sched = nullptr;       // HP-ARMA: [rot_steps][8] the Jacobi sweep as steps of up to eight column-disjoint rotations (j | k << 8, -1 = none)
   int rot_steps = 0, rot_width = 8;

@@ -13,6 +13,17 @@
 // 30 twiddles -- 256 VGPRs, 2 blocks (8 wavefronts) per CU, two 35 KB exchange buffers per block.
 // Per frame the arithmetic is exactly spectro16x.hip's (same pairing, same scales), so the rows are
 // bit-identical to it.
+//
+// HALF (five tapers, no in-kernel mean): the taper tables stay in registers as mirror-symmetric half tables.  DPSS tapers
+// satisfy v_k[N-1-n] = (-1)^k v_k[n], and the plan's scaled float tables keep that to the bit (glfer_hip.cpp builds the
+// half table only then).  In pass 0 lane t takes the samples r + 256 m of residue r = glfer_yhalf_residue(t) instead of
+// r = t: residues r and 255 - r then sit at mirrored positions of one 16-lane DPP row, so for m >= 8 a lane's taper value
+// is +- its row_mirror partner's value at 15 - m, taken as the DPP operand of the multiply itself.  A lane keeps m = 0..7
+// of every taper, 40 floats loaded once per workgroup, and the steady-state loop has no table loads left (they were L2
+// hits that queued behind other wavefronts' HBM misses on the CU's in-order return path: profiles/y_half_tapers.txt).
+// The permutation touches the sample gather and the column of the first exchange's writes only; what every lane reads
+// back from that exchange, and everything after it, is unchanged, and per frame the same operations meet the same values
+// in the same order: the rows are bit-identical to the full-table form's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "odd_taper.hpp"
@@ -23,6 +34,10 @@
 #ifndef GLFER16Y_SKEW
 #define GLFER16Y_SKEW 1           /* stockham16_passes2s: frame B's exchange reads and the buffer-release barrier under frame A's arithmetic (+1.5 %,
                                      profiles/r03_y_skew.txt); 2: the shared round's barrier in front of its last stage too (stockham16_passes1s) */
+#endif
+#ifndef GLFER16Y_HALF
+#define GLFER16Y_HALF 1           /* the half-table form where the plan has the table (0: every plan keeps the full-table form);
+                                     1: all 40 floats resident, 2: the pairs' 32 resident, the last taper's 8 loaded per iteration */
 #endif
 #ifndef GLFER16Y_TW1_REGS
 #define GLFER16Y_TW1_REGS 1       /* the lane's 15 pass-1 twiddles in registers instead of 15 LDS reads per transform (where they fit without a spill:
@@ -46,12 +61,14 @@ struct LaunchY {
 // butterfly over the wavefront, the four wavefronts through LDS across the barriers that end the
 // shared round), and x - mu is formed once, before the frames' first round.  A hop's mean comes from
 // the same lanes' same registers in the same order whichever frame it is seen in.
-template <int FMT, int ABL = 0, int HIST = 0, int KM = 0, int BAT = 0>
+template <int FMT, int ABL = 0, int HIST = 0, int KM = 0, int BAT = 0, int HALF = 0>
 __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
   // the stream of the batch (blockIdx.y; 0 outside a batch); the mean forms only in their batch instantiations (BAT), so that the
   // single-stream ones keep their registers
   if constexpr (KM == 0 || BAT != 0) glfer_batch_select(p);
   static_assert(KM == 0 || (HIST == 0 && (KM == 16 || KM == 8 || KM == 4)), "in-kernel mean removal: history from the stream");
+  // (the hop sums of the mean forms reduce across lanes in lane order: a lane permutation would change their bits)
+  static_assert(HALF == 0 || (KM == 0 && GLFER16_X0_ROWS != 0 && GLFER16_BARRIER_AFTER_READS != 0), "half tables: the plain forms, row layout of exchange 0");
   constexpr int NH = KM > 0 ? 16 / KM : 1;
   __shared__ float mred[KM > 0 ? 4 * (NH + 1) : 1];
   using C = Plan16<12>;
@@ -64,6 +81,7 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
   extern __shared__ v2f32 lds[];                    // L::LDS_WORDS entries (72 KB: above the static limit)
 
   const unsigned t = threadIdx.x;
+  const unsigned rc = HALF ? glfer_yhalf_residue(t) : t;   // the lane's residue in pass 0: samples rc + T*m, column rc of exchange 0
   v2f32 *xbA = lds, *xbB = lds + PADN;
   v2f32 *tw1 = lds + 2 * PADN;
   float *red = reinterpret_cast<float *>(lds + 2 * PADN + 16 * 17);   // [2][4]
@@ -103,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
   // (loads are unconditional -- a frame index past the end re-reads the last frame -- so that the
   // compiler has nothing to turn into selects; what such a slot computes is dropped)
   auto load_x = [&](float (&dst)[16], long long f) {
-    load_frame16<FMT, T, HIST>(p, t, 0u, f < p.nframes ? f : (long long)p.nframes - 1, dst);
+    load_frame16<FMT, T, HIST>(p, rc, 0u, f < p.nframes ? f : (long long)p.nframes - 1, dst);
   };
   v2f32 pt[16];          // full round: the next taper pair; shared round: pt[0..7] = the last taper
   auto prefetch_taps = [&](int pair) {
@@ -124,6 +142,42 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
     });
   };
 
+  // HALF: [lane][40] floats = pair 0 (m = 0..7 as (even, odd) taper), pair 1, the last taper
+  v2f32 hp[16];
+  float hl[8];
+  const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float *>(p.ytaps), 0, HALF ? T * GLFER_YHALF_FLOATS * 4 : 0, 0x00020000);
+  const unsigned yoff = t * (unsigned)(GLFER_YHALF_FLOATS * 4);
+  auto load_half_last = [&] {
+    static_for<0, 2>([&](auto cc) {
+      constexpr int c = decltype(cc)::value;
+      const v4f32 q = __builtin_bit_cast(v4f32, __builtin_amdgcn_raw_buffer_load_b128(yrsrc, yoff, 128u + c * 16u, 0));
+      hl[4 * c] = q.x;
+      hl[4 * c + 1] = q.y;
+      hl[4 * c + 2] = q.z;
+      hl[4 * c + 3] = q.w;
+    });
+  };
+  if constexpr (HALF != 0) {
+    static_for<0, 8>([&](auto cc) {
+      constexpr int c = decltype(cc)::value;
+      const v4f32 q = __builtin_bit_cast(v4f32, __builtin_amdgcn_raw_buffer_load_b128(yrsrc, yoff, c * 16u, 0));
+      hp[2 * c] = v2f32{q.x, q.y};
+      hp[2 * c + 1] = v2f32{q.z, q.w};
+    });
+    if constexpr (HALF == 1) load_half_last();
+  }
+  // the row_mirror partner's value (lane t ^ 15: residue 255 - rc); all lanes are active wherever this is used
+  auto mirror = [](float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, true));
+  };
+  // taper pair P at register m: (v_2P, v_2P+1)[rc + T*m]; the upper half from the partner, the odd taper negated
+  auto half_pair = [&](auto pc, auto mc) {
+    constexpr int P = decltype(pc)::value, m = decltype(mc)::value;
+    if constexpr (m < 8) return hp[P * 8 + m];
+    else return v2f32{mirror(hp[P * 8 + 15 - m].x), -mirror(hp[P * 8 + 15 - m].y)};
+  };
+
   long long fA = (long long)xcd_block_index() * 2;
   if (fA >= p.nframes) return;
   float xA[16], xB[16];
@@ -133,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
 #pragma unroll
     for (int m = 0; m < 16; m++) xB[m] = 0.0f;
   }
-  prefetch_taps(0);
+  if constexpr (HALF == 0) prefetch_taps(0);
 
   // ---- KM: the hop sums of frames A (NH hops) and B (its newest hop), wavefront-reduced, into mred
   auto publish_hop_sums = [&] {
@@ -202,6 +256,41 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
       float accA[16], accB[16];
 #pragma unroll
       for (int r = 0; r < 16; r++) accA[r] = accB[r] = 0.0f;     // (dead when NP >= 1: pair 0 overwrites)
+      if constexpr (HALF != 0) {
+        // ---- five tapers: the two full rounds written out, their tables in registers (same operations as the loop below)
+        static_for<0, 2>([&](auto pc) {
+          constexpr int P = decltype(pc)::value;
+          float zrA[16], ziA[16], zrB[16], ziB[16];
+          GLFER_STAMP(0);                            // dual round start
+          static_for<0, 16>([&](auto mc) {
+            constexpr int m = decltype(mc)::value;
+            const v2f32 w = half_pair(pc, mc);
+            zrA[m] = xA[m] * w.x;
+            ziA[m] = xA[m] * w.y;
+            zrB[m] = xB[m] * w.x;
+            ziB[m] = xB[m] * w.y;
+          });
+          auto dual = [&](const auto &tw1sel) {
+            auto hook = [] {};
+            if constexpr (GLFER16Y_SKEW != 0) stockham16_passes2s<12, NT>(zrA, ziA, xbA, zrB, ziB, xbB, t, rc, tw1sel, twr, twi, hook);
+            else stockham16_passes2<12, NT>(zrA, ziA, xbA, zrB, ziB, xbB, t, rc, tw1sel, twr, twi, hook);
+          };
+          if constexpr (TW1R) dual(tw1reg);
+          else dual(tw1row);
+#pragma unroll
+          for (int r = 0; r < 16; r++) {
+            if constexpr (P == 0) {                  // the first pair starts the sums (no zeroing pass)
+              accA[r] = __builtin_fmaf(zrA[r], zrA[r], ziA[r] * ziA[r]);
+              accB[r] = __builtin_fmaf(zrB[r], zrB[r], ziB[r] * ziB[r]);
+            } else {
+              accA[r] = __builtin_fmaf(zrA[r], zrA[r], __builtin_fmaf(ziA[r], ziA[r], accA[r]));
+              accB[r] = __builtin_fmaf(zrB[r], zrB[r], __builtin_fmaf(ziB[r], ziB[r], accB[r]));
+            }
+          }
+          GLFER_STAMP(15);                           // dual round end
+        });
+        if constexpr (HALF == 2) load_half_last();   // (the transform registers are dead here)
+      } else
       for (int pair = 0; pair < NP; pair++) {
         // ---- one full round of both frames: re = x*taper(2*pair), im = x*taper(2*pair+1)
         float zrA[16], ziA[16], zrB[16], ziB[16];
@@ -291,7 +380,7 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
 
     if constexpr (ABL == 1) {
       if (has_next) {
-        prefetch_taps(0);
+        if constexpr (HALF == 0) prefetch_taps(0);
         load_x(xA, nfA);
         load_x(xB, nfA + 1);
       }
@@ -305,24 +394,35 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
     GLFER_STAMP(0);                                  // shared round start
     {
       const float sA = scale_in(hxA), sB = scale_in(hxB);
+      if constexpr (HALF != 0) {
+        static_for<0, 16>([&](auto mc) {             // (the last of five tapers has even order: no sign)
+          constexpr int m = decltype(mc)::value;
+          float v;
+          if constexpr (m < 8) v = hl[m];
+          else v = mirror(hl[15 - m]);
+          zr[m] = (xA[m] * v) * sA;
+          zi[m] = (xB[m] * v) * sB;
+        });
+      } else {
 #pragma unroll
-      for (int m = 0; m < 16; m++) {
-        const float v = (m & 1) ? pt[m / 2].y : pt[m / 2].x;
-        zr[m] = (xA[m] * v) * sA;
-        zi[m] = (xB[m] * v) * sB;                    // no frame B: xB is all zeros (set below)
+        for (int m = 0; m < 16; m++) {
+          const float v = (m & 1) ? pt[m / 2].y : pt[m / 2].x;
+          zr[m] = (xA[m] * v) * sA;
+          zi[m] = (xB[m] * v) * sB;                  // no frame B: xB is all zeros (set below)
+        }
       }
     }
     // the next iteration's samples and first taper pair go out after the first exchange's writes
     auto shared_round = [&](const auto &tw1sel) {
       auto hook = [&] {
         if (has_next) {
-          prefetch_taps(0);
+          if constexpr (HALF == 0) prefetch_taps(0);
           load_x(xA, nfA);
           load_x(xB, nfA + 1);
         }
       };
-      if constexpr (GLFER16Y_SKEW >= 2) stockham16_passes1s<12, NT>(zr, zi, xbA, t, tw1sel, twr, twi, hook);
-      else stockham16_passes<12, NT>(zr, zi, xbA, t, tw1sel, twr, twi, hook);
+      if constexpr (GLFER16Y_SKEW >= 2) stockham16_passes1s<12, NT>(zr, zi, xbA, t, rc, tw1sel, twr, twi, hook);
+      else stockham16_passes<12, NT>(zr, zi, xbA, t, rc, tw1sel, twr, twi, hook);
     };
     if constexpr (TW1R) shared_round(tw1reg);
     else shared_round(tw1row);
@@ -384,6 +484,18 @@ static hipError_t launch16y_fmt(const SpectroParams &p, hipStream_t st) {
     if (km == 4) GLFER_Y_MEAN(4);
 #undef GLFER_Y_MEAN
     return hipErrorInvalidValue;
+  }
+  if (GLFER16Y_HALF != 0 && p.ytaps && p.npairs == 3) {   // five tapers, exactly (anti)symmetric tables: the half-table form
+#define GLFER_Y_HALF(HIST)                                                                                           \
+  do {                                                                                                               \
+    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, HIST, 0, 0, GLFER16Y_HALF>), shmem); \
+    if (e != hipSuccess) return e;                                                                                   \
+    hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, HIST, 0, 0, GLFER16Y_HALF>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p); \
+    return hipGetLastError();                                                                                        \
+  } while (0)
+    if (p.history_mode) GLFER_Y_HALF(1);
+    else GLFER_Y_HALF(0);
+#undef GLFER_Y_HALF
   }
   if (p.history_mode) hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p);
   else hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p);

@@ -37,6 +37,8 @@ struct SpectroParams {
   const float *xtaps;      /* device: [4][N/16][4] last taper, sqrt(1/(4N(1+sig))) folded               */
   /* odd taper counts with LDS-resident half tables, spectro16xl.hip; NULL when not built */
   const float *ltaps;      /* device: [npairs-1][8][N/16][2] pair halves, then [8][N/16] the last taper */
+  /* five tapers at N = 4096, spectro16y.hip's half-table form: the tables a lane keeps in registers; NULL when not built */
+  const float *ytaps;      /* device: [256][GLFER_YHALF_FLOATS], see glfer_yhalf_residue()                */
   float *psd;              /* device: [nframes][pitch], the first N/2+1 floats of a row are its bins */
   int pitch;               /* floats from one PSD row to the next (cfg.psd_pitch; N/2+1 = dense)      */
   float *spec;             /* device, optional: [nframes][N] halfcomplex spectrum            */
@@ -95,6 +97,18 @@ struct SpectroParams {
   long long avg_batch_stride;   /* doubles from one stream's first averaged row (avg) to the next one's                        */
   long long avg_ret_batch_stride;   /* doubles from one stream's first return values (avg_ret) to the next one's               */
 };
+
+/* spectro16y.hip's half-table form (N = 4096, T = 256 lanes, five tapers).  In pass 0 lane t = 16 j + p holds the samples
+   r + 256 m of residue r = glfer_yhalf_residue(t), so that residues r and 255 - r sit at mirrored positions of one 16-lane
+   row: glfer_yhalf_residue(t ^ 15) = 255 - glfer_yhalf_residue(t).  Sample (r, m) mirrors to (255 - r, 15 - m) about the
+   frame centre, so a lane keeps m = 0..7 only and takes m >= 8 from lane t ^ 15 at 15 - m, with the taper's parity as sign.
+   ytaps[t][e]: e = 16 P + 2 m + k for taper 2 P + k of pair P = 0, 1 at m = 0..7
+   (scale sqrt(1/(2N(1+sig)))), e = 32 + m for the last taper (scale sqrt(1/(4N(1+sig)))). */
+enum { GLFER_YHALF_FLOATS = 40 };
+static inline __host__ __device__ unsigned glfer_yhalf_residue(unsigned t) {
+  const unsigned j = t >> 4, p = t & 15u;
+  return p < 8u ? 8u * j + p : 240u - 8u * j + p;
+}
 
 /* A launcher's persistent grid for a batch: `cap` workgroups for the whole launch, shared among its streams, so that
    gridDim.x x nbatch stays near the single-stream cap.  The caller keeps gridDim.x a multiple of 8 once it is >= 64

@@ -234,7 +234,7 @@ struct PassTwiddles {
 // lane's later-pass twiddles.  after_first_write() runs between the first exchange's writes
 // and its barrier: the place where the next round's global loads are issued.
 template <int LOGM, int NT, class Tw1, class Hook>
-__device__ __forceinline__ void stockham16_passes(float (&zr)[16], float (&zi)[16], v2f32 *xb, unsigned t,
+__device__ __forceinline__ void stockham16_passes(float (&zr)[16], float (&zi)[16], v2f32 *xb, unsigned t, unsigned col0,
                                                   const Tw1 &tw1row, const float (&twr)[NT],
                                                   const float (&twi)[NT], Hook &&after_first_write) {
   using C = Plan16<LOGM>;
@@ -273,7 +273,7 @@ __device__ __forceinline__ void stockham16_passes(float (&zr)[16], float (&zi)[1
       const int k = (int)t & (Ls - 1);
       const int a0 = ((int)t - k) * R + k;
       constexpr bool kRows = GLFER16_X0_ROWS != 0 && i == 0 && T >= 32;
-      v2f32 *wbase = kRows ? xb + t : xb + a0 + (a0 >> xpad_shift(i));
+      v2f32 *wbase = kRows ? xb + col0 : xb + a0 + (a0 >> xpad_shift(i));
       if constexpr (kFold) dit_head_tw<R, 1, 0, 16>(zr, zi, twf);
       else dit_head<R, 1, 0, 16>(zr, zi);
       dit_tail<R, 1, 0, 16>(zr, zi, [&](auto qc, auto rc) {
@@ -361,7 +361,7 @@ __device__ __forceinline__ void stockham16_passes(float (&zr)[16], float (&zi)[1
 // lane's own registers (const v2f32 (&)[16]: GLFER16Y_TW1_REGS)
 template <int LOGM, int NT, class Tw1, class Hook>
 __device__ __forceinline__ void stockham16_passes2(float (&zrA)[16], float (&ziA)[16], v2f32 *xbA, float (&zrB)[16],
-                                                   float (&ziB)[16], v2f32 *xbB, unsigned t, const Tw1 &tw1row,
+                                                   float (&ziB)[16], v2f32 *xbB, unsigned t, unsigned col0, const Tw1 &tw1row,
                                                    const float (&twr)[NT], const float (&twi)[NT],
                                                    Hook &&after_first_write) {
   using C = Plan16<LOGM>;
@@ -400,7 +400,7 @@ __device__ __forceinline__ void stockham16_passes2(float (&zrA)[16], float (&ziA
         const int k = (int)t & (Ls - 1);
         const int a0 = ((int)t - k) * R + k;
         constexpr bool kRows = GLFER16_X0_ROWS != 0 && i == 0 && T >= 32;
-        v2f32 *wbase = kRows ? xb + t : xb + a0 + (a0 >> xpad_shift(i));
+        v2f32 *wbase = kRows ? xb + col0 : xb + a0 + (a0 >> xpad_shift(i));
         if constexpr (kFold) dit_head_tw<R, 1, 0, 16>(zr, zi, twf);
         else dit_head<R, 1, 0, 16>(zr, zi);
         dit_tail<R, 1, 0, 16>(zr, zi, [&](auto qc, auto rc) {
@@ -481,7 +481,7 @@ __device__ __forceinline__ void stockham16_passes2(float (&zrA)[16], float (&ziA
 // the operations and their order are those of stockham16_passes2: bit-identical results.  Radix-16 passes only.
 template <int LOGM, int NT, class Tw1, class Hook>
 __device__ __forceinline__ void stockham16_passes2s(float (&zrA)[16], float (&ziA)[16], v2f32 *xbA, float (&zrB)[16],
-                                                    float (&ziB)[16], v2f32 *xbB, unsigned t, const Tw1 &tw1row,
+                                                    float (&ziB)[16], v2f32 *xbB, unsigned t, unsigned col0, const Tw1 &tw1row,
                                                     const float (&twr)[NT], const float (&twi)[NT],
                                                     Hook &&after_first_write) {
   using C = Plan16<LOGM>;
@@ -521,7 +521,7 @@ __device__ __forceinline__ void stockham16_passes2s(float (&zrA)[16], float (&zi
         const int k = (int)t & (Ls - 1);
         const int a0 = ((int)t - k) * R + k;
         constexpr bool kRows = i == 0;
-        v2f32 *wbase = kRows ? xb + t : xb + a0 + (a0 >> xpad_shift(i));
+        v2f32 *wbase = kRows ? xb + col0 : xb + a0 + (a0 >> xpad_shift(i));
         dit_tail<R, 1, 0, 16>(zr, zi, [&](auto qc, auto rc) {
           constexpr int q = decltype(qc)::value, reg = decltype(rc)::value;
           wbase[kRows ? q * (T + 2) : xpad_offset(i, q * Ls)] = v2f32{zr[reg], zi[reg]};
@@ -582,7 +582,7 @@ __device__ __forceinline__ void stockham16_passes2s(float (&zrA)[16], float (&zi
 // stockham16_passes2s: the reads cannot hide under anything, but every wavefront reaches the barrier with its arithmetic
 // done).  Same operations in the same order as stockham16_passes.  Radix-16 passes only.
 template <int LOGM, int NT, class Tw1, class Hook>
-__device__ __forceinline__ void stockham16_passes1s(float (&zr)[16], float (&zi)[16], v2f32 *xb, unsigned t, const Tw1 &tw1row,
+__device__ __forceinline__ void stockham16_passes1s(float (&zr)[16], float (&zi)[16], v2f32 *xb, unsigned t, unsigned col0, const Tw1 &tw1row,
                                                     const float (&twr)[NT], const float (&twi)[NT], Hook &&after_first_write) {
   using C = Plan16<LOGM>;
   constexpr int T = C::T, NPASS = C::NPASS, TW1 = 15;
@@ -596,7 +596,7 @@ __device__ __forceinline__ void stockham16_passes1s(float (&zr)[16], float (&zi)
         const int k = (int)t & (Ls - 1);
         const int a0 = ((int)t - k) * R + k;
         constexpr bool kRows = i == 0;
-        v2f32 *wbase = kRows ? xb + t : xb + a0 + (a0 >> xpad_shift(i));
+        v2f32 *wbase = kRows ? xb + col0 : xb + a0 + (a0 >> xpad_shift(i));
         dit_tail<R, 1, 0, 16>(zr, zi, [&](auto qc, auto rc) {
           constexpr int q = decltype(qc)::value, reg = decltype(rc)::value;
           wbase[kRows ? q * (T + 2) : xpad_offset(i, q * Ls)] = v2f32{zr[reg], zi[reg]};
@@ -656,6 +656,31 @@ __device__ __forceinline__ void stockham16_passes1s(float (&zr)[16], float (&zi)
       }
     }
   });
+}
+
+// The forms above with the lane's exchange-0 column equal to its index: every caller but spectro16y.hip's half-table form,
+// whose lanes take their pass-0 residues in another order (see there).
+template <int LOGM, int NT, class Tw1, class Hook>
+__device__ __forceinline__ void stockham16_passes(float (&zr)[16], float (&zi)[16], v2f32 *xb, unsigned t, const Tw1 &tw1row,
+                                                  const float (&twr)[NT], const float (&twi)[NT], Hook &&after_first_write) {
+  stockham16_passes<LOGM, NT>(zr, zi, xb, t, t, tw1row, twr, twi, after_first_write);
+}
+template <int LOGM, int NT, class Tw1, class Hook>
+__device__ __forceinline__ void stockham16_passes1s(float (&zr)[16], float (&zi)[16], v2f32 *xb, unsigned t, const Tw1 &tw1row,
+                                                    const float (&twr)[NT], const float (&twi)[NT], Hook &&after_first_write) {
+  stockham16_passes1s<LOGM, NT>(zr, zi, xb, t, t, tw1row, twr, twi, after_first_write);
+}
+template <int LOGM, int NT, class Tw1, class Hook>
+__device__ __forceinline__ void stockham16_passes2(float (&zrA)[16], float (&ziA)[16], v2f32 *xbA, float (&zrB)[16],
+                                                   float (&ziB)[16], v2f32 *xbB, unsigned t, const Tw1 &tw1row,
+                                                   const float (&twr)[NT], const float (&twi)[NT], Hook &&after_first_write) {
+  stockham16_passes2<LOGM, NT>(zrA, ziA, xbA, zrB, ziB, xbB, t, t, tw1row, twr, twi, after_first_write);
+}
+template <int LOGM, int NT, class Tw1, class Hook>
+__device__ __forceinline__ void stockham16_passes2s(float (&zrA)[16], float (&ziA)[16], v2f32 *xbA, float (&zrB)[16],
+                                                    float (&ziB)[16], v2f32 *xbB, unsigned t, const Tw1 &tw1row,
+                                                    const float (&twr)[NT], const float (&twi)[NT], Hook &&after_first_write) {
+  stockham16_passes2s<LOGM, NT>(zrA, ziA, xbA, zrB, ziB, xbB, t, t, tw1row, twr, twi, after_first_write);
 }
 
 }  // namespace glfer

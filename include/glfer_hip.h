@@ -183,6 +183,15 @@ int glfer_hip_get_tapers(const glfer_hip_plan *plan, double *tapers, double *sig
 int glfer_hip_make_window(int window_type, int n, float *window);
 int glfer_hip_make_dpss(int n, int kmax, double nw, double *tapers, double *sig);
 
+/* Host only, for checking the register-resident half tables of the five-taper N = 4096 multitaper kernel (n = 4096,
+ * kmax = 4) against the full tables of the same plan.  half: [256][40] floats, row t = what lane t keeps (the samples
+ * r(t) + 256 m, m = 0..7, r(16 j + p) = p < 8 ? 8 j + p : 240 - 8 j + p: floats 16 P + 2 m + k = taper 2 P + k of pair
+ * P = 0, 1, floats 32 + m = the last taper); pairs (optional): [2][8][256][4] = { taper 2P @m, taper 2P+1 @m, the same
+ * @m+1 } for sample t + 256 m of lane t; last (optional): [4][256][4] = the last taper at m = 4 q .. 4 q + 3.
+ * Returns 1 if the plan's scaled float tables are exactly (anti)symmetric about the frame centre, so that a plan keeps
+ * half tables (half is filled), 0 if not (the plan keeps the full tables; half is left alone), < 0 on error. */
+int glfer_hip_y_half_tables(int n, int kmax, double nw, float *half, float *pairs, float *last);
+
 /* THE hot path: frames [first_frame, first_frame+nframes) of a device-resident stream.
  *   d_stream : device pointer to sample 0 of the stream (format = cfg.sample_format)
  *   nsamples : samples in the stream (for bounds: frame f reads [f*H-(N-H), f*H+H))

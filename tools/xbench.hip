@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #define GLFER_NO_LAUNCHERS
 #include "spectro16.hip"
@@ -33,6 +34,25 @@ int main(int argc, char **argv) {
     const int t = i % TT, m = i / TT;
     xt[((size_t)(m / 4) * TT + t) * 4 + (size_t)(m & 3)] = (float)(tapers[(size_t)(T - 1) * N + i] * sqrt(1.0 / (4.0 * N * (1.0 + sig[T - 1]))));
   }
+  // the half tables of spectro16y's half-table form (spectro_params.h: glfer_yhalf_residue), built as the plan builds them:
+  // only where the scaled floats are exactly (anti)symmetric
+  std::vector<float> yt((size_t)TT * GLFER_YHALF_FLOATS);
+  bool yhalf = true;
+  {
+    auto pairv = [&](int j, int i) { return taps[(size_t)(j / 2) * N * 2 + ((size_t)((i / TT) / 2) * TT + i % TT) * 4 + (size_t)((i / TT) & 1) * 2 + (j & 1)]; };
+    auto lastv = [&](int i) { return xt[((size_t)((i / TT) / 4) * TT + i % TT) * 4 + (size_t)((i / TT) & 3)]; };
+    for (int i = 0; i < N / 2; i++) {
+      for (int j = 0; j < 4; j++) yhalf = yhalf && pairv(j, N - 1 - i) == ((j & 1) ? -pairv(j, i) : pairv(j, i));
+      yhalf = yhalf && lastv(N - 1 - i) == lastv(i);
+    }
+    for (int t = 0; t < TT; t++) {
+      const int r = (int)glfer_yhalf_residue((unsigned)t);
+      for (int m = 0; m < 8; m++) {
+        for (int j = 0; j < 4; j++) yt[(size_t)t * GLFER_YHALF_FLOATS + 16 * (j / 2) + 2 * m + (j & 1)] = pairv(j, r + TT * m);
+        yt[(size_t)t * GLFER_YHALF_FLOATS + 32 + m] = lastv(r + TT * m);
+      }
+    }
+  }
   std::vector<float> tw((size_t)2 * glfer::make_twiddles16(LOGN, nullptr) * TT);
   glfer::make_twiddles16(LOGN, tw.data());
   const size_t ns = (size_t)nframes * H;
@@ -40,11 +60,13 @@ int main(int argc, char **argv) {
   unsigned s = 12345;
   for (size_t i = 0; i < ns; i++) { s = s * 1664525u + 1013904223u; x[i] = (float)((s >> 8) * (1.0 / 16777216.0) - 0.5) + 0.3f * sinf(0.01f * (float)i); }
   for (size_t i = (size_t)3 * H; i < (size_t)4 * H; i++) x[i] *= 1e-4f;   // a quiet frame next to loud ones
-  float *d_x, *d_taps, *d_xt, *d_psd1, *d_psd2;
+  float *d_x, *d_taps, *d_xt, *d_yt, *d_psd1, *d_psd2;
   float2 *d_tw;
   CK(hipMalloc((void **)&d_x, ns * 4));
   CK(hipMalloc((void **)&d_taps, taps.size() * 4));
   CK(hipMalloc((void **)&d_xt, xt.size() * 4));
+  CK(hipMalloc((void **)&d_yt, yt.size() * 4));
+  CK(hipMemcpy(d_yt, yt.data(), yt.size() * 4, hipMemcpyHostToDevice));
   CK(hipMalloc((void **)&d_tw, tw.size() * 4));
   CK(hipMalloc((void **)&d_psd1, (size_t)nframes * P * 4));
   CK(hipMalloc((void **)&d_psd2, (size_t)nframes * P * 4));
@@ -55,6 +77,7 @@ int main(int argc, char **argv) {
   SpectroParams sp = {};
   sp.stream = d_x; sp.nframes = nframes; sp.H = H; sp.R = N - H; sp.npairs = NP; sp.fmt = GLFER_FMT_F32;
   sp.taps = d_taps; sp.tw = d_tw; sp.xtaps = d_xt; sp.spec_unscale = 1.0f;
+  sp.pitch = P;                                    // dense rows
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
@@ -116,6 +139,27 @@ int main(int argc, char **argv) {
       timeit("y, grid 8192", [&] { hipLaunchKernelGGL(k0, dim3(8192), dim3(256), shy, 0, sp); });
       timeit("y, grid 8192, ABL: no shared round", [&] { hipLaunchKernelGGL(k1, dim3(8192), dim3(256), shy, 0, sp); });
     }
+  }
+  if (yhalf) {   // full tables against half tables in registers, alternating; then the two forms' rows bit for bit
+    auto kf = glfer::spectro16y_kernel<GLFER_FMT_F32, 0, 0, 0, 0, 0>;
+    auto kh = glfer::spectro16y_kernel<GLFER_FMT_F32, 0, 0, 0, 0, 1>;
+    const size_t shy = (size_t)glfer::LaunchY::LDS_WORDS * 8;
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(kh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shy));
+    float *d_psd3;
+    CK(hipMalloc((void **)&d_psd3, (size_t)nframes * P * 4));
+    SpectroParams sh = sp;                         // (sp.psd = d_psd2: the full-table rows)
+    sh.ytaps = d_yt;
+    sh.psd = d_psd3;
+    for (int rep = 0; rep < 3; rep++) {
+      timeit("y, grid 8192, full tables", [&] { hipLaunchKernelGGL(kf, dim3(8192), dim3(256), shy, 0, sp); });
+      timeit("y, grid 8192, half tables in registers", [&] { hipLaunchKernelGGL(kh, dim3(8192), dim3(256), shy, 0, sh); });
+    }
+    std::vector<float> a((size_t)1024 * P), b((size_t)1024 * P);
+    CK(hipMemcpy(a.data(), d_psd2, a.size() * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(b.data(), d_psd3, b.size() * 4, hipMemcpyDeviceToHost));
+    printf("half tables vs full tables, first 1024 frames: %s\n", memcmp(a.data(), b.data(), a.size() * 4) ? "ROWS DIFFER" : "bit-identical");
+  } else {
+    printf("half tables: the float tables are not exactly symmetric, form not timed\n");
   }
   std::vector<float> a((size_t)256 * P), b((size_t)256 * P);
   CK(hipMemcpy(a.data(), d_psd1, a.size() * 4, hipMemcpyDeviceToHost));
