@@ -73,3 +73,46 @@ def multitaper64(x, n, overlap, tapers, sig, sub_mean=0, history_mode=0):
     for j in range(len(sig)):                                                                # mtm.c:189-220
         out += np.abs(np.fft.rfft(fr * tapers[j], axis=1)) ** 2 / n / (1.0 + sig[j])
     return out
+
+
+def spectrum64(x, n, overlap, window32, sub_mean=0, history_mode=0):
+    """The unnormalised spectra X_k, k = 0 .. n/2, of the windowed frames: complex128 rows (P_k = |X_k|^2 / n)."""
+    fr = frames64(x, n, overlap, sub_mean, history_mode)
+    return np.fft.rfft(fr * np.asarray(window32, np.float64), axis=1)
+
+
+# ---- the float32 stand-in: what a correct float32 kernel can reach (tests/_rows_check.py takes its bounds from it) ----
+# The same frames (float32 samples, hop means removed as the reference does), then float32 all the way: the frame times the
+# float32 window / taper, torch.fft.rfft on CPU tensors in float32 (pocketfft: accurate twiddles), |X|^2 / n, the taper
+# weights and the taper sum in float32.  Independent of the device's and of the reference's transform.
+def _rfft32(rows32):
+    """Row by row: the batched transform of the same library is another algorithm at large N (measured at N = 1 048 576, three
+    rows: 2.4e-6 of the row's norm against 7e-8 row by row) and would set the bounds by the batch's shape."""
+    import torch
+    rows32 = np.ascontiguousarray(rows32, np.float32)
+    out = np.empty((rows32.shape[0], rows32.shape[1] // 2 + 1), np.complex64)
+    for f in range(rows32.shape[0]):
+        out[f] = torch.fft.rfft(torch.from_numpy(rows32[f])).numpy()
+    return out
+
+
+def spectrum32(x, n, overlap, window32, sub_mean=0, history_mode=0):
+    fr = frames64(x, n, overlap, sub_mean, history_mode).astype(np.float32)              # (exact: they are float32 values)
+    return _rfft32(fr * np.asarray(window32, np.float32))
+
+
+def _power32(X, n):
+    return (X.real * X.real + X.imag * X.imag) / np.float32(n)
+
+
+def periodogram32(x, n, overlap, window32, sub_mean=0, history_mode=0):
+    return _power32(spectrum32(x, n, overlap, window32, sub_mean, history_mode), n)
+
+
+def multitaper32(x, n, overlap, tapers, sig, sub_mean=0, history_mode=0):
+    fr = frames64(x, n, overlap, sub_mean, history_mode).astype(np.float32)
+    out = np.zeros((fr.shape[0], n // 2 + 1), np.float32)
+    for j in range(len(sig)):
+        wj = np.float32(1.0 / (1.0 + sig[j]))
+        out += _power32(_rfft32(fr * np.asarray(tapers[j], np.float32)), n) * wj
+    return out
