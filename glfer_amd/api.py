@@ -31,7 +31,7 @@ AVG_SUMAVG, AVG_PLAIN, AVG_SUMEXTREME = 1, 2, 3
 EXPORTS = [
     "glfer_hip_plan_create", "glfer_hip_plan_destroy", "glfer_hip_hop", "glfer_hip_bins",
     "glfer_hip_num_tapers", "glfer_hip_num_frames", "glfer_hip_get_window", "glfer_hip_get_tapers",
-    "glfer_hip_make_window", "glfer_hip_make_dpss", "glfer_hip_y_half_tables", "glfer_hip_spectrogram_device",
+    "glfer_hip_make_window", "glfer_hip_make_dpss", "glfer_hip_y_half_tables", "glfer_hip_y_queue_shape", "glfer_hip_spectrogram_device",
     "glfer_hip_spectrum_device", "glfer_hip_spectrogram_host", "glfer_hip_wav_probe",
     "glfer_hip_spectrogram_wav", "glfer_hip_submean_device",
     "glfer_hip_floor_device",
@@ -136,6 +136,9 @@ def lib():
     L.glfer_hip_make_dpss.argtypes = [C.c_int, C.c_int, C.c_double, vp, vp]
     if hasattr(L, "glfer_hip_y_half_tables"):          # (absent from older builds loaded through GLFER_LIB_PATH for A/B runs)
         L.glfer_hip_y_half_tables.argtypes = [C.c_int, C.c_int, C.c_double, vp, vp, vp]
+    if hasattr(L, "glfer_hip_y_queue_shape"):
+        L.glfer_hip_y_queue_shape.argtypes = [vp, vp]
+        L.glfer_hip_y_queue_shape.restype = None
     L.glfer_hip_spectrogram_device.argtypes = [vp, vp, sz, sz, sz, vp, vp]
     L.glfer_hip_spectrogram_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp]
     L.glfer_hip_spectrum_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp]

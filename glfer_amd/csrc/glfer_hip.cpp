@@ -1292,6 +1292,12 @@ int glfer_hip_plan_create(const glfer_hip_config *cfg, glfer_hip_plan **out) {
     e = hipMalloc((void **)&p->d_ytaps, ytaps.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(p->d_ytaps, ytaps.data(), ytaps.size() * sizeof(float), hipMemcpyHostToDevice);
   }
+  if (e == hipSuccess && !xtaps.empty() && n == 4096) {
+    p->yq = new glfer_yqueue;
+    const size_t bytes = (size_t)glfer_yqueue::SLOTS * glfer_yqueue::PITCH * sizeof(unsigned);
+    e = hipMalloc((void **)&p->yq->d_counters, bytes);
+    if (e == hipSuccess) e = hipMemset(p->yq->d_counters, 0, bytes);
+  }
   if (e == hipSuccess && !ltaps.empty()) {
     e = hipMalloc((void **)&p->d_ltaps, ltaps.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(p->d_ltaps, ltaps.data(), ltaps.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -1335,6 +1341,10 @@ void glfer_hip_plan_destroy(glfer_hip_plan *p) {
   if (p->d_bigtw) (void)hipFree(p->d_bigtw);
   if (p->d_ltaps) (void)hipFree(p->d_ltaps);
   if (p->d_ytaps) (void)hipFree(p->d_ytaps);
+  if (p->yq) {
+    if (p->yq->d_counters) (void)hipFree(p->yq->d_counters);
+    delete p->yq;
+  }
   if (p->d_lagmap) (void)hipFree(p->d_lagmap);
   if (p->d_rot_sched) (void)hipFree(p->d_rot_sched);
   if (p->d_unit) (void)hipFree(p->d_unit);
@@ -1382,6 +1392,11 @@ int glfer_hip_y_half_tables(int n, int kmax, double nw, float *half, float *pair
   if (pairs) memcpy(pairs, taps.data(), (size_t)4 * n * sizeof(float));
   if (last) memcpy(last, xtaps.data(), (size_t)n * sizeof(float));
   return build_y_half_table(n, taps.data(), xtaps.data(), half) ? 1 : 0;
+}
+
+void glfer_hip_y_queue_shape(int *blocks, int *chunk) {
+  if (blocks) *blocks = GLFER_YQ_BLOCKS;
+  if (chunk) *chunk = GLFER_YQ_CHUNK;
 }
 
 int glfer_hip_make_dpss(int n, int kmax, double nw, double *tapers, double *sig) {
@@ -1458,14 +1473,51 @@ static bool y_full_tables_forced() {
   return e && !strcmp(e, "full");
 }
 
+// GLFER_Y_QUEUE=0 in the environment: spectro16y.hip keeps the static stride where it would draw its frame pairs from the
+// plan's counter (same-box A/B runs and the tests that compare the two launch shapes' rows; read per launch).
+// GLFER_Y_CHUNK=<pairs per ticket> overrides GLFER_YQ_CHUNK (the chunk sweep of profiles/y_frame_queue.txt).
+static bool y_queue_off() {
+  const char *e = getenv("GLFER_Y_QUEUE");
+  return e && !strcmp(e, "0");
+}
+static int y_queue_chunk() {
+  const char *e = getenv("GLFER_Y_CHUNK");
+  const int c = e && *e ? atoi(e) : 0;
+  return c >= 1 && c <= 64 ? c : GLFER_YQ_CHUNK;
+}
+
+// spectro16y.hip with its frame pairs from the plan's counter where that applies (see glfer_yqueue in plan.h for the streams
+// that get a counter), else with the static stride
+static hipError_t launch_y(SpectroParams &q, hipStream_t st) {
+  q.yq_counter = nullptr;
+  glfer_yqueue *yq = q.yq;
+  if (!yq || q.mean_inkernel || q.nbatch > 1 || y_queue_off() || st == hipStreamPerThread) return glfer_launch_spectro16y_n12(&q, st);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+    (void)hipGetLastError();
+    return glfer_launch_spectro16y_n12(&q, st);
+  }
+  if (cs != hipStreamCaptureStatusNone) return glfer_launch_spectro16y_n12(&q, st);
+  std::lock_guard<std::mutex> lock(yq->mu);
+  int slot = 0;
+  while (slot < yq->used && yq->owner[slot] != st) slot++;
+  if (slot == yq->used) {
+    if (slot == glfer_yqueue::SLOTS) return glfer_launch_spectro16y_n12(&q, st);
+    yq->owner[yq->used++] = st;
+  }
+  q.yq_counter = yq->d_counters + (size_t)slot * glfer_yqueue::PITCH;
+  q.yq_base = yq->base[slot];
+  q.yq_chunk = y_queue_chunk();
+  const hipError_t e = glfer_launch_spectro16y_n12(&q, st);
+  if (e == hipSuccess) yq->base[slot] += (unsigned)glfer_yq_chunks(q.nframes, q.yq_chunk);   // the tickets the launch draws
+  return e;
+}
+
 static hipError_t launch_shared_odd(const SpectroParams &sp, int n, hipStream_t st) {
   if (n == 4096) {                     // two frames interleaved per wavefront
-    if (sp.ytaps && y_full_tables_forced()) {
-      SpectroParams q = sp;
-      q.ytaps = nullptr;
-      return glfer_launch_spectro16y_n12(&q, st);
-    }
-    return glfer_launch_spectro16y_n12(&sp, st);
+    SpectroParams q = sp;
+    if (sp.ytaps && y_full_tables_forced()) q.ytaps = nullptr;
+    return launch_y(q, st);
   }
   if (sp.ltaps) {                      // taper half tables resident in LDS
     switch (n) {
@@ -1615,6 +1667,7 @@ static void fill_params(const glfer_hip_plan *p, SpectroParams &sp) {
   sp.xtaps = p->d_xtaps;
   sp.ltaps = p->d_ltaps;
   sp.ytaps = p->d_ytaps;
+  sp.yq = p->yq;
   sp.wtaps = p->d_wtaps;
   sp.wtapers = p->wtapers;
   sp.wtw = p->d_wtw;

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -81,6 +82,22 @@ size_t ingest_ring_spare_bytes(int dev);       // pinned host + device bytes of 
 
 }  // namespace glfer
 
+// The ticket counters of spectro16y.hip's queue form (SpectroParams::yq_counter), made with the plan and zeroed once.
+// A counter is never reset: the host keeps the value it will have when the next launch starts (base) and advances it by
+// the launch's chunks after a launch call that succeeded.  That holds while the launches that share a counter run one
+// after another, so a counter belongs to ONE stream: the first SLOTS streams a plan is used on get one each (the host
+// entries' chunk ring runs one plan on two streams), a launch on any further stream, on hipStreamPerThread (one handle,
+// a stream per host thread) or on a stream that is being captured (a graph replays the base it was captured with) keeps
+// the static stride.
+struct glfer_yqueue {
+  static constexpr int SLOTS = 8, PITCH = 32;      // a 128-byte line per counter
+  unsigned *d_counters = nullptr;                  // [SLOTS][PITCH]
+  hipStream_t owner[SLOTS] = {};
+  unsigned base[SLOTS] = {};
+  int used = 0;
+  std::mutex mu;                                   // held from reading a base to advancing it
+};
+
 #define HIP_TRY(call)                                          \
   do {                                                         \
     hipError_t e_ = (call);                                    \
@@ -110,6 +127,7 @@ struct glfer_hip_plan {
   float *d_xtaps = nullptr;         // odd taper counts (spectro16x.hip): the last taper alone, [4][n/16][4]
   float *d_ltaps = nullptr;         // odd taper counts, LDS-resident half tables (spectro16xl.hip)
   float *d_ytaps = nullptr;         // five tapers at N = 4096, register-resident half tables (spectro16y.hip); NULL: not exactly symmetric
+  glfer_yqueue *yq = nullptr;       // spectro16y.hip's queue form: the plan's ticket counters (N = 4096, odd taper counts)
   uint16_t *d_lagmap = nullptr;     // HP-ARMA: [t][p_e+1] lag held by each matrix cell
   int *d_rot_sched = nullptr;       // HP-ARMA: [rot_steps][8] the Jacobi sweep as steps of up to eight column-disjoint rotations (j | k << 8, -1 = none)
   int rot_steps = 0, rot_width = 8;

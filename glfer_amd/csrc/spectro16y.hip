@@ -24,6 +24,16 @@
 // The permutation touches the sample gather and the column of the first exchange's writes only; what every lane reads
 // back from that exchange, and everything after it, is unchanged, and per frame the same operations meet the same values
 // in the same order: the rows are bit-identical to the full-table form's.
+//
+// QUEUE (the plain forms: no in-kernel mean, one stream): one workgroup per resident slot, and frame pairs handed out in
+// chunks of p.yq_chunk consecutive pairs.  A workgroup's first chunk is the static one (xcd_block_index()); every later one is
+// gridDim.x + a ticket drawn from p.yq_counter.  Lane 0 of wavefront 0 draws the ticket (a vector atomic add with return) at
+// the start of a chunk's first iteration, parks it in the pad word of the pass-1 twiddle table in front of the barrier of the
+// mirror fold, and every wavefront reads it behind that barrier: the next chunk is known two dual rounds after it was asked
+// for and before the shared round's hook requests its samples.  A ticket at or past the end ends the workgroup after the
+// iteration in flight; a workgroup draws exactly one ticket per chunk it takes, so a launch of P chunks draws P tickets
+// whatever the order (P - gridDim.x that succeed, gridDim.x that fail), and the host passes the counter's value before the
+// launch as p.yq_base instead of zeroing it.  Which workgroup takes a pair changes nothing that is computed for it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "odd_taper.hpp"
@@ -44,6 +54,12 @@
                                      not with history zeroed per frame, not the 75 % mean form): +1.5...2 %, profiles/r03_y_tw1_regs.txt */
 #endif
 
+// tools/yqbench only: GLFER_BLOCK_MARK(k) records a workgroup's clock at entry (0), in front of its first iteration (1) and
+// behind its last (2).  Expands to nothing in the product build.
+#ifndef GLFER_BLOCK_MARK
+#define GLFER_BLOCK_MARK(k)
+#endif
+
 namespace glfer {
 
 hipError_t allow_dynamic_lds(const void *kernel, size_t bytes);   // plan.h / glfer_hip.cpp: once per device, kernel and size class
@@ -61,14 +77,16 @@ struct LaunchY {
 // butterfly over the wavefront, the four wavefronts through LDS across the barriers that end the
 // shared round), and x - mu is formed once, before the frames' first round.  A hop's mean comes from
 // the same lanes' same registers in the same order whichever frame it is seen in.
-template <int FMT, int ABL = 0, int HIST = 0, int KM = 0, int BAT = 0, int HALF = 0>
+template <int FMT, int ABL = 0, int HIST = 0, int KM = 0, int BAT = 0, int HALF = 0, int QUEUE = 0>
 __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
+  GLFER_BLOCK_MARK(0);
   // the stream of the batch (blockIdx.y; 0 outside a batch); the mean forms only in their batch instantiations (BAT), so that the
   // single-stream ones keep their registers
   if constexpr (KM == 0 || BAT != 0) glfer_batch_select(p);
   static_assert(KM == 0 || (HIST == 0 && (KM == 16 || KM == 8 || KM == 4)), "in-kernel mean removal: history from the stream");
   // (the hop sums of the mean forms reduce across lanes in lane order: a lane permutation would change their bits)
   static_assert(HALF == 0 || (KM == 0 && GLFER16_X0_ROWS != 0 && GLFER16_BARRIER_AFTER_READS != 0), "half tables: the plain forms, row layout of exchange 0");
+  static_assert(QUEUE == 0 || (KM == 0 && BAT == 0 && ABL == 0), "frame queue: the plain single-stream forms");
   constexpr int NH = KM > 0 ? 16 / KM : 1;
   __shared__ float mred[KM > 0 ? 4 * (NH + 1) : 1];
   using C = Plan16<12>;
@@ -178,8 +196,13 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
     else return v2f32{mirror(hp[P * 8 + 15 - m].x), -mirror(hp[P * 8 + 15 - m].y)};
   };
 
-  long long fA = (long long)xcd_block_index() * 2;
+  // QUEUE: a chunk is `span` frames from a multiple of span; fEnd = the end of the chunk fA lies in, fresh = fA is its first pair
+  const long long span = QUEUE ? 2LL * p.yq_chunk : 2;
+  unsigned *qword = reinterpret_cast<unsigned *>(tw1 + 16);   // (column 16 of the table's padded rows is never read)
+  long long fA = (long long)xcd_block_index() * span;
   if (fA >= p.nframes) return;
+  long long fEnd = fA + span < p.nframes ? fA + span : (long long)p.nframes, next_chunk = 0;
+  bool fresh = true;
   float xA[16], xB[16];
   load_x(xA, fA);
   if (fA + 1 < p.nframes) load_x(xB, fA + 1);
@@ -247,9 +270,14 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
   constexpr int RL = C::radix(NPASS - 1), BL = 16 / RL;
   auto rho_of = [](int m) constexpr { return (m % BL) + BL * brev(m / BL, RL); };   // register of bin t + T*m
 
+  GLFER_BLOCK_MARK(1);
   while (true) {                                     // one iteration: frames A = fA and B = fA + 1
-    const long long nfA = fA + stride;
-    const bool has_next = nfA < p.nframes;
+    long long nfA = fA + stride;
+    bool has_next = nfA < p.nframes;
+    unsigned ticket = 0;
+    if constexpr (QUEUE != 0) {
+      if (fresh && t == 0) ticket = __hip_atomic_fetch_add(p.yq_counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     float psdA[8], psdB[8], nyqA, nyqB;
     int hxA, hxB;
     {
@@ -355,7 +383,15 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
         red[t >> 6] = eA;
         red[4 + (t >> 6)] = eB;
       }
+      if constexpr (QUEUE != 0) {
+        if (fresh && t == 0) *qword = ticket - p.yq_base;
+      }
       __syncthreads();
+      if constexpr (QUEUE != 0) {
+        if (fresh) next_chunk = ((long long)gridDim.x + (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)*qword)) * span;
+        nfA = fA + 2 < fEnd ? fA + 2 : next_chunk;
+        has_next = nfA < p.nframes;
+      }
       eA = (red[0] + red[1]) + (red[2] + red[3]);
       eB = (red[4] + red[5]) + (red[6] + red[7]);
       hxA = scale_exponent(eA);
@@ -440,12 +476,17 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
       }
     }
     if (!has_next) break;
+    if constexpr (QUEUE != 0) {
+      fresh = fA + 2 >= fEnd;
+      if (fresh) fEnd = nfA + span < p.nframes ? nfA + span : (long long)p.nframes;
+    }
     fA = nfA;
     if (fA + 1 >= p.nframes) {
 #pragma unroll
       for (int m = 0; m < 16; m++) xB[m] = 0.0f;
     }
   }
+  GLFER_BLOCK_MARK(2);
 }
 
 }  // namespace glfer
@@ -453,10 +494,33 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
 #ifndef GLFER_NO_LAUNCHERS
 using namespace glfer;
 
+// The queue form (p.yq_counter set by the host, which keeps the ticket base: glfer_hip.cpp): one workgroup per resident slot
+template <int FMT>
+static hipError_t launch16y_queue(const SpectroParams &p, hipStream_t st) {
+  if (p.mean_inkernel || p.nbatch > 1 || p.yq_chunk < 1) return hipErrorInvalidValue;
+  const unsigned grid = glfer_yq_grid(glfer_yq_chunks(p.nframes, p.yq_chunk));
+  constexpr size_t shmem = (size_t)LaunchY::LDS_WORDS * 8;
+#define GLFER_Y_QUEUE(HIST, HALF)                                                                                    \
+  do {                                                                                                               \
+    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, HIST, 0, 0, HALF, 1>), shmem); \
+    if (e != hipSuccess) return e;                                                                                   \
+    hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, HIST, 0, 0, HALF, 1>), dim3(grid), dim3(256), shmem, st, p);        \
+    return hipGetLastError();                                                                                        \
+  } while (0)
+  if (GLFER16Y_HALF != 0 && p.ytaps && p.npairs == 3) {
+    if (p.history_mode) GLFER_Y_QUEUE(1, GLFER16Y_HALF);
+    else GLFER_Y_QUEUE(0, GLFER16Y_HALF);
+  }
+  if (p.history_mode) GLFER_Y_QUEUE(1, 0);
+  else GLFER_Y_QUEUE(0, 0);
+#undef GLFER_Y_QUEUE
+}
+
 template <int FMT>
 static hipError_t launch16y_fmt(const SpectroParams &p, hipStream_t st) {
   const long long work = ((long long)p.nframes + 1) / 2;
   if (work == 0) return hipSuccess;
+  if (p.yq_counter) return launch16y_queue<FMT>(p, st);
   const long long resident = 256LL * 2;
   const long long cap = glfer_batch_cap(16 * resident, p.nbatch);   // (a batch shares it among its streams)
   unsigned grid = (unsigned)(work < cap ? work : cap);   // tools/xbench: 16x beats 4x by ~2 %

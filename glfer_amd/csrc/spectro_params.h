@@ -39,6 +39,14 @@ struct SpectroParams {
   const float *ltaps;      /* device: [npairs-1][8][N/16][2] pair halves, then [8][N/16] the last taper */
   /* five tapers at N = 4096, spectro16y.hip's half-table form: the tables a lane keeps in registers; NULL when not built */
   const float *ytaps;      /* device: [256][GLFER_YHALF_FLOATS], see glfer_yhalf_residue()                */
+  /* spectro16y.hip's queue form (the plain forms, one stream): frame pairs handed out in chunks from a counter the plan owns.
+     yq_counter NULL: the static stride.  The counter is never reset: a launch of P chunks draws exactly P tickets, the host
+     (glfer_hip.cpp) keeps the value it has before the launch and the kernel subtracts it.  32 bits, modulo 2^32 on both sides:
+     only the difference is used, and a launch has fewer than 2^31 chunks. */
+  unsigned *yq_counter;    /* device                                                         */
+  unsigned yq_base;        /* the counter's value when this launch starts                    */
+  int yq_chunk;            /* consecutive frame pairs per ticket                             */
+  struct glfer_yqueue *yq; /* HOST: the plan's counters (glfer_hip.cpp); kernels do not touch it */
   float *psd;              /* device: [nframes][pitch], the first N/2+1 floats of a row are its bins */
   int pitch;               /* floats from one PSD row to the next (cfg.psd_pitch; N/2+1 = dense)      */
   float *spec;             /* device, optional: [nframes][N] halfcomplex spectrum            */
@@ -108,6 +116,18 @@ enum { GLFER_YHALF_FLOATS = 40 };
 static inline __host__ __device__ unsigned glfer_yhalf_residue(unsigned t) {
   const unsigned j = t >> 4, p = t & 15u;
   return p < 8u ? 8u * j + p : 240u - 8u * j + p;
+}
+
+/* spectro16y.hip's queue form: chunks of a launch (= the tickets it draws) and its grid -- one workgroup per resident slot
+   (256 CUs x 2), fewer when there are fewer chunks, whole XCD slices from 64 up (xcd_block_index) */
+enum { GLFER_YQ_BLOCKS = 512, GLFER_YQ_CHUNK = 4 };   /* 4: profiles/y_frame_queue.txt, the chunk sweep */
+static inline long long glfer_yq_chunks(int nframes, int chunk) {
+  return (((long long)nframes + 1) / 2 + chunk - 1) / chunk;
+}
+static inline unsigned glfer_yq_grid(long long nchunks) {
+  unsigned grid = (unsigned)(nchunks < GLFER_YQ_BLOCKS ? nchunks : GLFER_YQ_BLOCKS);
+  if (grid >= 64) grid &= ~7u;
+  return grid;
 }
 
 /* A launcher's persistent grid for a batch: `cap` workgroups for the whole launch, shared among its streams, so that

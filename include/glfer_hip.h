@@ -192,6 +192,11 @@ int glfer_hip_make_dpss(int n, int kmax, double nw, double *tapers, double *sig)
  * half tables (half is filled), 0 if not (the plan keeps the full tables; half is left alone), < 0 on error. */
 int glfer_hip_y_half_tables(int n, int kmax, double nw, float *half, float *pairs, float *last);
 
+/* Host only: the launch shape of that kernel's queue form (the plain single-stream launches draw their frame pairs in
+ * chunks from a counter the plan owns; GLFER_Y_QUEUE=0 in the environment keeps the static stride).  *blocks: the
+ * workgroups of a launch with at least that many chunks; *chunk: consecutive frame pairs per ticket. */
+void glfer_hip_y_queue_shape(int *blocks, int *chunk);
+
 /* THE hot path: frames [first_frame, first_frame+nframes) of a device-resident stream.
  *   d_stream : device pointer to sample 0 of the stream (format = cfg.sample_format)
  *   nsamples : samples in the stream (for bounds: frame f reads [f*H-(N-H), f*H+H))
