@@ -52,7 +52,7 @@ EXPORTS = [
     "glfer_hip_workers_spectrogram_wav", "glfer_hip_workers_spectrogram_host",
     # many streams per call
     "glfer_hip_spectrogram_batch_device", "glfer_hip_avg_batch_device", "glfer_hip_spectrogram_avg_batch_device",
-    "glfer_hip_waterfall_batch_device",
+    "glfer_hip_waterfall_batch_device", "glfer_hip_mtm_ftest_batch_device",
 ]
 
 
@@ -157,6 +157,8 @@ def lib():
     L.glfer_hip_frame_range.restype = None
     L.glfer_hip_prepare_device.argtypes = [vp, vp, sz, sz, sz, vp, vp]
     L.glfer_hip_mtm_ftest_device.argtypes = [vp, vp, sz, sz, sz, vp, C.c_int, vp]
+    if hasattr(L, "glfer_hip_mtm_ftest_batch_device"):  # (absent from older builds loaded through GLFER_LIB_PATH for A/B runs)
+        L.glfer_hip_mtm_ftest_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, C.c_int, vp]
     L.glfer_hip_host_alloc.argtypes = [sz]
     L.glfer_hip_host_alloc.restype = vp
     L.glfer_hip_host_free.argtypes = [vp]
@@ -460,6 +462,26 @@ class Spectrogram:
         st = C.c_void_p(torch.cuda.current_stream(stream.device).cuda_stream)
         _check(lib().glfer_hip_mtm_ftest_device(self._h, stream.data_ptr(), stream.numel(), first_frame, nframes,
                                                 out.data_ptr(), 1 if mu_live else 0, st), "glfer_hip_mtm_ftest_device")
+        return out
+
+    def ftest_batch(self, streams, first_frame=0, nframes=None, mu_live=True, out=None):
+        """ftest for many streams in one call (glfer_hip_mtm_ftest_batch_device).  streams as run_batch takes them: 2-D [B, T]
+        on this GPU, of the plan's sample dtype, stride(1) == 1 (stride(0) is the distance between streams, in samples).
+        Returns a float tensor [B][nframes][bins] -- out[b] holds the bits of ftest(streams[b]) -- launched on torch's
+        current stream."""
+        torch = _torch()
+        assert streams.is_cuda and streams.dim() == 2 and (streams.stride(1) == 1 or streams.size(1) <= 1)
+        assert streams.dtype == self._sample_dtype(), (streams.dtype, self._sample_dtype())
+        nb, total = streams.size(0), streams.size(1)
+        if nframes is None:
+            nframes = self.num_frames(total) - first_frame
+        if out is None:
+            out = torch.empty((nb, nframes, self.bins), dtype=torch.float32, device=streams.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= nb * nframes * self.bins
+        st = C.c_void_p(torch.cuda.current_stream(streams.device).cuda_stream)
+        _check(lib().glfer_hip_mtm_ftest_batch_device(self._h, C.c_void_p(streams.data_ptr()), nb, streams.stride(0), total,
+                                                      first_frame, nframes, C.c_void_p(out.data_ptr()), 1 if mu_live else 0, st),
+               "glfer_hip_mtm_ftest_batch_device")
         return out
 
     def prepare(self, stream, first_frame=0, nframes=None):

@@ -2247,22 +2247,11 @@ int glfer_hip_prepare_device(glfer_hip_plan *p, const void *d_stream, size_t nsa
   return rc;
 }
 
-// The harmonic F-test of mtm_do (mtm.c:165-174, 203-233) as an optional output of the multitaper
-// path.  The tapered spectra y_j(f) and mu(f) come from the estimator's own spectrum output (one
-// single-taper launch of spectro16_kernel per taper and one for hn), the statistic from a per-bin
-// epilogue (stats_kernels.hip).  Frames are processed in groups that keep the spectra scratch
-// under ~256 MiB.
-int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t nsamples, size_t first,
-                               size_t nframes, float *d_ftest, int mu_live, void *hip_stream) {
-  if (!p || !d_stream || (!d_ftest && nframes) || p->cfg.mode != GLFER_MODE_MTM) return GLFER_E_ARG;
-  if (p->n > 16384) return GLFER_E_ARG;              // needs the packed form's spectrum output
-  if (nframes == 0) return GLFER_OK;
-  if ((first + nframes) > nsamples / (size_t)p->hop || nframes > 0x7fffffffu) return GLFER_E_ARG;
-  hipStream_t st = (hipStream_t)hip_stream;
-  DeviceGuard guard(p->cfg.device);
-  HIP_TRY(guard.error());
+// The F-test's tables, made on the first F call of a plan (either entry) and kept with it.
+static int ftest_tables(glfer_hip_plan *p) {
   const int n = p->n, T = p->ntapers;
-  if (!p->d_ftaps) {                     // tables of mtm.c:76-83, 124-136, once per plan
+  if (p->d_ftaps) return GLFER_OK;       // tables of mtm.c:76-83, 124-136, once per plan
+  {
     p->U0.resize(T);
     p->hn.resize(n);
     glfer::make_ftest_tables(n, T - 1, p->tapers.data(), p->U0.data(), p->hn.data(), &p->sum_U0_sqr);
@@ -2319,15 +2308,71 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t n
     p->d_ftaps2 = d2;
     p->d_ftaps2_nomu = d2 + (size_t)r_mu * 2 * n;
   }
-  SpectroParams sp;
+  return GLFER_OK;
+}
+
+// The argument block both F entries start from: the packed kernel (it is the one with the spectrum output), one table per launch.
+static void ftest_params(const glfer_hip_plan *p, SpectroParams &sp) {
   fill_params(p, sp);
-  sp.pitch = p->bins;                    // (the statistic and this entry's scratch rows are dense)
-  sp.stream = d_stream;
+  sp.pitch = p->bins;                    // (the statistic and the entries' scratch rows are dense)
   sp.npairs = 1;
   sp.nonlin = 0;
   sp.post_scale = sp.spec_unscale = 1.0f;
-  sp.htaps = nullptr;                    // the packed kernel: it is the one with the spectrum output
+  sp.htaps = nullptr;
   sp.xtaps = sp.ltaps = sp.ytaps = nullptr;
+}
+
+// N >= 256, one launch: every round of spectro16_kernel's FT form transforms the frame under one taper (or two sequences, the
+// paired form) and keeps what the statistic needs in registers (no spectrum goes through HBM).  sp: ftest_params with the stream set.
+static SpectroParams ftest_in_launch(const glfer_hip_plan *p, const SpectroParams &sp, size_t first, size_t nframes, float *d_ftest,
+                                     int mu_live) {
+  const int n = p->n, T = p->ntapers;
+  SpectroParams q = sp;
+  q.frame0 = (long long)first;
+  q.nframes = (int)nframes;
+  q.psd = nullptr;
+  q.spec = nullptr;
+  q.ftest = d_ftest;
+  q.ft_U0 = p->d_U0;
+  q.ft_sum_U0_sqr = p->sum_U0_sqr;
+  q.ft_mu_live = mu_live ? 1 : 0;
+  q.npairs = mu_live ? T + 1 : T;                    // rounds: hn first (mu), then the tapers
+  q.taps = mu_live ? p->d_ftaps_mu_first : p->d_ftaps;
+  // round 5: two sequences per transform, separated through the mirror bins (GLFER_FTEST_PAIRED=0: one per transform, for A/B runs and tests)
+  // Measured (gpurun_out/r5/ftest_rate.txt): N = 4096, 5 tapers 39.2 against 33.5 M frames/s; N = 1024, 8 tapers 94.3 against 105.9 -- the
+  // mirror exchange (two barriers, 16 LDS writes, 9 reads a round) costs a short transform more than it saves: paired from N = 2048.
+  const char *pe = getenv("GLFER_FTEST_PAIRED");
+  if (pe && *pe ? *pe != '0' : n >= 2048) {
+    q.ft_nseq = mu_live ? T + 1 : T;
+    q.npairs = (q.ft_nseq + 1) / 2;
+    q.taps = mu_live ? p->d_ftaps2 : p->d_ftaps2_nomu;
+    q.ft_mu_unscale = 1.0f / p->hn_scale;
+  }
+  return q;
+}
+
+// The harmonic F-test of mtm_do (mtm.c:165-174, 203-233) as an optional output of the multitaper
+// path.  The tapered spectra y_j(f) and mu(f) come from the estimator's own spectrum output (one
+// single-taper launch of spectro16_kernel per taper and one for hn), the statistic from a per-bin
+// epilogue (stats_kernels.hip).  Frames are processed in groups that keep the spectra scratch
+// under ~256 MiB.
+int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t nsamples, size_t first,
+                               size_t nframes, float *d_ftest, int mu_live, void *hip_stream) {
+  if (!p || !d_stream || (!d_ftest && nframes) || p->cfg.mode != GLFER_MODE_MTM) return GLFER_E_ARG;
+  if (p->n > 16384) return GLFER_E_ARG;              // needs the packed form's spectrum output
+  if (nframes == 0) return GLFER_OK;
+  if ((first + nframes) > nsamples / (size_t)p->hop || nframes > 0x7fffffffu) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  DeviceGuard guard(p->cfg.device);
+  HIP_TRY(guard.error());
+  const int n = p->n, T = p->ntapers;
+  {
+    const int trc = ftest_tables(p);
+    if (trc != GLFER_OK) return trc;
+  }
+  SpectroParams sp;
+  ftest_params(p, sp);
+  sp.stream = d_stream;
   float *scratch = nullptr;
   int rc = GLFER_OK;
   if (p->cfg.sub_mean) {
@@ -2335,29 +2380,7 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t n
     rc = submean_scratch(p, sp, first, nframes, st, &scratch);
   }
   if (rc == GLFER_OK && n >= 256) {
-    // one launch: every round of spectro16_kernel's FT form transforms the frame under one taper and
-    // keeps what the statistic needs in registers (no spectrum goes through HBM)
-    SpectroParams q = sp;
-    q.frame0 = (long long)first;
-    q.nframes = (int)nframes;
-    q.psd = nullptr;
-    q.spec = nullptr;
-    q.ftest = d_ftest;
-    q.ft_U0 = p->d_U0;
-    q.ft_sum_U0_sqr = p->sum_U0_sqr;
-    q.ft_mu_live = mu_live ? 1 : 0;
-    q.npairs = mu_live ? T + 1 : T;                    // rounds: hn first (mu), then the tapers
-    q.taps = mu_live ? p->d_ftaps_mu_first : p->d_ftaps;
-    // round 5: two sequences per transform, separated through the mirror bins (GLFER_FTEST_PAIRED=0: one per transform, for A/B runs and tests)
-    // Measured (gpurun_out/r5/ftest_rate.txt): N = 4096, 5 tapers 39.2 against 33.5 M frames/s; N = 1024, 8 tapers 94.3 against 105.9 -- the
-    // mirror exchange (two barriers, 16 LDS writes, 9 reads a round) costs a short transform more than it saves: paired from N = 2048.
-    const char *pe = getenv("GLFER_FTEST_PAIRED");
-    if (pe && *pe ? *pe != '0' : n >= 2048) {
-      q.ft_nseq = mu_live ? T + 1 : T;
-      q.npairs = (q.ft_nseq + 1) / 2;
-      q.taps = mu_live ? p->d_ftaps2 : p->d_ftaps2_nomu;
-      q.ft_mu_unscale = 1.0f / p->hn_scale;
-    }
+    const SpectroParams q = ftest_in_launch(p, sp, first, nframes, d_ftest, mu_live);
     hipError_t e = launch_packed(q, n, st);
     if (e != hipSuccess) rc = hip_fail(e, "ftest launch");
     if (scratch) glfer::scratch_free(scratch, st);
@@ -2393,6 +2416,71 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t n
   if (dummy) glfer::scratch_free(dummy, st);
   if (scratch) glfer::scratch_free(scratch, st);
   return rc;
+}
+
+// glfer_hip_mtm_ftest_device over many streams (glfer_hip.h).  N >= 256: the launches of one stream -- the corrected copies under
+// mean removal (batch_submean_scratch), then spectro16_kernel's FT form with blockIdx.y as the stream, the form chosen as the
+// single entry chooses it -- so the launch count does not grow with the batch; below 256 the single entry, stream by stream.
+int glfer_hip_mtm_ftest_batch_device(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch,
+                                     size_t nsamples, size_t first, size_t nframes, float *d_ftest, int mu_live,
+                                     void *hip_stream) {
+  if (!p) return GLFER_E_ARG;
+  if (p->cfg.mode != GLFER_MODE_MTM || p->n > 16384) return GLFER_E_ARG;
+  if (nstreams == 0 || nframes == 0) return GLFER_OK;
+  if (!d_streams || !d_ftest) return GLFER_E_ARG;
+  if ((first + nframes) > nsamples / (size_t)p->hop) return GLFER_E_ARG;   // frame past the stream
+  if (nframes > 0x7fffffffu) return GLFER_E_ARG;
+  const int fmt = p->cfg.sample_format;
+  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
+  // (as glfer_hip_spectrogram_batch_device: every stream of a batch must see the same alignment)
+  if (fmt != GLFER_FMT_F32 && (stream_pitch & 1)) return GLFER_E_ARG;
+  const size_t rows = (size_t)p->bins;
+  if (stream_pitch > (SIZE_MAX / esz) / nstreams || nframes > (SIZE_MAX / sizeof(float) / rows) / nstreams) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  const char *base = static_cast<const char *>(d_streams);
+  const size_t ft_bs = nframes * rows;                       // floats from one stream's first F row to the next one's
+  const int n = p->n;
+  if (n < 256 || nstreams == 1) {
+    for (size_t b = 0; b < nstreams; b++) {
+      const int rc = glfer_hip_mtm_ftest_device(p, base + b * stream_pitch * esz, nsamples, first, nframes, d_ftest + b * ft_bs, mu_live,
+                                                hip_stream);
+      if (rc != GLFER_OK) return rc;
+    }
+    return GLFER_OK;
+  }
+  DeviceGuard guard(p->cfg.device);
+  HIP_TRY(guard.error());
+  {
+    const int trc = ftest_tables(p);
+    if (trc != GLFER_OK) return trc;
+  }
+  int dev = 0, ymax = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  HIP_TRY(hipDeviceGetAttribute(&ymax, hipDeviceAttributeMaxGridDimY, dev));
+  ymax = std::max(1, std::min(ymax, 65535));
+  for (size_t c0 = 0; c0 < nstreams; c0 += (size_t)ymax) {      // batches above the grid's y limit: chunks of it
+    const unsigned nb = (unsigned)std::min(nstreams - c0, (size_t)ymax);
+    SpectroParams sp;
+    ftest_params(p, sp);
+    sp.stream = base + c0 * stream_pitch * esz;
+    sp.nbatch = (int)nb;
+    sp.batch_stride = (long long)(stream_pitch * esz);
+    float *scratch = nullptr;
+    int rc = GLFER_OK;
+    if (p->cfg.sub_mean) {
+      sp.frame0 = (long long)first;
+      rc = batch_submean_scratch(p, sp, first, nframes, nb, st, &scratch);
+    }
+    if (rc == GLFER_OK) {
+      SpectroParams q = ftest_in_launch(p, sp, first, nframes, d_ftest + c0 * ft_bs, mu_live);
+      q.ftest_batch_stride = (long long)ft_bs;                  // (psd NULL, psd_batch_stride 0)
+      const hipError_t e = launch_packed(q, n, st);
+      if (e != hipSuccess) rc = hip_fail(e, "ftest launch (batch)");
+    }
+    if (scratch) glfer::scratch_free(scratch, st);
+    if (rc != GLFER_OK) return rc;
+  }
+  return GLFER_OK;
 }
 
 int glfer_hip_submean_device(const void *d_in, float *d_out, int hop, size_t nhops, int sample_format,

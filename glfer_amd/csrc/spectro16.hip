@@ -69,8 +69,10 @@ namespace glfer {
 template <int LOGN, int FMT, bool GEN, int WPS = GLFER16_WAVES_PER_SIMD, int STG = GLFER16_STAGGER, int KM = 0, int FT = 0, int BAT = 0>
 __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(SpectroParams p) {
   // BAT: the instantiations a batch launches (nbatch > 1) -- blockIdx.y is the stream; the single-stream ones are the code as it was
-  static_assert(BAT == 0 || FT == 0, "the F statistic is never batched");
-  if constexpr (BAT != 0) glfer_batch_select(p);
+  if constexpr (BAT != 0) {
+    glfer_batch_select(p);
+    if constexpr (FT != 0) p.ftest += (long long)blockIdx.y * p.ftest_batch_stride;   // (psd stays NULL: psd_batch_stride is 0)
+  }
   static_assert(KM == 0 || (!GEN && (KM == 16 || KM == 8 || KM == 4)), "in-kernel mean removal: the plain path");
   static_assert(FT == 0 || !GEN, "F statistic: the plain path");
   constexpr int NH = KM > 0 ? 16 / KM : 1;
@@ -571,12 +573,11 @@ static hipError_t launch16_fmt(const SpectroParams &p, hipStream_t st) {
   unsigned grid = (unsigned)(work < cap ? work : cap);
   if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
   if (p.ftest) {
-    if (BAT) return hipErrorInvalidValue;           // (never batched)
     // the F statistic: one taper per round (two spill-free wavefronts per SIMD: mu and the sums are 48 more registers)
     if (p.nonlin || p.spec || p.mean_inkernel || !p.ft_U0) return hipErrorInvalidValue;
     // (the paired form keeps mu and the sums for the bins k <= N/2 only -- 27 registers, not 48: three wavefronts per SIMD)
-    if (p.ft_nseq > 0) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 3, GLFER16_STAGGER, 0, 2, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    if (p.ft_nseq > 0) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 3, GLFER16_STAGGER, 0, 2, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     return hipGetLastError();
   }
   if (p.mean_inkernel) {

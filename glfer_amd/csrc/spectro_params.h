@@ -104,6 +104,8 @@ struct SpectroParams {
   long long means_batch_stride; /* floats from one stream's given hop-means table (means) to the next one's                  */
   long long avg_batch_stride;   /* doubles from one stream's first averaged row (avg) to the next one's                        */
   long long avg_ret_batch_stride;   /* doubles from one stream's first return values (avg_ret) to the next one's               */
+  long long ftest_batch_stride; /* floats from one stream's first F row (ftest) to the next one's (glfer_hip_mtm_ftest_batch_device:
+                                   psd NULL and psd_batch_stride 0 there); spectro16_kernel's FT forms add it at entry          */
 };
 
 /* spectro16y.hip's half-table form (N = 4096, T = 256 lanes, five tapers).  In pass 0 lane t = 16 j + p holds the samples

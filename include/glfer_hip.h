@@ -232,8 +232,9 @@ int glfer_hip_spectrogram_device(glfer_hip_plan *plan, const void *d_stream, siz
  * are never taken by this entry.
  * The moving average of many streams: glfer_hip_spectrogram_avg_batch_device and glfer_hip_avg_batch_device below; their
  * waterfalls: glfer_hip_waterfall_batch_device.
- * Not covered: ragged batches (one length per stream), batched host / WAV / workers entries, the F-test and
- * halfcomplex-spectrum outputs, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as they are. */
+ * The harmonic F-test of many streams: glfer_hip_mtm_ftest_batch_device below.
+ * Not covered: ragged batches (one length per stream), batched host / WAV / workers entries, the
+ * halfcomplex-spectrum output, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as they are. */
 int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams,
                                        size_t stream_pitch, size_t nsamples, size_t first_frame,
                                        size_t nframes, float *d_psd, void *hip_stream);
@@ -267,6 +268,31 @@ int glfer_hip_prepare_device(glfer_hip_plan *plan, const void *d_stream, size_t 
 int glfer_hip_mtm_ftest_device(glfer_hip_plan *plan, const void *d_stream, size_t nsamples,
                                size_t first_frame, size_t nframes, float *d_ftest, int mu_live,
                                void *hip_stream);
+
+/* glfer_hip_mtm_ftest_device for nstreams streams laid out as glfer_hip_spectrogram_batch_device takes them: stream b is
+ * d_streams + b * stream_pitch samples, nsamples long, starting with zero history -- what the single entry would be given
+ * as d_stream -- and the same frames [first_frame, first_frame + nframes) of each.
+ *   d_ftest : device, [nstreams][nframes][N/2+1] floats; row i of stream b at d_ftest + (b * nframes + i) * (N/2+1), dense
+ *             whatever cfg.psd_pitch is, as in the single entry
+ * Every row is bit for bit the row glfer_hip_mtm_ftest_device writes for that stream on the same plan (the Nyquist column's
+ * x/0 included), with the same mu_live.  Asynchronous on hip_stream.
+ * Arguments, in this order: GLFER_E_ARG for a NULL plan; for a plan that is not MTM or has N > 16384; then GLFER_OK with
+ * nothing launched for nstreams == 0 or nframes == 0; then GLFER_E_ARG for a NULL d_streams or d_ftest, a frame past the
+ * stream, nframes > 0x7fffffff, an odd stream_pitch with s16 / u8 samples (the reason given at
+ * glfer_hip_spectrogram_batch_device: every stream of a batch must meet the same kernels), or sizes that overflow size_t.
+ * N = 256 .. 16384 run the whole batch in the launches one stream takes: the F statistic's kernel carries the stream as
+ * blockIdx.y, in both of its forms (one sequence per transform, and two separated through the mirror bins; the form is chosen
+ * as the single entry chooses it, GLFER_FTEST_PAIRED read per call, paired from N = 2048 by default), and mean removal
+ * (sub_mean 1 and 2) goes through the batch's corrected copies and hop-means tables, so the launch count does not grow with
+ * nstreams.  A batch above the device's grid y limit (65 535) is cut into chunks of that many streams.  Scratch under mean
+ * removal: the corrected float copies of all streams' hops at once.  N < 256 (the spectra go through memory and a per-bin
+ * epilogue forms the statistic) goes stream by stream inside the call, the single entry's launches per stream.
+ * The F-test tables are made by the first F call on a plan, whichever entry it is; the plan is left as the single entry leaves it.
+ * Not built: the multitaper rows and F from one pass over the samples (two calls), LMP / HP-ARMA batches in one launch set,
+ * ragged batches (one length per stream), batched host / WAV entries. */
+int glfer_hip_mtm_ftest_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams, size_t stream_pitch,
+                                     size_t nsamples, size_t first_frame, size_t nframes, float *d_ftest, int mu_live,
+                                     void *hip_stream);
 
 /* Host-buffer entry: h_stream goes to the device in chunks through a two-deep ring (two pinned
  * sample buffers, two device buffers each way; uploads on one stream, kernels and downloads on two:
