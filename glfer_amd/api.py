@@ -53,6 +53,8 @@ EXPORTS = [
     # many streams per call
     "glfer_hip_spectrogram_batch_device", "glfer_hip_avg_batch_device", "glfer_hip_spectrogram_avg_batch_device",
     "glfer_hip_waterfall_batch_device", "glfer_hip_mtm_ftest_batch_device",
+    # the multitaper rows and F from one pass over the samples
+    "glfer_hip_mtm_rows_ftest_device", "glfer_hip_mtm_rows_ftest_batch_device",
 ]
 
 
@@ -159,6 +161,10 @@ def lib():
     L.glfer_hip_mtm_ftest_device.argtypes = [vp, vp, sz, sz, sz, vp, C.c_int, vp]
     if hasattr(L, "glfer_hip_mtm_ftest_batch_device"):  # (absent from older builds loaded through GLFER_LIB_PATH for A/B runs)
         L.glfer_hip_mtm_ftest_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, C.c_int, vp]
+    if hasattr(L, "glfer_hip_mtm_rows_ftest_device"):
+        L.glfer_hip_mtm_rows_ftest_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, C.c_int, vp]
+    if hasattr(L, "glfer_hip_mtm_rows_ftest_batch_device"):
+        L.glfer_hip_mtm_rows_ftest_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, C.c_int, vp]
     L.glfer_hip_host_alloc.argtypes = [sz]
     L.glfer_hip_host_alloc.restype = vp
     L.glfer_hip_host_free.argtypes = [vp]
@@ -483,6 +489,51 @@ class Spectrogram:
                                                       first_frame, nframes, C.c_void_p(out.data_ptr()), 1 if mu_live else 0, st),
                "glfer_hip_mtm_ftest_batch_device")
         return out
+
+    def rows_ftest(self, stream, first_frame=0, nframes=None, mu_live=True, out=None):
+        """The multitaper rows and the harmonic F rows of the same frames from one pass over the samples
+        (glfer_hip_mtm_rows_ftest_device): (psd [nframes][pitch], ftest [nframes][bins]).  The F rows hold the bits of
+        ftest(stream, ...); the PSD rows are run(stream, ...)'s to float rounding.  out: a (psd, ftest) pair to write into.
+        stream as ftest takes it; launched on torch's current stream."""
+        torch = _torch()
+        assert stream.is_cuda and stream.dim() == 1 and stream.is_contiguous()
+        assert stream.dtype == self._sample_dtype(), (stream.dtype, self._sample_dtype())
+        if nframes is None:
+            nframes = self.num_frames(stream.numel()) - first_frame
+        if out is None:
+            out = (torch.empty((nframes, self.pitch), dtype=torch.float32, device=stream.device),
+                   torch.empty((nframes, self.bins), dtype=torch.float32, device=stream.device))
+        psd, ft = out
+        for o, w in ((psd, self.pitch), (ft, self.bins)):
+            assert o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and o.numel() >= nframes * w
+        st = C.c_void_p(torch.cuda.current_stream(stream.device).cuda_stream)
+        _check(lib().glfer_hip_mtm_rows_ftest_device(self._h, C.c_void_p(stream.data_ptr()), stream.numel(), first_frame, nframes,
+                                                     C.c_void_p(psd.data_ptr()), C.c_void_p(ft.data_ptr()), 1 if mu_live else 0, st),
+               "glfer_hip_mtm_rows_ftest_device")
+        return psd, ft
+
+    def rows_ftest_batch(self, streams, first_frame=0, nframes=None, mu_live=True, out=None):
+        """rows_ftest for many streams in one call (glfer_hip_mtm_rows_ftest_batch_device).  streams as ftest_batch takes them:
+        2-D [B, T] on this GPU, of the plan's sample dtype, stride(1) == 1.  Returns (psd [B][nframes][pitch],
+        ftest [B][nframes][bins]); both hold, for stream b, the bits of rows_ftest(streams[b])."""
+        torch = _torch()
+        assert streams.is_cuda and streams.dim() == 2 and (streams.stride(1) == 1 or streams.size(1) <= 1)
+        assert streams.dtype == self._sample_dtype(), (streams.dtype, self._sample_dtype())
+        nb, total = streams.size(0), streams.size(1)
+        if nframes is None:
+            nframes = self.num_frames(total) - first_frame
+        if out is None:
+            out = (torch.empty((nb, nframes, self.pitch), dtype=torch.float32, device=streams.device),
+                   torch.empty((nb, nframes, self.bins), dtype=torch.float32, device=streams.device))
+        psd, ft = out
+        for o, w in ((psd, self.pitch), (ft, self.bins)):
+            assert o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and o.numel() >= nb * nframes * w
+        st = C.c_void_p(torch.cuda.current_stream(streams.device).cuda_stream)
+        _check(lib().glfer_hip_mtm_rows_ftest_batch_device(self._h, C.c_void_p(streams.data_ptr()), nb, streams.stride(0), total,
+                                                           first_frame, nframes, C.c_void_p(psd.data_ptr()), C.c_void_p(ft.data_ptr()),
+                                                           1 if mu_live else 0, st),
+               "glfer_hip_mtm_rows_ftest_batch_device")
+        return psd, ft
 
     def prepare(self, stream, first_frame=0, nframes=None):
         """prepare_audio's inbuf_fft (fft.c:66-165) for every frame: float tensor [nframes][n]."""

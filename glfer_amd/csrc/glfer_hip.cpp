@@ -53,6 +53,9 @@ extern "C" hipError_t glfer_launch_lmp(const float *rows, long long row0, long l
                                        int nl, float *out, hipStream_t st);
 extern "C" hipError_t glfer_launch_ftest(const float *spec, size_t nframes, int n, int ntap, const double *U0,
                                          float sum_U0_sqr, int mu_live, float *ftest, hipStream_t st);
+extern "C" hipError_t glfer_launch_ftest_rows(const float *spec, size_t nframes, int n, int ntap, const double *U0,
+                                              float sum_U0_sqr, int mu_live, float *ftest, const float *cj, float *psd, int pitch,
+                                              hipStream_t st);
 extern "C" hipError_t glfer_launch_submean_tail_ex(const void *raw_last, const float *prev, float *out, int H, int fresh, int exact,
                                                    int fmt, hipStream_t st);
 extern "C" hipError_t glfer_launch_hop_means_seq(const void *in, float *means, int H, long long nhops, int fmt, hipStream_t st);
@@ -2263,9 +2266,13 @@ static int ftest_tables(glfer_hip_plan *p) {
     float *d = nullptr;
     double *du = nullptr;
     HIP_TRY(hipMalloc((void **)&d, taps.size() * sizeof(float)));
-    hipError_t e = hipMalloc((void **)&du, (size_t)T * sizeof(double));
+    // [U0: T doubles][c_j = 1 / (n (1 + sig_j)): T floats], the rows' weights of the rows-and-F entries (the tables above stay unscaled)
+    std::vector<float> cj((size_t)T);
+    for (int j = 0; j < T; j++) cj[j] = (float)(1.0 / ((double)n * (1.0 + p->sig[j])));
+    hipError_t e = hipMalloc((void **)&du, (size_t)T * (sizeof(double) + sizeof(float)));
     if (e == hipSuccess) e = hipMemcpy(d, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(du, p->U0.data(), (size_t)T * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(du + T, cj.data(), (size_t)T * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
       (void)hipFree(d);
       (void)hipFree(du);
@@ -2274,6 +2281,7 @@ static int ftest_tables(glfer_hip_plan *p) {
     p->d_ftaps_mu_first = d;
     p->d_ftaps = d + (size_t)2 * n;
     p->d_U0 = du;
+    p->d_rows_cj = reinterpret_cast<float *>(du + T);
     // the paired form's tables: two real sequences per N-point transform (re / im), each halved (X_a = (Z[k] + conj Z[N-k]) / 2)
     // hn = sum_j U0_j v_j / sum(U0^2) has the 2-norm 1 / sqrt(sum(U0^2)) against a taper's 1: sharing a transform with taper 0 as it is,
     // mu would come out of the separation with the rounding of a spectrum ~ sqrt(sum(U0^2)) times its size (up to 128 at N = 16384),
@@ -2324,13 +2332,18 @@ static void ftest_params(const glfer_hip_plan *p, SpectroParams &sp) {
 
 // N >= 256, one launch: every round of spectro16_kernel's FT form transforms the frame under one taper (or two sequences, the
 // paired form) and keeps what the statistic needs in registers (no spectrum goes through HBM).  sp: ftest_params with the stream set.
+// d_psd (the rows-and-F entries): the multitaper rows of the same frames at the plan's pitch, from the same rounds (the ROWS forms).
 static SpectroParams ftest_in_launch(const glfer_hip_plan *p, const SpectroParams &sp, size_t first, size_t nframes, float *d_ftest,
-                                     int mu_live) {
+                                     int mu_live, float *d_psd = nullptr) {
   const int n = p->n, T = p->ntapers;
   SpectroParams q = sp;
   q.frame0 = (long long)first;
   q.nframes = (int)nframes;
-  q.psd = nullptr;
+  q.psd = d_psd;
+  if (d_psd) {
+    q.pitch = p->pitch;
+    q.ft_cj = p->d_rows_cj;
+  }
   q.spec = nullptr;
   q.ftest = d_ftest;
   q.ft_U0 = p->d_U0;
@@ -2356,13 +2369,23 @@ static SpectroParams ftest_in_launch(const glfer_hip_plan *p, const SpectroParam
 // single-taper launch of spectro16_kernel per taper and one for hn), the statistic from a per-bin
 // epilogue (stats_kernels.hip).  Frames are processed in groups that keep the spectra scratch
 // under ~256 MiB.
+static int ftest_single(glfer_hip_plan *p, const void *d_stream, size_t first, size_t nframes, float *d_psd, float *d_ftest,
+                        int mu_live, hipStream_t st);
+
 int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t nsamples, size_t first,
                                size_t nframes, float *d_ftest, int mu_live, void *hip_stream) {
   if (!p || !d_stream || (!d_ftest && nframes) || p->cfg.mode != GLFER_MODE_MTM) return GLFER_E_ARG;
   if (p->n > 16384) return GLFER_E_ARG;              // needs the packed form's spectrum output
   if (nframes == 0) return GLFER_OK;
   if ((first + nframes) > nsamples / (size_t)p->hop || nframes > 0x7fffffffu) return GLFER_E_ARG;
-  hipStream_t st = (hipStream_t)hip_stream;
+  return ftest_single(p, d_stream, first, nframes, nullptr, d_ftest, mu_live, (hipStream_t)hip_stream);
+}
+
+// The body of the single-stream F entries, arguments checked.  d_psd NULL: F alone (glfer_hip_mtm_ftest_device); else the multitaper
+// rows of the same frames too, at the plan's pitch (glfer_hip_mtm_rows_ftest_device) -- from the same rounds of the same launch at
+// N >= 256, from the same spectra in the per-bin epilogue below that.
+static int ftest_single(glfer_hip_plan *p, const void *d_stream, size_t first, size_t nframes, float *d_psd, float *d_ftest,
+                        int mu_live, hipStream_t st) {
   DeviceGuard guard(p->cfg.device);
   HIP_TRY(guard.error());
   const int n = p->n, T = p->ntapers;
@@ -2380,7 +2403,7 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t n
     rc = submean_scratch(p, sp, first, nframes, st, &scratch);
   }
   if (rc == GLFER_OK && n >= 256) {
-    const SpectroParams q = ftest_in_launch(p, sp, first, nframes, d_ftest, mu_live);
+    const SpectroParams q = ftest_in_launch(p, sp, first, nframes, d_ftest, mu_live, d_psd);
     hipError_t e = launch_packed(q, n, st);
     if (e != hipSuccess) rc = hip_fail(e, "ftest launch");
     if (scratch) glfer::scratch_free(scratch, st);
@@ -2408,7 +2431,10 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t n
       q.spec = spec + (size_t)j * g * n;
       e = launch_packed(q, n, st);
     }
-    if (e == hipSuccess)
+    if (e == hipSuccess && d_psd)
+      e = glfer_launch_ftest_rows(spec, g, n, T, p->d_U0, p->sum_U0_sqr, mu_live ? 1 : 0, d_ftest + done * (size_t)p->bins,
+                                  p->d_rows_cj, d_psd + done * (size_t)p->pitch, p->pitch, st);
+    else if (e == hipSuccess)
       e = glfer_launch_ftest(spec, g, n, T, p->d_U0, p->sum_U0_sqr, mu_live ? 1 : 0, d_ftest + done * (size_t)p->bins, st);
     if (e != hipSuccess) rc = hip_fail(e, "ftest launch");
   }
@@ -2421,29 +2447,74 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t n
 // glfer_hip_mtm_ftest_device over many streams (glfer_hip.h).  N >= 256: the launches of one stream -- the corrected copies under
 // mean removal (batch_submean_scratch), then spectro16_kernel's FT form with blockIdx.y as the stream, the form chosen as the
 // single entry chooses it -- so the launch count does not grow with the batch; below 256 the single entry, stream by stream.
-int glfer_hip_mtm_ftest_batch_device(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch,
-                                     size_t nsamples, size_t first, size_t nframes, float *d_ftest, int mu_live,
-                                     void *hip_stream) {
+// (The multitaper rows and F from one pass over the samples: glfer_hip_mtm_rows_ftest_device / _batch_device below, the same bodies.)
+static int ftest_batch(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch, size_t first, size_t nframes,
+                       float *d_psd, float *d_ftest, int mu_live, hipStream_t st);
+
+// The batched F entries' argument checks, in the order glfer_hip.h states.  want_psd: the rows-and-F entry (both outputs required;
+// its PSD rows lie at the plan's pitch, the wider of the two row sizes).
+static int ftest_batch_args(const glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch, size_t nsamples,
+                            size_t first, size_t nframes, const float *d_psd, bool want_psd, const float *d_ftest, bool *empty) {
+  *empty = false;
   if (!p) return GLFER_E_ARG;
   if (p->cfg.mode != GLFER_MODE_MTM || p->n > 16384) return GLFER_E_ARG;
-  if (nstreams == 0 || nframes == 0) return GLFER_OK;
-  if (!d_streams || !d_ftest) return GLFER_E_ARG;
+  if (nstreams == 0 || nframes == 0) {
+    *empty = true;
+    return GLFER_OK;
+  }
+  if (!d_streams || !d_ftest || (want_psd && !d_psd)) return GLFER_E_ARG;
   if ((first + nframes) > nsamples / (size_t)p->hop) return GLFER_E_ARG;   // frame past the stream
   if (nframes > 0x7fffffffu) return GLFER_E_ARG;
   const int fmt = p->cfg.sample_format;
   const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
   // (as glfer_hip_spectrogram_batch_device: every stream of a batch must see the same alignment)
   if (fmt != GLFER_FMT_F32 && (stream_pitch & 1)) return GLFER_E_ARG;
-  const size_t rows = (size_t)p->bins;
+  const size_t rows = want_psd ? (size_t)p->pitch : (size_t)p->bins;
   if (stream_pitch > (SIZE_MAX / esz) / nstreams || nframes > (SIZE_MAX / sizeof(float) / rows) / nstreams) return GLFER_E_ARG;
-  hipStream_t st = (hipStream_t)hip_stream;
+  return GLFER_OK;
+}
+
+int glfer_hip_mtm_ftest_batch_device(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch,
+                                     size_t nsamples, size_t first, size_t nframes, float *d_ftest, int mu_live,
+                                     void *hip_stream) {
+  bool empty = false;
+  const int rc = ftest_batch_args(p, d_streams, nstreams, stream_pitch, nsamples, first, nframes, nullptr, false, d_ftest, &empty);
+  if (rc != GLFER_OK || empty) return rc;
+  return ftest_batch(p, d_streams, nstreams, stream_pitch, first, nframes, nullptr, d_ftest, mu_live, (hipStream_t)hip_stream);
+}
+
+// The multitaper rows and the F rows of the same frames from one pass over the samples (glfer_hip.h).
+int glfer_hip_mtm_rows_ftest_device(glfer_hip_plan *p, const void *d_stream, size_t nsamples, size_t first, size_t nframes,
+                                    float *d_psd, float *d_ftest, int mu_live, void *hip_stream) {
+  bool empty = false;
+  const int rc = ftest_batch_args(p, d_stream, 1, 0, nsamples, first, nframes, d_psd, true, d_ftest, &empty);
+  if (rc != GLFER_OK || empty) return rc;
+  return ftest_single(p, d_stream, first, nframes, d_psd, d_ftest, mu_live, (hipStream_t)hip_stream);
+}
+
+int glfer_hip_mtm_rows_ftest_batch_device(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch,
+                                          size_t nsamples, size_t first, size_t nframes, float *d_psd, float *d_ftest, int mu_live,
+                                          void *hip_stream) {
+  bool empty = false;
+  const int rc = ftest_batch_args(p, d_streams, nstreams, stream_pitch, nsamples, first, nframes, d_psd, true, d_ftest, &empty);
+  if (rc != GLFER_OK || empty) return rc;
+  return ftest_batch(p, d_streams, nstreams, stream_pitch, first, nframes, d_psd, d_ftest, mu_live, (hipStream_t)hip_stream);
+}
+
+// The body of the batched F entries, arguments checked.  d_psd NULL: F alone; else stream b's multitaper rows at
+// d_psd + b * nframes * pitch beside its F rows, from the same launch (the ROWS forms carry a PSD stride next to the F stride).
+static int ftest_batch(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch, size_t first, size_t nframes,
+                       float *d_psd, float *d_ftest, int mu_live, hipStream_t st) {
+  const int fmt = p->cfg.sample_format;
+  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
   const char *base = static_cast<const char *>(d_streams);
-  const size_t ft_bs = nframes * rows;                       // floats from one stream's first F row to the next one's
+  const size_t ft_bs = nframes * (size_t)p->bins;            // floats from one stream's first F row to the next one's
+  const size_t psd_bs = nframes * (size_t)p->pitch;          // and from one stream's first PSD row to the next one's
   const int n = p->n;
   if (n < 256 || nstreams == 1) {
     for (size_t b = 0; b < nstreams; b++) {
-      const int rc = glfer_hip_mtm_ftest_device(p, base + b * stream_pitch * esz, nsamples, first, nframes, d_ftest + b * ft_bs, mu_live,
-                                                hip_stream);
+      const int rc = ftest_single(p, base + b * stream_pitch * esz, first, nframes, d_psd ? d_psd + b * psd_bs : nullptr,
+                                  d_ftest + b * ft_bs, mu_live, st);
       if (rc != GLFER_OK) return rc;
     }
     return GLFER_OK;
@@ -2472,8 +2543,9 @@ int glfer_hip_mtm_ftest_batch_device(glfer_hip_plan *p, const void *d_streams, s
       rc = batch_submean_scratch(p, sp, first, nframes, nb, st, &scratch);
     }
     if (rc == GLFER_OK) {
-      SpectroParams q = ftest_in_launch(p, sp, first, nframes, d_ftest + c0 * ft_bs, mu_live);
-      q.ftest_batch_stride = (long long)ft_bs;                  // (psd NULL, psd_batch_stride 0)
+      SpectroParams q = ftest_in_launch(p, sp, first, nframes, d_ftest + c0 * ft_bs, mu_live, d_psd ? d_psd + c0 * psd_bs : nullptr);
+      q.ftest_batch_stride = (long long)ft_bs;                  // (F alone: psd NULL, psd_batch_stride 0)
+      if (d_psd) q.psd_batch_stride = (long long)psd_bs;
       const hipError_t e = launch_packed(q, n, st);
       if (e != hipSuccess) rc = hip_fail(e, "ftest launch (batch)");
     }

@@ -138,6 +138,7 @@ struct glfer_hip_plan {
   float *d_ftaps2 = nullptr;        // the paired form (round 5): [ceil((ntapers+1)/2)][2n] with (hn_scale hn, taper 0), (taper 1, taper 2) ... as (re, im), halved;
   float *d_ftaps2_nomu = nullptr;   //   then [ceil(ntapers/2)][2n] with (taper 0, taper 1) ... (mu_live = 0); one allocation
   double *d_U0 = nullptr;           // [ntapers]
+  float *d_rows_cj = nullptr;       // [ntapers] 1 / (n (1 + sig_j)), in d_U0's allocation behind it: the rows' weights of the rows-and-F entries
   std::vector<double> U0;           // [ntapers]
   std::vector<float> hn;            // [n]
   float sum_U0_sqr = 0.0f;

@@ -38,6 +38,13 @@
 #endif
 #endif
 
+#ifndef GLFER16_ROWS_PAIRED_WPS
+/* the paired F form with the rows output: two wavefronts per SIMD.  At three (its F twin's) the nine row sums spill 20-30 more
+   registers than the twin does; measured at N = 4096, 5 tapers: 31.2-31.4 M frames/s at two against 30.6-30.7 at three
+   (profiles/rows_ftest_rate.txt, profiles/rows_ftest_kernel_resources.txt) */
+#define GLFER16_ROWS_PAIRED_WPS 2
+#endif
+
 #ifndef GLFER16_TW1_REGS
 #define GLFER16_TW1_REGS 1
 #endif
@@ -66,13 +73,19 @@ namespace glfer {
 // go through three packed transforms, two sequences each (re / im), and every pair is separated through the mirror bins in LDS:
 // with Z = FFT(a + i b), X_a[k] = (Z[k] + conj Z[N-k]) / 2 and X_b[k] = (Z[k] - conj Z[N-k]) / (2 i) (the halves ride in the tables).
 // The accumulation per taper, its order and its statement types are those of FT = 1.
-template <int LOGN, int FMT, bool GEN, int WPS = GLFER16_WAVES_PER_SIMD, int STG = GLFER16_STAGGER, int KM = 0, int FT = 0, int BAT = 0>
+// ROWS (with FT = 1 or 2): the multitaper rows of the same frames beside F (mtm.c:212-219) -- every taper's spectrum is in registers
+// already, so each taper's round also adds c_j |y_j[k]|^2, c_j = 1 / (N (1 + sig_j)) (SpectroParams::ft_cj), to a float sum per bin
+// k <= N/2 (nine of a lane's sixteen registers), stored at p.psd's pitch after the frame's last round.  Each taper has its own
+// real-input spectrum here (FT = 2: the separated X_a, X_b, never the hn sequence), so the PSD path's mirror fold is not needed.
+template <int LOGN, int FMT, bool GEN, int WPS = GLFER16_WAVES_PER_SIMD, int STG = GLFER16_STAGGER, int KM = 0, int FT = 0, int BAT = 0, int ROWS = 0>
 __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(SpectroParams p) {
   // BAT: the instantiations a batch launches (nbatch > 1) -- blockIdx.y is the stream; the single-stream ones are the code as it was
   if constexpr (BAT != 0) {
     glfer_batch_select(p);
-    if constexpr (FT != 0) p.ftest += (long long)blockIdx.y * p.ftest_batch_stride;   // (psd stays NULL: psd_batch_stride is 0)
+    // (F alone: psd stays NULL, psd_batch_stride is 0; ROWS: glfer_batch_select has moved psd on by psd_batch_stride)
+    if constexpr (FT != 0) p.ftest += (long long)blockIdx.y * p.ftest_batch_stride;
   }
+  static_assert(ROWS == 0 || FT != 0, "rows beside F: the F forms");
   static_assert(KM == 0 || (!GEN && (KM == 16 || KM == 8 || KM == 4)), "in-kernel mean removal: the plain path");
   static_assert(FT == 0 || !GEN, "F statistic: the plain path");
   constexpr int NH = KM > 0 ? 16 / KM : 1;
@@ -191,6 +204,7 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(S
 #pragma unroll
   for (int r = 0; r < 16; r++) acc[r] = 0.0f;
   float ftmur[FT ? 16 : 1], ftmui[FT ? 16 : 1], ftsum[FT ? 16 : 1];   // FT: mu (re, im) and the per-bin sum, by register
+  float ftrow[ROWS ? 16 : 1];                                          // ROWS: the weighted eigenspectrum sum (registers of bins <= N/2 only)
 
   while (true) {
     if constexpr (KM > 0) {
@@ -290,13 +304,17 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(S
           ftmur[rho] = xr * p.ft_mu_unscale;
           ftmui[rho] = xi * p.ft_mu_unscale;
           ftsum[rho] = 0.0f;
+          if constexpr (ROWS != 0) ftrow[rho] = 0.0f;
           return;
         }
         if (!p.ft_mu_live && seq == 0) {
           ftmur[rho] = 0.0f;
           ftmui[rho] = 0.0f;
           ftsum[rho] = 0.0f;
+          if constexpr (ROWS != 0) ftrow[rho] = 0.0f;
         }
+        if constexpr (ROWS != 0)                                   // (xi is an exact zero at k = 0 and k = N/2: Z[N-k] is Z[k] itself there)
+          ftrow[rho] = __builtin_fmaf(p.ft_cj[jt], __builtin_fmaf(xr, xr, xi * xi), ftrow[rho]);
         const double U0j = p.ft_U0[jt];
         {
 #pragma clang fp contract(off)
@@ -332,16 +350,29 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(S
       if (jt < 0) {
 #pragma unroll
         for (int r = 0; r < 16; r++) { ftmur[r] = zr[r]; ftmui[r] = zi[r]; ftsum[r] = 0.0f; }
+        if constexpr (ROWS != 0) {
+#pragma unroll
+          for (int r = 0; r < 16; r++) ftrow[r] = 0.0f;
+        }
       } else {
         if (!p.ft_mu_live && pair == 0) {
 #pragma unroll
           for (int r = 0; r < 16; r++) { ftmur[r] = 0.0f; ftmui[r] = 0.0f; ftsum[r] = 0.0f; }
+          if constexpr (ROWS != 0) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) ftrow[r] = 0.0f;
+          }
         }
         const double U0j = p.ft_U0[jt];
         static_for<0, 16>([&](auto rc) {
           constexpr int rho = decltype(rc)::value;
           constexpr int b = rho % B, qp = brev(rho / B, R);
           const int k = (int)t + T * (b + B * qp);
+          if constexpr (ROWS != 0 && b + B * qp <= 8) {
+            // fft_psd (fft.c:212-216) has no imaginary part at DC and Nyquist; the complex transform leaves its rounding there
+            const float im2 = (k == 0 || k == N / 2) ? 0.0f : zi[rho] * zi[rho];
+            ftrow[rho] = __builtin_fmaf(p.ft_cj[jt], __builtin_fmaf(zr[rho], zr[rho], im2), ftrow[rho]);
+          }
           {
 #pragma clang fp contract(off)
             // mtm.c:203-210: tmpr = ob[i] - mu[i]*U0[j] (double), ft (float) += tmpr*tmpr + tmpi*tmpi; bin 0 has no imaginary part
@@ -373,6 +404,17 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(S
             o[k] = (float)(num / ft);
           }
         });
+        if constexpr (ROWS != 0) {                                 // the frame's multitaper row, at the plan's pitch
+          float *row = p.psd + (size_t)f * (size_t)p.pitch;
+          static_for<0, 16>([&](auto rc) {
+            constexpr int rho = decltype(rc)::value;
+            constexpr int b = rho % B, qp = brev(rho / B, R);
+            if constexpr (b + B * qp <= 8) {
+              const int k = (int)t + T * (b + B * qp);
+              if (k <= N / 2) row[k] = ftrow[rho];
+            }
+          });
+        }
       }
     }
     if constexpr (GEN) {
@@ -576,6 +618,13 @@ static hipError_t launch16_fmt(const SpectroParams &p, hipStream_t st) {
     // the F statistic: one taper per round (two spill-free wavefronts per SIMD: mu and the sums are 48 more registers)
     if (p.nonlin || p.spec || p.mean_inkernel || !p.ft_U0) return hipErrorInvalidValue;
     // (the paired form keeps mu and the sums for the bins k <= N/2 only -- 27 registers, not 48: three wavefronts per SIMD)
+    if (p.psd) {
+      // the multitaper rows beside F (glfer_hip_mtm_rows_ftest_device): nine more registers a lane for the rows' sums
+      if (!p.ft_cj) return hipErrorInvalidValue;
+      if (p.ft_nseq > 0) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_ROWS_PAIRED_WPS, GLFER16_STAGGER, 0, 2, BAT, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      else hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1, BAT, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      return hipGetLastError();
+    }
     if (p.ft_nseq > 0) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 3, GLFER16_STAGGER, 0, 2, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     else hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     return hipGetLastError();

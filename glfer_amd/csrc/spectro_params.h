@@ -106,6 +106,10 @@ struct SpectroParams {
   long long avg_ret_batch_stride;   /* doubles from one stream's first return values (avg_ret) to the next one's               */
   long long ftest_batch_stride; /* floats from one stream's first F row (ftest) to the next one's (glfer_hip_mtm_ftest_batch_device:
                                    psd NULL and psd_batch_stride 0 there); spectro16_kernel's FT forms add it at entry          */
+  /* the multitaper rows beside F (glfer_hip_mtm_rows_ftest_device): psd != NULL with ftest, pitch and psd_batch_stride as for the rows */
+  const float *ft_cj;      /* device: [ntap], 1 / (N (1 + sig_j)): the weight of taper j's |y_j|^2 in the row (mtm.c:212-219, fft.c:212-216).
+                              The F tables hold the tapers unscaled, so the rows' weights ride here; read by the ROWS forms only.
+                              (Last in the block: every earlier member keeps its offset.)                                            */
 };
 
 /* spectro16y.hip's half-table form (N = 4096, T = 256 lanes, five tapers).  In pass 0 lane t = 16 j + p holds the samples

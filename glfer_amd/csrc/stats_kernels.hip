@@ -213,9 +213,13 @@ __global__ __launch_bounds__(256) void lmp_ring_any_kernel(const float *__restri
 // One thread per (frame, bin).  spec: [ntap + 1][nframes][n] halfcomplex spectra (fft_radix2.c
 // layout) of the frame under taper j, the last one under hn (mu); mu_live = 0: mu is all zeros (the
 // reference build without FFTW never writes it, mtm.c:173).
+// ROWS: the multitaper row of the frame too (mtm.c:212-219 over fft_psd, fft.c:212-216), from the same spectra:
+// psd[fi][i] = sum_j cj[j] |y_j[i]|^2 with cj[j] = 1 / (n (1 + sig_j)), rows `pitch` floats apart (glfer_hip_mtm_rows_ftest_device).
+template <bool ROWS>
 __global__ __launch_bounds__(256) void ftest_kernel(const float *__restrict__ spec, long long nframes, int n, int ntap,
                                                     const double *__restrict__ U0, float sum_U0_sqr, int mu_live,
-                                                    float *__restrict__ ftest) {
+                                                    float *__restrict__ ftest, const float *__restrict__ cj, float *__restrict__ psd,
+                                                    int pitch) {
   const long long fi = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
   const int bins = n / 2 + 1;
@@ -243,6 +247,15 @@ __global__ __launch_bounds__(256) void ftest_kernel(const float *__restrict__ sp
   if (i == 0) num_ftest = k * (mur * mur) * sum_U0_sqr;            // mtm.c:222-223
   else num_ftest = k * (mur * mur + mui * mui) * sum_U0_sqr;       // mtm.c:225, 230 (the Nyquist bin counts mu[n/2] twice)
   ftest[(size_t)fi * bins + i] = num_ftest / ft;
+  if constexpr (ROWS) {
+    float row = 0.0f;
+    for (int j = 0; j < ntap; j++) {
+      const float *ob = spec + (size_t)j * fstride + (size_t)fi * n;
+      const float re = ob[i], im = (i == 0 || 2 * i == n) ? 0.0f : ob[n - i];     // no imaginary part at DC and Nyquist
+      row += cj[j] * (re * re + im * im);
+    }
+    psd[(size_t)fi * (size_t)pitch + i] = row;
+  }
 }
 
 // prepare_audio's output (fft.c:98-156) for frames [frame0, frame0 + nframes): history / zero
@@ -355,8 +368,19 @@ extern "C" hipError_t glfer_launch_ftest(const float *spec, size_t nframes, int 
                                          float sum_U0_sqr, int mu_live, float *ftest, hipStream_t st) {
   if (nframes == 0) return hipSuccess;
   if (nframes > 65535 || ntap < 1) return hipErrorInvalidValue;    // the caller chunks the frames
-  hipLaunchKernelGGL(ftest_kernel, dim3((unsigned)((n / 2 + 1 + 255) / 256), (unsigned)nframes), dim3(256), 0, st, spec,
-                     (long long)nframes, n, ntap, U0, sum_U0_sqr, mu_live, ftest);
+  hipLaunchKernelGGL(ftest_kernel<false>, dim3((unsigned)((n / 2 + 1 + 255) / 256), (unsigned)nframes), dim3(256), 0, st, spec,
+                     (long long)nframes, n, ntap, U0, sum_U0_sqr, mu_live, ftest, (const float *)nullptr, (float *)nullptr, 0);
+  return hipGetLastError();
+}
+
+// the same with the multitaper rows of the frames beside F (psd rows `pitch` floats apart, pitch >= n/2+1)
+extern "C" hipError_t glfer_launch_ftest_rows(const float *spec, size_t nframes, int n, int ntap, const double *U0,
+                                              float sum_U0_sqr, int mu_live, float *ftest, const float *cj, float *psd, int pitch,
+                                              hipStream_t st) {
+  if (nframes == 0) return hipSuccess;
+  if (nframes > 65535 || ntap < 1 || !cj || !psd || pitch < n / 2 + 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ftest_kernel<true>, dim3((unsigned)((n / 2 + 1 + 255) / 256), (unsigned)nframes), dim3(256), 0, st, spec,
+                     (long long)nframes, n, ntap, U0, sum_U0_sqr, mu_live, ftest, cj, psd, pitch);
   return hipGetLastError();
 }
 

@@ -288,11 +288,41 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *plan, const void *d_stream, size_
  * removal: the corrected float copies of all streams' hops at once.  N < 256 (the spectra go through memory and a per-bin
  * epilogue forms the statistic) goes stream by stream inside the call, the single entry's launches per stream.
  * The F-test tables are made by the first F call on a plan, whichever entry it is; the plan is left as the single entry leaves it.
- * Not built: the multitaper rows and F from one pass over the samples (two calls), LMP / HP-ARMA batches in one launch set,
- * ragged batches (one length per stream), batched host / WAV entries. */
+ * The multitaper rows and F from one pass over the samples: glfer_hip_mtm_rows_ftest_device and its batch form below.
+ * Not built: LMP / HP-ARMA batches in one launch set, ragged batches (one length per stream), batched host / WAV entries. */
 int glfer_hip_mtm_ftest_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams, size_t stream_pitch,
                                      size_t nsamples, size_t first_frame, size_t nframes, float *d_ftest, int mu_live,
                                      void *hip_stream);
+
+/* The two things mtm_do computes from the same tapered transforms of a frame (mtm.c:154-239) in one call and one pass over
+ * the samples: the weighted eigenspectrum sum (mtm.c:212-219: the rows glfer_hip_spectrogram_device writes for an MTM plan)
+ * and the harmonic F statistic (glfer_hip_mtm_ftest_device).  Every sample is read once, mean removal runs once and every
+ * taper's transform is computed once; a caller who wants one of the two has the entries above.
+ *   d_psd   : device, [nframes][cfg.psd_pitch or N/2+1] floats, laid out as glfer_hip_spectrogram_device lays its rows out;
+ *             the floats between N/2+1 and the pitch are not touched
+ *   d_ftest : device, [nframes][N/2+1] floats, dense, as in glfer_hip_mtm_ftest_device
+ * Both are required.  MTM plans only, N <= 16384.
+ * The F rows are bit for bit glfer_hip_mtm_ftest_device's for the same call (same mu_live, same GLFER_FTEST_PAIRED).  The PSD
+ * rows are sum_j |y_j|^2 / (N (1 + sig_j)) taken from the F transforms -- each taper's own real-input spectrum, summed in float
+ * in taper order -- so they agree with glfer_hip_spectrogram_device's rows to float rounding, not bit for bit (that entry packs
+ * two tapers per transform with the weights folded into its tables).
+ * N = 256 .. 16384: one launch; each taper's round of the F kernel also adds its weighted |y_j|^2 to a per-bin sum in
+ * registers, in both forms of that kernel.  N < 256: the spectra go through memory as for F, and the per-bin epilogue forms
+ * the rows from them too.  Mean removal, history_mode and frame ranges as in the F entry.
+ * The batch form takes the streams as glfer_hip_mtm_ftest_batch_device does (stream b at d_streams + b * stream_pitch, zero
+ * history); stream b's PSD rows start at d_psd + (b * nframes) * pitch, its F rows at d_ftest + (b * nframes) * (N/2+1), and
+ * both hold the bits of the single entry for that stream.  N >= 256: the launches of one stream (blockIdx.y is the stream;
+ * chunks of the grid's y limit); N < 256: stream by stream.
+ * Arguments (both entries; the single one as a batch of one stream), in this order: GLFER_E_ARG for a NULL plan; for a plan
+ * that is not MTM or has N > 16384; then GLFER_OK with nothing launched for nstreams == 0 or nframes == 0; then GLFER_E_ARG
+ * for a NULL d_stream(s), d_psd or d_ftest, a frame past the stream, nframes > 0x7fffffff, an odd stream_pitch with s16 / u8
+ * samples (batch), or sizes that overflow size_t.
+ * The F-test tables are made by the first F call on a plan, whichever entry it is; the plan is left as the F entry leaves it. */
+int glfer_hip_mtm_rows_ftest_device(glfer_hip_plan *plan, const void *d_stream, size_t nsamples, size_t first_frame,
+                                    size_t nframes, float *d_psd, float *d_ftest, int mu_live, void *hip_stream);
+int glfer_hip_mtm_rows_ftest_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams, size_t stream_pitch,
+                                          size_t nsamples, size_t first_frame, size_t nframes, float *d_psd, float *d_ftest,
+                                          int mu_live, void *hip_stream);
 
 /* Host-buffer entry: h_stream goes to the device in chunks through a two-deep ring (two pinned
  * sample buffers, two device buffers each way; uploads on one stream, kernels and downloads on two:
