@@ -55,6 +55,8 @@ EXPORTS = [
     "glfer_hip_waterfall_batch_device", "glfer_hip_mtm_ftest_batch_device",
     # the multitaper rows and F from one pass over the samples
     "glfer_hip_mtm_rows_ftest_device", "glfer_hip_mtm_rows_ftest_batch_device",
+    # streams of unequal length in one call
+    "glfer_hip_spectrogram_ragged_device", "glfer_hip_ragged_frames",
 ]
 
 
@@ -165,6 +167,11 @@ def lib():
         L.glfer_hip_mtm_rows_ftest_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, C.c_int, vp]
     if hasattr(L, "glfer_hip_mtm_rows_ftest_batch_device"):
         L.glfer_hip_mtm_rows_ftest_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, C.c_int, vp]
+    if hasattr(L, "glfer_hip_spectrogram_ragged_device"):
+        L.glfer_hip_spectrogram_ragged_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    if hasattr(L, "glfer_hip_ragged_frames"):
+        L.glfer_hip_ragged_frames.argtypes = [vp, sz, vp, vp]
+        L.glfer_hip_ragged_frames.restype = sz
     L.glfer_hip_host_alloc.argtypes = [sz]
     L.glfer_hip_host_alloc.restype = vp
     L.glfer_hip_host_free.argtypes = [vp]
@@ -394,6 +401,59 @@ class Spectrogram:
                                                         first_frame, nframes, C.c_void_p(out.data_ptr()), st),
                "glfer_hip_spectrogram_batch_device")
         return out
+
+    def ragged_frames(self, lengths):
+        """(total rows, row_starts int64 [len(lengths) + 1]) of a ragged call over streams of these lengths, in samples
+        (glfer_hip_ragged_frames; no device involved)."""
+        lens = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
+        starts = np.zeros(lens.size + 1, np.uint64)
+        total = lib().glfer_hip_ragged_frames(self._h, lens.size, lens.ctypes.data, starts.ctypes.data)
+        return int(total), starts.astype(np.int64)
+
+    def run_ragged(self, samples, offsets, lengths, out=None):
+        """Streams of unequal length in one call (glfer_hip_spectrogram_ragged_device).  samples: 1-D torch tensor of the plan's
+        sample dtype on this GPU; stream b is samples[offsets[b] : offsets[b] + lengths[b]] (any order, gaps and overlaps
+        allowed; even offsets for s16 / u8).  Returns (psd [sum of frames][pitch], row_starts): stream b's rows are
+        psd[row_starts[b] : row_starts[b + 1]] and equal run(samples[offsets[b] : offsets[b] + lengths[b]]); row_starts is a
+        numpy int64 array of len(offsets) + 1.  Launched on torch's current stream."""
+        torch = _torch()
+        assert samples.is_cuda and samples.dim() == 1 and samples.is_contiguous()
+        assert samples.dtype == self._sample_dtype(), (samples.dtype, self._sample_dtype())
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        lens = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
+        assert offs.size == lens.size
+        total, _ = self.ragged_frames(lens)
+        if total == 2 ** 64 - 1:
+            raise GlferHipError("run_ragged: the row count overflows")
+        # (a stream past the tensor's end is the caller's error, as in C; checked here because it is cheap)
+        if lens.size:
+            assert max(int(o) + int(n) for o, n in zip(offs, lens)) <= samples.numel(), "a stream reaches past `samples`"
+        if out is None:
+            out = torch.empty((total, self.pitch), dtype=torch.float32, device=samples.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= total * self.pitch
+        starts = np.zeros(lens.size + 1, np.uint64)
+        st = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+        _check(lib().glfer_hip_spectrogram_ragged_device(self._h, C.c_void_p(samples.data_ptr()), lens.size, offs.ctypes.data,
+                                                         lens.ctypes.data, C.c_void_p(out.data_ptr()), starts.ctypes.data, st),
+               "glfer_hip_spectrogram_ragged_device")
+        return out, starts.astype(np.int64)
+
+    def run_list(self, streams):
+        """streams: a list of 1-D torch tensors of the plan's sample dtype on this GPU.  Concatenates them on the device (every
+        stream at an even offset, which the integer formats need) and returns the list of per-stream row views
+        [frames_b][pitch] of one run_ragged call."""
+        torch = _torch()
+        assert len(streams) > 0
+        offs, at = [], 0
+        for t in streams:
+            assert t.dim() == 1 and t.dtype == self._sample_dtype()
+            offs.append(at)
+            at += t.numel() + (t.numel() & 1)
+        buf = torch.zeros(max(at, 1), dtype=self._sample_dtype(), device=streams[0].device)
+        for o, t in zip(offs, streams):
+            buf[o:o + t.numel()] = t
+        psd, starts = self.run_ragged(buf, offs, [t.numel() for t in streams])
+        return [psd[int(starts[b]):int(starts[b + 1])] for b in range(len(streams))]
 
     def run_avg(self, stream, avg_mode, depth, minbin, maxbin, max0=0, n_out=None, want_psd=False, want_ret=True,
                 first_frame=0, nframes=None):

@@ -1411,28 +1411,32 @@ extern "C" hipError_t glfer_launch_spectro_small(const SpectroParams *p, int n, 
 extern "C" hipError_t glfer_launch_spectro16w_n15(const SpectroParams *p, hipStream_t st);
 extern "C" hipError_t glfer_launch_spectro_big(const SpectroParams *p, int n, hipStream_t st);
 
+// a launcher of N = 256 .. 16384 and its ragged twin (the same source compiled with GLFER_RAGGED: the stream from sp.ragged)
+#define GLFER_LAUNCH16(kind, logn, sp) \
+  ((sp).ragged ? glfer_launch_##kind##_ragged_n##logn(&(sp), st) : glfer_launch_##kind##_n##logn(&(sp), st))
+
 static hipError_t launch_packed(const SpectroParams &sp, int n, hipStream_t st) {
   if (n < 256) return glfer_launch_spectro_small(&sp, n, sp.taps, st);   // the same role below the 16-points-per-lane range
   switch (n) {
-    case 256: return glfer_launch_spectro16_n8(&sp, st);
-    case 512: return glfer_launch_spectro16_n9(&sp, st);
-    case 1024: return glfer_launch_spectro16_n10(&sp, st);
-    case 2048: return glfer_launch_spectro16_n11(&sp, st);
-    case 4096: return glfer_launch_spectro16_n12(&sp, st);
-    case 8192: return glfer_launch_spectro16_n13(&sp, st);
-    case 16384: return glfer_launch_spectro16_n14(&sp, st);
+    case 256: return GLFER_LAUNCH16(spectro16, 8, sp);
+    case 512: return GLFER_LAUNCH16(spectro16, 9, sp);
+    case 1024: return GLFER_LAUNCH16(spectro16, 10, sp);
+    case 2048: return GLFER_LAUNCH16(spectro16, 11, sp);
+    case 4096: return GLFER_LAUNCH16(spectro16, 12, sp);
+    case 8192: return GLFER_LAUNCH16(spectro16, 13, sp);
+    case 16384: return GLFER_LAUNCH16(spectro16, 14, sp);
   }
   return hipErrorInvalidValue;
 }
 
 static hipError_t launch_real_input(const SpectroParams &sp, int n, hipStream_t st) {
   switch (n) {
-    case 512: return glfer_launch_spectro16h_n9(&sp, st);
-    case 1024: return glfer_launch_spectro16h_n10(&sp, st);
-    case 2048: return glfer_launch_spectro16h_n11(&sp, st);
-    case 4096: return glfer_launch_spectro16h_n12(&sp, st);
-    case 8192: return glfer_launch_spectro16h_n13(&sp, st);
-    case 16384: return glfer_launch_spectro16h_n14(&sp, st);
+    case 512: return GLFER_LAUNCH16(spectro16h, 9, sp);
+    case 1024: return GLFER_LAUNCH16(spectro16h, 10, sp);
+    case 2048: return GLFER_LAUNCH16(spectro16h, 11, sp);
+    case 4096: return GLFER_LAUNCH16(spectro16h, 12, sp);
+    case 8192: return GLFER_LAUNCH16(spectro16h, 13, sp);
+    case 16384: return GLFER_LAUNCH16(spectro16h, 14, sp);
   }
   return hipErrorInvalidValue;
 }
@@ -1448,10 +1452,10 @@ static int form_override();
 
 static hipError_t launch_wave_private(const SpectroParams &sp, int n, hipStream_t st) {
   switch (n) {
-    case 2048: return glfer_launch_spectro16w_n11(&sp, st);
-    case 4096: return glfer_launch_spectro16w_n12(&sp, st);
-    case 8192: return glfer_launch_spectro16w_n13(&sp, st);
-    case 16384: return glfer_launch_spectro16w_n14(&sp, st);
+    case 2048: return GLFER_LAUNCH16(spectro16w, 11, sp);
+    case 4096: return GLFER_LAUNCH16(spectro16w, 12, sp);
+    case 8192: return GLFER_LAUNCH16(spectro16w, 13, sp);
+    case 16384: return GLFER_LAUNCH16(spectro16w, 14, sp);
     // N = 32768: the two-kernel form is the faster one (profiles/r02_big_blocks.txt); spectro16w.hip's single-kernel
     // form keeps the halfcomplex spectrum output and GLFER_FORM=w
     case 32768: return (sp.spec || form_override() == 'w') ? glfer_launch_spectro16w_n15(&sp, st) : glfer_launch_spectro_big(&sp, n, st);
@@ -1494,18 +1498,18 @@ static int y_queue_chunk() {
 static hipError_t launch_y(SpectroParams &q, hipStream_t st) {
   q.yq_counter = nullptr;
   glfer_yqueue *yq = q.yq;
-  if (!yq || q.mean_inkernel || q.nbatch > 1 || y_queue_off() || st == hipStreamPerThread) return glfer_launch_spectro16y_n12(&q, st);
+  if (!yq || q.mean_inkernel || q.nbatch > 1 || y_queue_off() || st == hipStreamPerThread) return GLFER_LAUNCH16(spectro16y, 12, q);
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
     (void)hipGetLastError();
-    return glfer_launch_spectro16y_n12(&q, st);
+    return GLFER_LAUNCH16(spectro16y, 12, q);
   }
-  if (cs != hipStreamCaptureStatusNone) return glfer_launch_spectro16y_n12(&q, st);
+  if (cs != hipStreamCaptureStatusNone) return GLFER_LAUNCH16(spectro16y, 12, q);
   std::lock_guard<std::mutex> lock(yq->mu);
   int slot = 0;
   while (slot < yq->used && yq->owner[slot] != st) slot++;
   if (slot == yq->used) {
-    if (slot == glfer_yqueue::SLOTS) return glfer_launch_spectro16y_n12(&q, st);
+    if (slot == glfer_yqueue::SLOTS) return GLFER_LAUNCH16(spectro16y, 12, q);
     yq->owner[yq->used++] = st;
   }
   q.yq_counter = yq->d_counters + (size_t)slot * glfer_yqueue::PITCH;
@@ -1524,16 +1528,16 @@ static hipError_t launch_shared_odd(const SpectroParams &sp, int n, hipStream_t 
   }
   if (sp.ltaps) {                      // taper half tables resident in LDS
     switch (n) {
-      case 256: return glfer_launch_spectro16xl_n8(&sp, st);
-      case 512: return glfer_launch_spectro16xl_n9(&sp, st);
-      case 1024: return glfer_launch_spectro16xl_n10(&sp, st);
-      case 2048: return glfer_launch_spectro16xl_n11(&sp, st);
+      case 256: return GLFER_LAUNCH16(spectro16xl, 8, sp);
+      case 512: return GLFER_LAUNCH16(spectro16xl, 9, sp);
+      case 1024: return GLFER_LAUNCH16(spectro16xl, 10, sp);
+      case 2048: return GLFER_LAUNCH16(spectro16xl, 11, sp);
     }
   }
   switch (n) {
-    case 256: return glfer_launch_spectro16x_n8(&sp, st);
-    case 512: return glfer_launch_spectro16x_n9(&sp, st);
-    case 1024: return glfer_launch_spectro16x_n10(&sp, st);
+    case 256: return GLFER_LAUNCH16(spectro16x, 8, sp);
+    case 512: return GLFER_LAUNCH16(spectro16x, 9, sp);
+    case 1024: return GLFER_LAUNCH16(spectro16x, 10, sp);
   }
   return hipErrorInvalidValue;
 }
@@ -2209,6 +2213,347 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
         if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch)");
       }
       if (scratch) glfer::scratch_free(scratch, st);
+    }
+    if (rc != GLFER_OK) return rc;
+  }
+  return GLFER_OK;
+}
+
+}  // extern "C"
+
+// Streams of unequal length in one call (glfer_hip.h).  Every launch the single-stream entry would make for a stream -- the
+// packed kernel for its first frames and for the frames off the frame groups, the route's kernel for its body, the hop means and
+// the corrected copies of the mean removal -- is made ONCE for all streams: blockIdx.y indexes a table (GlferRaggedEntry /
+// GlferRaggedHops, spectro_params.h) that holds each stream's samples, rows, means and its own frames of that launch, cut as
+// launch_by_n and launch_mean_inkernel cut them.  The tables are built here and go to stream-ordered scratch.
+namespace {
+
+struct RaggedStream {
+  size_t off;        // first sample, in elements from the call's d_samples
+  size_t frames;     // lengths[b] / hop
+  size_t row;        // first row of d_psd
+};
+
+// one ragged launch set over the streams of a chunk (nb <= the grid's y limit, >= 2)
+struct RaggedChunk {
+  glfer_hip_plan *p;
+  const RaggedStream *s;
+  unsigned nb;
+  const char *base;    // the call's d_samples
+  float *d_psd;
+  hipStream_t st;
+  size_t esz;
+  size_t first_inside;
+
+  // a table to the device: stream-ordered scratch and an async copy (pageable source: hipMemcpyAsync stages it before returning)
+  template <typename T>
+  int upload(const std::vector<T> &host, T **dev) const {
+    HIP_TRY(glfer::scratch_malloc((void **)dev, host.size() * sizeof(T), st));
+    const hipError_t e = hipMemcpyAsync(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) {
+      glfer::scratch_free(*dev, st);
+      *dev = nullptr;
+      return hip_fail(e, "ragged table upload");
+    }
+    return GLFER_OK;
+  }
+
+  // the frame groups of a route's kernel (launch_by_n, launch_mean_inkernel)
+  size_t groups(BodyRoute r) const {
+    const size_t lanes = (size_t)p->n / 16;
+    return r == ROUTE_SHARED_ODD ? 2 * (lanes >= 256 ? 1 : 256 / lanes) : 1;
+  }
+
+  // one launch over a table; sp: everything but frame0 / nframes / nbatch / ragged.  r: the kernel (ROUTE_PACKED: the packed one)
+  int launch(SpectroParams sp, const std::vector<GlferRaggedEntry> &tab, BodyRoute r) const {
+    long long f0 = -1;
+    int longest = 0;
+    for (const GlferRaggedEntry &e : tab)
+      if (e.nframes > 0) {
+        if (f0 < 0 || e.frame0 < f0) f0 = e.frame0;
+        longest = std::max(longest, e.nframes);
+      }
+    if (longest == 0) return GLFER_OK;
+    GlferRaggedEntry *d_tab = nullptr;
+    const int rc = upload(tab, &d_tab);
+    if (rc != GLFER_OK) return rc;
+    sp.frame0 = f0;                  // (the launchers check the range and size the grid with these; the kernels read the table)
+    sp.nframes = longest;
+    sp.nbatch = (int)nb;
+    sp.ragged = d_tab;
+    hipError_t e;
+    if (r == ROUTE_PACKED) e = launch_packed(sp, p->n, st);
+    else if (r == ROUTE_WAVE_PRIVATE) e = launch_wave_private(sp, p->n, st);
+    else e = r == ROUTE_REAL_INPUT ? launch_real_input(sp, p->n, st) : launch_shared_odd(sp, p->n, st);
+    glfer::scratch_free(d_tab, st);
+    return e == hipSuccess ? GLFER_OK : hip_fail(e, "estimator launch (ragged)");
+  }
+
+  // launch_by_n over the streams: frames [from[b], to[b]) of stream b, whose sample 0 is soff[b] bytes from sp.stream
+  int by_n(const SpectroParams &sp, const std::vector<long long> &soff, const std::vector<size_t> &from,
+           const std::vector<size_t> &to) const {
+    // the route of THESE samples, as launch_by_n reads it: a corrected copy is f32 whatever the raw format, so its frames may
+    // take a real-input kernel where the raw stream's alignment (or an odd hop) keeps the raw samples on the packed one
+    SpectroParams r0 = sp;
+    r0.stream = reinterpret_cast<const char *>(sp.stream) + soff[0];
+    const BodyRoute r = body_route(r0, p->n);
+    const size_t G = groups(r);
+    std::vector<GlferRaggedEntry> head(nb), tail(nb), body(nb);
+    auto entry = [&](unsigned b, size_t f0, size_t f1) {
+      GlferRaggedEntry e = {};
+      if (f1 > f0) {
+        e.stream_off = soff[b];
+        e.psd_off = (long long)((s[b].row + f0) * (size_t)p->pitch);
+        e.frame0 = (long long)f0;
+        e.nframes = (int)(f1 - f0);
+      }
+      return e;
+    };
+    for (unsigned b = 0; b < nb; b++) {
+      const size_t lo = from[b], hi = std::max(to[b], from[b]);
+      size_t b0 = (std::max(lo, first_inside) + G - 1) / G * G, b1 = hi / G * G;
+      if (r == ROUTE_PACKED || b0 >= b1) b0 = b1 = hi;                 // (launch_by_n: everything to the packed kernel)
+      head[b] = entry(b, lo, b0);
+      body[b] = entry(b, b0, b1);
+      tail[b] = entry(b, b1, hi);
+    }
+    SpectroParams q = sp;
+    q.mean_inkernel = 0;
+    q.means = nullptr;
+    int rc = launch(q, head, ROUTE_PACKED);
+    if (rc == GLFER_OK) rc = launch(q, tail, ROUTE_PACKED);
+    if (rc == GLFER_OK) rc = launch(q, body, r);
+    return rc;
+  }
+
+  // submean_scratch over the streams: the corrected copy of hops [hlo[b], hhi[b]) of stream b, side by side in one block;
+  // soff[b] leaves as the copy's virtual sample 0 in bytes from *scratch
+  int submean(int fmt, const std::vector<size_t> &hlo, const std::vector<size_t> &hhi, float **scratch, std::vector<long long> &soff) const {
+    const size_t H = (size_t)p->hop;
+    size_t total = 0, longest = 0;
+    for (unsigned b = 0; b < nb; b++) {
+      const size_t n = hhi[b] > hlo[b] ? hhi[b] - hlo[b] : 0;
+      total += n;
+      longest = std::max(longest, n);
+    }
+    *scratch = nullptr;
+    if (total == 0) return GLFER_OK;
+    float *means = nullptr;
+    HIP_TRY(glfer::scratch_malloc((void **)scratch, total * H * sizeof(float), st));
+    const bool exact = reference_means(p);
+    hipError_t e = exact ? glfer::scratch_malloc((void **)&means, total * sizeof(float), st) : hipSuccess;
+    std::vector<GlferRaggedHops> tab(nb);
+    size_t at = 0;
+    for (unsigned b = 0; b < nb; b++) {
+      const size_t n = hhi[b] > hlo[b] ? hhi[b] - hlo[b] : 0;
+      tab[b].in = base + (s[b].off + hlo[b] * H) * esz;
+      tab[b].out = *scratch + at * H;
+      tab[b].means = means ? means + at : nullptr;
+      tab[b].nhops = (long long)n;
+      soff[b] = ((long long)at - (long long)hlo[b]) * (long long)(H * sizeof(float));
+      at += n;
+    }
+    GlferRaggedHops *d_tab = nullptr;
+    int rc = e == hipSuccess ? upload(tab, &d_tab) : hip_fail(e, "scratch (hop means, ragged)");
+    if (rc == GLFER_OK) {
+      if (exact) e = glfer_launch_hop_means_seq_ragged(d_tab, nb, p->hop, (long long)longest, fmt, st);
+      if (e == hipSuccess) e = glfer_launch_submean_ragged(d_tab, nb, p->hop, (long long)longest, fmt, exact ? 1 : 0, st);
+      if (e != hipSuccess) rc = hip_fail(e, "glfer_launch_submean_ragged");
+    }
+    if (d_tab) glfer::scratch_free(d_tab, st);
+    if (means) glfer::scratch_free(means, st);
+    if (rc != GLFER_OK) {
+      glfer::scratch_free(*scratch, st);
+      *scratch = nullptr;
+    }
+    return rc;
+  }
+
+  // frames [from[b], to[b]) through corrected copies (launch_mean_inkernel's by_copy, and the plans whose kernels take no means)
+  int by_copy(const SpectroParams &sp, const std::vector<size_t> &from, const std::vector<size_t> &to) const {
+    const size_t hops_back = sp.history_mode ? 0 : first_inside;
+    std::vector<size_t> hlo(nb), hhi(nb);
+    std::vector<long long> soff(nb);
+    for (unsigned b = 0; b < nb; b++) {
+      hlo[b] = from[b] > hops_back ? from[b] - hops_back : 0;
+      hhi[b] = to[b] > from[b] ? to[b] : hlo[b];
+    }
+    float *scratch = nullptr;
+    int rc = submean(sp.fmt, hlo, hhi, &scratch, soff);
+    if (rc != GLFER_OK || !scratch) return rc;
+    SpectroParams hs = sp;
+    hs.stream = scratch;
+    hs.fmt = GLFER_FMT_F32;
+    rc = by_n(hs, soff, from, to);
+    glfer::scratch_free(scratch, st);
+    return rc;
+  }
+
+  int run() {
+    SpectroParams sp;
+    fill_params(p, sp);
+    sp.stream = base;
+    sp.psd = d_psd;
+    esz = sp.fmt == GLFER_FMT_F32 ? 4 : (sp.fmt == GLFER_FMT_S16 ? 2 : 1);
+    // (every stream sees the route of stream 0: integer samples sit at even offsets -- glfer_hip.h; by_n reads the route of the
+    // samples a launch is given, raw or corrected copy, as launch_by_n does)
+    SpectroParams s0 = sp;
+    s0.stream = base + s[0].off * esz;
+    first_inside = (size_t)((p->keep + p->hop - 1) / p->hop);
+    std::vector<size_t> zero(nb, 0), end(nb);
+    std::vector<long long> raw(nb);
+    for (unsigned b = 0; b < nb; b++) {
+      end[b] = s[b].frames;
+      raw[b] = (long long)(s[b].off * esz);
+    }
+    if (!p->cfg.sub_mean) return by_n(sp, raw, zero, end);
+    if (!mean_inkernel_ok(p, s0, nullptr, -1)) return by_copy(sp, zero, end);
+    // launch_mean_inkernel per stream: [0, b0) and [b1, end) through the copies, [b0, b1) from the raw samples (their route)
+    const BodyRoute route = body_route(s0, p->n);
+    const size_t G = groups(route);
+    std::vector<size_t> b0(nb), b1(nb), tail(nb);
+    for (unsigned b = 0; b < nb; b++) {
+      b0[b] = (first_inside + G - 1) / G * G;
+      b1[b] = end[b] / G * G;
+      if (b0[b] >= b1[b]) b0[b] = b1[b] = end[b];
+      tail[b] = std::max(b1[b], std::min(b0[b], end[b]));
+    }
+    int rc = by_copy(sp, zero, b0);
+    if (rc != GLFER_OK) return rc;
+    {
+      SpectroParams bs = sp;
+      bs.mean_inkernel = 1;
+      std::vector<GlferRaggedEntry> body(nb);
+      float *means = nullptr;
+      GlferRaggedHops *d_hops = nullptr;
+      if (reference_means(p)) {                      // the hop means in the reference's order: hops [b0 - first_inside, b1) of each stream
+        std::vector<GlferRaggedHops> hops(nb);
+        size_t total = 0, longest = 0;
+        for (unsigned b = 0; b < nb; b++) total += b1[b] > b0[b] ? b1[b] - (b0[b] - first_inside) : 0;
+        if (total) {
+          HIP_TRY(glfer::scratch_malloc((void **)&means, total * sizeof(float), st));
+          size_t at = 0;
+          for (unsigned b = 0; b < nb; b++) {
+            const size_t hop_lo = b0[b] - first_inside, n = b1[b] > b0[b] ? b1[b] - hop_lo : 0;
+            hops[b].in = base + (s[b].off + hop_lo * (size_t)p->hop) * esz;
+            hops[b].out = nullptr;
+            hops[b].means = means + at;
+            hops[b].nhops = (long long)n;
+            body[b].means_off = (long long)at - (long long)hop_lo;       // indexed by the stream's own hop (= frame) index
+            longest = std::max(longest, n);
+            at += n;
+          }
+          rc = upload(hops, &d_hops);
+          if (rc == GLFER_OK) {
+            const hipError_t e = glfer_launch_hop_means_seq_ragged(d_hops, nb, p->hop, (long long)longest, sp.fmt, st);
+            if (e != hipSuccess) rc = hip_fail(e, "hop means (ragged)");
+          }
+          bs.means = means;
+        }
+      }
+      for (unsigned b = 0; b < nb && rc == GLFER_OK; b++) {
+        if (b1[b] <= b0[b]) {
+          body[b] = GlferRaggedEntry{};
+          continue;
+        }
+        body[b].stream_off = raw[b];
+        body[b].psd_off = (long long)((s[b].row + b0[b]) * (size_t)p->pitch);
+        body[b].frame0 = (long long)b0[b];
+        body[b].nframes = (int)(b1[b] - b0[b]);
+      }
+      if (rc == GLFER_OK) rc = launch(bs, body, route);
+      if (d_hops) glfer::scratch_free(d_hops, st);
+      if (means) glfer::scratch_free(means, st);
+      if (rc != GLFER_OK) return rc;
+    }
+    return by_copy(sp, tail, end);
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+size_t glfer_hip_ragged_frames(const glfer_hip_plan *p, size_t nstreams, const size_t *lengths, size_t *row_starts) {
+  if (!p || (nstreams && !lengths)) return 0;
+  size_t total = 0;
+  for (size_t b = 0; b < nstreams; b++) {
+    if (row_starts) row_starts[b] = total;
+    const size_t f = lengths[b] / (size_t)p->hop;
+    if (f > SIZE_MAX - total) return SIZE_MAX;
+    total += f;
+  }
+  if (row_starts) row_starts[nstreams] = total;
+  return total;
+}
+
+int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *p, const void *d_samples, size_t nstreams, const size_t *offsets,
+                                        const size_t *lengths, float *d_psd, size_t *row_starts, void *hip_stream) {
+  if (!p) return GLFER_E_ARG;
+  if (nstreams == 0) {
+    if (row_starts) row_starts[0] = 0;
+    return GLFER_OK;
+  }
+  if (!offsets || !lengths) return GLFER_E_ARG;
+  const int fmt = p->cfg.sample_format;
+  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
+  // the arguments, before anything is read or written: the host arrays are all this looks at
+  std::vector<RaggedStream> s(nstreams);
+  size_t total = 0;
+  for (size_t b = 0; b < nstreams; b++) {
+    const size_t f = lengths[b] / (size_t)p->hop;
+    if (f > 0x7fffffffu) return GLFER_E_ARG;
+    if (lengths[b] > SIZE_MAX / esz || offsets[b] > SIZE_MAX / esz - lengths[b]) return GLFER_E_ARG;
+    // body_route and the launchers read a stream's alignment for integer samples (pairs come with one load): every stream of a
+    // launch must see the same kernels, so an odd offset is refused rather than routed per stream (as the batch entry's odd pitch)
+    if (fmt != GLFER_FMT_F32 && (offsets[b] & 1)) return GLFER_E_ARG;
+    if (f > SIZE_MAX / sizeof(float) / (size_t)p->pitch - total) return GLFER_E_ARG;
+    s[b] = RaggedStream{offsets[b], f, total};
+    total += f;
+  }
+  if (row_starts) {
+    for (size_t b = 0; b < nstreams; b++) row_starts[b] = s[b].row;
+    row_starts[nstreams] = total;
+  }
+  if (total == 0) return GLFER_OK;
+  if (!d_samples || !d_psd) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  {
+    // the per-stream tables are uploaded from host memory that is gone when the call returns: a copy node of a captured graph
+    // would read it at every replay, so a capturing stream is refused
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (st != hipStreamPerThread && hipStreamIsCapturing(st, &cs) == hipSuccess) {
+      if (cs != hipStreamCaptureStatusNone) return GLFER_E_ARG;
+    } else {
+      (void)hipGetLastError();
+    }
+  }
+  const char *base = static_cast<const char *>(d_samples);
+  auto single = [&](size_t b) {
+    if (!s[b].frames) return (int)GLFER_OK;
+    return glfer_run_device(p, base + s[b].off * esz, lengths[b], 0, s[b].frames, d_psd + s[b].row * (size_t)p->pitch, nullptr, st);
+  };
+  if (!batch_one_launch(p) || nstreams == 1) {      // LMP, HP-ARMA, N outside 256 .. 16384: stream by stream, as batch_rows
+    for (size_t b = 0; b < nstreams; b++) {
+      const int rc = single(b);
+      if (rc != GLFER_OK) return rc;
+    }
+    return GLFER_OK;
+  }
+  DeviceGuard guard(p->cfg.device);
+  HIP_TRY(guard.error());
+  int dev = 0, ymax = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  HIP_TRY(hipDeviceGetAttribute(&ymax, hipDeviceAttributeMaxGridDimY, dev));
+  ymax = std::max(2, std::min(ymax, 65535));
+  for (size_t c0 = 0; c0 < nstreams; c0 += (size_t)ymax) {      // above the grid's y limit: chunks of it
+    const unsigned nb = (unsigned)std::min(nstreams - c0, (size_t)ymax);
+    int rc;
+    if (nb == 1) {
+      rc = single(c0);
+    } else {
+      RaggedChunk c{p, s.data() + c0, nb, base, d_psd, st, esz, 0};
+      rc = c.run();
     }
     if (rc != GLFER_OK) return rc;
   }

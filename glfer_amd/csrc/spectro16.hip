@@ -49,6 +49,14 @@
 #define GLFER16_TW1_REGS 1
 #endif
 
+// GLFER_RAGGED (the Makefile compiles this source once more with it): the instantiations of the ragged batches -- the stream
+// and its own frames come from SpectroParams::ragged[blockIdx.y] (GLFER_STREAM_SELECT, spectro_params.h) -- under names of their
+// own, so that the instantiations without it are compiled from the code they were.
+#ifdef GLFER_RAGGED
+#define spectro16_kernel spectro16_ragged_kernel
+#define glfer_launch_spectro16_n glfer_launch_spectro16_ragged_n
+#endif
+
 namespace glfer {
 
 // One kernel, persistent blocks.  The work of a block is a flat sequence of ROUNDS
@@ -81,7 +89,7 @@ template <int LOGN, int FMT, bool GEN, int WPS = GLFER16_WAVES_PER_SIMD, int STG
 __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(SpectroParams p) {
   // BAT: the instantiations a batch launches (nbatch > 1) -- blockIdx.y is the stream; the single-stream ones are the code as it was
   if constexpr (BAT != 0) {
-    glfer_batch_select(p);
+    GLFER_STREAM_SELECT(p);
     // (F alone: psd stays NULL, psd_batch_stride is 0; ROWS: glfer_batch_select has moved psd on by psd_batch_stride)
     if constexpr (FT != 0) p.ftest += (long long)blockIdx.y * p.ftest_batch_stride;
   }
@@ -471,12 +479,22 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(S
 // ---------------------------------------------------------------------------
 // K0: per-hop mean removal (fft.c:86-96).  One block per hop; writes a float copy of the
 // stream (the reference mutates the caller's hop buffer in place).
-template <int FMT>
+// RAG (glfer_launch_submean_ragged): streams of unequal length -- `in` is the launch's GlferRaggedHops table, entry blockIdx.y
+// holds the stream's samples, its copy, its means (when `means` is not NULL) and its own hop count.
+template <int FMT, int RAG = 0>
 __global__ __launch_bounds__(256) void submean_kernel(const void *in, float *out, int H, long long nhops, const float *means,
                                                       long long in_bstride, long long out_bstride, long long means_bstride) {
-  in = reinterpret_cast<const char *>(in) + (long long)blockIdx.y * in_bstride;   // the stream of a batch (blockIdx.y; 0 otherwise)
-  out += (long long)blockIdx.y * out_bstride;
-  if (means) means += (long long)blockIdx.y * means_bstride;
+  if constexpr (RAG != 0) {
+    const GlferRaggedHops e = reinterpret_cast<const GlferRaggedHops *>(in)[blockIdx.y];
+    in = e.in;
+    out = e.out;
+    if (means) means = e.means;
+    nhops = e.nhops;
+  } else {
+    in = reinterpret_cast<const char *>(in) + (long long)blockIdx.y * in_bstride;   // the stream of a batch (blockIdx.y; 0 otherwise)
+    out += (long long)blockIdx.y * out_bstride;
+    if (means) means += (long long)blockIdx.y * means_bstride;
+  }
   __shared__ float part[256];
   const long long hop = blockIdx.x;
   if (hop >= nhops) return;
@@ -516,12 +534,20 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
-template <int FMT, int GROUP, int EPL>
+template <int FMT, int GROUP, int EPL, int RAG = 0>
 __global__ __launch_bounds__(256) void submean_reg_kernel(const void *in, float *out, int H, long long nhops, const float *means,
                                                           long long in_bstride, long long out_bstride, long long means_bstride) {
-  in = reinterpret_cast<const char *>(in) + (long long)blockIdx.y * in_bstride;   // the stream of a batch (blockIdx.y; 0 otherwise)
-  out += (long long)blockIdx.y * out_bstride;
-  if (means) means += (long long)blockIdx.y * means_bstride;
+  if constexpr (RAG != 0) {                         // (as submean_kernel)
+    const GlferRaggedHops e = reinterpret_cast<const GlferRaggedHops *>(in)[blockIdx.y];
+    in = e.in;
+    out = e.out;
+    if (means) means = e.means;
+    nhops = e.nhops;
+  } else {
+    in = reinterpret_cast<const char *>(in) + (long long)blockIdx.y * in_bstride;   // the stream of a batch (blockIdx.y; 0 otherwise)
+    out += (long long)blockIdx.y * out_bstride;
+    if (means) means += (long long)blockIdx.y * means_bstride;
+  }
   constexpr unsigned esz = FMT == GLFER_FMT_F32 ? 4 : (FMT == GLFER_FMT_S16 ? 2 : 1);
   __shared__ float part[4];
   const unsigned l = GROUP == 64 ? (threadIdx.x & 63u) : threadIdx.x;
@@ -614,6 +640,9 @@ static hipError_t launch16_fmt(const SpectroParams &p, hipStream_t st) {
   const long long cap = glfer_batch_cap(4 * resident, p.nbatch);   // (a batch shares it among its streams)
   unsigned grid = (unsigned)(work < cap ? work : cap);
   if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
+#ifdef GLFER_RAGGED
+  if (p.ftest) return hipErrorInvalidValue;          // (the rows entry only)
+#else
   if (p.ftest) {
     // the F statistic: one taper per round (two spill-free wavefronts per SIMD: mu and the sums are 48 more registers)
     if (p.nonlin || p.spec || p.mean_inkernel || !p.ft_U0) return hipErrorInvalidValue;
@@ -629,6 +658,7 @@ static hipError_t launch16_fmt(const SpectroParams &p, hipStream_t st) {
     else hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     return hipGetLastError();
   }
+#endif
   if (p.mean_inkernel) {
     // frames inside the stream only, history from the stream, a hop of 4, 8 or 16 sixteenths of the block
     if (p.nonlin || p.spec || p.history_mode || p.frame0 * (long long)p.H < (long long)p.R) return hipErrorInvalidValue;
@@ -647,15 +677,25 @@ static hipError_t launch16_fmt(const SpectroParams &p, hipStream_t st) {
 }
 
 extern "C" hipError_t GLFER_CAT(glfer_launch_spectro16_n, GLFER_LOGN)(const SpectroParams *p, hipStream_t st) {
+#ifdef GLFER_RAGGED
+  if (!p->ragged || p->nbatch < 2) return hipErrorInvalidValue;
+  switch (p->fmt) {
+    case GLFER_FMT_F32: return launch16_fmt<GLFER_FMT_F32, 1>(*p, st);
+    case GLFER_FMT_S16: return launch16_fmt<GLFER_FMT_S16, 1>(*p, st);
+    case GLFER_FMT_U8: return launch16_fmt<GLFER_FMT_U8, 1>(*p, st);
+  }
+  return hipErrorInvalidValue;
+#else
   switch (p->fmt) {
     case GLFER_FMT_F32: return p->nbatch > 1 ? launch16_fmt<GLFER_FMT_F32, 1>(*p, st) : launch16_fmt<GLFER_FMT_F32, 0>(*p, st);
     case GLFER_FMT_S16: return p->nbatch > 1 ? launch16_fmt<GLFER_FMT_S16, 1>(*p, st) : launch16_fmt<GLFER_FMT_S16, 0>(*p, st);
     case GLFER_FMT_U8: return p->nbatch > 1 ? launch16_fmt<GLFER_FMT_U8, 1>(*p, st) : launch16_fmt<GLFER_FMT_U8, 0>(*p, st);
   }
   return hipErrorInvalidValue;
+#endif
 }
 
-#if GLFER_LOGN == 12
+#if GLFER_LOGN == 12 && !defined(GLFER_RAGGED)
 extern "C" hipError_t glfer_launch_submean_batch(const void *in, float *out, int H, long long nhops, int fmt, hipStream_t st,
                                                  const float *means, unsigned nb, long long in_bstride, long long out_bstride,
                                                  long long means_bstride) {
@@ -685,6 +725,42 @@ extern "C" hipError_t glfer_launch_submean_batch(const void *in, float *out, int
     case GLFER_FMT_S16: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_S16>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); break;
     case GLFER_FMT_U8: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_U8>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); break;
     default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// the same over nb streams of unequal length (tab: device, one entry per stream; max_nhops: the longest): the kernel the hop
+// picks is the one above, so a hop's sum -- and the copy -- come out as they do there
+extern "C" hipError_t glfer_launch_submean_ragged(const GlferRaggedHops *tab, unsigned nb, int H, long long max_nhops, int fmt,
+                                                  int with_means, hipStream_t st) {
+  if (max_nhops <= 0 || nb == 0) return hipSuccess;
+  if (nb > 65535 || !tab) return hipErrorInvalidValue;
+  if (fmt != GLFER_FMT_F32 && fmt != GLFER_FMT_S16 && fmt != GLFER_FMT_U8) return hipErrorInvalidValue;
+  const void *in = tab;
+  float *const out = nullptr;
+  const float *const means = with_means ? reinterpret_cast<const float *>(tab) : nullptr;   // (a flag: the entry holds the pointer)
+  const long long nhops = max_nhops;
+#define GLFER_SUBMEAN_REG(G, E)                                                                                     \
+  do {                                                                                                              \
+    const unsigned grid = G == 64 ? (unsigned)((nhops + 3) / 4) : (unsigned)nhops;                                  \
+    if (fmt == GLFER_FMT_F32) hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_F32, G, E, 1>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); \
+    else if (fmt == GLFER_FMT_S16) hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_S16, G, E, 1>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); \
+    else hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_U8, G, E, 1>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); \
+    return hipGetLastError();                                                                                       \
+  } while (0)
+  if (H <= 64 * 2) GLFER_SUBMEAN_REG(64, 2);
+  if (H <= 64 * 4) GLFER_SUBMEAN_REG(64, 4);
+  if (H <= 64 * 8) GLFER_SUBMEAN_REG(64, 8);
+  if (H <= 64 * 16) GLFER_SUBMEAN_REG(64, 16);
+  if (H <= 256 * 8) GLFER_SUBMEAN_REG(256, 8);
+  if (H <= 256 * 16) GLFER_SUBMEAN_REG(256, 16);
+  if (H <= 256 * 32) GLFER_SUBMEAN_REG(256, 32);
+  if (H <= 256 * 64) GLFER_SUBMEAN_REG(256, 64);
+#undef GLFER_SUBMEAN_REG
+  switch (fmt) {
+    case GLFER_FMT_F32: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_F32, 1>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); break;
+    case GLFER_FMT_S16: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_S16, 1>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); break;
+    default: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_U8, 1>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); break;
   }
   return hipGetLastError();
 }

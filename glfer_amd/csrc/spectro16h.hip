@@ -58,6 +58,9 @@
 #ifndef GLFER16H_SHIFT_BUILDS
 #define GLFER16H_SHIFT_BUILDS 1    /* build the register-reuse forms for 75 % and 50 % overlap */
 #endif
+#if defined(GLFER_RAGGED) && !defined(GLFER16H_AVG_BUILDS)
+#define GLFER16H_AVG_BUILDS 0      /* the ragged instantiations: the rows entry only */
+#endif
 #ifndef GLFER16H_AVG_BUILDS
 #define GLFER16H_AVG_BUILDS (GLFER_LOGN_OR(12) <= 12)   /* the average taken inside the kernel (AVG = 1): N = 512 .. 4096 */
 #endif
@@ -91,6 +94,14 @@
 #ifndef GLFER16H_STAGE_ROWS
 #define GLFER16H_STAGE_ROWS 0   /* measured, C2: 320 -> 264 M frames/s (HBM writes 1.09x -> see profiles/r03_c2_staged_rows.txt): one more barrier, 8 KB more LDS
                                    writes per frame and 24 spilled VGPRs cost more than the aligned stores save; kept for A/B builds */
+#endif
+
+// GLFER_RAGGED (the Makefile compiles this source once more with it): the instantiations of the ragged batches -- the stream
+// and its own frames come from SpectroParams::ragged[blockIdx.y] (GLFER_STREAM_SELECT, spectro_params.h) -- under names of their
+// own, so that the instantiations without it are compiled from the code they were.
+#ifdef GLFER_RAGGED
+#define spectro16h_kernel spectro16h_ragged_kernel
+#define glfer_launch_spectro16h_n glfer_launch_spectro16h_ragged_n
 #endif
 
 namespace glfer {
@@ -239,7 +250,7 @@ template <int LOGN, int FMT, int WPS = GLFER16H_WAVES_PER_SIMD, int VAR = GLFER1
 __global__ __launch_bounds__(LaunchH<LOGN>::BLOCK, WPS) void spectro16h_kernel(SpectroParams p) {
   // the stream of the batch (blockIdx.y; 0 outside a batch); the average forms select it only in their batch instantiations
   // (AVG = 2), so that the single-stream ones (AVG = 1) keep their registers
-  if constexpr (AVG == 0) glfer_batch_select(p);
+  if constexpr (AVG == 0) GLFER_STREAM_SELECT(p);
   if constexpr (AVG == 2) glfer_batch_select_avg(p);
   static_assert(AVG == 0 || (MT == 0 && HIST == 0 && ((MEAN == 0 && MTAB == 0) || (MEAN == 1 && MTAB == 1))),
                 "the average inside the kernel: the periodogram, plain or with GIVEN hop means (the reference's default, sub_mean = opt.autoscale), history from the stream");
@@ -1023,6 +1034,9 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
   const long long work = ((long long)p.nframes + LC::FPB - 1) / LC::FPB;
   if (work == 0) return hipSuccess;
   if (p.nbatch > 1 && p.nprod) return hipErrorInvalidValue;   // the in-launch producers: one stream only
+#ifdef GLFER_RAGGED
+  if (!p.ragged || p.nbatch < 2) return hipErrorInvalidValue;
+#endif
   const long long per_cu = (GLFER16H_WAVES_PER_SIMD * 256) / LC::BLOCK > 0 ? (GLFER16H_WAVES_PER_SIMD * 256) / LC::BLOCK : 1;
   const long long resident = 256LL * per_cu;
   const long long cap = glfer_batch_cap(8 * resident, p.nbatch);   // (a batch shares it among its streams)
@@ -1142,6 +1156,7 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
         grid += (unsigned)p.nprod;
         g += (unsigned)p.nprod;
       }
+#ifndef GLFER_RAGGED                             /* (an experiment of the single-stream table form) */
       // GLFER_MTAB_WPS=2 (experiment, profiles/r04_piecewise_means.txt): two wavefronts per SIMD, so that a hop-means launch of the
       // NEXT piece (side stream) finds registers and LDS beside this one
       static const bool two = [] { const char *e = getenv("GLFER_MTAB_WPS"); return e && *e == '2'; }();
@@ -1153,6 +1168,7 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
         else return hipErrorInvalidValue;
         return hipGetLastError();
       }
+#endif
       if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 0, 1, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
       else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 2, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
       else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 4, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);

@@ -68,6 +68,14 @@
 #define GLFER16W_TW1_REGS 1
 #endif
 
+// GLFER_RAGGED (the Makefile compiles this source once more with it): the instantiations of the ragged batches -- the stream
+// and its own frames come from SpectroParams::ragged[blockIdx.y] (GLFER_STREAM_SELECT, spectro_params.h) -- under names of their
+// own, so that the instantiations without it are compiled from the code they were.
+#ifdef GLFER_RAGGED
+#define spectro16w_kernel spectro16w_ragged_kernel
+#define glfer_launch_spectro16w_n glfer_launch_spectro16w_ragged_n
+#endif
+
 namespace glfer {
 
 template <int LOGN>
@@ -98,7 +106,7 @@ struct LaunchW {
 // (a power of two) sits in the taper tables as before.
 template <int LOGN, int FMT, int MT, int VAR, int SETS, int WPS, int GEN = 0, int HIST = 0, int KM = 0>
 __global__ __launch_bounds__(LaunchW<LOGN>::BLOCK, WPS) void spectro16w_kernel(SpectroParams p) {
-  if constexpr (LOGN <= 14) glfer_batch_select(p);   // the stream of the batch (blockIdx.y; 0 outside a batch); N = 32768 is never batched
+  if constexpr (LOGN <= 14) GLFER_STREAM_SELECT(p);   // the stream of the batch (blockIdx.y; 0 outside a batch); N = 32768 is never batched
   static_assert(KM == 0 || ((KM == 16 || KM == 8 || KM == 4) && MT != 0 && GEN == 0 && HIST == 0),
                 "in-kernel mean removal: the multitaper form, hop = 16, 8 or 4 of a lane's 16 sample registers");
   constexpr int NH = KM ? 16 / KM : 1;                     // hops per frame
@@ -656,6 +664,9 @@ static hipError_t launch16w_fmt(const SpectroParams &p, hipStream_t st) {
   const long long work = ((long long)p.nframes + LC::FPB - 1) / LC::FPB;
 #if GLFER_LOGN >= 15
   if (p.nbatch > 1) return hipErrorInvalidValue;     // N = 32768 is never batched (glfer_hip_spectrogram_batch_device goes stream by stream)
+#endif
+#ifdef GLFER_RAGGED
+  if (!p.ragged || p.nbatch < 2) return hipErrorInvalidValue;
 #endif
   if (work == 0) return hipSuccess;
   constexpr int WPS = GLFER16W_WAVES_PER_SIMD;

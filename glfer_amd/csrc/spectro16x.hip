@@ -30,6 +30,14 @@
 #define GLFER16X_TW1_REGS 0
 #endif
 
+// GLFER_RAGGED (the Makefile compiles this source once more with it): the instantiations of the ragged batches -- the stream
+// and its own frames come from SpectroParams::ragged[blockIdx.y] (GLFER_STREAM_SELECT, spectro_params.h) -- under names of their
+// own, so that the instantiations without it are compiled from the code they were.
+#ifdef GLFER_RAGGED
+#define spectro16x_kernel spectro16x_ragged_kernel
+#define glfer_launch_spectro16x_n glfer_launch_spectro16x_ragged_n
+#endif
+
 namespace glfer {
 
 template <int LOGN>
@@ -47,7 +55,7 @@ struct LaunchX {
 // KM > 0: per-hop mean removal inside the kernel (load_frame16_mean, odd_taper.hpp)
 template <int LOGN, int FMT, int WPS = GLFER16X_WAVES_PER_SIMD, int KM = 0>
 __global__ __launch_bounds__(LaunchX<LOGN>::BLOCK, WPS) void spectro16x_kernel(SpectroParams p) {
-  glfer_batch_select(p);                          // the stream of the batch (blockIdx.y; 0 outside a batch)
+  GLFER_STREAM_SELECT(p);                          // the stream of the batch (blockIdx.y; 0 outside a batch)
   using C = Plan16<LOGN>;
   using L = LaunchX<LOGN>;
   constexpr int N = C::N, T = C::T, NPASS = C::NPASS, FPB = L::FPB, PADN = L::PADN, WPF = L::WPF;
@@ -252,6 +260,9 @@ static hipError_t launch16x_fmt(const SpectroParams &p, hipStream_t st) {
   constexpr int L = GLFER_LOGN;
   using LC = LaunchX<L>;
   const long long work = ((long long)p.nframes + 2 * LC::FPB - 1) / (2 * LC::FPB);
+#ifdef GLFER_RAGGED
+  if (!p.ragged || p.nbatch < 2) return hipErrorInvalidValue;
+#endif
   if (work == 0) return hipSuccess;
   const long long per_cu = (GLFER16X_WAVES_PER_SIMD * 256) / LC::BLOCK > 0 ? (GLFER16X_WAVES_PER_SIMD * 256) / LC::BLOCK : 1;
   const long long resident = 256LL * per_cu;

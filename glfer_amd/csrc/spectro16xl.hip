@@ -22,6 +22,14 @@
 #define GLFER16XL_TW1_REGS 1
 #endif
 
+// GLFER_RAGGED (the Makefile compiles this source once more with it): the instantiations of the ragged batches -- the stream
+// and its own frames come from SpectroParams::ragged[blockIdx.y] (GLFER_STREAM_SELECT, spectro_params.h) -- under names of their
+// own, so that the instantiations without it are compiled from the code they were.
+#ifdef GLFER_RAGGED
+#define spectro16xl_kernel spectro16xl_ragged_kernel
+#define glfer_launch_spectro16xl_n glfer_launch_spectro16xl_ragged_n
+#endif
+
 namespace glfer {
 hipError_t allow_dynamic_lds(const void *kernel, size_t bytes);   // plan.h / glfer_hip.cpp: once per device, kernel and size class
 }
@@ -45,7 +53,7 @@ struct LaunchXL {
 // KM > 0: per-hop mean removal inside the kernel (load_frame16_mean, odd_taper.hpp)
 template <int LOGN, int FMT, int KM = 0>
 __global__ __launch_bounds__(256, 2) void spectro16xl_kernel(SpectroParams p) {
-  glfer_batch_select(p);                          // the stream of the batch (blockIdx.y; 0 outside a batch)
+  GLFER_STREAM_SELECT(p);                          // the stream of the batch (blockIdx.y; 0 outside a batch)
   using C = Plan16<LOGN>;
   using L = LaunchXL<LOGN>;
   constexpr int N = C::N, T = C::T, NPASS = C::NPASS, FPB = L::FPB, PADN = L::PADN, WPF = L::WPF;
@@ -253,6 +261,9 @@ static hipError_t launch16xl_fmt(const SpectroParams &p, hipStream_t st) {
   using LC = LaunchXL<L>;
   const size_t shmem = LC::lds_bytes(p.npairs - 1);
   if (shmem > 80 * 1024) return hipErrorInvalidValue;            // two blocks per CU or not at all
+#ifdef GLFER_RAGGED
+  if (!p.ragged || p.nbatch < 2) return hipErrorInvalidValue;
+#endif
   const long long work = ((long long)p.nframes + 2 * LC::FPB - 1) / (2 * LC::FPB);
   if (work == 0) return hipSuccess;
   const long long resident = 256LL * 2;

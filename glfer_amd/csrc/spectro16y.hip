@@ -60,6 +60,14 @@
 #define GLFER_BLOCK_MARK(k)
 #endif
 
+// GLFER_RAGGED (the Makefile compiles this source once more with it): the instantiations of the ragged batches -- the stream
+// and its own frames come from SpectroParams::ragged[blockIdx.y] (GLFER_STREAM_SELECT, spectro_params.h) -- under names of their
+// own, so that the instantiations without it are compiled from the code they were.
+#ifdef GLFER_RAGGED
+#define spectro16y_kernel spectro16y_ragged_kernel
+#define glfer_launch_spectro16y_n12 glfer_launch_spectro16y_ragged_n12
+#endif
+
 namespace glfer {
 
 hipError_t allow_dynamic_lds(const void *kernel, size_t bytes);   // plan.h / glfer_hip.cpp: once per device, kernel and size class
@@ -82,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
   GLFER_BLOCK_MARK(0);
   // the stream of the batch (blockIdx.y; 0 outside a batch); the mean forms only in their batch instantiations (BAT), so that the
   // single-stream ones keep their registers
-  if constexpr (KM == 0 || BAT != 0) glfer_batch_select(p);
+  if constexpr (KM == 0 || BAT != 0) GLFER_STREAM_SELECT(p);
   static_assert(KM == 0 || (HIST == 0 && (KM == 16 || KM == 8 || KM == 4)), "in-kernel mean removal: history from the stream");
   // (the hop sums of the mean forms reduce across lanes in lane order: a lane permutation would change their bits)
   static_assert(HALF == 0 || (KM == 0 && GLFER16_X0_ROWS != 0 && GLFER16_BARRIER_AFTER_READS != 0), "half tables: the plain forms, row layout of exchange 0");
@@ -495,6 +503,7 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
 using namespace glfer;
 
 // The queue form (p.yq_counter set by the host, which keeps the ticket base: glfer_hip.cpp): one workgroup per resident slot
+#ifndef GLFER_RAGGED                                 /* (the queue form: one stream) */
 template <int FMT>
 static hipError_t launch16y_queue(const SpectroParams &p, hipStream_t st) {
   if (p.mean_inkernel || p.nbatch > 1 || p.yq_chunk < 1) return hipErrorInvalidValue;
@@ -515,12 +524,17 @@ static hipError_t launch16y_queue(const SpectroParams &p, hipStream_t st) {
   else GLFER_Y_QUEUE(0, 0);
 #undef GLFER_Y_QUEUE
 }
+#endif
 
 template <int FMT>
 static hipError_t launch16y_fmt(const SpectroParams &p, hipStream_t st) {
   const long long work = ((long long)p.nframes + 1) / 2;
   if (work == 0) return hipSuccess;
+#ifdef GLFER_RAGGED
+  if (p.yq_counter || !p.ragged || p.nbatch < 2) return hipErrorInvalidValue;
+#else
   if (p.yq_counter) return launch16y_queue<FMT>(p, st);
+#endif
   const long long resident = 256LL * 2;
   const long long cap = glfer_batch_cap(16 * resident, p.nbatch);   // (a batch shares it among its streams)
   unsigned grid = (unsigned)(work < cap ? work : cap);   // tools/xbench: 16x beats 4x by ~2 %
@@ -533,6 +547,15 @@ static hipError_t launch16y_fmt(const SpectroParams &p, hipStream_t st) {
   if (p.mean_inkernel) {
     if (p.history_mode) return hipErrorInvalidValue;
     const int km = p.H % 256 == 0 ? p.H / 256 : 0;
+#ifdef GLFER_RAGGED                                  /* (always a launch over several streams: the BAT forms) */
+#define GLFER_Y_MEAN(K)                                                                                              \
+  do {                                                                                                               \
+    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, 0, K, 1>), shmem);       \
+    if (e != hipSuccess) return e;                                                                                   \
+    hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0, K, 1>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p); \
+    return hipGetLastError();                                                                                        \
+  } while (0)
+#else
 #define GLFER_Y_MEAN(K)                                                                                              \
   do {                                                                                                               \
     const void *k_ = p.nbatch > 1 ? reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, 0, K, 1>)                 \
@@ -543,6 +566,7 @@ static hipError_t launch16y_fmt(const SpectroParams &p, hipStream_t st) {
     else hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0, K, 0>), dim3(grid, 1), dim3(256), shmem, st, p);          \
     return hipGetLastError();                                                                                        \
   } while (0)
+#endif
     if (km == 16) GLFER_Y_MEAN(16);
     if (km == 8) GLFER_Y_MEAN(8);
     if (km == 4) GLFER_Y_MEAN(4);

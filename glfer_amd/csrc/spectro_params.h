@@ -6,6 +6,25 @@
 
 enum { GLFER_FMT_F32 = 0, GLFER_FMT_S16 = 1, GLFER_FMT_U8 = 2 };
 
+/* One stream of a ragged launch (glfer_hip_spectrogram_ragged_device): SpectroParams::ragged[blockIdx.y].  The offsets are
+   relative to the launch's own stream / psd / means (virtual bases, so they may be negative); frame0 and nframes are the
+   stream's own piece of this launch (its head, its body or its tail frames).  nframes <= 0: nothing for this stream here. */
+struct GlferRaggedEntry {
+  long long stream_off;    /* bytes                                                          */
+  long long psd_off;       /* floats                                                         */
+  long long means_off;     /* floats (with given hop means)                                  */
+  long long frame0;
+  int nframes;
+  int reserved;
+};
+/* One stream of a ragged hop-means / corrected-copy launch (submean_seq.hip, spectro16.hip's submean kernels, RAG forms) */
+struct GlferRaggedHops {
+  const void *in;          /* the stream's first hop of the launch                           */
+  float *out;              /* its corrected copy (the copy kernels)                          */
+  float *means;            /* its hop means: written by the means kernel, read by the copy kernels (NULL there: summed by the kernel) */
+  long long nhops;
+};
+
 struct SpectroParams {
   const void *stream;      /* device: sample stream (f32 / s16 / u8)                        */
   long long frame0;        /* index of this launch's first frame in the whole stream        */
@@ -109,7 +128,12 @@ struct SpectroParams {
   /* the multitaper rows beside F (glfer_hip_mtm_rows_ftest_device): psd != NULL with ftest, pitch and psd_batch_stride as for the rows */
   const float *ft_cj;      /* device: [ntap], 1 / (N (1 + sig_j)): the weight of taper j's |y_j|^2 in the row (mtm.c:212-219, fft.c:212-216).
                               The F tables hold the tapers unscaled, so the rows' weights ride here; read by the ROWS forms only.
-                              (Last in the block: every earlier member keeps its offset.)                                            */
+                              (Appended: every earlier member keeps its offset.)                                                     */
+  /* ragged batches (glfer_hip_spectrogram_ragged_device): streams of unequal length in one launch.  ragged != NULL: blockIdx.y
+     indexes this device table, one entry per stream of the launch (nbatch of them), and the entry -- not the batch strides --
+     gives the stream's samples, rows, hop means, frame0 and nframes; the launch's own frame0 / nframes are those of its longest
+     stream (the launchers size the grid and check the range with them).  The kernels' ragged instantiations only.             */
+  const struct GlferRaggedEntry *ragged;
 };
 
 /* spectro16y.hip's half-table form (N = 4096, T = 256 lanes, five tapers).  In pass 0 lane t = 16 j + p holds the samples
@@ -152,6 +176,24 @@ __device__ __forceinline__ void glfer_batch_select(SpectroParams &p) {
   p.psd = p.psd + b * p.psd_batch_stride;
   if (p.means) p.means = p.means + b * p.means_batch_stride;
 }
+/* kernel entry of the ragged instantiations: this workgroup's stream of the launch and its own frames; false: the stream has
+   no frames in this launch and the workgroup leaves (uniformly, before its first barrier) */
+__device__ __forceinline__ bool glfer_ragged_select(SpectroParams &p) {
+  const GlferRaggedEntry e = p.ragged[blockIdx.y];
+  if (e.nframes <= 0) return false;
+  p.stream = reinterpret_cast<const char *>(p.stream) + e.stream_off;
+  p.psd = p.psd + e.psd_off;
+  if (p.means) p.means = p.means + e.means_off;
+  p.frame0 = e.frame0;
+  p.nframes = e.nframes;
+  return true;
+}
+/* what a kernel does at entry: the stream of the batch, or -- the ragged instantiations -- the stream's table entry */
+#ifdef GLFER_RAGGED
+#define GLFER_STREAM_SELECT(p) do { if (!glfer_ragged_select(p)) return; } while (0)
+#else
+#define GLFER_STREAM_SELECT(p) glfer_batch_select(p)
+#endif
 /* the same for the average taken inside the launch (glfer_hip_spectrogram_avg_batch_device; psd_batch_stride 0 when no PSD rows are
    asked for, so that psd stays NULL) */
 __device__ __forceinline__ void glfer_batch_select_avg(SpectroParams &p) {
@@ -190,6 +232,32 @@ hipError_t glfer_launch_spectro16w_n11(const SpectroParams *p, hipStream_t st);
 hipError_t glfer_launch_spectro16w_n12(const SpectroParams *p, hipStream_t st);
 hipError_t glfer_launch_spectro16w_n13(const SpectroParams *p, hipStream_t st);
 hipError_t glfer_launch_spectro16w_n14(const SpectroParams *p, hipStream_t st);
+/* the ragged instantiations (p->ragged != NULL, p->nbatch >= 2) */
+hipError_t glfer_launch_spectro16_ragged_n8(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16_ragged_n9(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16_ragged_n10(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16_ragged_n11(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16_ragged_n12(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16_ragged_n13(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16_ragged_n14(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16x_ragged_n8(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16x_ragged_n9(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16x_ragged_n10(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16xl_ragged_n8(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16xl_ragged_n9(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16xl_ragged_n10(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16xl_ragged_n11(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16y_ragged_n12(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16h_ragged_n9(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16h_ragged_n10(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16h_ragged_n11(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16h_ragged_n12(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16h_ragged_n13(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16h_ragged_n14(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16w_ragged_n11(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16w_ragged_n12(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16w_ragged_n13(const SpectroParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16w_ragged_n14(const SpectroParams *p, hipStream_t st);
 size_t glfer_levels_scratch_floats(size_t nframes);
 hipError_t glfer_launch_levels(const float *stats, size_t nframes, int scale_log, int autoscale,
                                int first_buffer, float overlap, float max_lvl0, float min_lvl0,
@@ -208,6 +276,11 @@ hipError_t glfer_launch_submean_batch(const void *in, float *out, int H, long lo
                                       unsigned nb, long long in_bstride, long long out_bstride, long long means_bstride);
 hipError_t glfer_launch_hop_means_seq_batch(const void *in, float *means, int H, long long nhops, int fmt, unsigned nb,
                                             long long in_bstride, long long means_bstride, hipStream_t st);
+/* the two over nb streams of unequal length: tab[b] (device) holds stream b's pointers and its own hop count, max_nhops (the
+   longest) sizes the grid; with_means: the copy subtracts tab[b].means instead of summing the hops itself */
+hipError_t glfer_launch_hop_means_seq_ragged(const GlferRaggedHops *tab, unsigned nb, int H, long long max_nhops, int fmt, hipStream_t st);
+hipError_t glfer_launch_submean_ragged(const GlferRaggedHops *tab, unsigned nb, int H, long long max_nhops, int fmt, int with_means,
+                                       hipStream_t st);
 #ifdef __cplusplus
 }
 #endif

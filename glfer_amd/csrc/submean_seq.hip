@@ -20,11 +20,20 @@
 
 namespace glfer {
 
-template <int FMT, int TILE>
+// RAG (glfer_launch_hop_means_seq_ragged): streams of unequal length -- `in` is the launch's GlferRaggedHops table, entry
+// blockIdx.y holds the stream's samples, its means table and its own hop count; the other arguments but H are not read.
+template <int FMT, int TILE, int RAG = 0>
 __global__ __launch_bounds__(256) void hop_means_seq_kernel(const void *in, float *means, int H, long long nhops, long long in_bstride,
                                                              long long means_bstride) {
-  in = reinterpret_cast<const char *>(in) + (long long)blockIdx.y * in_bstride;   // the stream of a batch (blockIdx.y; 0 otherwise)
-  means += (long long)blockIdx.y * means_bstride;
+  if constexpr (RAG != 0) {
+    const GlferRaggedHops e = reinterpret_cast<const GlferRaggedHops *>(in)[blockIdx.y];
+    in = e.in;
+    means = e.means;
+    nhops = e.nhops;
+  } else {
+    in = reinterpret_cast<const char *>(in) + (long long)blockIdx.y * in_bstride;   // the stream of a batch (blockIdx.y; 0 otherwise)
+    means += (long long)blockIdx.y * means_bstride;
+  }
   constexpr unsigned esz = FMT == GLFER_FMT_F32 ? 4 : (FMT == GLFER_FMT_S16 ? 2 : 1);
   __shared__ float tile_all[4][64 * (TILE + 1)];
   const unsigned l = threadIdx.x & 63u;
@@ -196,6 +205,21 @@ extern "C" hipError_t glfer_launch_hop_means_seq_batch(const void *in, float *me
     case GLFER_FMT_F32: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_F32, 64>), grid, dim3(256), 0, st, in, means, H, nhops, in_bstride, means_bstride); break;
     case GLFER_FMT_S16: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_S16, 64>), grid, dim3(256), 0, st, in, means, H, nhops, in_bstride, means_bstride); break;
     case GLFER_FMT_U8: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_U8, 64>), grid, dim3(256), 0, st, in, means, H, nhops, in_bstride, means_bstride); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+extern "C" hipError_t glfer_launch_hop_means_seq_ragged(const GlferRaggedHops *tab, unsigned nb, int H, long long max_nhops, int fmt,
+                                                        hipStream_t st) {
+  if (max_nhops <= 0 || nb == 0) return hipSuccess;
+  if (nb > 65535 || !tab) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((max_nhops + 255) / 256), nb);
+  const void *in = tab;
+  switch (fmt) {
+    case GLFER_FMT_F32: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_F32, 64, 1>), grid, dim3(256), 0, st, in, (float *)nullptr, H, max_nhops, 0LL, 0LL); break;
+    case GLFER_FMT_S16: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_S16, 64, 1>), grid, dim3(256), 0, st, in, (float *)nullptr, H, max_nhops, 0LL, 0LL); break;
+    case GLFER_FMT_U8: hipLaunchKernelGGL((hop_means_seq_kernel<GLFER_FMT_U8, 64, 1>), grid, dim3(256), 0, st, in, (float *)nullptr, H, max_nhops, 0LL, 0LL); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

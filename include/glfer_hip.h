@@ -233,11 +233,46 @@ int glfer_hip_spectrogram_device(glfer_hip_plan *plan, const void *d_stream, siz
  * The moving average of many streams: glfer_hip_spectrogram_avg_batch_device and glfer_hip_avg_batch_device below; their
  * waterfalls: glfer_hip_waterfall_batch_device.
  * The harmonic F-test of many streams: glfer_hip_mtm_ftest_batch_device below.
- * Not covered: ragged batches (one length per stream), batched host / WAV / workers entries, the
- * halfcomplex-spectrum output, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as they are. */
+ * Streams of unequal length: glfer_hip_spectrogram_ragged_device below (the rows entry only).
+ * Not covered: batched host / WAV / workers entries, the halfcomplex-spectrum output, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as they are. */
 int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams,
                                        size_t stream_pitch, size_t nsamples, size_t first_frame,
                                        size_t nframes, float *d_psd, void *hip_stream);
+
+/* Ragged batches: nstreams streams of one plan, each with its own length, in one call.
+ *   d_samples  : device, one buffer that holds every stream, in samples of cfg.sample_format
+ *   offsets,
+ *   lengths    : HOST arrays [nstreams], in samples: stream b is the lengths[b] samples at d_samples + offsets[b].  Any
+ *                order, gaps and overlaps allowed (the samples are only read).  With s16 / u8 samples every offsets[b] must
+ *                be even (GLFER_E_ARG otherwise), for the reason the batch entry refuses an odd pitch: the kernel choice
+ *                reads a stream's alignment and must not differ between the streams of a launch.  f32 offsets are free.
+ *                d_samples itself may have any alignment the single-stream entry takes: each launch reads its route from
+ *                the samples it is given (the raw streams, or their corrected f32 copies), as that entry does.
+ *                Both arrays are consumed before the call returns.
+ *   d_psd      : device, [sum of frames][pitch] floats (cfg.psd_pitch honoured).  Stream b is processed WHOLE, from its own
+ *                zero history: frames_b = lengths[b] / hop rows (none for a stream shorter than a hop), packed -- its
+ *                rows start at row R_b = frames_0 + ... + frames_(b-1)
+ *   row_starts : HOST, optional, [nstreams + 1]: receives R_0 .. R_nstreams
+ * Stream b's rows are float for float those of glfer_hip_spectrogram_device(plan, d_samples + offsets[b], lengths[b], 0,
+ * frames_b, ...).  glfer_hip_ragged_frames(plan, nstreams, lengths, row_starts) returns the total row count (and the same
+ * row_starts, optional) so that d_psd can be sized first; it touches no device.  It returns 0 for a NULL plan or NULL
+ * lengths, SIZE_MAX if the sum overflows.
+ * FFT and MTM modes at N = 256 .. 16384 -- every sub_mean value, RA9MB / limiter and ZERO_ALWAYS included -- take a number of
+ * kernel launches and copies that does not depend on nstreams or on the lengths: each launch the single-stream entry makes
+ * for one stream (first frames, body, frames off the frame groups, hop means, corrected copies) is made once over all
+ * streams, blockIdx.y indexing a small per-stream table the call builds and uploads; more than 65 535 streams go in chunks
+ * of that many.  HP-ARMA, LMP and N outside 256 .. 16384 go stream by stream inside the call, and so does a call (or a
+ * chunk) of one stream.
+ * GLFER_E_ARG: NULL plan; NULL offsets / lengths with nstreams > 0; NULL d_samples or d_psd while any stream has a frame; an
+ * odd offset with integer samples; a stream of more than 2^31 - 1 frames; sizes that overflow size_t -- all checked before
+ * anything on the device is touched; a hip_stream that is being captured into a graph (the per-stream tables are uploaded from
+ * host memory that is gone when the call returns, which a captured copy would read at every replay).  nstreams == 0 or no frame at all: GLFER_OK, nothing written.
+ * Limits: whole streams only (no first_frame / nframes sub-range), the rows entry only (no ragged average, waterfall or
+ * F-test), device-resident samples only.  Asynchronous on hip_stream. */
+size_t glfer_hip_ragged_frames(const glfer_hip_plan *plan, size_t nstreams, const size_t *lengths, size_t *row_starts);
+int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *plan, const void *d_samples, size_t nstreams,
+                                        const size_t *offsets, const size_t *lengths, float *d_psd,
+                                        size_t *row_starts, void *hip_stream);
 
 /* In LMP mode (GLFER_MODE_LMP, lmp.c:101-181) the same entry writes the detection statistic:
  * per frame the rectangular-window periodogram of the assembled frame (lmp.c:114-125), then per
