@@ -9,6 +9,7 @@
 #include "plan.h"
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -17,8 +18,11 @@
 #include <mutex>
 #include <new>
 
+#include "frame_cuts.h"
 #include "host_tables.h"
 #include "spectro_params.h"
+
+static_assert(GLFER_FMT_F32 == GLFER_SAMPLES_F32 && GLFER_FMT_S16 == GLFER_SAMPLES_S16 && GLFER_FMT_U8 == GLFER_SAMPLES_U8, "glfer_sample_size");
 
 extern "C" hipError_t glfer_launch_hparma(const SpectroParams *sp, int n, int t, int ncol, const int *rot_sched, int rot_steps, int rot_width, const uint16_t *lagmap,
                                           const float2 *unit, hipStream_t st);
@@ -1554,7 +1558,7 @@ enum BodyRoute { ROUTE_PACKED, ROUTE_REAL_INPUT, ROUTE_SHARED_ODD, ROUTE_WAVE_PR
 static BodyRoute body_route(const SpectroParams &sp, int n) {
   // spectro16h.hip fetches y[2j], y[2j+1] with one load: integer samples must then sit on naturally
   // aligned pairs (even hop, so every frame starts on an even sample, and an aligned stream)
-  const unsigned esz = sp.fmt == GLFER_FMT_F32 ? 4u : (sp.fmt == GLFER_FMT_S16 ? 2u : 1u);
+  const unsigned esz = (unsigned)glfer_sample_size(sp.fmt);
   const bool pairs_aligned = sp.fmt == GLFER_FMT_F32 ||
                              ((sp.H & 1) == 0 && (reinterpret_cast<uintptr_t>(sp.stream) & (2u * esz - 1u)) == 0);
   const int force = form_override();
@@ -1609,20 +1613,15 @@ static hipError_t launch_by_n(const SpectroParams &sp, int n, hipStream_t st) {
   const bool real_input = route == ROUTE_REAL_INPUT || route == ROUTE_WAVE_PRIVATE, wave_private = route == ROUTE_WAVE_PRIVATE;
   if (sp.mean_inkernel && !route_takes_mean(route, sp, n)) return hipErrorInvalidValue;
   if (route == ROUTE_PACKED) return launch_packed(sp, n, st);
-  const long long first_inside = ((long long)sp.R + sp.H - 1) / sp.H;          // first frame f with f*H >= R
+  const long long first_inside = (long long)glfer_first_inside((size_t)sp.R, (size_t)sp.H);
   if (sp.mean_inkernel && sp.frame0 < first_inside) return hipErrorInvalidValue;   // (the caller sends the head frames another way)
-  // spectro16x.hip works on groups of G consecutive frames (frame f shares its last transform with
-  // frame f + G/2).  Groups are aligned to GLOBAL frame indices and only whole groups go to it, so a
-  // frame's result does not depend on how the stream was cut into launches, chunks or shards, as
-  // long as the cuts fall on multiples of GLFER_FRAME_ALIGN (shard.py and the WAV reader see to it).
-  const int lanes = n / 16;
-  const long long G = real_input ? 1 : 2 * (lanes >= 256 ? 1 : 256 / lanes);
+  // only whole, globally aligned frame groups go to the route's kernel (frame_cuts.h; shard.py and the WAV reader cut streams
+  // on multiples of GLFER_FRAME_ALIGN)
   const long long lo = sp.frame0, hi = sp.frame0 + sp.nframes;
-  long long b0 = lo > first_inside ? lo : first_inside;
-  b0 = (b0 + G - 1) / G * G;
-  long long b1 = hi / G * G;
+  const glfer_frame_cut cut = glfer_cut_frames((size_t)lo, (size_t)hi, (size_t)first_inside, glfer_frame_group(route == ROUTE_SHARED_ODD, n));
+  const long long b0 = (long long)cut.b0, b1 = (long long)cut.b1;
   if (sp.mean_inkernel && (b0 != lo || b1 != hi)) return hipErrorInvalidValue;   // (the caller cuts at the frame groups)
-  if (b0 >= b1) return launch_packed(sp, n, st);
+  if (b0 == b1) return launch_packed(sp, n, st);
   auto sub = [&](long long from, long long to) {
     SpectroParams q = sp;
     q.frame0 = from;
@@ -1684,6 +1683,7 @@ static void fill_params(const glfer_hip_plan *p, SpectroParams &sp) {
 
 // cfg.sub_mean: any non-zero value but GLFER_SUBMEAN_FAST asks for the reference's rows, i.e. the hop means in
 // the reference's own summation order (1 = GLFER_SUBMEAN_EXACT is what fft_init stores: sub_mean = opt.autoscale)
+static size_t plan_first_inside(const glfer_hip_plan *p) { return glfer_first_inside((size_t)p->keep, (size_t)p->hop); }
 static bool reference_means(const glfer_hip_plan *p) { return p->cfg.sub_mean != 0 && p->cfg.sub_mean != GLFER_SUBMEAN_FAST; }
 
 // K0 (fft.c:86-96) for the hops that frames [first, first+nframes) touch: the mean of each hop's
@@ -1701,18 +1701,20 @@ static bool reference_means(const glfer_hip_plan *p) { return p->cfg.sub_mean !=
 // the last hop is rebuilt from the corrected previous hop before its own mean is taken.
 static int submean_scratch(const glfer_hip_plan *p, SpectroParams &sp, size_t first, size_t nframes, hipStream_t st,
                            float **scratch_out, long tail_fresh = -1) {
+  // A batch (sp.nbatch streams, sp.batch_stride bytes apart): one copy per stream, side by side in one scratch block, from
+  // launches that cover the whole batch; sp leaves with the copy of stream 0 and the copies' stride.
+  const unsigned nb = glfer_batch_y(sp);
+  assert(tail_fresh < 0 || nb == 1);   // (a trailing partial block is a file source's: one stream; no batch caller passes one)
   // ZERO_ALWAYS frames use only their own hop, and no kernel loads the history it would zero
   // (round 3: odd_taper.hpp::load_frame16, spectro16h / spectro16w's HIST gathers start their
   // descriptor at the frame's own hop), so the copy starts there too -- a piece cut for that mode
   // carries no history below its first hop (glfer_hip.h, "Cutting a stream", rule 2).
-  const size_t hops_back = sp.history_mode ? 0 : (size_t)((p->keep + p->hop - 1) / p->hop);
-  size_t hop_lo = (first > hops_back) ? first - hops_back : 0;
-  const size_t last = first + nframes - 1;
-  if (tail_fresh >= 0 && last > 0 && hop_lo > last - 1) hop_lo = last - 1;   // the stale part needs the hop before
-  const size_t nhops = first + nframes - hop_lo;
+  const size_t hops_back = glfer_hops_back(sp.history_mode, plan_first_inside(p));
+  const glfer_hop_span h = glfer_copy_hops(first, nframes, hops_back, tail_fresh >= 0);
+  const size_t hop_lo = h.lo, nhops = h.n, per = nhops * (size_t)p->hop;
   float *scratch = nullptr;
-  HIP_TRY(glfer::scratch_malloc((void **)&scratch, nhops * (size_t)p->hop * sizeof(float), st));
-  const size_t esz = sp.fmt == GLFER_FMT_F32 ? 4 : (sp.fmt == GLFER_FMT_S16 ? 2 : 1);
+  HIP_TRY(glfer::scratch_malloc((void **)&scratch, (size_t)nb * per * sizeof(float), st));
+  const size_t esz = glfer_sample_size(sp.fmt);
   const char *src = (const char *)sp.stream + hop_lo * (size_t)p->hop * esz;
   // GLFER_SUBMEAN_EXACT: the hop means first, accumulated sample after sample as fft.c:88-92 does
   // (submean_seq.hip: one more read of the stream), then the copy with those means
@@ -1720,10 +1722,13 @@ static int submean_scratch(const glfer_hip_plan *p, SpectroParams &sp, size_t fi
   float *means = nullptr;
   hipError_t e = hipSuccess;
   if (exact) {
-    e = glfer::scratch_malloc((void **)&means, nhops * sizeof(float), st);
-    if (e == hipSuccess) e = glfer_launch_hop_means_seq(src, means, p->hop, (long long)nhops, sp.fmt, st);
+    e = glfer::scratch_malloc((void **)&means, (size_t)nb * nhops * sizeof(float), st);
+    if (e == hipSuccess)
+      e = glfer_launch_hop_means_seq_batch(src, means, p->hop, (long long)nhops, sp.fmt, nb, sp.batch_stride, (long long)nhops, st);
   }
-  if (e == hipSuccess) e = glfer_launch_submean(src, scratch, p->hop, (long long)nhops, sp.fmt, st, means);
+  if (e == hipSuccess)
+    e = glfer_launch_submean_batch(src, scratch, p->hop, (long long)nhops, sp.fmt, st, means, nb, sp.batch_stride, (long long)per,
+                                   (long long)nhops);
   if (e == hipSuccess && tail_fresh >= 0)
     e = glfer_launch_submean_tail_ex(src + (nhops - 1) * (size_t)p->hop * esz, nhops > 1 ? scratch + (nhops - 2) * (size_t)p->hop : nullptr,
                                      scratch + (nhops - 1) * (size_t)p->hop, p->hop, (int)tail_fresh, exact ? 1 : 0, sp.fmt, st);
@@ -1734,6 +1739,7 @@ static int submean_scratch(const glfer_hip_plan *p, SpectroParams &sp, size_t fi
   }
   sp.stream = reinterpret_cast<const char *>(scratch) - hop_lo * (size_t)p->hop * sizeof(float);
   sp.fmt = GLFER_FMT_F32;
+  if (nb > 1) sp.batch_stride = (long long)(per * sizeof(float));
   *scratch_out = scratch;
   return GLFER_OK;
 }
@@ -1761,7 +1767,7 @@ static bool mean_inkernel_ok(const glfer_hip_plan *p, const SpectroParams &sp, c
 // wavefront, whichever still gives the pass a few thousand wavefronts -- else 64 hops per wavefront.
 static hipError_t launch_reference_means(const glfer_hip_plan *p, const SpectroParams &sp, size_t hop_lo, size_t nhops, float *means,
                                          unsigned blocks, hipStream_t st) {
-  const size_t esz = sp.fmt == GLFER_FMT_F32 ? 4 : (sp.fmt == GLFER_FMT_S16 ? 2 : 1);
+  const size_t esz = glfer_sample_size(sp.fmt);
   const char *src = (const char *)sp.stream + hop_lo * (size_t)p->hop * esz;
   const int forced = [] { const char *e = getenv("GLFER_MEANS_HPW"); return e && *e ? atoi(e) : 0; }();
   int hpw = forced;
@@ -1793,9 +1799,9 @@ static int launch_body_with_reference_means(glfer_hip_plan *p, const SpectroPara
     return v < 1 ? 1 : (v > 3 ? 3 : v);
   }();
   const unsigned means_blocks = [] { const char *e = getenv("GLFER_MEANS_BLOCKS"); return e && *e ? (unsigned)atol(e) : 0u; }();
-  const size_t hops_back = (size_t)((p->keep + p->hop - 1) / p->hop);
-  const size_t hop_lo = b0 - hops_back, nhops = b1 - hop_lo;                  // (b0 >= first_inside >= hops_back)
-  const size_t esz = bs.fmt == GLFER_FMT_F32 ? 4 : (bs.fmt == GLFER_FMT_S16 ? 2 : 1);
+  const glfer_hop_span h = glfer_means_hops(b0, b1, 0, plan_first_inside(p));
+  const size_t hop_lo = h.lo, nhops = h.n;
+  const size_t esz = glfer_sample_size(bs.fmt);
   // frames per piece: a multiple of 64 frames (the frame groups of every form and GLFER_FRAME_ALIGN)
   size_t piece = b1 - b0;
   if (piece_mb > 0) {
@@ -1931,21 +1937,17 @@ static int launch_body_with_reference_means(glfer_hip_plan *p, const SpectroPara
   return e == hipSuccess ? GLFER_OK : hip_fail(e, "estimator launch (given hop means, piecewise)");
 }
 
-// Periodograms of frames [first, first + nframes) with the mean removal (fft.c:86-96) done inside the
-// periodogram kernel: the frames that lie inside the stream read the RAW stream and no corrected
-// copy is written for them; the first ceil(R/H) frames of a stream (zero history: the packed
-// kernel) keep the copy, a few hops long.  sp: fill_params + the raw stream.
-static int launch_mean_inkernel(glfer_hip_plan *p, const SpectroParams &sp, size_t first, size_t nframes, float *d_psd,
-                                hipStream_t st) {
-  const size_t first_inside = (size_t)((p->keep + p->hop - 1) / p->hop);
-  // the shared-odd-taper kernels take whole, globally aligned groups of frames (launch_by_n): pairs at N = 4096
-  const size_t lanes = (size_t)p->n / 16;
-  const size_t G = body_route(sp, p->n) == ROUTE_SHARED_ODD ? 2 * (lanes >= 256 ? 1 : 256 / lanes) : 1;
-  const size_t end = first + nframes;
-  size_t b0 = std::max(first, first_inside);
-  b0 = (b0 + G - 1) / G * G;
-  size_t b1 = end / G * G;
-  if (b0 >= b1) b0 = b1 = end;                                   // no body: everything through the copy
+// Periodograms of frames [sp.frame0, sp.frame0 + sp.nframes), to sp.psd, with the mean removal (fft.c:86-96) done inside the
+// estimator kernel: the frames that lie inside the stream read the RAW stream and no corrected copy is written for them; the
+// first ceil(R/H) frames of a stream (zero history: the packed kernel) and the frames off the route's frame groups keep the
+// copy, a few hops long.  sp: fill_params + the raw stream -- or the raw streams of a batch (nbatch and the batch strides):
+// every launch then covers the whole batch, and the body's reference-order hop means are one table per stream.
+static int launch_mean_inkernel(glfer_hip_plan *p, const SpectroParams &sp, hipStream_t st) {
+  const size_t first = (size_t)sp.frame0, end = first + (size_t)sp.nframes;
+  const size_t first_inside = plan_first_inside(p);
+  const glfer_frame_cut cut = glfer_cut_frames(first, end, first_inside, glfer_frame_group(body_route(sp, p->n) == ROUTE_SHARED_ODD, p->n));
+  const size_t b0 = cut.b0, b1 = cut.b1;
+  const unsigned nb = glfer_batch_y(sp);
   int rc = GLFER_OK;
   // frames [from, to) through the corrected copy (the stream's first frames, a lone frame off the pair grid)
   auto by_copy = [&](size_t from, size_t to) {
@@ -1953,31 +1955,43 @@ static int launch_mean_inkernel(glfer_hip_plan *p, const SpectroParams &sp, size
     SpectroParams hs = sp;
     hs.frame0 = (long long)from;
     hs.nframes = (int)(to - from);
-    hs.psd = d_psd + (from - first) * (size_t)p->pitch;
+    hs.psd = sp.psd + (from - first) * (size_t)p->pitch;
     float *scratch = nullptr;
     rc = submean_scratch(p, hs, from, to - from, st, &scratch);
     if (rc == GLFER_OK) {
       hipError_t e = launch_by_n(hs, p->n, st);
-      if (e != hipSuccess) rc = hip_fail(e, "estimator launch (frames through the corrected copy)");
+      if (e != hipSuccess) rc = hip_fail(e, nb > 1 ? "estimator launch (batch, frames through the corrected copies)" : "estimator launch (frames through the corrected copy)");
     }
     if (scratch) glfer::scratch_free(scratch, st);
   };
-  by_copy(first, std::min(b0, end));
+  by_copy(first, b0);
   if (rc == GLFER_OK && b1 > b0) {
     SpectroParams bs = sp;
     bs.frame0 = (long long)b0;
     bs.nframes = (int)(b1 - b0);
-    bs.psd = d_psd + (b0 - first) * (size_t)p->pitch;
+    bs.psd = sp.psd + (b0 - first) * (size_t)p->pitch;
     bs.spec = nullptr;
     bs.mean_inkernel = 1;
     if (!reference_means(p)) {
       hipError_t e = launch_by_n(bs, p->n, st);
-      if (e != hipSuccess) rc = hip_fail(e, "estimator launch (mean removal in the kernel)");
-    } else {
+      if (e != hipSuccess) rc = hip_fail(e, nb > 1 ? "estimator launch (batch, mean removal in the kernel)" : "estimator launch (mean removal in the kernel)");
+    } else if (sp.nbatch == 0) {                                         // the single-stream entry (a batch chunk of one stream keeps the batch's launches)
       rc = launch_body_with_reference_means(p, bs, b0, b1, st);
+    } else {                                                             // a batch: one table per stream, nhops apart, from one launch
+      const glfer_hop_span h = glfer_means_hops(b0, b1, 0, first_inside);
+      float *means = nullptr;
+      hipError_t e = glfer::scratch_malloc((void **)&means, (size_t)nb * h.n * sizeof(float), st);
+      if (e == hipSuccess)
+        e = glfer_launch_hop_means_seq_batch((const char *)sp.stream + h.lo * (size_t)p->hop * glfer_sample_size(sp.fmt), means, p->hop,
+                                             (long long)h.n, sp.fmt, nb, sp.batch_stride, (long long)h.n, st);
+      bs.means = means - h.lo;                                           // indexed by the stream's own hop (= frame) index
+      bs.means_batch_stride = (long long)h.n;
+      if (e == hipSuccess) e = launch_by_n(bs, p->n, st);
+      if (means) glfer::scratch_free(means, st);
+      if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch, mean removal in the kernel)");
     }
   }
-  by_copy(std::max(b1, std::min(b0, end)), end);
+  by_copy(b1, end);
   return rc;
 }
 
@@ -2003,7 +2017,7 @@ int glfer_run_device(glfer_hip_plan *p, const void *d_stream, size_t nsamples, s
   int rc = GLFER_OK;
   if (tail_fresh >= 0 && (tail_fresh >= (long)p->hop || p->cfg.mode == GLFER_MODE_LMP)) return GLFER_E_ARG;
   const bool inkernel = p->cfg.sub_mean && mean_inkernel_ok(p, sp, d_spec, tail_fresh);
-  if (inkernel && p->cfg.mode != GLFER_MODE_LMP) return launch_mean_inkernel(p, sp, first, nframes, d_psd, st);
+  if (inkernel && p->cfg.mode != GLFER_MODE_LMP) return launch_mean_inkernel(p, sp, st);
   if (p->cfg.sub_mean && !inkernel) rc = submean_scratch(p, sp, first, nframes, st, &scratch, tail_fresh);
   if (rc == GLFER_OK && p->cfg.mode == GLFER_MODE_LMP) {
     // lmp.c:101-181: periodograms of the frames the ring holds when frame first+nframes-1 is done
@@ -2013,7 +2027,10 @@ int glfer_run_device(glfer_hip_plan *p, const void *d_stream, size_t nsamples, s
     hipError_t e = glfer::scratch_malloc((void **)&rows, nrows * (size_t)p->bins * sizeof(float), st);
     if (e != hipSuccess) rc = hip_fail(e, "hipMallocAsync(lmp rows)");
     if (rc == GLFER_OK && inkernel) {
-      rc = launch_mean_inkernel(p, sp, first - back, nrows, rows, st);
+      sp.frame0 = (long long)(first - back);
+      sp.nframes = (int)nrows;
+      sp.psd = rows;
+      rc = launch_mean_inkernel(p, sp, st);
       if (rc == GLFER_OK) {
         e = glfer_launch_lmp(rows, (long long)(first - back), (long long)first, nframes, p->bins, p->lmp_av, d_psd, st);
         if (e != hipSuccess) rc = hip_fail(e, "lmp launch");
@@ -2062,90 +2079,13 @@ int glfer_hip_spectrogram_device(glfer_hip_plan *p, const void *d_stream, size_t
 // stream (launch_by_n, launch_mean_inkernel, submean_scratch), and every launch they produce covers the whole batch, so the
 // rows are those of the single-stream entry and the launch count does not grow with the batch.
 
-// submean_scratch over nb streams (sp: the raw stream 0 with its batch_stride): one corrected copy per stream, nhops hops
-// each, side by side in one scratch block; sp leaves with the copy of stream 0 (virtual base) and the copies' stride.
-static int batch_submean_scratch(const glfer_hip_plan *p, SpectroParams &sp, size_t first, size_t nframes, unsigned nb,
-                                 hipStream_t st, float **scratch_out) {
-  const size_t hops_back = sp.history_mode ? 0 : (size_t)((p->keep + p->hop - 1) / p->hop);
-  const size_t hop_lo = (first > hops_back) ? first - hops_back : 0;
-  const size_t nhops = first + nframes - hop_lo, per = nhops * (size_t)p->hop;
-  float *scratch = nullptr, *means = nullptr;
-  HIP_TRY(glfer::scratch_malloc((void **)&scratch, (size_t)nb * per * sizeof(float), st));
-  const size_t esz = sp.fmt == GLFER_FMT_F32 ? 4 : (sp.fmt == GLFER_FMT_S16 ? 2 : 1);
-  const char *src = (const char *)sp.stream + hop_lo * (size_t)p->hop * esz;
-  hipError_t e = hipSuccess;
-  if (reference_means(p)) {
-    e = glfer::scratch_malloc((void **)&means, (size_t)nb * nhops * sizeof(float), st);
-    if (e == hipSuccess)
-      e = glfer_launch_hop_means_seq_batch(src, means, p->hop, (long long)nhops, sp.fmt, nb, sp.batch_stride, (long long)nhops, st);
-  }
-  if (e == hipSuccess)
-    e = glfer_launch_submean_batch(src, scratch, p->hop, (long long)nhops, sp.fmt, st, means, nb, sp.batch_stride, (long long)per,
-                                   (long long)nhops);
-  if (means) glfer::scratch_free(means, st);
-  if (e != hipSuccess) {
-    glfer::scratch_free(scratch, st);
-    return hip_fail(e, "glfer_launch_submean_batch");
-  }
-  sp.stream = reinterpret_cast<const char *>(scratch) - hop_lo * (size_t)p->hop * sizeof(float);
-  sp.fmt = GLFER_FMT_F32;
-  sp.batch_stride = (long long)(per * sizeof(float));
-  *scratch_out = scratch;
+// the streams one launch takes: the current device's grid y limit, at least `floor`
+static int grid_y_limit(int floor, size_t *ymax) {
+  int dev = 0, y = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  HIP_TRY(hipDeviceGetAttribute(&y, hipDeviceAttributeMaxGridDimY, dev));
+  *ymax = (size_t)std::max(floor, std::min(y, 65535));
   return GLFER_OK;
-}
-
-// launch_mean_inkernel over nb streams: the head / tail frames through the batch's corrected copies, the body from the raw
-// streams with the hop means summed by the kernel, or (the reference's order) given -- one table per stream, nhops apart.
-static int batch_mean_inkernel(glfer_hip_plan *p, const SpectroParams &sp, size_t first, size_t nframes, unsigned nb,
-                               hipStream_t st) {
-  const size_t first_inside = (size_t)((p->keep + p->hop - 1) / p->hop);
-  const size_t lanes = (size_t)p->n / 16;
-  const size_t G = body_route(sp, p->n) == ROUTE_SHARED_ODD ? 2 * (lanes >= 256 ? 1 : 256 / lanes) : 1;
-  const size_t end = first + nframes;
-  size_t b0 = std::max(first, first_inside);
-  b0 = (b0 + G - 1) / G * G;
-  size_t b1 = end / G * G;
-  if (b0 >= b1) b0 = b1 = end;
-  int rc = GLFER_OK;
-  auto by_copy = [&](size_t from, size_t to) {
-    if (rc != GLFER_OK || from >= to) return;
-    SpectroParams hs = sp;
-    hs.frame0 = (long long)from;
-    hs.nframes = (int)(to - from);
-    hs.psd = sp.psd + (from - first) * (size_t)p->pitch;
-    float *scratch = nullptr;
-    rc = batch_submean_scratch(p, hs, from, to - from, nb, st, &scratch);
-    if (rc == GLFER_OK) {
-      hipError_t e = launch_by_n(hs, p->n, st);
-      if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch, frames through the corrected copies)");
-    }
-    if (scratch) glfer::scratch_free(scratch, st);
-  };
-  by_copy(first, std::min(b0, end));
-  if (rc == GLFER_OK && b1 > b0) {
-    SpectroParams bs = sp;
-    bs.frame0 = (long long)b0;
-    bs.nframes = (int)(b1 - b0);
-    bs.psd = sp.psd + (b0 - first) * (size_t)p->pitch;
-    bs.mean_inkernel = 1;
-    float *means = nullptr;
-    hipError_t e = hipSuccess;
-    if (reference_means(p)) {
-      const size_t hop_lo = b0 - first_inside, nhops = b1 - hop_lo;      // (b0 >= first_inside)
-      const size_t esz = sp.fmt == GLFER_FMT_F32 ? 4 : (sp.fmt == GLFER_FMT_S16 ? 2 : 1);
-      e = glfer::scratch_malloc((void **)&means, (size_t)nb * nhops * sizeof(float), st);
-      if (e == hipSuccess)
-        e = glfer_launch_hop_means_seq_batch((const char *)sp.stream + hop_lo * (size_t)p->hop * esz, means, p->hop, (long long)nhops,
-                                             sp.fmt, nb, sp.batch_stride, (long long)nhops, st);
-      bs.means = means - hop_lo;                                         // indexed by the stream's own hop (= frame) index
-      bs.means_batch_stride = (long long)nhops;
-    }
-    if (e == hipSuccess) e = launch_by_n(bs, p->n, st);
-    if (means) glfer::scratch_free(means, st);
-    if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch, mean removal in the kernel)");
-  }
-  by_copy(std::max(b1, std::min(b0, end)), end);
-  return rc;
 }
 
 // the plans whose rows a batch computes in the launches of one stream (the others go stream by stream)
@@ -2163,7 +2103,7 @@ int glfer_hip_spectrogram_batch_device(glfer_hip_plan *p, const void *d_streams,
   if ((first + nframes) > nsamples / (size_t)p->hop) return GLFER_E_ARG;   // frame past the stream
   if (nframes > 0x7fffffffu) return GLFER_E_ARG;
   const int fmt = p->cfg.sample_format;
-  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
+  const size_t esz = glfer_sample_size(fmt);
   // body_route (and spectro16w's launcher) read the stream's alignment for integer samples: every stream must see the
   // same kernels, so an odd pitch -- every other stream off the pair alignment -- is refused rather than routed per stream
   if (fmt != GLFER_FMT_F32 && (stream_pitch & 1)) return GLFER_E_ARG;
@@ -2176,7 +2116,7 @@ int glfer_hip_spectrogram_batch_device(glfer_hip_plan *p, const void *d_streams,
 static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch, size_t nsamples, size_t first,
                       size_t nframes, float *d_psd, size_t psd_bs, hipStream_t st) {
   const int fmt = p->cfg.sample_format;
-  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
+  const size_t esz = glfer_sample_size(fmt);
   const char *base = static_cast<const char *>(d_streams);
   if (!batch_one_launch(p) || nstreams == 1) {
     for (size_t b = 0; b < nstreams; b++) {
@@ -2187,12 +2127,10 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
   }
   DeviceGuard guard(p->cfg.device);
   HIP_TRY(guard.error());
-  int dev = 0, ymax = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipDeviceGetAttribute(&ymax, hipDeviceAttributeMaxGridDimY, dev));
-  ymax = std::max(1, std::min(ymax, 65535));
-  for (size_t c0 = 0; c0 < nstreams; c0 += (size_t)ymax) {      // batches above the grid's y limit: chunks of it
-    const unsigned nb = (unsigned)std::min(nstreams - c0, (size_t)ymax);
+  size_t ymax = 0;
+  if (const int yrc = grid_y_limit(1, &ymax); yrc != GLFER_OK) return yrc;
+  for (size_t c0 = 0; c0 < nstreams; c0 += ymax) {      // batches above the grid's y limit: chunks of it
+    const unsigned nb = (unsigned)std::min(nstreams - c0, ymax);
     SpectroParams sp;
     fill_params(p, sp);
     sp.stream = base + c0 * stream_pitch * esz;
@@ -2204,10 +2142,10 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
     sp.psd_batch_stride = (long long)psd_bs;
     int rc = GLFER_OK;
     if (p->cfg.sub_mean && mean_inkernel_ok(p, sp, nullptr, -1)) {
-      rc = batch_mean_inkernel(p, sp, first, nframes, nb, st);
+      rc = launch_mean_inkernel(p, sp, st);
     } else {
       float *scratch = nullptr;
-      if (p->cfg.sub_mean) rc = batch_submean_scratch(p, sp, first, nframes, nb, st, &scratch);
+      if (p->cfg.sub_mean) rc = submean_scratch(p, sp, first, nframes, st, &scratch);
       if (rc == GLFER_OK) {
         const hipError_t e = launch_by_n(sp, p->n, st);
         if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch)");
@@ -2224,8 +2162,9 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
 // Streams of unequal length in one call (glfer_hip.h).  Every launch the single-stream entry would make for a stream -- the
 // packed kernel for its first frames and for the frames off the frame groups, the route's kernel for its body, the hop means and
 // the corrected copies of the mean removal -- is made ONCE for all streams: blockIdx.y indexes a table (GlferRaggedEntry /
-// GlferRaggedHops, spectro_params.h) that holds each stream's samples, rows, means and its own frames of that launch, cut as
-// launch_by_n and launch_mean_inkernel cut them.  The tables are built here and go to stream-ordered scratch.
+// GlferRaggedHops, spectro_params.h) that holds each stream's samples, rows, means and its own frames of that launch, cut stream
+// by stream with the functions launch_by_n and launch_mean_inkernel cut with (frame_cuts.h).  The tables are built here and go to
+// stream-ordered scratch.
 namespace {
 
 struct RaggedStream {
@@ -2256,12 +2195,6 @@ struct RaggedChunk {
       return hip_fail(e, "ragged table upload");
     }
     return GLFER_OK;
-  }
-
-  // the frame groups of a route's kernel (launch_by_n, launch_mean_inkernel)
-  size_t groups(BodyRoute r) const {
-    const size_t lanes = (size_t)p->n / 16;
-    return r == ROUTE_SHARED_ODD ? 2 * (lanes >= 256 ? 1 : 256 / lanes) : 1;
   }
 
   // one launch over a table; sp: everything but frame0 / nframes / nbatch / ragged.  r: the kernel (ROUTE_PACKED: the packed one)
@@ -2297,7 +2230,7 @@ struct RaggedChunk {
     SpectroParams r0 = sp;
     r0.stream = reinterpret_cast<const char *>(sp.stream) + soff[0];
     const BodyRoute r = body_route(r0, p->n);
-    const size_t G = groups(r);
+    const size_t G = glfer_frame_group(r == ROUTE_SHARED_ODD, p->n);
     std::vector<GlferRaggedEntry> head(nb), tail(nb), body(nb);
     auto entry = [&](unsigned b, size_t f0, size_t f1) {
       GlferRaggedEntry e = {};
@@ -2311,11 +2244,11 @@ struct RaggedChunk {
     };
     for (unsigned b = 0; b < nb; b++) {
       const size_t lo = from[b], hi = std::max(to[b], from[b]);
-      size_t b0 = (std::max(lo, first_inside) + G - 1) / G * G, b1 = hi / G * G;
-      if (r == ROUTE_PACKED || b0 >= b1) b0 = b1 = hi;                 // (launch_by_n: everything to the packed kernel)
-      head[b] = entry(b, lo, b0);
-      body[b] = entry(b, b0, b1);
-      tail[b] = entry(b, b1, hi);
+      glfer_frame_cut c = glfer_cut_frames(lo, hi, first_inside, G);
+      if (r == ROUTE_PACKED) c.b0 = c.b1 = hi;                         // (the packed route: everything is head)
+      head[b] = entry(b, lo, c.b0);
+      body[b] = entry(b, c.b0, c.b1);
+      tail[b] = entry(b, c.b1, hi);
     }
     SpectroParams q = sp;
     q.mean_inkernel = 0;
@@ -2371,12 +2304,13 @@ struct RaggedChunk {
 
   // frames [from[b], to[b]) through corrected copies (launch_mean_inkernel's by_copy, and the plans whose kernels take no means)
   int by_copy(const SpectroParams &sp, const std::vector<size_t> &from, const std::vector<size_t> &to) const {
-    const size_t hops_back = sp.history_mode ? 0 : first_inside;
+    const size_t hops_back = glfer_hops_back(sp.history_mode, first_inside);
     std::vector<size_t> hlo(nb), hhi(nb);
     std::vector<long long> soff(nb);
     for (unsigned b = 0; b < nb; b++) {
-      hlo[b] = from[b] > hops_back ? from[b] - hops_back : 0;
-      hhi[b] = to[b] > from[b] ? to[b] : hlo[b];
+      const glfer_hop_span h = glfer_copy_hops(from[b], to[b] > from[b] ? to[b] - from[b] : 0, hops_back, 0);
+      hlo[b] = h.lo;
+      hhi[b] = h.lo + h.n;
     }
     float *scratch = nullptr;
     int rc = submean(sp.fmt, hlo, hhi, &scratch, soff);
@@ -2394,12 +2328,12 @@ struct RaggedChunk {
     fill_params(p, sp);
     sp.stream = base;
     sp.psd = d_psd;
-    esz = sp.fmt == GLFER_FMT_F32 ? 4 : (sp.fmt == GLFER_FMT_S16 ? 2 : 1);
+    esz = glfer_sample_size(sp.fmt);
     // (every stream sees the route of stream 0: integer samples sit at even offsets -- glfer_hip.h; by_n reads the route of the
     // samples a launch is given, raw or corrected copy, as launch_by_n does)
     SpectroParams s0 = sp;
     s0.stream = base + s[0].off * esz;
-    first_inside = (size_t)((p->keep + p->hop - 1) / p->hop);
+    first_inside = plan_first_inside(p);
     std::vector<size_t> zero(nb, 0), end(nb);
     std::vector<long long> raw(nb);
     for (unsigned b = 0; b < nb; b++) {
@@ -2410,13 +2344,12 @@ struct RaggedChunk {
     if (!mean_inkernel_ok(p, s0, nullptr, -1)) return by_copy(sp, zero, end);
     // launch_mean_inkernel per stream: [0, b0) and [b1, end) through the copies, [b0, b1) from the raw samples (their route)
     const BodyRoute route = body_route(s0, p->n);
-    const size_t G = groups(route);
-    std::vector<size_t> b0(nb), b1(nb), tail(nb);
+    const size_t G = glfer_frame_group(route == ROUTE_SHARED_ODD, p->n);
+    std::vector<size_t> b0(nb), b1(nb);
     for (unsigned b = 0; b < nb; b++) {
-      b0[b] = (first_inside + G - 1) / G * G;
-      b1[b] = end[b] / G * G;
-      if (b0[b] >= b1[b]) b0[b] = b1[b] = end[b];
-      tail[b] = std::max(b1[b], std::min(b0[b], end[b]));
+      const glfer_frame_cut c = glfer_cut_frames(0, end[b], first_inside, G);
+      b0[b] = c.b0;
+      b1[b] = c.b1;
     }
     int rc = by_copy(sp, zero, b0);
     if (rc != GLFER_OK) return rc;
@@ -2429,12 +2362,13 @@ struct RaggedChunk {
       if (reference_means(p)) {                      // the hop means in the reference's order: hops [b0 - first_inside, b1) of each stream
         std::vector<GlferRaggedHops> hops(nb);
         size_t total = 0, longest = 0;
-        for (unsigned b = 0; b < nb; b++) total += b1[b] > b0[b] ? b1[b] - (b0[b] - first_inside) : 0;
+        for (unsigned b = 0; b < nb; b++) total += glfer_means_hops(b0[b], b1[b], 0, first_inside).n;
         if (total) {
           HIP_TRY(glfer::scratch_malloc((void **)&means, total * sizeof(float), st));
           size_t at = 0;
           for (unsigned b = 0; b < nb; b++) {
-            const size_t hop_lo = b0[b] - first_inside, n = b1[b] > b0[b] ? b1[b] - hop_lo : 0;
+            const glfer_hop_span h = glfer_means_hops(b0[b], b1[b], 0, first_inside);
+            const size_t hop_lo = h.lo, n = h.n;
             hops[b].in = base + (s[b].off + hop_lo * (size_t)p->hop) * esz;
             hops[b].out = nullptr;
             hops[b].means = means + at;
@@ -2466,7 +2400,7 @@ struct RaggedChunk {
       if (means) glfer::scratch_free(means, st);
       if (rc != GLFER_OK) return rc;
     }
-    return by_copy(sp, tail, end);
+    return by_copy(sp, b1, end);
   }
 };
 
@@ -2496,7 +2430,7 @@ int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *p, const void *d_samples
   }
   if (!offsets || !lengths) return GLFER_E_ARG;
   const int fmt = p->cfg.sample_format;
-  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
+  const size_t esz = glfer_sample_size(fmt);
   // the arguments, before anything is read or written: the host arrays are all this looks at
   std::vector<RaggedStream> s(nstreams);
   size_t total = 0;
@@ -2542,12 +2476,10 @@ int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *p, const void *d_samples
   }
   DeviceGuard guard(p->cfg.device);
   HIP_TRY(guard.error());
-  int dev = 0, ymax = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipDeviceGetAttribute(&ymax, hipDeviceAttributeMaxGridDimY, dev));
-  ymax = std::max(2, std::min(ymax, 65535));
-  for (size_t c0 = 0; c0 < nstreams; c0 += (size_t)ymax) {      // above the grid's y limit: chunks of it
-    const unsigned nb = (unsigned)std::min(nstreams - c0, (size_t)ymax);
+  size_t ymax = 0;
+  if (const int yrc = grid_y_limit(2, &ymax); yrc != GLFER_OK) return yrc;
+  for (size_t c0 = 0; c0 < nstreams; c0 += ymax) {      // above the grid's y limit: chunks of it
+    const unsigned nb = (unsigned)std::min(nstreams - c0, ymax);
     int rc;
     if (nb == 1) {
       rc = single(c0);
@@ -2790,7 +2722,7 @@ static int ftest_single(glfer_hip_plan *p, const void *d_stream, size_t first, s
 }
 
 // glfer_hip_mtm_ftest_device over many streams (glfer_hip.h).  N >= 256: the launches of one stream -- the corrected copies under
-// mean removal (batch_submean_scratch), then spectro16_kernel's FT form with blockIdx.y as the stream, the form chosen as the
+// mean removal (submean_scratch), then spectro16_kernel's FT form with blockIdx.y as the stream, the form chosen as the
 // single entry chooses it -- so the launch count does not grow with the batch; below 256 the single entry, stream by stream.
 // (The multitaper rows and F from one pass over the samples: glfer_hip_mtm_rows_ftest_device / _batch_device below, the same bodies.)
 static int ftest_batch(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch, size_t first, size_t nframes,
@@ -2811,7 +2743,7 @@ static int ftest_batch_args(const glfer_hip_plan *p, const void *d_streams, size
   if ((first + nframes) > nsamples / (size_t)p->hop) return GLFER_E_ARG;   // frame past the stream
   if (nframes > 0x7fffffffu) return GLFER_E_ARG;
   const int fmt = p->cfg.sample_format;
-  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
+  const size_t esz = glfer_sample_size(fmt);
   // (as glfer_hip_spectrogram_batch_device: every stream of a batch must see the same alignment)
   if (fmt != GLFER_FMT_F32 && (stream_pitch & 1)) return GLFER_E_ARG;
   const size_t rows = want_psd ? (size_t)p->pitch : (size_t)p->bins;
@@ -2851,7 +2783,7 @@ int glfer_hip_mtm_rows_ftest_batch_device(glfer_hip_plan *p, const void *d_strea
 static int ftest_batch(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch, size_t first, size_t nframes,
                        float *d_psd, float *d_ftest, int mu_live, hipStream_t st) {
   const int fmt = p->cfg.sample_format;
-  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
+  const size_t esz = glfer_sample_size(fmt);
   const char *base = static_cast<const char *>(d_streams);
   const size_t ft_bs = nframes * (size_t)p->bins;            // floats from one stream's first F row to the next one's
   const size_t psd_bs = nframes * (size_t)p->pitch;          // and from one stream's first PSD row to the next one's
@@ -2870,12 +2802,10 @@ static int ftest_batch(glfer_hip_plan *p, const void *d_streams, size_t nstreams
     const int trc = ftest_tables(p);
     if (trc != GLFER_OK) return trc;
   }
-  int dev = 0, ymax = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipDeviceGetAttribute(&ymax, hipDeviceAttributeMaxGridDimY, dev));
-  ymax = std::max(1, std::min(ymax, 65535));
-  for (size_t c0 = 0; c0 < nstreams; c0 += (size_t)ymax) {      // batches above the grid's y limit: chunks of it
-    const unsigned nb = (unsigned)std::min(nstreams - c0, (size_t)ymax);
+  size_t ymax = 0;
+  if (const int yrc = grid_y_limit(1, &ymax); yrc != GLFER_OK) return yrc;
+  for (size_t c0 = 0; c0 < nstreams; c0 += ymax) {      // batches above the grid's y limit: chunks of it
+    const unsigned nb = (unsigned)std::min(nstreams - c0, ymax);
     SpectroParams sp;
     ftest_params(p, sp);
     sp.stream = base + c0 * stream_pitch * esz;
@@ -2885,7 +2815,7 @@ static int ftest_batch(glfer_hip_plan *p, const void *d_streams, size_t nstreams
     int rc = GLFER_OK;
     if (p->cfg.sub_mean) {
       sp.frame0 = (long long)first;
-      rc = batch_submean_scratch(p, sp, first, nframes, nb, st, &scratch);
+      rc = submean_scratch(p, sp, first, nframes, st, &scratch);
     }
     if (rc == GLFER_OK) {
       SpectroParams q = ftest_in_launch(p, sp, first, nframes, d_ftest + c0 * ft_bs, mu_live, d_psd ? d_psd + c0 * psd_bs : nullptr);
@@ -2964,8 +2894,9 @@ static bool avg_in_launch(const glfer_hip_plan *p, const SpectroParams &sp, int 
                      !p->cfg.history_mode && p->n >= 512 && p->n <= 4096 && n_out <= 2 * p->n && body_route(sp, p->n) == ROUTE_REAL_INPUT &&
                      (!with_means || (reference_means(p) && route_takes_mean(ROUTE_REAL_INPUT, sp, p->n) && !getenv("GLFER_MEAN_PREPASS")));
   // the first frame every one of whose depth-1 predecessors lies inside the stream AND inside this call's averaging state
-  const size_t first_inside = (size_t)((p->keep + p->hop - 1) / p->hop), end = first + nframes;
-  *b0 = std::max(first, first_inside) + (size_t)(depth - 1);
+  const size_t end = first + nframes;
+  // (G = 1: the cut's b0 is the call's first frame inside the stream -- or `end` when it has none, and the test below fails)
+  *b0 = glfer_cut_frames(first, end, plan_first_inside(p), 1).b0 + (size_t)(depth - 1);
   return fused && *b0 + 256 <= end;                       // (short calls: the lead frames of every slot would outweigh the rest)
 }
 
@@ -3031,10 +2962,10 @@ int glfer_hip_spectrogram_avg_device(glfer_hip_plan *p, const void *d_stream, si
   }
   // the hop means of everything the body touches: its frames, the depth-1 frames a slot recomputes in front of them, their history
   float *means = nullptr;
-  const size_t hops_back = (size_t)((p->keep + p->hop - 1) / p->hop), hop_lo = b0 - (size_t)(depth - 1) - hops_back;
+  const glfer_hop_span mh = glfer_means_hops(b0, end, (size_t)(depth - 1), plan_first_inside(p));
   if (with_means) {
-    hipError_t e = glfer::scratch_malloc((void **)&means, (end - hop_lo) * sizeof(float), st);
-    if (e == hipSuccess) e = launch_reference_means(p, sp, hop_lo, end - hop_lo, means, 0, st);
+    hipError_t e = glfer::scratch_malloc((void **)&means, mh.n * sizeof(float), st);
+    if (e == hipSuccess) e = launch_reference_means(p, sp, mh.lo, mh.n, means, 0, st);
     if (e != hipSuccess) {
       if (means) glfer::scratch_free(means, st);
       if (ret_scratch) glfer::scratch_free(ret_scratch, st);
@@ -3046,7 +2977,7 @@ int glfer_hip_spectrogram_avg_device(glfer_hip_plan *p, const void *d_stream, si
     SpectroParams q = sp;
     if (with_means) {
       q.mean_inkernel = 1;
-      q.means = means - hop_lo;                              // indexed by GLOBAL hop (= frame) index
+      q.means = means - mh.lo;                               // indexed by GLOBAL hop (= frame) index
     }
     q.frame0 = (long long)f0;
     q.nframes = (int)nf;
@@ -3102,7 +3033,7 @@ int glfer_hip_spectrogram_avg_batch_device(glfer_hip_plan *p, const void *d_stre
   if (nstreams == 0 || nframes == 0) return GLFER_OK;
   if (!d_streams || !d_avg) return GLFER_E_ARG;
   if ((first + nframes) > nsamples / (size_t)p->hop || nframes > 0x7fffffffu) return GLFER_E_ARG;
-  const size_t esz = fmt == GLFER_FMT_F32 ? 4 : (fmt == GLFER_FMT_S16 ? 2 : 1);
+  const size_t esz = glfer_sample_size(fmt);
   const size_t bins = (size_t)p->bins;
   if (stream_pitch > (SIZE_MAX / esz) / nstreams || nframes > (SIZE_MAX / sizeof(double) / (size_t)n_out) / nstreams) return GLFER_E_ARG;
   hipStream_t st = (hipStream_t)hip_stream;
@@ -3168,8 +3099,8 @@ int glfer_hip_spectrogram_avg_batch_device(glfer_hip_plan *p, const void *d_stre
     // the hop means of everything the body touches, one table per stream: its frames, the depth-1 frames a slot recomputes in
     // front of them, their history
     float *means = nullptr;
-    const size_t hops_back = (size_t)((p->keep + p->hop - 1) / p->hop), hop_lo = b0 - (size_t)(depth - 1) - hops_back;
-    const size_t nhops = end - hop_lo;
+    const glfer_hop_span mh = glfer_means_hops(b0, end, (size_t)(depth - 1), plan_first_inside(p));
+    const size_t hop_lo = mh.lo, nhops = mh.n;
     if (with_means) {
       hipError_t e = glfer::scratch_malloc((void **)&means, (size_t)nb * nhops * sizeof(float), st);
       if (e == hipSuccess)

@@ -11,6 +11,7 @@
 // -- come out as in a one-shot run.  Rows go straight into the caller's memory when it is pinned
 // (glfer_hip_host_alloc), otherwise through the pinned row buffers and a host copy.
 #include "plan.h"
+#include "frame_cuts.h"
 
 #include <algorithm>
 #include <cctype>
@@ -148,7 +149,7 @@ struct NodeBinding {
 
 std::mutex g_ring_mu;
 
-size_t sample_bytes(int fmt) { return fmt == GLFER_SAMPLES_F32 ? 4 : (fmt == GLFER_SAMPLES_S16 ? 2 : 1); }
+size_t sample_bytes(int fmt) { return glfer_sample_size(fmt); }
 
 // memcpy spread over a few threads: the destination is usually fresh pageable memory, where the
 // page faults, not the copy, set the pace
@@ -396,7 +397,7 @@ int run_job(const Job &job, size_t *frames_done) {
   const size_t hop = (size_t)p->hop, bins = (size_t)p->bins;
   // history in front of every chunk: whole hops covering the N-H overlap (per-hop means need
   // complete hops), plus the frames the LMP ring reaches back
-  const size_t halo_hops = (size_t)((p->keep + p->hop - 1) / p->hop) +
+  const size_t halo_hops = glfer_first_inside((size_t)p->keep, (size_t)p->hop) +
                            (p->cfg.mode == GLFER_MODE_LMP ? (size_t)p->lmp_av - 1 : 0);
   const double t_job = now_s();
   const size_t chunk = pick_chunk(p, job.frames, job.chunk_frames);
@@ -640,7 +641,7 @@ int reserve_psd_ring(glfer_hip_plan *p, size_t chunk) {
   DeviceGuard guard(p->cfg.device);
   HIP_TRY(guard.error());
   const size_t esz = sample_bytes(p->cfg.sample_format), hop = (size_t)p->hop, bins = (size_t)p->bins;
-  const size_t halo_hops = (size_t)((p->keep + p->hop - 1) / p->hop) + (p->cfg.mode == GLFER_MODE_LMP ? (size_t)p->lmp_av - 1 : 0);
+  const size_t halo_hops = glfer_first_inside((size_t)p->keep, (size_t)p->hop) + (p->cfg.mode == GLFER_MODE_LMP ? (size_t)p->lmp_av - 1 : 0);
   const size_t in_bytes = (halo_hops + chunk + 1) * hop * esz, rows_cap = chunk + 1;
   {
     // (the ring is claimed under the lock and filled outside it: eight workers reserve theirs side by side)
