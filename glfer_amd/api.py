@@ -57,6 +57,8 @@ EXPORTS = [
     "glfer_hip_mtm_rows_ftest_device", "glfer_hip_mtm_rows_ftest_batch_device",
     # streams of unequal length in one call
     "glfer_hip_spectrogram_ragged_device", "glfer_hip_ragged_frames",
+    # their moving average and waterfall
+    "glfer_hip_avg_ragged_device", "glfer_hip_spectrogram_avg_ragged_device", "glfer_hip_waterfall_ragged_device",
 ]
 
 
@@ -172,6 +174,14 @@ def lib():
     if hasattr(L, "glfer_hip_ragged_frames"):
         L.glfer_hip_ragged_frames.argtypes = [vp, sz, vp, vp]
         L.glfer_hip_ragged_frames.restype = sz
+    if hasattr(L, "glfer_hip_avg_ragged_device"):
+        L.glfer_hip_avg_ragged_device.argtypes = [C.c_int, vp, sz, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    if hasattr(L, "glfer_hip_spectrogram_avg_ragged_device"):
+        L.glfer_hip_spectrogram_avg_ragged_device.argtypes = [vp, vp, sz, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                              vp, vp, vp, vp, vp]
+    if hasattr(L, "glfer_hip_waterfall_ragged_device"):
+        L.glfer_hip_waterfall_ragged_device.argtypes = [C.POINTER(Display), sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp,
+                                                        vp, vp]
     L.glfer_hip_host_alloc.argtypes = [sz]
     L.glfer_hip_host_alloc.restype = vp
     L.glfer_hip_host_free.argtypes = [vp]
@@ -454,6 +464,41 @@ class Spectrogram:
             buf[o:o + t.numel()] = t
         psd, starts = self.run_ragged(buf, offs, [t.numel() for t in streams])
         return [psd[int(starts[b]):int(starts[b + 1])] for b in range(len(streams))]
+
+    def run_avg_ragged(self, samples, offsets, lengths, avg_mode, depth, minbin, maxbin, max0=0, n_out=None, want_psd=False,
+                       want_ret=True):
+        """run_avg for streams of unequal length in one call (glfer_hip_spectrogram_avg_ragged_device).  samples, offsets and
+        lengths as run_ragged takes them.  Returns (avg [sum of frames][n_out] float64, ret [sum of frames][4] float64 or None,
+        psd [sum of frames][bins] float32 or None, row_starts): stream b's rows are [row_starts[b], row_starts[b + 1]) of each
+        and equal run() followed by update_avg() on that stream."""
+        torch = _torch()
+        if samples.dim() != 1 or samples.dtype != self._sample_dtype():
+            raise ValueError("samples: a 1-D tensor of the plan's sample dtype")
+        if not (samples.is_cuda and samples.is_contiguous()):
+            raise ValueError("samples: contiguous, on the GPU")
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        lens = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
+        if offs.size != lens.size:
+            raise ValueError("one offset and one length per stream")
+        total, _ = self.ragged_frames(lens)
+        if total == 2 ** 64 - 1:
+            raise GlferHipError("run_avg_ragged: the row count overflows")
+        if lens.size and max(int(o) + int(n) for o, n in zip(offs, lens)) > samples.numel():
+            raise ValueError("a stream reaches past `samples`")
+        n_out = n_out or self.bins
+        dev = samples.device
+        avg = torch.empty((total, n_out), dtype=torch.float64, device=dev)
+        ret = torch.empty((total, 4), dtype=torch.float64, device=dev) if want_ret else None
+        psd = torch.empty((total, self.bins), dtype=torch.float32, device=dev) if want_psd else None
+        starts = np.zeros(lens.size + 1, np.uint64)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(lib().glfer_hip_spectrogram_avg_ragged_device(self._h, C.c_void_p(samples.data_ptr()), lens.size, offs.ctypes.data,
+                                                             lens.ctypes.data, int(avg_mode), int(depth), int(minbin), int(maxbin),
+                                                             int(max0), int(n_out), C.c_void_p(psd.data_ptr() if want_psd else None),
+                                                             C.c_void_p(avg.data_ptr()), C.c_void_p(ret.data_ptr() if want_ret else None),
+                                                             starts.ctypes.data, st),
+               "glfer_hip_spectrogram_avg_ragged_device")
+        return avg, ret, psd, starts.astype(np.int64)
 
     def run_avg(self, stream, avg_mode, depth, minbin, maxbin, max0=0, n_out=None, want_psd=False, want_ret=True,
                 first_frame=0, nframes=None):
@@ -880,6 +925,74 @@ def waterfall_batch(disps, psd, avg_mode=0, depth=1, minbin=0, maxbin=1, max0=0,
     for d, out in zip(disps, arr):
         C.memmove(C.addressof(d), C.addressof(out), C.sizeof(Display))
     return rgb, lev, stats
+
+
+def _row_starts(row_starts, rows):
+    """row_starts as the C entries take it: uint64 [nstreams + 1], non-decreasing, ending at most at `rows`."""
+    starts = np.asarray(row_starts)
+    if starts.ndim != 1 or starts.size < 1 or starts.dtype.kind not in "iu":
+        raise ValueError("row_starts: a 1-D integer array of nstreams + 1 entries")
+    if starts.size and (int(starts.min()) < 0 or np.any(np.diff(starts.astype(np.int64)) < 0)):
+        raise ValueError("row_starts: non-negative and non-decreasing")
+    if int(starts[-1]) > rows:
+        raise ValueError("row_starts: the last entry reaches past the rows given")
+    return np.ascontiguousarray(starts, dtype=np.uint64)
+
+
+def waterfall_ragged(disps, psd, row_starts, avg_mode=0, depth=1, minbin=0, maxbin=1, max0=0, want_lev=True, want_stats=False):
+    """glfer_hip_waterfall_ragged_device: waterfall() over streams of unequal length in one call.  psd [rows][bins] float32 on
+    the GPU, packed as Spectrogram.run_ragged returns it; stream b is rows [row_starts[b], row_starts[b + 1]).  Rows at a
+    pitch (displays that carry psd_pitch): give the view rows[:, :bins] of the [rows][pitch] tensor.  disps: one Display per
+    stream, the same options, each carrying its stream's state in and out (updated in place; a stream without rows keeps its
+    own).  Returns (rgb [rows][bins][3], lev [rows][bins] | None, stats [rows][4] | None, row_starts)."""
+    torch = _torch()
+    if psd.dim() != 2 or psd.dtype != torch.float32:
+        raise ValueError("psd: a 2-D float32 tensor")
+    starts = _row_starts(row_starts, psd.size(0))
+    nb = starts.size - 1
+    if len(disps) != nb:
+        raise ValueError("one Display per stream: len(disps) == len(row_starts) - 1")
+    if not psd.is_cuda:
+        raise ValueError("psd: on the GPU")
+    bins = psd.size(1)
+    pitch = (int(disps[0].psd_pitch) if nb else 0) or bins
+    if psd.size(0) > 1 and not (psd.stride(1) == 1 and psd.stride(0) == pitch):
+        raise ValueError("psd: rows of `bins` floats, psd_pitch (or bins) floats apart")
+    rows = int(starts[-1])
+    arr = (Display * max(nb, 1))(*disps)
+    rgb = torch.empty((rows, bins, 3), dtype=torch.uint8, device=psd.device)
+    lev = torch.empty((rows, bins), dtype=torch.int16, device=psd.device) if want_lev else None
+    stats = torch.empty((rows, 4), dtype=torch.float32, device=psd.device) if want_stats else None
+    st = C.c_void_p(torch.cuda.current_stream(psd.device).cuda_stream)
+    _check(lib().glfer_hip_waterfall_ragged_device(arr, nb, int(avg_mode), depth, minbin, maxbin, int(max0), psd.data_ptr(),
+                                                   starts.ctypes.data, bins, rgb.data_ptr(), lev.data_ptr() if want_lev else None,
+                                                   stats.data_ptr() if want_stats else None, st), "glfer_hip_waterfall_ragged_device")
+    for d, out in zip(disps, arr):
+        C.memmove(C.addressof(d), C.addressof(out), C.sizeof(Display))
+    return rgb, lev, stats, starts.astype(np.int64)
+
+
+def update_avg_ragged(mode, psd, row_starts, depth, minbin, maxbin, max0=0, n_out=None):
+    """update_avg over packed rows of streams of unequal length (glfer_hip_avg_ragged_device): psd [rows][bins] float32 on the
+    GPU as Spectrogram.run_ragged returns it (dense rows), stream b its rows [row_starts[b], row_starts[b + 1]), the averaging
+    state empty at row 0 of each stream.  Returns (avg [rows][n_out] float64, ret [rows][4] float64, row_starts); stream b's
+    rows are update_avg(mode, psd[row_starts[b]:row_starts[b + 1]], ...)'s."""
+    torch = _torch()
+    if psd.dim() != 2 or psd.dtype != torch.float32:
+        raise ValueError("psd: a 2-D float32 tensor")
+    starts = _row_starts(row_starts, psd.size(0))
+    if not (psd.is_cuda and psd.is_contiguous()):
+        raise ValueError("psd: contiguous, on the GPU")
+    bins = psd.size(1)
+    n_out = bins if n_out is None else n_out
+    rows = int(starts[-1])
+    avg = torch.empty((rows, n_out), dtype=torch.float64, device=psd.device)
+    ret = torch.empty((rows, 4), dtype=torch.float64, device=psd.device)
+    st = C.c_void_p(torch.cuda.current_stream(psd.device).cuda_stream)
+    _check(lib().glfer_hip_avg_ragged_device(int(mode), psd.data_ptr(), starts.size - 1, starts.ctypes.data, bins, n_out, depth, minbin,
+                                             maxbin, int(max0), avg.data_ptr(), ret.data_ptr(), st),
+           "glfer_hip_avg_ragged_device")
+    return avg, ret, starts.astype(np.int64)
 
 
 def avg_cum(psd, depth, minbin, maxbin, n_out=None):

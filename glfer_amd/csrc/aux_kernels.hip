@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include "display_map.hpp"
 #include "div_exact.hpp"
+#include "ragged_cols.hpp"
 #include <stdint.h>
 #include <type_traits>
 
@@ -397,19 +398,33 @@ __global__ __launch_bounds__(256) void floor_wave_kernel(const float *__restrict
 // not).  131 072 rows: 2.1 M rows/s as one chain per bin, HBM-bound in chunks.
 // BAT (glfer_launch_avg_batch): blockIdx.z is the stream, its rows and sums psd_bs / avg_bs apart; the frames and the
 // chunks are the stream's own, so every stream's sums are those of a launch over it alone.
+// RAG (glfer_launch_avg_ragged): streams of unequal length, packed rows.  The last argument is a table (ragged_cols.hpp) instead
+// of the strides; blockIdx.x is the launch's flat list of chunks (an entry's blk0 counts chunks of AVG_CHUNK), blockIdx.y the
+// 256 bins of the band.  The chunk, its lead-in rows and the frame count are the stream's own.
 constexpr int AVG_CHUNK = 128;
 struct AvgBatchStrides { long long psd, avg, ret; };   // per stream of a batch: floats of rows, doubles of averages, doubles of return values
-template <bool BAT = false>
+template <bool RAG> using AvgStreams = std::conditional_t<RAG, RaggedCols, AvgBatchStrides>;
+template <bool BAT = false, bool RAG = false>
 __global__ __launch_bounds__(256) void avg_cum_kernel(const float *__restrict__ psd, long long nframes,
                                                       int bins, int n_out, int depth, int minbin,
-                                                      int maxbin, double *__restrict__ avg, AvgBatchStrides bst) {
+                                                      int maxbin, double *__restrict__ avg, AvgStreams<RAG> bst) {
   if constexpr (BAT) {
     psd += (long long)blockIdx.z * bst.psd;
     avg += (long long)blockIdx.z * bst.avg;
   }
-  const int b = minbin + blockIdx.x * 256 + threadIdx.x;
+  long long chunk_index = blockIdx.y;
+  unsigned bin_block = blockIdx.x;
+  if constexpr (RAG) {
+    const RaggedColsEntry e = ragged_cols_find(bst, blockIdx.x);
+    psd += e.row0 * bins;
+    avg += e.out0 * n_out;
+    nframes = e.nframes;
+    chunk_index = (long long)blockIdx.x - e.blk0;
+    bin_block = blockIdx.y;
+  }
+  const int b = minbin + bin_block * 256 + threadIdx.x;
   if (b >= maxbin) return;
-  const long long f0 = (long long)blockIdx.y * AVG_CHUNK;
+  const long long f0 = chunk_index * AVG_CHUNK;
   const long long f1 = f0 + AVG_CHUNK < nframes ? f0 + AVG_CHUNK : nframes;
   double cum = 0.0;
   for (long long g = f0 > depth ? f0 - depth : 0; g < f0; g++) cum += (double)psd[(size_t)g * bins + b];
@@ -439,19 +454,28 @@ __global__ __launch_bounds__(256) void avg_cum_kernel(const float *__restrict__ 
 // K5b.  Per-frame reductions over the band and the output normalisation of the three
 // modes (avg.c:129-156, 185-215, 248-294).  One block per frame, in place on the avg row.
 // mode: 1 sumavg, 2 plain, 3 sumextreme (glfer.h:56-58).  BAT: blockIdx.y is the stream of a batch.
-template <bool BAT = false>
+// RAG: blockIdx.x is the launch's flat list of rows (an entry's blk0 counts rows); f is the frame within the entry's stream.
+template <bool BAT = false, bool RAG = false>
 __global__ __launch_bounds__(256) void avg_norm_kernel(const float *__restrict__ psd, int bins, int n_out,
                                                        int depth, int minbin, int maxbin, int mode,
                                                        int max0, double *__restrict__ avg,
-                                                       double *__restrict__ ret, AvgBatchStrides bst) {
+                                                       double *__restrict__ ret, AvgStreams<RAG> bst) {
   if constexpr (BAT) {
     psd += (long long)blockIdx.y * bst.psd;
     avg += (long long)blockIdx.y * bst.avg;
     ret += (long long)blockIdx.y * bst.ret;
   }
+  long long frame = blockIdx.x;
+  if constexpr (RAG) {
+    const RaggedColsEntry e = ragged_cols_find(bst, blockIdx.x);
+    psd += e.row0 * bins;
+    avg += e.out0 * n_out;
+    ret += e.out0 * 4;
+    frame = (long long)blockIdx.x - e.blk0;
+  }
   __shared__ double r_sum[256], r_max[256], r_min[256], r_var[256];
   __shared__ int r_idx[256], r_cnt[256];
-  const long long f = blockIdx.x;
+  const long long f = frame;
   const int tid = threadIdx.x;
   double *row = avg + (size_t)f * n_out;
   const int eff = (f + 1 < depth) ? (int)(f + 1) : depth;   // effdepth after this frame
@@ -593,11 +617,32 @@ struct AvgMapArgs {
 // or ret, so their strides say where the stream's columns are instead -- bst.avg columns from one stream's rgb / lev to the
 // next's, bst.ret rows from one stream's levels to the next's; fbeg and nframes are the stream's own too (a tile's lead-in
 // reads back into the stream's own rows only).
-template <int BPT, bool RING, bool MAP, int NT = 256, bool BAT = false>
+// RAG (glfer_launch_avg_ragged, glfer_launch_avgmap_ragged): streams of unequal length, packed rows.  blockIdx.x is the launch's
+// flat list of chunks; the entry (ragged_cols.hpp) gives the stream's rows, its frame count and ITS OWN chunk length -- the one a
+// launch over the stream alone takes, so its restarts fall where that launch's fall -- and blk0 counts chunks of that length.
+// Outputs (avg / ret, or with MAP the levels and the columns) start at the entry's out0.  BPT, the ring and the LDS layout depend
+// on the band and depth only: launch-wide.
+template <int BPT, bool RING, bool MAP, int NT = 256, bool BAT = false, bool RAG = false>
 __global__ __launch_bounds__(NT) void avg_fused_kernel(const float *__restrict__ psd, long long nframes, int chunk, int bins,
                                                         int n_out, int depth, int minbin, int maxbin, int mode, int max0,
                                                         double *__restrict__ avg, double *__restrict__ ret, AvgMapArgs ma,
-                                                        AvgBatchStrides bst) {
+                                                        AvgStreams<RAG> bst) {
+  long long chunk_index = blockIdx.x;
+  if constexpr (RAG) {
+    const RaggedColsEntry e = ragged_cols_find(bst, blockIdx.x);
+    psd += e.row0 * bins;
+    nframes = e.nframes;
+    chunk = e.chunk;
+    chunk_index = (long long)blockIdx.x - e.blk0;
+    if constexpr (MAP) {
+      ma.levels += e.out0 * 4;
+      ma.rgb += e.out0 * n_out * 3;
+      if (ma.lev) ma.lev += e.out0 * n_out;
+    } else {
+      avg += e.out0 * n_out;
+      ret += e.out0 * 4;
+    }
+  }
   if constexpr (BAT) {
     const long long sb = blockIdx.y;
     psd += sb * bst.psd;
@@ -626,7 +671,7 @@ __global__ __launch_bounds__(NT) void avg_fused_kernel(const float *__restrict__
   double *const stage = reinterpret_cast<double *>(dyn_lds + pix_words);
   float *const hist = dyn_lds + pix_words + (MAP && GLFER_AVGMAP_STAGE ? 2 * (size_t)BPT * NT : 0);
   const int tid = threadIdx.x, wave = tid >> 6;
-  const long long f0 = (MAP ? ma.fbeg : 0) + (long long)blockIdx.x * chunk;
+  const long long f0 = (MAP ? ma.fbeg : 0) + chunk_index * chunk;
   const long long f1 = f0 + chunk < nframes ? f0 + chunk : nframes;
   if constexpr (MAP)
     if (tid < 256) tab[tid] = (unsigned)ma.colortab[3 * tid] | ((unsigned)ma.colortab[3 * tid + 1] << 8) | ((unsigned)ma.colortab[3 * tid + 2] << 16);
@@ -977,6 +1022,12 @@ extern "C" hipError_t glfer_launch_floor(const float *psd, size_t nframes, int b
   return hipGetLastError();
 }
 
+// the frames a fused block walks: 128-frame chunks for long batches, shorter ones (down to 8) to keep ~1000 blocks in flight
+static int avg_chunk_of(long long nf) {
+  int chunk = AVG_CHUNK;
+  while (chunk > 8 && nf / chunk < 1024) chunk /= 2;
+  return chunk;
+}
 static int bpt_of(int bpt) { return bpt <= 3 ? bpt : (bpt <= 5 ? 5 : (bpt <= 9 ? 9 : (bpt <= 17 ? 17 : 33))); }   // the BPT the fused kernel is built for
 
 // BAT: nb streams (blockIdx.y of the fused form, z of the cum kernel, y of the norm kernel), nframes rows each, bst apart.  The
@@ -989,12 +1040,10 @@ static hipError_t launch_avg(int mode, const float *psd, size_t nframes, int bin
   const int band = maxbin - minbin;
   if (band < 1 || minbin < 0 || maxbin > bins || maxbin > n_out || depth < 1 || nb > 65535 || (!BAT && nb != 1)) return hipErrorInvalidValue;
   const long long nf = (long long)nframes;
-  // A fused block walks `chunk` frames in order, so the launch has nframes/chunk blocks: 128-frame
-  // chunks for long batches, shorter ones (down to 8) to keep ~1000 blocks in flight for short ones.
+  // A fused block walks `chunk` frames in order, so the launch has nframes/chunk blocks.
   // Every chunk restarts from the `depth` rows before it: once that costs more than the chunk itself
   // the two-pass form (parallel over bins as well) is the better one.
-  int chunk = AVG_CHUNK;
-  while (chunk > 8 && nf / chunk < 1024) chunk /= 2;
+  const int chunk = avg_chunk_of(nf);
   const int bpt = (band + 255) / 256;
   if (bpt <= 33 && depth <= 2 * chunk) {
     const unsigned blocks = (unsigned)((nf + chunk - 1) / chunk);
@@ -1039,6 +1088,70 @@ extern "C" hipError_t glfer_launch_avg_batch(int mode, const float *psd, size_t 
   return launch_avg<true>(mode, psd, nframes, bins, n_out, depth, minbin, maxbin, max0, avg, ret, nb, AvgBatchStrides{psd_bs, avg_bs, ret_bs}, st);
 }
 
+// update_avg_* over streams of unequal length: streams[i] gives stream i's first row in psd (row0), its first row in avg / ret
+// (out0) and its frame count; entries without frames are skipped.  Every stream takes the shape launch_avg takes for its frame
+// count alone -- its own chunk, and from it the fused or the two-pass form -- so the streams of a call fall into at most two
+// classes, each with its own table and launches: one fused launch, one cum and one norm launch, whatever n and the lengths
+// (save pieces of 2^31 - 1 blocks).  BPT and the ring depend on the band and depth only.
+extern "C" hipError_t glfer_launch_avg_ragged(int mode, const float *psd, const RaggedColsEntry *streams, size_t n, int bins,
+                                              int n_out, int depth, int minbin, int maxbin, int max0, double *avg, double *ret,
+                                              hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  const int band = maxbin - minbin;
+  if (band < 1 || minbin < 0 || maxbin > bins || maxbin > n_out || depth < 1) return hipErrorInvalidValue;
+  const int bpt = (band + 255) / 256;
+  RaggedTable fused, cum, norm;
+  for (size_t i = 0; i < n; i++) {
+    RaggedColsEntry e = streams[i];
+    if (e.nframes <= 0) continue;
+    if (e.nframes > 0x7fffffffll) return hipErrorInvalidValue;
+    const int chunk = avg_chunk_of(e.nframes);
+    if (bpt <= 33 && depth <= 2 * chunk) {
+      e.chunk = chunk;
+      fused.add(e, (e.nframes + chunk - 1) / chunk);
+    } else {
+      e.chunk = AVG_CHUNK;
+      cum.add(e, (e.nframes + AVG_CHUNK - 1) / AVG_CHUNK);
+      norm.add(e, e.nframes);
+    }
+  }
+  RaggedColsEntry *d_tabs = nullptr;
+  hipError_t err = ragged_upload({&fused, &cum, &norm}, &d_tabs, st);
+  if (err != hipSuccess || !d_tabs) return err;
+  const size_t ring_bytes = (size_t)depth * bpt_of(bpt) * 256 * sizeof(float);
+  const bool ring = ring_bytes <= 60 * 1024;                   // (launch_avg's rule)
+  for (const RaggedPiece &pc : fused.pieces) {
+    const RaggedCols rc = fused.cols(d_tabs, pc);
+    const unsigned blocks = (unsigned)pc.blocks;
+#define GLFER_AVG_FUSED_RAG(B)                                                                                          \
+  do {                                                                                                                  \
+    if (ring) hipLaunchKernelGGL((avg_fused_kernel<B, true, false, 256, false, true>), dim3(blocks), dim3(256), ring_bytes, st, psd, 0ll, 0, bins, n_out, depth, minbin, maxbin, mode, max0, avg, ret, AvgMapArgs{}, rc); \
+    else hipLaunchKernelGGL((avg_fused_kernel<B, false, false, 256, false, true>), dim3(blocks), dim3(256), 0, st, psd, 0ll, 0, bins, n_out, depth, minbin, maxbin, mode, max0, avg, ret, AvgMapArgs{}, rc); \
+  } while (0)
+    if (bpt <= 1) GLFER_AVG_FUSED_RAG(1);
+    else if (bpt <= 2) GLFER_AVG_FUSED_RAG(2);
+    else if (bpt <= 3) GLFER_AVG_FUSED_RAG(3);
+    else if (bpt <= 5) GLFER_AVG_FUSED_RAG(5);
+    else if (bpt <= 9) GLFER_AVG_FUSED_RAG(9);
+    else if (bpt <= 17) GLFER_AVG_FUSED_RAG(17);
+    else GLFER_AVG_FUSED_RAG(33);
+#undef GLFER_AVG_FUSED_RAG
+    if (err == hipSuccess) err = hipGetLastError();
+  }
+  for (const RaggedPiece &pc : cum.pieces) {
+    hipLaunchKernelGGL((avg_cum_kernel<false, true>), dim3((unsigned)pc.blocks, (unsigned)((band + 255) / 256)), dim3(256), 0, st, psd, 0ll,
+                       bins, n_out, depth, minbin, maxbin, avg, cum.cols(d_tabs, pc));
+    if (err == hipSuccess) err = hipGetLastError();
+  }
+  for (const RaggedPiece &pc : norm.pieces) {
+    hipLaunchKernelGGL((avg_norm_kernel<false, true>), dim3((unsigned)pc.blocks), dim3(256), 0, st, psd, bins, n_out, depth, minbin, maxbin,
+                       mode, max0, avg, ret, norm.cols(d_tabs, pc));
+    if (err == hipSuccess) err = hipGetLastError();
+  }
+  scratch_free(d_tabs, st);
+  return err;
+}
+
 // update_avg_* and the column mapping in one kernel (avg_fused_kernel<.., MAP>): frames [fbeg, nframes)
 // of the batch `psd` (the sums reach back before fbeg).  levels / rgb / lev are indexed from fbeg.
 // Returns hipErrorNotSupported where the fused form does not apply (very wide bands, windows much
@@ -1053,8 +1166,7 @@ extern "C" hipError_t glfer_launch_avg_batch(int mode, const float *psd, size_t 
 #endif
 struct AvgMapShape { int chunk, bpt, nt; bool ring; size_t shmem; bool ok; };
 static AvgMapShape avgmap_shape(long long walk, int bins, int depth, int minbin, int maxbin) {
-  AvgMapShape a{AVG_CHUNK, 0, 256, false, 0, false};
-  while (a.chunk > 8 && walk / a.chunk < 1024) a.chunk /= 2;
+  AvgMapShape a{avg_chunk_of(walk), 0, 256, false, 0, false};
   if (GLFER_AVGMAP_WIDE && maxbin - minbin >= 1024) a.nt = 512;
   a.bpt = (maxbin - minbin + a.nt - 1) / a.nt;
   const size_t pix_bytes = 2 * (((size_t)bins + 1) & ~(size_t)1) * sizeof(unsigned) +
@@ -1135,6 +1247,71 @@ extern "C" hipError_t glfer_launch_avgmap_batch(int mode, const float *psd, size
                                                 long long col_bs, hipStream_t st) {
   return launch_avgmap<true>(mode, psd, fbeg, nframes, bins, depth, minbin, maxbin, max0, scale_log, thr255, one_m_thr, levels,
                              colortab, log_thr, rgb, lev, nb, AvgBatchStrides{psd_bs, col_bs, lv_bs}, st);
+}
+
+// glfer_launch_avgmap over streams of unequal length (the ragged waterfall's fused class): every stream whole (fbeg 0), its rows
+// at row0 of psd, its levels and columns at out0 of levels / rgb / lev, its chunk the one avgmap_shape gives for its own frame
+// count.  hipErrorNotSupported if the fused form does not apply to one of the streams (the caller asks glfer_avgmap_applies
+// stream by stream first and gives the others to the staged class).
+extern "C" hipError_t glfer_launch_avgmap_ragged(int mode, const float *psd, const RaggedColsEntry *streams, size_t n, int bins,
+                                                 int depth, int minbin, int maxbin, int max0, int scale_log, double thr255,
+                                                 double one_m_thr, const float *levels, const unsigned char *colortab,
+                                                 const double *log_thr, unsigned char *rgb, short *lev, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  const int band = maxbin - minbin;
+  if (band < 1 || minbin < 0 || maxbin > bins || depth < 1) return hipErrorInvalidValue;
+  RaggedTable tab;
+  AvgMapShape shape{};
+  for (size_t i = 0; i < n; i++) {
+    RaggedColsEntry e = streams[i];
+    if (e.nframes <= 0) continue;
+    if (e.nframes > 0x7fffffffll) return hipErrorInvalidValue;
+    shape = avgmap_shape(e.nframes, bins, depth, minbin, maxbin);        // (bpt, nt, ring, shmem: the same for every stream)
+    if (!shape.ok) return hipErrorNotSupported;
+    e.chunk = shape.chunk;
+    tab.add(e, (e.nframes + shape.chunk - 1) / shape.chunk);
+  }
+  RaggedColsEntry *d_tabs = nullptr;
+  hipError_t err = ragged_upload({&tab}, &d_tabs, st);
+  if (err != hipSuccess || !d_tabs) return err;
+  const int bpt = shape.bpt;
+  const bool ring = shape.ring;
+  const size_t shmem = shape.shmem;
+  const AvgMapArgs ma{levels, colortab, log_thr, rgb, lev, scale_log, thr255, one_m_thr, 0};
+  for (const RaggedPiece &pc : tab.pieces) {
+    const RaggedCols rc = tab.cols(d_tabs, pc);
+    const unsigned blocks = (unsigned)pc.blocks;
+#define GLFER_AVGMAP_RAG_NT(B, NT)                                                                                      \
+  do {                                                                                                                  \
+    const void *fn = ring ? reinterpret_cast<const void *>(avg_fused_kernel<B, true, true, NT, false, true>)            \
+                          : reinterpret_cast<const void *>(avg_fused_kernel<B, false, true, NT, false, true>);          \
+    hipError_t e = allow_dynamic_lds(fn, shmem);                                                                        \
+    if (e != hipSuccess) { scratch_free(d_tabs, st); return e; }                                                        \
+    if (ring) hipLaunchKernelGGL((avg_fused_kernel<B, true, true, NT, false, true>), dim3(blocks), dim3(NT), shmem, st, psd, 0ll, 0, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma, rc); \
+    else hipLaunchKernelGGL((avg_fused_kernel<B, false, true, NT, false, true>), dim3(blocks), dim3(NT), shmem, st, psd, 0ll, 0, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma, rc); \
+  } while (0)
+#if GLFER_AVGMAP_WIDE
+#define GLFER_AVGMAP_RAG(B)                                                                                             \
+  do {                                                                                                                  \
+    if (shape.nt == 512) GLFER_AVGMAP_RAG_NT(B, 512);                                                                   \
+    else GLFER_AVGMAP_RAG_NT(B, 256);                                                                                   \
+  } while (0)
+#else
+#define GLFER_AVGMAP_RAG(B) GLFER_AVGMAP_RAG_NT(B, 256)
+#endif
+    if (bpt <= 1) GLFER_AVGMAP_RAG(1);
+    else if (bpt <= 2) GLFER_AVGMAP_RAG(2);
+    else if (bpt <= 3) GLFER_AVGMAP_RAG(3);
+    else if (bpt <= 5) GLFER_AVGMAP_RAG(5);
+    else if (bpt <= 9) GLFER_AVGMAP_RAG(9);
+    else if (bpt <= 17) GLFER_AVGMAP_RAG(17);
+    else GLFER_AVGMAP_RAG(33);
+#undef GLFER_AVGMAP_RAG_NT
+#undef GLFER_AVGMAP_RAG
+    if (err == hipSuccess) err = hipGetLastError();
+  }
+  scratch_free(d_tabs, st);
+  return err;
 }
 
 // avgdata->cum alone (the shims hand it back to the caller's avg_data_t)

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "display_map.hpp"
+#include "ragged_cols.hpp"
 
 namespace glfer {
 
@@ -28,6 +29,14 @@ struct LevelsBatch {
   long long stats_bs, levels_bs;       // floats from one stream's statistics / levels to the next's
   float *state;
 };
+// RAG (glfer_launch_levels_ragged): streams of unequal length, statistics and levels packed row by row.  blockIdx.x is the
+// launch's flat list of chunks (ragged_cols.hpp: an entry's blk0 counts chunks of LEV_CHUNK, and its chunk states start there);
+// the chunks, their warm-ups and the seeded start are the stream's own, the carried state is row `stream` of `state`.
+struct LevelsRagged {
+  RaggedCols cols;
+  float *state;
+};
+template <bool RAG> using LevelsStreams = std::conditional_t<RAG, LevelsRagged, LevelsBatch>;
 
 // levels: [nframes][4] = {display_max, display_min, display_max_lvl, display_min_lvl}
 //
@@ -135,13 +144,26 @@ __device__ __forceinline__ void levels_walk(const float *__restrict__ stats, lon
 
 // chunk state: [chunk][4] = {warm-up end max, min, final max, min}
 // BAT: blockIdx.y is the stream; its chunks are its own (a warm-up never reads another stream's columns)
-template <bool BAT = false>
+template <bool BAT = false, bool RAG = false>
 __global__ __launch_bounds__(64) void levels_kernel(const float *__restrict__ stats, long long nframes,
                                                     LevelsParams p, float *__restrict__ levels,
-                                                    float *__restrict__ chunk_state, LevelsBatch lb) {
+                                                    float *__restrict__ chunk_state, LevelsStreams<RAG> lb) {
   __shared__ float sx[2][64];
   __shared__ float sy[2][64];
   const int lane = threadIdx.x;
+  long long chunk_index = blockIdx.x;
+  if constexpr (RAG) {
+    const RaggedColsEntry e = ragged_cols_find(lb.cols, blockIdx.x);
+    stats += e.row0 * 4;
+    levels += e.row0 * 4;
+    chunk_state += e.blk0 * 4;
+    nframes = e.nframes;
+    chunk_index = (long long)blockIdx.x - e.blk0;
+    const float *s = lb.state + (long long)e.stream * 3;
+    p.first_buffer = s[0] != 0.0f;
+    p.max_lvl0 = s[1];
+    p.min_lvl0 = s[2];
+  }
   if constexpr (BAT) {
     const long long b = blockIdx.y;
     stats += b * lb.stats_bs;
@@ -152,7 +174,7 @@ __global__ __launch_bounds__(64) void levels_kernel(const float *__restrict__ st
     p.max_lvl0 = s[1];
     p.min_lvl0 = s[2];
   }
-  const long long c = blockIdx.x, begin = c * LEV_CHUNK;
+  const long long c = chunk_index, begin = c * LEV_CHUNK;
   const long long end = begin + LEV_CHUNK < nframes ? begin + LEV_CHUNK : nframes;
   const long long ws = begin - LEV_WARM_SEEDED;
   float lvl = (lane == 0) ? p.max_lvl0 : p.min_lvl0;       // the state carried into the call
@@ -213,13 +235,24 @@ __global__ __launch_bounds__(64) void levels_kernel(const float *__restrict__ st
 // the successor's comparison stale: the successor is walked again too (always correct, and rarer still).
 // BAT: one block per stream (blockIdx.x), its chunks compared with its own only; the block then carries the stream's
 // final state into its row of lb.state (first_buffer 0, g_main.c:1120).
-template <bool BAT = false>
+// RAG: one block per ENTRY of the table (blockIdx.x), its chunks its own; the final state goes to row `stream` of lb.state.
+template <bool BAT = false, bool RAG = false>
 __global__ __launch_bounds__(64) void levels_fixup_kernel(const float *__restrict__ stats, long long nframes,
                                                           LevelsParams p, float *__restrict__ levels,
-                                                          float *__restrict__ chunk_state, int nchunks, LevelsBatch lb) {
+                                                          float *__restrict__ chunk_state, int nchunks, LevelsStreams<RAG> lb) {
   __shared__ float sx[2][64];
   __shared__ float sy[2][64];
   const int lane = threadIdx.x;
+  long long state_row = blockIdx.x;
+  if constexpr (RAG) {
+    const RaggedColsEntry e = lb.cols.tab[blockIdx.x];
+    stats += e.row0 * 4;
+    levels += e.row0 * 4;
+    chunk_state += e.blk0 * 4;
+    nframes = e.nframes;
+    nchunks = (int)((e.nframes + LEV_CHUNK - 1) / LEV_CHUNK);
+    state_row = e.stream;
+  }
   if constexpr (BAT) {
     const long long b = blockIdx.x;
     stats += b * lb.stats_bs;
@@ -255,8 +288,8 @@ __global__ __launch_bounds__(64) void levels_fixup_kernel(const float *__restric
       }
     }
   }
-  if constexpr (BAT) {
-    float *s = lb.state + (long long)blockIdx.x * 3;
+  if constexpr (BAT || RAG) {
+    float *s = lb.state + state_row * 3;
     if (lane < 2) s[1 + lane] = chunk_state[(long long)(nchunks - 1) * 4 + 2 + lane];
     if (lane == 0) s[0] = 0.0f;
   }
@@ -278,14 +311,18 @@ __global__ __launch_bounds__(256) void levels_fixed_kernel(long long nframes, fl
 // twelve byte stores and four short stores; the palette sits in LDS as one dword per colour.
 // BAT (glfer_launch_map_batch): blockIdx.y is the stream, its rows, levels and columns mb apart -- a frame tile of a batch of
 // streams is not one run of rows, so the flattened launch does not serve there.
+// RAG (glfer_launch_map_ragged, the staged class of the ragged waterfall): blockIdx.x is the launch's flat list of rows (an
+// entry's blk0 counts rows); the stream's source rows start at out0 of src (averaged rows packed class by class in scratch), its
+// levels and columns at row0 (packed as the PSD rows are).
 struct MapBatch { long long src, levels, rgb, lev; };   // per stream: SRC values, floats of levels, bytes of rgb, shorts of lev
-template <typename SRC, bool BAT = false>
+template <bool RAG> using MapStreams = std::conditional_t<RAG, RaggedCols, MapBatch>;
+template <typename SRC, bool BAT = false, bool RAG = false>
 __global__ __launch_bounds__(256) void map_kernel(const SRC *__restrict__ src, int n, int src_pitch, int scale_log,
                                                   double thr255, double one_m_thr,
                                                   const float *__restrict__ levels,
                                                   const unsigned char *__restrict__ colortab,
                                                   const double *__restrict__ log_thr,
-                                                  unsigned char *__restrict__ rgb, short *__restrict__ lev, MapBatch mb) {
+                                                  unsigned char *__restrict__ rgb, short *__restrict__ lev, MapStreams<RAG> mb) {
   if constexpr (BAT) {
     const long long b = blockIdx.y;
     src += b * mb.src;
@@ -301,8 +338,13 @@ __global__ __launch_bounds__(256) void map_kernel(const SRC *__restrict__ src, i
     return (unsigned)colortab[3 * v] | ((unsigned)colortab[3 * v + 1] << 8) | ((unsigned)colortab[3 * v + 2] << 16);
   };
   tab[c0] = rgb_of(c0);
-  const size_t fr = blockIdx.x;
-  const SRC *row = src + fr * (size_t)src_pitch;
+  size_t fr = blockIdx.x, src_row = blockIdx.x;
+  if constexpr (RAG) {
+    const RaggedColsEntry e = ragged_cols_find(mb, blockIdx.x);
+    fr = (size_t)(e.row0 + ((long long)blockIdx.x - e.blk0));
+    src_row = (size_t)(e.out0 + ((long long)blockIdx.x - e.blk0));
+  }
+  const SRC *row = src + src_row * (size_t)src_pitch;
   const float display_max = levels[fr * 4 + 0];
   const float display_min = levels[fr * 4 + 1];
   const RowScale rs = row_scale(display_max, display_min);
@@ -447,4 +489,62 @@ extern "C" hipError_t glfer_launch_map_batch(const float *psd, const double *avg
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// The autoscale walk of streams of unequal length: streams[i] gives stream i's first row in stats / levels (row0), its column
+// count and its row of `state` ([..][3] = {first_buffer, display_max_lvl, display_min_lvl} in, the state after its last column
+// out); entries without columns are skipped and their state rows stay as they are.  chunk_state: device scratch of the sum of
+// glfer_levels_scratch_floats(nframes_i) floats.  Two launches whatever n (save pieces of 2^31 - 1 chunks); the fix-up always
+// runs (one block per stream): it is what carries the state.
+extern "C" hipError_t glfer_launch_levels_ragged(const float *stats, const RaggedColsEntry *streams, size_t n, int scale_log,
+                                                 float overlap, float *state, float *levels, float *chunk_state, hipStream_t st) {
+  RaggedTable tab;
+  long long chunks_before = 0;
+  std::vector<long long> piece_chunk0;                     // chunk states: packed over the whole call, not per piece
+  for (size_t i = 0; i < n; i++) {
+    const RaggedColsEntry &e = streams[i];
+    if (e.nframes <= 0) continue;
+    if (e.nframes > 0x7fffffffll) return hipErrorInvalidValue;
+    const long long nchunks = (e.nframes + LEV_CHUNK - 1) / LEV_CHUNK;
+    const size_t pieces = tab.pieces.size();
+    tab.add(e, nchunks);
+    if (tab.pieces.size() != pieces) piece_chunk0.push_back(chunks_before);
+    chunks_before += nchunks;
+  }
+  RaggedColsEntry *d_tabs = nullptr;
+  hipError_t err = ragged_upload({&tab}, &d_tabs, st);
+  if (err != hipSuccess || !d_tabs) return err;
+  LevelsParams p{scale_log, 1, 0, overlap, 0.0f, 0.0f};
+  for (size_t k = 0; k < tab.pieces.size(); k++) {
+    const RaggedPiece &pc = tab.pieces[k];
+    const LevelsRagged lr{tab.cols(d_tabs, pc), state};
+    float *cs = chunk_state + piece_chunk0[k] * 4;
+    hipLaunchKernelGGL((levels_kernel<false, true>), dim3((unsigned)pc.blocks), dim3(64), 0, st, stats, 0ll, p, levels, cs, lr);
+    if (err == hipSuccess) err = hipGetLastError();
+    hipLaunchKernelGGL((levels_fixup_kernel<false, true>), dim3((unsigned)pc.count), dim3(64), 0, st, stats, 0ll, p, levels, cs, 0, lr);
+    if (err == hipSuccess) err = hipGetLastError();
+  }
+  scratch_free(d_tabs, st);
+  return err;
+}
+
+// The map of averaged rows of streams of unequal length (the ragged waterfall's staged class): streams[i] gives stream i's first
+// averaged row in avg (out0: the rows of a class are packed on their own), its first row in levels / rgb / lev (row0) and its
+// column count.  One launch whatever n (save pieces of 2^31 - 1 rows).
+extern "C" hipError_t glfer_launch_map_ragged(const double *avg, const RaggedColsEntry *streams, size_t n, int bins, int scale_log,
+                                              double thr255, double one_m_thr, const float *levels, const unsigned char *colortab,
+                                              const double *log_thr, unsigned char *rgb, short *lev, hipStream_t st) {
+  RaggedTable tab;
+  for (size_t i = 0; i < n; i++)
+    if (streams[i].nframes > 0) tab.add(streams[i], streams[i].nframes);
+  RaggedColsEntry *d_tabs = nullptr;
+  hipError_t err = ragged_upload({&tab}, &d_tabs, st);
+  if (err != hipSuccess || !d_tabs) return err;
+  for (const RaggedPiece &pc : tab.pieces) {
+    hipLaunchKernelGGL((map_kernel<double, false, true>), dim3((unsigned)pc.blocks), dim3(256), 0, st, avg, bins, bins, scale_log, thr255,
+                       one_m_thr, levels, colortab, log_thr, rgb, lev, tab.cols(d_tabs, pc));
+    if (err == hipSuccess) err = hipGetLastError();
+  }
+  scratch_free(d_tabs, st);
+  return err;
 }

@@ -20,6 +20,7 @@
 
 #include "frame_cuts.h"
 #include "host_tables.h"
+#include "ragged_cols.hpp"
 #include "spectro_params.h"
 
 static_assert(GLFER_FMT_F32 == GLFER_SAMPLES_F32 && GLFER_FMT_S16 == GLFER_SAMPLES_S16 && GLFER_FMT_U8 == GLFER_SAMPLES_U8, "glfer_sample_size");
@@ -51,6 +52,18 @@ extern "C" hipError_t glfer_launch_map_batch(const float *psd, const double *avg
                                              double thr255, double one_m_thr, const float *levels, const unsigned char *colortab,
                                              const double *log_thr, unsigned char *rgb, short *lev, unsigned nb, long long src_bs,
                                              long long levels_bs, long long rgb_bs, long long lev_bs, hipStream_t st);
+extern "C" hipError_t glfer_launch_avg_ragged(int mode, const float *psd, const glfer::RaggedColsEntry *streams, size_t n, int bins,
+                                              int n_out, int depth, int minbin, int maxbin, int max0, double *avg, double *ret,
+                                              hipStream_t st);
+extern "C" hipError_t glfer_launch_avgmap_ragged(int mode, const float *psd, const glfer::RaggedColsEntry *streams, size_t n, int bins,
+                                                 int depth, int minbin, int maxbin, int max0, int scale_log, double thr255,
+                                                 double one_m_thr, const float *levels, const unsigned char *colortab,
+                                                 const double *log_thr, unsigned char *rgb, short *lev, hipStream_t st);
+extern "C" hipError_t glfer_launch_levels_ragged(const float *stats, const glfer::RaggedColsEntry *streams, size_t n, int scale_log,
+                                                 float overlap, float *state, float *levels, float *chunk_state, hipStream_t st);
+extern "C" hipError_t glfer_launch_map_ragged(const double *avg, const glfer::RaggedColsEntry *streams, size_t n, int bins, int scale_log,
+                                              double thr255, double one_m_thr, const float *levels, const unsigned char *colortab,
+                                              const double *log_thr, unsigned char *rgb, short *lev, hipStream_t st);
 extern "C" hipError_t glfer_launch_avg_cum(const float *psd, size_t nframes, int bins, int n_out, int depth,
                                            int minbin, int maxbin, double *cum, hipStream_t st);
 extern "C" hipError_t glfer_launch_lmp(const float *rows, long long row0, long long first, size_t nframes, int bins,
@@ -896,6 +909,232 @@ int glfer_hip_waterfall_batch_device(glfer_hip_display *disps, size_t nstreams, 
   }
   return rc;
 }
+
+}  // extern "C"
+
+// ---- ragged rows: the per-column stages over streams of unequal length (glfer_hip.h)
+// true where `st` is being captured into a graph: the per-stream tables are uploaded from host memory that is gone when the call
+// returns, which a captured copy would read at every replay
+static bool stream_is_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (st != hipStreamPerThread && hipStreamIsCapturing(st, &cs) == hipSuccess) return cs != hipStreamCaptureStatusNone;
+  (void)hipGetLastError();
+  return false;
+}
+// row_starts of nstreams streams: non-decreasing, at most 2^31 - 1 rows a stream
+static bool ragged_rows_ok(const size_t *row_starts, size_t nstreams) {
+  if (nstreams > 0x7fffffffu) return false;
+  for (size_t b = 0; b < nstreams; b++)
+    if (row_starts[b + 1] < row_starts[b] || row_starts[b + 1] - row_starts[b] > 0x7fffffffu) return false;
+  return true;
+}
+// the streams that have rows, as the ragged launchers take them (out0 = row0: outputs packed as the rows are)
+static std::vector<glfer::RaggedColsEntry> ragged_streams(const size_t *row_starts, size_t nstreams) {
+  std::vector<glfer::RaggedColsEntry> s;
+  for (size_t b = 0; b < nstreams; b++)
+    if (row_starts[b + 1] > row_starts[b])
+      s.push_back(glfer::RaggedColsEntry{(long long)row_starts[b], (long long)row_starts[b], (long long)(row_starts[b + 1] - row_starts[b]), 0, 0, (int)b});
+  return s;
+}
+
+extern "C" {
+
+// glfer_hip_waterfall_batch_device for packed rows of streams of unequal length (glfer_hip.h).  Every stream takes the route
+// glfer_hip_waterfall_device takes for its own frame count (waterfall_route): the per-row stages -- compute_floor, the plain
+// map, the fixed levels -- run over the packed rows as one run; the autoscale walk, the average-and-map kernel and the staged
+// average read a per-stream table (ragged_cols.hpp).  Streams whose route is the fused one and streams whose route is staged are
+// two classes with a launch set each.  A stream its route would cut into tiles sends the whole call through the single entry.
+int glfer_hip_waterfall_ragged_device(glfer_hip_display *disps, size_t nstreams, int avg_mode, int depth, int minbin, int maxbin,
+                                      int max0, const float *d_psd, const size_t *row_starts, int bins, unsigned char *d_rgb,
+                                      short *d_lev, float *d_stats, void *hip_stream) {
+  if (nstreams == 0) return GLFER_OK;
+  if (!disps) return GLFER_E_ARG;
+  for (size_t b = 1; b < nstreams; b++)                  // one plan, many streams
+    if (!same_display_options(disps[0], disps[b])) return GLFER_E_ARG;
+  const glfer_hip_display &d0 = disps[0];
+  const int pitch = d0.psd_pitch == 0 ? bins : d0.psd_pitch;
+  if (bins < 1 || bins > 32769 || pitch < bins) return GLFER_E_ARG;     // (waterfall_columns' rules)
+  const bool averaging = avg_mode != 0;
+  if (averaging && (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME || depth < 1 || minbin < 0 ||
+                    maxbin <= minbin || maxbin > bins))
+    return GLFER_E_ARG;
+  if (d0.scale_type < GLFER_SCALE_LIN || d0.scale_type > GLFER_SCALE_LOG_MAX0) return GLFER_E_ARG;   // (display_columns')
+  if (!row_starts || !ragged_rows_ok(row_starts, nstreams)) return GLFER_E_ARG;
+  const size_t rows_lo = row_starts[0], rows_hi = row_starts[nstreams];
+  if (rows_hi > SIZE_MAX / sizeof(double) / (size_t)pitch) return GLFER_E_ARG;
+  if (rows_hi == rows_lo) return GLFER_OK;
+  if (!d_psd || !d_rgb) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (stream_is_capturing(st)) return GLFER_E_ARG;
+  DeviceGuard guard(data_device(d_psd));
+  HIP_TRY(guard.error());
+  const size_t bins_z = (size_t)bins;
+
+  // every stream's own route
+  std::vector<glfer::RaggedColsEntry> all = ragged_streams(row_starts, nstreams), fused_s, staged_s;
+  bool tiled = false;
+  for (const glfer::RaggedColsEntry &e : all) {
+    bool fused = false;
+    size_t tile = 0;
+    waterfall_route(avg_mode, depth, minbin, maxbin, bins, pitch, (size_t)e.nframes, &fused, &tile);
+    if (tile < (size_t)e.nframes) tiled = true;
+    if (averaging) (fused ? fused_s : staged_s).push_back(e);
+  }
+  if (tiled) {
+    // stream by stream through the single entry (on copies: an error leaves disps as it was)
+    std::vector<glfer_hip_display> copy(disps, disps + nstreams);
+    for (const glfer::RaggedColsEntry &e : all) {
+      const size_t r = (size_t)e.row0;
+      const int rc = waterfall_columns(&copy[e.stream], avg_mode, depth, minbin, maxbin, max0, d_psd + r * (size_t)pitch, 0, (size_t)e.nframes,
+                                       bins, d_rgb + r * bins_z * 3, d_lev ? d_lev + r * bins_z : nullptr, d_stats ? d_stats + r * 4 : nullptr,
+                                       st, nullptr, pitch);
+      if (rc != GLFER_OK) return rc;
+    }
+    std::copy(copy.begin(), copy.end(), disps);
+    return GLFER_OK;
+  }
+  const bool autoscale = d0.autoscale != 0;
+  const int scale_log = d0.scale_type == GLFER_SCALE_LOG || d0.scale_type == GLFER_SCALE_LOG_MAX0;
+
+  // one small allocation: palette, dB table, the carried states [nstreams][3]; one upload
+  const size_t thr_bytes = (2 * glfer::kLogThrK + 1) * sizeof(double);
+  const size_t small_bytes = 768 + thr_bytes + nstreams * 3 * sizeof(float);
+  std::vector<unsigned char> host(small_bytes);
+  glfer::make_palette(d0.palette, host.data());
+  memcpy(host.data() + 768, glfer::log_thresholds(), thr_bytes);
+  float *h_state = reinterpret_cast<float *>(host.data() + 768 + thr_bytes);
+  for (size_t b = 0; b < nstreams; b++) {
+    h_state[b * 3 + 0] = disps[b].first_buffer != 0 ? 1.0f : 0.0f;
+    h_state[b * 3 + 1] = disps[b].display_max_lvl;
+    h_state[b * 3 + 2] = disps[b].display_min_lvl;
+  }
+  unsigned char *small = nullptr;
+  HIP_TRY(glfer::scratch_malloc((void **)&small, small_bytes, st));
+  const unsigned char *d_tab = small;
+  const double *d_thr = reinterpret_cast<const double *>(small + 768);
+  float *d_state = reinterpret_cast<float *>(small + 768 + thr_bytes);
+  int rc = GLFER_OK;
+  auto fail = [&](hipError_t err, const char *what) {
+    if (rc == GLFER_OK) rc = hip_fail(err, what);
+  };
+  hipError_t e = hipMemcpyAsync(small, host.data(), small_bytes, hipMemcpyHostToDevice, st);   // (pageable source: staged before it returns)
+  if (e != hipSuccess) fail(e, "glfer_hip_waterfall_ragged_device (upload)");
+
+  // scratch, indexed by packed row: statistics (without d_stats), levels; the chunk states of the walks; a group's averaged rows
+  size_t st_floats = 0;
+  if (autoscale)
+    for (const glfer::RaggedColsEntry &s : all) st_floats += glfer_levels_scratch_floats((size_t)s.nframes);
+  // staged: groups of streams whose averaged rows stay within the single entry's 4 GiB (one stream alone always goes)
+  const size_t group_rows_max = std::max<size_t>(1, ((size_t)4 << 30) / (bins_z * sizeof(double)));
+  std::vector<size_t> group_end;                          // staged_s[group_end[g-1] .. group_end[g])
+  size_t scratch_rows = 0;
+  for (size_t i = 0, in_group = 0; i < staged_s.size(); i++) {
+    const size_t n = (size_t)staged_s[i].nframes;
+    if (in_group && in_group + n > group_rows_max) {
+      group_end.push_back(i);
+      in_group = 0;
+    }
+    staged_s[i].out0 = (long long)in_group;               // the averaged rows of a group are packed on their own
+    in_group += n;
+    scratch_rows = std::max(scratch_rows, in_group);
+    if (i + 1 == staged_s.size()) group_end.push_back(i + 1);
+  }
+  float *stats = d_stats, *levels = nullptr;
+  double *avg = nullptr, *ret = nullptr;
+  if (rc == GLFER_OK && !d_stats) {
+    e = glfer::scratch_malloc((void **)&stats, rows_hi * 4 * sizeof(float), st);
+    if (e != hipSuccess) { stats = nullptr; fail(e, "scratch (waterfall statistics, ragged)"); }
+  }
+  if (rc == GLFER_OK) {
+    e = glfer::scratch_malloc((void **)&levels, (rows_hi * 4 + st_floats) * sizeof(float), st);
+    if (e != hipSuccess) { levels = nullptr; fail(e, "scratch (waterfall levels, ragged)"); }
+  }
+  float *chunk_state = levels ? levels + rows_hi * 4 : nullptr;
+  if (rc == GLFER_OK && scratch_rows) {
+    e = glfer::scratch_malloc((void **)&avg, scratch_rows * bins_z * sizeof(double), st);
+    if (e == hipSuccess) e = glfer::scratch_malloc((void **)&ret, scratch_rows * 4 * sizeof(double), st);
+    if (e != hipSuccess) fail(e, "scratch (averaged rows, ragged waterfall)");
+  }
+
+  // compute_floor of every row: the packed rows are one run (pieces: the grid's x limit)
+  const int m = bins - (int)(bins * 0.95);                           // fft.c:271 (glfer_hip_floor_device_pitched)
+  const size_t piece = (size_t)1 << 22;
+  for (size_t r0 = rows_lo; rc == GLFER_OK && r0 < rows_hi; r0 += piece) {
+    e = glfer_launch_floor(d_psd + r0 * (size_t)pitch, std::min(piece, rows_hi - r0), bins, pitch, m, stats + r0 * 4, st);
+    if (e != hipSuccess) fail(e, "compute_floor launch (ragged)");
+  }
+  const float thr_level = d0.thr_level / 100.0;                                // g_main.c:1099
+  const double thr255 = 255.0 * thr_level, one_m_thr = 1.0 - thr_level;
+  float mx = 0.0f, mn = 0.0f;
+  if (rc == GLFER_OK) {
+    if (autoscale) {
+      e = glfer_launch_levels_ragged(stats, all.data(), all.size(), scale_log, d0.overlap, d_state, levels, chunk_state, st);
+      if (e != hipSuccess) fail(e, "level tracking launch (ragged)");
+    } else {                                                                   // g_main.c:1125-1139
+      mx = pow(10.0, d0.max_level_db / 10.0);
+      mn = pow(10.0, d0.min_level_db / 10.0);
+      mn = (mx > mn ? mn : mx / 10.0);
+      const float dmax = scale_log ? (float)(10.0 * log10(mx)) : mx;
+      const float dmin = scale_log ? (float)(10.0 * log10(mn)) : mn;
+      e = glfer_launch_levels_fixed(rows_hi - rows_lo, dmax, dmin, mx, mn, levels + rows_lo * 4, st);
+      if (e != hipSuccess) fail(e, "levels launch (ragged)");
+    }
+  }
+  if (rc == GLFER_OK && !averaging) {
+    const size_t map_piece = (size_t)1 << 30;
+    for (size_t r0 = rows_lo; rc == GLFER_OK && r0 < rows_hi; r0 += map_piece) {
+      e = glfer_launch_map(d_psd + r0 * (size_t)pitch, nullptr, std::min(map_piece, rows_hi - r0), bins, pitch, scale_log, thr255, one_m_thr,
+                           levels + r0 * 4, d_tab, d_thr, d_rgb + r0 * bins_z * 3, d_lev ? d_lev + r0 * bins_z : nullptr, st);
+      if (e != hipSuccess) fail(e, "map launch (ragged)");
+    }
+  }
+  if (rc == GLFER_OK && !fused_s.empty()) {
+    e = glfer_launch_avgmap_ragged(avg_mode, d_psd, fused_s.data(), fused_s.size(), bins, depth, minbin, maxbin, max0 ? 1 : 0, scale_log,
+                                   thr255, one_m_thr, levels, d_tab, d_thr, d_rgb, d_lev, st);
+    if (e != hipSuccess) fail(e, "average-and-map launch (ragged)");
+  }
+  for (size_t g = 0, i0 = 0; rc == GLFER_OK && g < group_end.size(); i0 = group_end[g++]) {
+    const glfer::RaggedColsEntry *gs = staged_s.data() + i0;
+    const size_t gn = group_end[g] - i0;
+    // (update_avg's `bins` is its rows' stride; the band is minbin..maxbin, the averaged rows are dense)
+    e = glfer_launch_avg_ragged(avg_mode, d_psd, gs, gn, pitch, bins, depth, minbin, maxbin, max0 ? 1 : 0, avg, ret, st);
+    if (e != hipSuccess) fail(e, "update_avg launch (ragged waterfall)");
+    if (rc == GLFER_OK) {
+      e = glfer_launch_map_ragged(avg, gs, gn, bins, scale_log, thr255, one_m_thr, levels, d_tab, d_thr, d_rgb, d_lev, st);
+      if (e != hipSuccess) fail(e, "map launch (ragged waterfall)");
+    }
+  }
+  std::vector<float> back_state(autoscale ? nstreams * 3 : 0);
+  if (rc == GLFER_OK && autoscale) {
+    e = hipMemcpyAsync(back_state.data(), d_state, nstreams * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) fail(e, "glfer_hip_waterfall_ragged_device (state download)");
+  }
+  if (avg) glfer::scratch_free(avg, st);
+  if (ret) glfer::scratch_free(ret, st);
+  if (levels) glfer::scratch_free(levels, st);
+  if (!d_stats && stats) glfer::scratch_free(stats, st);
+  glfer::scratch_free(small, st);
+  e = hipStreamSynchronize(st);              // the carried states come back to the host
+  if (e != hipSuccess) fail(e, "glfer_hip_waterfall_ragged_device");
+  if (rc == GLFER_OK) {
+    for (const glfer::RaggedColsEntry &s : all) {        // (a stream without rows keeps its display as it is)
+      glfer_hip_display &d = disps[s.stream];
+      if (autoscale) {
+        d.display_max_lvl = back_state[(size_t)s.stream * 3 + 1];
+        d.display_min_lvl = back_state[(size_t)s.stream * 3 + 2];
+        d.first_buffer = 0;                                                    // g_main.c:1120
+      } else {
+        d.display_max_lvl = mx;
+        d.display_min_lvl = mn;
+      }
+    }
+  }
+  return rc;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 size_t glfer_hip_scratch_trim(int device, size_t keep_bytes) {
   size_t ring = 0;
@@ -2452,16 +2691,9 @@ int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *p, const void *d_samples
   if (total == 0) return GLFER_OK;
   if (!d_samples || !d_psd) return GLFER_E_ARG;
   hipStream_t st = (hipStream_t)hip_stream;
-  {
-    // the per-stream tables are uploaded from host memory that is gone when the call returns: a copy node of a captured graph
-    // would read it at every replay, so a capturing stream is refused
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (st != hipStreamPerThread && hipStreamIsCapturing(st, &cs) == hipSuccess) {
-      if (cs != hipStreamCaptureStatusNone) return GLFER_E_ARG;
-    } else {
-      (void)hipGetLastError();
-    }
-  }
+  // the per-stream tables are uploaded from host memory that is gone when the call returns: a copy node of a captured graph
+  // would read it at every replay, so a capturing stream is refused
+  if (stream_is_capturing(st)) return GLFER_E_ARG;
   const char *base = static_cast<const char *>(d_samples);
   auto single = [&](size_t b) {
     if (!s[b].frames) return (int)GLFER_OK;
@@ -3141,6 +3373,78 @@ int glfer_hip_spectrogram_avg_batch_device(glfer_hip_plan *p, const void *d_stre
     if (means) glfer::scratch_free(means, st);
     if (ret_scratch) glfer::scratch_free(ret_scratch, st);
   }
+  return rc;
+}
+
+// update_avg_* over packed rows of streams of unequal length (glfer_hip.h): glfer_launch_avg_ragged over the streams that have rows
+int glfer_hip_avg_ragged_device(int avg_mode, const float *d_psd, size_t nstreams, const size_t *row_starts, int bins, int n_out,
+                                int depth, int minbin, int maxbin, int max0, double *d_avg, double *d_ret, void *hip_stream) {
+  if (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME) return GLFER_E_ARG;
+  if (depth < 1 || minbin < 0 || maxbin <= minbin || maxbin > bins || maxbin > n_out || n_out < 1) return GLFER_E_ARG;
+  if (nstreams == 0) return GLFER_OK;
+  if (!row_starts || !ragged_rows_ok(row_starts, nstreams)) return GLFER_E_ARG;
+  const size_t rows_hi = row_starts[nstreams];
+  if (rows_hi > SIZE_MAX / sizeof(double) / (size_t)std::max(bins, n_out)) return GLFER_E_ARG;
+  if (rows_hi == row_starts[0]) return GLFER_OK;
+  if (!d_psd || !d_avg) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (stream_is_capturing(st)) return GLFER_E_ARG;
+  DeviceGuard guard(data_device(d_psd));
+  HIP_TRY(guard.error());
+  const std::vector<glfer::RaggedColsEntry> s = ragged_streams(row_starts, nstreams);
+  double *ret = d_ret;                                   // (the kernels always form the return values: without d_ret they land in scratch)
+  if (!ret) HIP_TRY(glfer::scratch_malloc((void **)&ret, rows_hi * 4 * sizeof(double), st));
+  const hipError_t e = glfer_launch_avg_ragged(avg_mode, d_psd, s.data(), s.size(), bins, n_out, depth, minbin, maxbin, max0 ? 1 : 0, d_avg,
+                                               ret, st);
+  if (!d_ret) glfer::scratch_free(ret, st);
+  return e == hipSuccess ? GLFER_OK : hip_fail(e, "update_avg launch (ragged)");
+}
+
+// The ragged rows, then the ragged average over them: the two-launch route of glfer_hip_spectrogram_avg_device, stream by stream
+// (glfer_hip.h; the average inside the estimator launch is not built for ragged calls).
+int glfer_hip_spectrogram_avg_ragged_device(glfer_hip_plan *p, const void *d_samples, size_t nstreams, const size_t *offsets,
+                                            const size_t *lengths, int avg_mode, int depth, int minbin, int maxbin, int max0,
+                                            int n_out, float *d_psd, double *d_avg, double *d_ret, size_t *row_starts,
+                                            void *hip_stream) {
+  if (!p) return GLFER_E_ARG;
+  if (p->cfg.mode == GLFER_MODE_HPARMA || p->pitch != p->bins) return GLFER_E_ARG;       // (glfer_hip_spectrogram_avg_device's rules)
+  if (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME) return GLFER_E_ARG;
+  if (depth < 1 || minbin < 0 || maxbin <= minbin || maxbin > p->bins || n_out < p->bins) return GLFER_E_ARG;
+  if (nstreams == 0) {
+    if (row_starts) row_starts[0] = 0;
+    return GLFER_OK;
+  }
+  if (!offsets || !lengths || nstreams > 0x7fffffffu) return GLFER_E_ARG;
+  // glfer_hip_spectrogram_ragged_device's rules, before scratch is taken for its rows
+  const int fmt = p->cfg.sample_format;
+  const size_t esz = glfer_sample_size(fmt), bins = (size_t)p->bins;
+  std::vector<size_t> starts(nstreams + 1);
+  size_t total = 0;
+  for (size_t b = 0; b < nstreams; b++) {
+    const size_t f = lengths[b] / (size_t)p->hop;
+    if (f > 0x7fffffffu) return GLFER_E_ARG;
+    if (lengths[b] > SIZE_MAX / esz || offsets[b] > SIZE_MAX / esz - lengths[b]) return GLFER_E_ARG;
+    if (fmt != GLFER_FMT_F32 && (offsets[b] & 1)) return GLFER_E_ARG;
+    if (f > SIZE_MAX / sizeof(double) / (size_t)n_out - total) return GLFER_E_ARG;
+    starts[b] = total;
+    total += f;
+  }
+  starts[nstreams] = total;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (total != 0) {
+    if (!d_samples || !d_avg) return GLFER_E_ARG;
+    if (stream_is_capturing(st)) return GLFER_E_ARG;
+  }
+  if (row_starts) std::copy(starts.begin(), starts.end(), row_starts);   // (past the last refusal: a refused call writes nothing)
+  if (total == 0) return GLFER_OK;
+  DeviceGuard guard(p->cfg.device);
+  HIP_TRY(guard.error());
+  float *rows = d_psd;
+  if (!rows) HIP_TRY(glfer::scratch_malloc((void **)&rows, total * bins * sizeof(float), st));
+  int rc = glfer_hip_spectrogram_ragged_device(p, d_samples, nstreams, offsets, lengths, rows, nullptr, st);
+  if (rc == GLFER_OK)
+    rc = glfer_hip_avg_ragged_device(avg_mode, rows, nstreams, starts.data(), (int)bins, n_out, depth, minbin, maxbin, max0, d_avg, d_ret, st);
+  if (!d_psd) glfer::scratch_free(rows, st);
   return rc;
 }
 

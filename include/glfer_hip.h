@@ -233,7 +233,8 @@ int glfer_hip_spectrogram_device(glfer_hip_plan *plan, const void *d_stream, siz
  * The moving average of many streams: glfer_hip_spectrogram_avg_batch_device and glfer_hip_avg_batch_device below; their
  * waterfalls: glfer_hip_waterfall_batch_device.
  * The harmonic F-test of many streams: glfer_hip_mtm_ftest_batch_device below.
- * Streams of unequal length: glfer_hip_spectrogram_ragged_device below (the rows entry only).
+ * Streams of unequal length: glfer_hip_spectrogram_ragged_device below; their moving average and waterfall:
+ * glfer_hip_avg_ragged_device, glfer_hip_spectrogram_avg_ragged_device and glfer_hip_waterfall_ragged_device.
  * Not covered: batched host / WAV / workers entries, the halfcomplex-spectrum output, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as they are. */
 int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams,
                                        size_t stream_pitch, size_t nsamples, size_t first_frame,
@@ -267,8 +268,10 @@ int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_strea
  * odd offset with integer samples; a stream of more than 2^31 - 1 frames; sizes that overflow size_t -- all checked before
  * anything on the device is touched; a hip_stream that is being captured into a graph (the per-stream tables are uploaded from
  * host memory that is gone when the call returns, which a captured copy would read at every replay).  nstreams == 0 or no frame at all: GLFER_OK, nothing written.
- * Limits: whole streams only (no first_frame / nframes sub-range), the rows entry only (no ragged average, waterfall or
- * F-test), device-resident samples only.  Asynchronous on hip_stream. */
+ * Limits: whole streams only (no first_frame / nframes sub-range), device-resident samples only.  The moving average and
+ * the waterfall of ragged rows: glfer_hip_avg_ragged_device, glfer_hip_spectrogram_avg_ragged_device and
+ * glfer_hip_waterfall_ragged_device below.  Not built: the ragged F-test and rows-and-F, the average taken inside the
+ * estimator launch for ragged calls, host / WAV ragged entries.  Asynchronous on hip_stream. */
 size_t glfer_hip_ragged_frames(const glfer_hip_plan *plan, size_t nstreams, const size_t *lengths, size_t *row_starts);
 int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *plan, const void *d_samples, size_t nstreams,
                                         const size_t *offsets, const size_t *lengths, float *d_psd,
@@ -628,10 +631,59 @@ int glfer_hip_waterfall_device(glfer_hip_display *disp, int avg_mode, int depth,
  * stay within 4 GiB per tile.  One upload, one download of the states and one synchronisation per call.
  * Argument rules are glfer_hip_waterfall_device's; disps NULL with nstreams > 0: GLFER_E_ARG; nstreams == 0 or
  * nframes == 0: GLFER_OK, nothing launched.  On any error no entry of disps is modified.
- * Not covered: per-stream options (palettes, scales), ragged batches, batched host / WAV / workers waterfalls, several GPUs. */
+ * Not covered: per-stream options (palettes, scales), batched host / WAV / workers waterfalls, several GPUs.  Streams of
+ * unequal length: glfer_hip_waterfall_ragged_device below. */
 int glfer_hip_waterfall_batch_device(glfer_hip_display *disps, size_t nstreams, int avg_mode, int depth, int minbin, int maxbin,
                                      int max0, const float *d_psd, size_t nframes, int bins, unsigned char *d_rgb, short *d_lev,
                                      float *d_stats, void *hip_stream);
+
+/* The moving average and the waterfall of RAGGED rows: streams of unequal length, packed the way
+ * glfer_hip_spectrogram_ragged_device writes them.  Stream b is rows [row_starts[b], row_starts[b + 1]).
+ *   row_starts : HOST, [nstreams + 1], non-decreasing, consumed before the call returns -- what glfer_hip_ragged_frames and
+ *                glfer_hip_spectrogram_ragged_device return
+ * The single-stream kernels choose their shape from the stream's own frame count -- the chunk a block walks (128 frames,
+ * halved down to 8 while there are fewer than 1024 chunks), and from it the fused or the two-pass form -- and a chunk restarts
+ * its sliding sums from a direct sum, which equals the recurrence only while the sums are exact: a stream's last bits depend
+ * on its OWN chunk length.  So the ragged kernels read a per-stream table (first row, frame count, the stream's own chunk
+ * length, its first block), built on the host per call and uploaded to stream-ordered scratch; the blocks of a launch are one
+ * flat list and a block finds its stream by bisection.  Streams that take the fused form and streams that take the two-pass
+ * (waterfall: staged) form are two classes, each with its own launch set and table: the launch count of a call does not
+ * depend on nstreams or on the lengths (save, staged, groups of streams whose averaged rows stay within 4 GiB).
+ * compute_floor, the plain pixel map and the fixed levels work per row: they run over the packed rows as one run.
+ * All three entries: nstreams == 0 or no rows at all: GLFER_OK, nothing written.  A decreasing row_starts, a NULL table, sizes
+ * that overflow: GLFER_E_ARG before the device is touched.  A hip_stream that is being captured into a graph is refused
+ * (GLFER_E_ARG): the tables come from host memory that is gone after the call.
+ *
+ * glfer_hip_avg_ragged_device: update_avg_* with the state empty at row 0 of each stream.  d_psd [rows][bins] (dense), d_avg
+ * [rows][n_out] doubles, d_ret [rows][4] doubles or NULL.  Stream b's outputs equal glfer_hip_avg_device over its rows alone,
+ * double for double.  Other arguments as glfer_hip_avg_device.
+ *
+ * glfer_hip_spectrogram_avg_ragged_device: the ragged rows (to d_psd, or to scratch when it is NULL), then the ragged average
+ * over them.  The contract is the TWO-LAUNCH route: stream b's outputs are bit for bit glfer_hip_spectrogram_device followed
+ * by glfer_hip_avg_device on that stream.  The average taken inside the estimator launch (glfer_hip_spectrogram_avg_device's
+ * route for the plain average over up to four frames) is not built for ragged calls, and where that route sums in another
+ * order (inexact sums only) the two entries differ in the last bits there.  The argument rules of both parents apply: HP-ARMA
+ * plans and plans with a row pitch are refused, n_out >= bins, even offsets for s16 / u8.  row_starts: optional, out.
+ *
+ * glfer_hip_waterfall_ragged_device: glfer_hip_waterfall_batch_device for packed rows.  d_psd [rows][pitch] (pitch =
+ * disps[0].psd_pitch, 0: bins), d_rgb [rows][bins][3], d_lev [rows][bins] or NULL, d_stats [rows][4] or NULL, all packed by
+ * row_starts.  disps[b] carries stream b's state in and out; the options must be the same in every entry.  Stream b's pixels,
+ * levbuf, statistics and returned state are byte for byte those of glfer_hip_waterfall_device over its rows with a copy of
+ * disps[b]; a stream without rows leaves its disps[b] untouched.  Each stream takes the route the single entry would take for
+ * its own length (the average inside the map, or staged: the ragged average into scratch, then the map);
+ * GLFER_WATERFALL_FUSED=0 forces the staged class for every stream.  Where any stream's own route would cut it into tiles (a
+ * stream longer than a tile; GLFER_WATERFALL_TILE below the longest stream) the call goes stream by stream through
+ * glfer_hip_waterfall_device -- still byte-equal, one launch set per stream.  Argument errors and option mismatches:
+ * GLFER_E_ARG, nothing launched, no entry of disps modified.  One download of the states and one synchronisation per call. */
+int glfer_hip_avg_ragged_device(int avg_mode, const float *d_psd, size_t nstreams, const size_t *row_starts, int bins, int n_out,
+                                int depth, int minbin, int maxbin, int max0, double *d_avg, double *d_ret, void *hip_stream);
+int glfer_hip_spectrogram_avg_ragged_device(glfer_hip_plan *plan, const void *d_samples, size_t nstreams, const size_t *offsets,
+                                            const size_t *lengths, int avg_mode, int depth, int minbin, int maxbin, int max0,
+                                            int n_out, float *d_psd, double *d_avg, double *d_ret, size_t *row_starts,
+                                            void *hip_stream);
+int glfer_hip_waterfall_ragged_device(glfer_hip_display *disps, size_t nstreams, int avg_mode, int depth, int minbin, int maxbin,
+                                      int max0, const float *d_psd, const size_t *row_starts, int bins, unsigned char *d_rgb,
+                                      short *d_lev, float *d_stats, void *hip_stream);
 
 /* The two halves of glfer_hip_waterfall_device for a waterfall whose columns live on several GPUs
  * (or are computed piece by piece).  The level tracking of main_window_draw (g_main.c:1111-1124) is
