@@ -27,43 +27,9 @@ static_assert(GLFER_FMT_F32 == GLFER_SAMPLES_F32 && GLFER_FMT_S16 == GLFER_SAMPL
 
 extern "C" hipError_t glfer_launch_hparma(const SpectroParams *sp, int n, int t, int ncol, const int *rot_sched, int rot_steps, int rot_width, const uint16_t *lagmap,
                                           const float2 *unit, hipStream_t st);
-extern "C" hipError_t glfer_launch_floor(const float *psd, size_t nframes, int bins, int pitch, int m, float *stats,
-                                         hipStream_t st);
 extern "C" hipError_t glfer_launch_avg(int mode, const float *psd, size_t nframes, int bins, int n_out,
                                        int depth, int minbin, int maxbin, int max0, double *avg,
                                        double *ret, hipStream_t st);
-extern "C" hipError_t glfer_launch_avg_batch(int mode, const float *psd, size_t nframes, int bins, int n_out, int depth, int minbin,
-                                             int maxbin, int max0, double *avg, double *ret, unsigned nb, long long psd_bs,
-                                             long long avg_bs, long long ret_bs, hipStream_t st);
-extern "C" int glfer_avgmap_applies(size_t walk, int bins, int depth, int minbin, int maxbin);
-extern "C" hipError_t glfer_launch_avgmap(int mode, const float *psd, size_t fbeg, size_t nframes, int bins, int depth,
-                                          int minbin, int maxbin, int max0, int scale_log, double thr255,
-                                          double one_m_thr, const float *levels, const unsigned char *colortab,
-                                          const double *log_thr, unsigned char *rgb, short *lev, hipStream_t st);
-extern "C" hipError_t glfer_launch_avgmap_batch(int mode, const float *psd, size_t fbeg, size_t nframes, int bins, int depth,
-                                                int minbin, int maxbin, int max0, int scale_log, double thr255, double one_m_thr,
-                                                const float *levels, const unsigned char *colortab, const double *log_thr,
-                                                unsigned char *rgb, short *lev, unsigned nb, long long psd_bs, long long lv_bs,
-                                                long long col_bs, hipStream_t st);
-extern "C" hipError_t glfer_launch_levels_batch(const float *stats, size_t nframes, int scale_log, float overlap, float *state,
-                                                long long stats_bs, long long levels_bs, float *levels, float *chunk_state,
-                                                unsigned nb, hipStream_t st);
-extern "C" hipError_t glfer_launch_map_batch(const float *psd, const double *avg, size_t nframes, int n, int psd_pitch, int scale_log,
-                                             double thr255, double one_m_thr, const float *levels, const unsigned char *colortab,
-                                             const double *log_thr, unsigned char *rgb, short *lev, unsigned nb, long long src_bs,
-                                             long long levels_bs, long long rgb_bs, long long lev_bs, hipStream_t st);
-extern "C" hipError_t glfer_launch_avg_ragged(int mode, const float *psd, const glfer::RaggedColsEntry *streams, size_t n, int bins,
-                                              int n_out, int depth, int minbin, int maxbin, int max0, double *avg, double *ret,
-                                              hipStream_t st);
-extern "C" hipError_t glfer_launch_avgmap_ragged(int mode, const float *psd, const glfer::RaggedColsEntry *streams, size_t n, int bins,
-                                                 int depth, int minbin, int maxbin, int max0, int scale_log, double thr255,
-                                                 double one_m_thr, const float *levels, const unsigned char *colortab,
-                                                 const double *log_thr, unsigned char *rgb, short *lev, hipStream_t st);
-extern "C" hipError_t glfer_launch_levels_ragged(const float *stats, const glfer::RaggedColsEntry *streams, size_t n, int scale_log,
-                                                 float overlap, float *state, float *levels, float *chunk_state, hipStream_t st);
-extern "C" hipError_t glfer_launch_map_ragged(const double *avg, const glfer::RaggedColsEntry *streams, size_t n, int bins, int scale_log,
-                                              double thr255, double one_m_thr, const float *levels, const unsigned char *colortab,
-                                              const double *log_thr, unsigned char *rgb, short *lev, hipStream_t st);
 extern "C" hipError_t glfer_launch_avg_cum(const float *psd, size_t nframes, int bins, int n_out, int depth,
                                            int minbin, int maxbin, double *cum, hipStream_t st);
 extern "C" hipError_t glfer_launch_lmp(const float *rows, long long row0, long long first, size_t nframes, int bins,
@@ -103,6 +69,11 @@ int device_of(const void *d_ptr) {
     return -1;
   }
   return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged ? at.device : -1;
+}
+int data_device(const void *d_ptr) {
+  int dev = device_of(d_ptr);
+  if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+  return dev;
 }
 // ---- scratch.  Three sources, by size:
 //   * under 1 MiB (statistics, tables, level states): a stream-ordered pool of their own, so that
@@ -373,15 +344,9 @@ hipError_t allow_dynamic_lds(const void *kernel, size_t bytes) {
 }
 
 }  // namespace glfer
+using glfer::data_device;
 using glfer::DeviceGuard;
 using glfer::hip_fail;
-
-// the device the data of a plan-less entry lives on: the pointer's, else the current one
-static int data_device(const void *d_ptr) {
-  int dev = glfer::device_of(d_ptr);
-  if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-  return dev;
-}
 
 static bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
 
@@ -452,684 +417,6 @@ int glfer_hip_palette(int palette, unsigned char colortab[768]) {
   if (!colortab) return GLFER_E_ARG;
   glfer::make_palette(palette, colortab);
   return GLFER_OK;
-}
-
-}  // extern "C"
-
-// update_avg_* inside the mapping (avg_fused_kernel<.., MAP>): the PSD batch the columns belong to,
-// their first row in it, and update_avg's arguments
-struct MapAverages {
-  int mode, depth, minbin, maxbin, max0;
-  const float *d_batch;
-  size_t first;
-};
-
-// The mapping part of main_window_draw for `nframes` columns: level tracking, then the pixel map of the
-// PSD rows, of averaged rows, or (fused) of the averages taken on the way.
-// d_levels_in: the columns' levels already known (the walk was done elsewhere -- over ALL columns of a
-// waterfall whose rows are spread over several GPUs, glfer_hip_levels_host): no walk, d_stats unused,
-// the carried state in *d untouched.
-static int display_columns(glfer_hip_display *d, const float *d_psd, const double *d_avg, const MapAverages *fused,
-                           const float *d_stats, size_t nframes, int bins, unsigned char *d_rgb, short *d_lev,
-                           float *d_levels, void *hip_stream, const float *d_levels_in = nullptr, int psd_pitch = 0) {
-  if (!d || (!d_stats && !d_levels_in) || !d_rgb || bins < 1) return GLFER_E_ARG;
-  if (psd_pitch == 0) psd_pitch = bins;                  // floats from one row of d_psd to the next (cfg.psd_pitch)
-  if (psd_pitch < bins || (fused && psd_pitch != bins)) return GLFER_E_ARG;
-  if ((d_psd != nullptr) + (d_avg != nullptr) + (fused != nullptr) != 1) return GLFER_E_ARG;
-  if (d->scale_type < GLFER_SCALE_LIN || d->scale_type > GLFER_SCALE_LOG_MAX0) return GLFER_E_ARG;
-  if (nframes == 0) return GLFER_OK;
-  hipStream_t st = (hipStream_t)hip_stream;
-  DeviceGuard guard(data_device(d_rgb));
-  HIP_TRY(guard.error());
-  const int scale_log = d->scale_type == GLFER_SCALE_LOG || d->scale_type == GLFER_SCALE_LOG_MAX0;
-
-  // one stream-ordered allocation: the palette, the table of the dB steps, the levels rows (when
-  // the caller does not want them) and the chunk states of the autoscale walk
-  const size_t lev_floats = (d_levels || d_levels_in) ? 0 : nframes * 4;
-  const size_t st_floats = (d->autoscale && !d_levels_in) ? glfer_levels_scratch_floats(nframes) : 0;
-  const size_t thr_bytes = (2 * glfer::kLogThrK + 1) * sizeof(double);
-  unsigned char *scratch = nullptr;
-  HIP_TRY(glfer::scratch_malloc((void **)&scratch, 768 + thr_bytes + (lev_floats + st_floats) * sizeof(float), st));
-  unsigned char *d_tab = scratch;
-  double *d_thr = reinterpret_cast<double *>(scratch + 768);
-  float *fs = reinterpret_cast<float *>(scratch + 768 + thr_bytes);
-  float *levels = d_levels_in ? const_cast<float *>(d_levels_in) : (d_levels ? d_levels : fs);
-  float *chunk_state = st_floats ? fs + lev_floats : nullptr;
-  int rc = GLFER_OK;
-  auto fail = [&](hipError_t err) { rc = hip_fail(err, "glfer_hip_display_device"); };
-  unsigned char tab[768];
-  glfer::make_palette(d->palette, tab);
-  // pageable source: hipMemcpyAsync stages it before returning, so `tab` may go out of scope
-  hipError_t e = hipMemcpyAsync(d_tab, tab, 768, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_thr, glfer::log_thresholds(), thr_bytes, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) fail(e);
-
-  if (rc == GLFER_OK && !d_levels_in) {
-    if (d->autoscale) {
-      e = glfer_launch_levels(d_stats, nframes, scale_log, 1, d->first_buffer, d->overlap, d->display_max_lvl,
-                              d->display_min_lvl, levels, chunk_state, st);
-    } else {                                                                   // g_main.c:1125-1139
-      float mx = pow(10.0, d->max_level_db / 10.0);
-      float mn = pow(10.0, d->min_level_db / 10.0);
-      mn = (mx > mn ? mn : mx / 10.0);
-      const float dmax = scale_log ? (float)(10.0 * log10(mx)) : mx;
-      const float dmin = scale_log ? (float)(10.0 * log10(mn)) : mn;
-      e = glfer_launch_levels_fixed(nframes, dmax, dmin, mx, mn, levels, st);
-    }
-    if (e != hipSuccess) fail(e);
-  }
-  if (rc == GLFER_OK) {
-    const float thr_level = d->thr_level / 100.0;                              // g_main.c:1099
-    if (fused)
-      e = glfer_launch_avgmap(fused->mode, fused->d_batch, fused->first, fused->first + nframes, bins, fused->depth,
-                              fused->minbin, fused->maxbin, fused->max0, scale_log, 255.0 * thr_level,
-                              1.0 - thr_level, levels, d_tab, d_thr, d_rgb, d_lev, st);
-    else
-      e = glfer_launch_map(d_psd, d_avg, nframes, bins, psd_pitch, scale_log, 255.0 * thr_level, 1.0 - thr_level, levels,
-                           d_tab, d_thr, d_rgb, d_lev, st);
-    if (e != hipSuccess) fail(e);
-  }
-  float last[4] = {0, 0, 0, 0};
-  if (rc == GLFER_OK && !d_levels_in) {
-    e = hipMemcpyAsync(last, levels + (nframes - 1) * 4, sizeof last, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) fail(e);
-  }
-  glfer::scratch_free(scratch, st);
-  e = hipStreamSynchronize(st);              // the carried state comes back to the host
-  if (e != hipSuccess && rc == GLFER_OK) fail(e);
-  if (rc == GLFER_OK && !d_levels_in) {
-    d->display_max_lvl = last[2];
-    d->display_min_lvl = last[3];
-    if (d->autoscale) d->first_buffer = 0;                                     // g_main.c:1120
-  }
-  return rc;
-}
-
-extern "C" {
-
-int glfer_hip_display_device(glfer_hip_display *d, const float *d_psd, const double *d_avg, const float *d_stats,
-                             size_t nframes, int bins, unsigned char *d_rgb, short *d_lev, float *d_levels,
-                             void *hip_stream) {
-  if (!d || (d_psd == nullptr) == (d_avg == nullptr)) return GLFER_E_ARG;
-  return display_columns(d, d_psd, d_avg, nullptr, d_stats, nframes, bins, d_rgb, d_lev, d_levels, hip_stream, nullptr, d->psd_pitch);
-}
-
-// compute_floor + update_avg_* + the display mapping of main_window_draw (g_main.c:1109-1236) for a
-// batch of PSD rows in one call.  The level tracking is a chain over the columns (g_main.c:1122-1123)
-// fed by every column's floor statistics, so a row is read twice -- once for its statistics (and its
-// moving sums), once to be mapped -- and the chain walk costs ~0.1 us per column of LATENCY however
-// few columns it is given (its chunks warm up over the 4096 columns before them, display.hip).
-// Cache-sized tiles (rows still in the 256 MiB Infinity Cache when the map reads them) were
-// measured: 15 M rows/s against 117 M stage by stage over the whole batch
-// (profiles/r02_aux_sweep.txt) -- the chain's latency per tile swamps the saved HBM read.  So the
-// stages run over tiles that only bound the scratch (averaged rows: 8 B/bin, 4 GiB per tile).
-}  // extern "C"
-
-// The route of a waterfall over `nframes` rows (glfer_hip_waterfall_device, and every stream of
-// glfer_hip_waterfall_batch_device): averages inside the mapping kernel (*fused) or staged, and the rows per tile.
-// Tiles only bound the scratch: the level walk costs its ~0.13 ms of latency per display call
-// however few columns it gets, so fewer, larger tiles are faster (two 65536-row tiles: 116 M rows/s
-// against 147 M stage by stage).  The averages are taken inside the mapping kernel where that form
-// applies (no averaged rows in memory at all: GLFER_WATERFALL_FUSED=0 forces the staged form, for
-// A/B runs and tests); staged, averaged rows are 8 B per bin: 4 GiB of them per tile.  Otherwise
-// only the 16 B of statistics per row are scratch.
-static void waterfall_route(int avg_mode, int depth, int minbin, int maxbin, int bins, int pitch, size_t nframes, bool *fused_out,
-                            size_t *tile_out) {
-  const bool averaging = avg_mode != 0;
-  bool fused = averaging && pitch == bins;               // (the average-in-the-map kernel walks dense rows)
-  if (const char *e = getenv("GLFER_WATERFALL_FUSED")) fused = fused && atoi(e) != 0;
-  size_t tile = (averaging && !fused) ? std::max<size_t>(16384, ((size_t)4 << 30) / ((size_t)bins * sizeof(double))) : (size_t)1 << 22;
-  if (const char *e = getenv("GLFER_WATERFALL_TILE")) {    // rows per tile, for tests of the tile seams and for tuning
-    const long v = atol(e);
-    if (v >= 64) tile = (size_t)v;
-  }
-  tile = std::min(tile, nframes);
-  tile = (nframes + (nframes + tile - 1) / tile - 1) / ((nframes + tile - 1) / tile);   // equal tiles: no short last one
-  // the form's chunking depends on the number of rows it walks, and the last tile may be a few rows
-  // shorter than the others: the fused form is taken only if it applies to BOTH lengths
-  const size_t last_tile = nframes - (nframes - 1) / tile * tile;
-  if (fused) fused = glfer_avgmap_applies(tile, bins, depth, minbin, maxbin) != 0 &&
-                     glfer_avgmap_applies(last_tile, bins, depth, minbin, maxbin) != 0;
-  *fused_out = fused;
-  *tile_out = tile;
-}
-
-// Rows [row0, row0 + nframes) of the batch d_psd.  row0 > 0 / d_levels_in: the second phase of a
-// waterfall whose columns are spread over several GPUs (glfer_hip_waterfall_map_device) -- the moving
-// sums of the first rows reach back into the batch's rows before row0, the levels are given.
-static int waterfall_columns(glfer_hip_display *d, int avg_mode, int depth, int minbin, int maxbin, int max0,
-                             const float *d_batch, size_t row0, size_t nframes, int bins, unsigned char *d_rgb, short *d_lev,
-                             float *d_stats, void *hip_stream, const float *d_levels_in, int pitch = 0) {
-  if (pitch == 0) pitch = bins;                          // floats from one PSD row to the next (cfg.psd_pitch)
-  const float *d_psd = d_batch ? d_batch + row0 * (size_t)pitch : nullptr;
-  if (!d || !d_psd || !d_rgb || bins < 1 || bins > 32769 || pitch < bins) return GLFER_E_ARG;
-  const bool averaging = avg_mode != 0;
-  if (averaging && (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME || depth < 1 || minbin < 0 ||
-                    maxbin <= minbin || maxbin > bins))
-    return GLFER_E_ARG;
-  if (nframes == 0) return GLFER_OK;
-  hipStream_t st = (hipStream_t)hip_stream;
-  DeviceGuard guard(data_device(d_psd));
-  HIP_TRY(guard.error());
-  bool fused = false;
-  size_t tile = 0;
-  waterfall_route(avg_mode, depth, minbin, maxbin, bins, pitch, nframes, &fused, &tile);
-  const size_t back = averaging ? (size_t)depth : 0;       // rows re-read in front of a tile to restart the sliding sums
-  float *stats = d_stats;
-  double *avg = nullptr, *ret = nullptr;
-  if (!stats && !d_levels_in) HIP_TRY(glfer::scratch_malloc((void **)&stats, tile * 4 * sizeof(float), st));
-  int rc = GLFER_OK;
-  if (averaging && !fused) {
-    hipError_t e = glfer::scratch_malloc((void **)&avg, (tile + back) * (size_t)bins * sizeof(double), st);
-    if (e == hipSuccess) e = glfer::scratch_malloc((void **)&ret, (tile + back) * 4 * sizeof(double), st);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMallocAsync(waterfall tile)");
-  }
-  for (size_t f0 = 0; rc == GLFER_OK && f0 < nframes; f0 += tile) {
-    const size_t nf = std::min(tile, nframes - f0);
-    float *tstats = d_stats ? d_stats + f0 * 4 : stats;
-    const float *tlevels = d_levels_in ? d_levels_in + f0 * 4 : nullptr;
-    unsigned char *trgb = d_rgb + f0 * (size_t)bins * 3;
-    short *tlev = d_lev ? d_lev + f0 * (size_t)bins : nullptr;
-    if (tstats) rc = glfer_hip_floor_device_pitched(d_psd + f0 * (size_t)pitch, nf, bins, pitch, tstats, st);
-    if (rc != GLFER_OK) break;
-    if (fused) {
-      // the sliding sums of the tile's first rows reach back into the rows before it by themselves
-      const MapAverages ma{avg_mode, depth, minbin, maxbin, max0 ? 1 : 0, d_batch, row0 + f0};
-      rc = display_columns(d, nullptr, nullptr, &ma, tstats, nf, bins, trgb, tlev, nullptr, st, tlevels);
-      continue;
-    }
-    const double *src_avg = nullptr;
-    if (averaging) {
-      // the sums of the tile's first rows reach `depth` rows back: run from there (from an empty
-      // state at row 0 of the batch, as update_avg does after alloc_avg) and use the tile's rows
-      const size_t lead = std::min(back, row0 + f0);
-      // (update_avg's `bins` is its rows' stride; the band is minbin..maxbin, the averaged rows are dense)
-      rc = glfer_hip_avg_device(avg_mode, d_batch + (row0 + f0 - lead) * (size_t)pitch, nf + lead, pitch, bins, depth, minbin, maxbin, max0,
-                                avg, ret, st);
-      src_avg = avg + lead * (size_t)bins;
-    }
-    if (rc == GLFER_OK)
-      rc = display_columns(d, averaging ? nullptr : d_psd + f0 * (size_t)pitch, src_avg, nullptr, tstats, nf, bins, trgb, tlev,
-                           nullptr, st, tlevels, pitch);
-  }
-  if (avg) glfer::scratch_free(avg, st);
-  if (ret) glfer::scratch_free(ret, st);
-  if (!d_stats && stats) glfer::scratch_free(stats, st);
-  return rc;
-}
-
-extern "C" {
-
-int glfer_hip_waterfall_device(glfer_hip_display *d, int avg_mode, int depth, int minbin, int maxbin, int max0,
-                               const float *d_psd, size_t nframes, int bins, unsigned char *d_rgb, short *d_lev,
-                               float *d_stats, void *hip_stream) {
-  return waterfall_columns(d, avg_mode, depth, minbin, maxbin, max0, d_psd, 0, nframes, bins, d_rgb, d_lev, d_stats, hip_stream,
-                           nullptr, d ? d->psd_pitch : 0);
-}
-
-// The two halves of glfer_hip_waterfall_device for columns that live on several GPUs.  The level
-// tracking (g_main.c:1111-1124) is ONE chain over all columns, fed by 16 bytes of floor statistics
-// per column; everything else is per column.  So: every GPU computes its rows and their statistics,
-// the statistics meet on the host, ONE walk over them (here: on `device`, the walk of
-// glfer_hip_display_device) gives every column its levels, and every GPU maps its own rows with its
-// slice of the levels.  Nothing but 16 + 16 bytes per column crosses between GPUs, through the host.
-int glfer_hip_levels_host(glfer_hip_display *d, const float *h_stats, size_t nframes, float *h_levels, int device) {
-  if (!d || !h_stats || !h_levels) return GLFER_E_ARG;
-  if (d->scale_type < GLFER_SCALE_LIN || d->scale_type > GLFER_SCALE_LOG_MAX0) return GLFER_E_ARG;
-  if (nframes == 0) return GLFER_OK;
-  DeviceGuard guard(device);
-  HIP_TRY(guard.error());
-  const int scale_log = d->scale_type == GLFER_SCALE_LOG || d->scale_type == GLFER_SCALE_LOG_MAX0;
-  const size_t st_floats = d->autoscale ? glfer_levels_scratch_floats(nframes) : 0;
-  float *buf = nullptr;
-  HIP_TRY(glfer::scratch_malloc((void **)&buf, (nframes * 8 + st_floats) * sizeof(float), nullptr));
-  float *d_stats = buf, *levels = buf + nframes * 4, *chunk_state = st_floats ? buf + nframes * 8 : nullptr;
-  int rc = GLFER_OK;
-  hipError_t e = hipMemcpyAsync(d_stats, h_stats, nframes * 4 * sizeof(float), hipMemcpyHostToDevice, nullptr);
-  if (e == hipSuccess) {
-    if (d->autoscale) {
-      e = glfer_launch_levels(d_stats, nframes, scale_log, 1, d->first_buffer, d->overlap, d->display_max_lvl,
-                              d->display_min_lvl, levels, chunk_state, nullptr);
-    } else {                                                                   // g_main.c:1125-1139
-      float mx = pow(10.0, d->max_level_db / 10.0);
-      float mn = pow(10.0, d->min_level_db / 10.0);
-      mn = (mx > mn ? mn : mx / 10.0);
-      const float dmax = scale_log ? (float)(10.0 * log10(mx)) : mx;
-      const float dmin = scale_log ? (float)(10.0 * log10(mn)) : mn;
-      e = glfer_launch_levels_fixed(nframes, dmax, dmin, mx, mn, levels, nullptr);
-    }
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h_levels, levels, nframes * 4 * sizeof(float), hipMemcpyDeviceToHost, nullptr);
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  glfer::scratch_free(buf, nullptr);
-  if (e != hipSuccess) rc = hip_fail(e, "glfer_hip_levels_host");
-  if (rc == GLFER_OK) {
-    d->display_max_lvl = h_levels[(nframes - 1) * 4 + 2];
-    d->display_min_lvl = h_levels[(nframes - 1) * 4 + 3];
-    if (d->autoscale) d->first_buffer = 0;                                     // g_main.c:1120
-  }
-  return rc;
-}
-
-int glfer_hip_waterfall_map_device(const glfer_hip_display *d, int avg_mode, int depth, int minbin, int maxbin, int max0,
-                                   const float *d_batch, size_t first, size_t nframes, int bins, const float *d_levels,
-                                   unsigned char *d_rgb, short *d_lev, void *hip_stream) {
-  if (!d || !d_levels) return GLFER_E_ARG;
-  glfer_hip_display copy = *d;               // the carried state is not touched: the walk was glfer_hip_levels_host's
-  return waterfall_columns(&copy, avg_mode, depth, minbin, maxbin, max0, d_batch, first, nframes, bins, d_rgb, d_lev, nullptr,
-                           hip_stream, d_levels, d->psd_pitch);
-}
-
-// glfer_hip_waterfall_device over many streams of one display plan (glfer_hip.h).  The route -- fused or staged average, the
-// frame tiles, the avgmap shape -- is that entry's for ONE stream's frames (waterfall_route); every launch it leads to covers
-// the batch: the floor statistics of all rows at once (the rows of all streams are one run), then per tile the autoscale walk
-// (blockIdx.y the stream, its carried state in a device table that stays there from tile to tile), and the map with a stream
-// dimension (fused: avg_fused_kernel<.., MAP, .., BAT>; staged: glfer_launch_avg_batch, then the map of the averaged rows).
-// One upload (palette, dB table, states), one download of the states and one synchronisation per call.
-static bool same_display_options(const glfer_hip_display &a, const glfer_hip_display &b) {
-  return a.scale_type == b.scale_type && a.autoscale == b.autoscale && a.overlap == b.overlap && a.max_level_db == b.max_level_db &&
-         a.min_level_db == b.min_level_db && a.thr_level == b.thr_level && a.palette == b.palette && a.psd_pitch == b.psd_pitch;
-}
-
-int glfer_hip_waterfall_batch_device(glfer_hip_display *disps, size_t nstreams, int avg_mode, int depth, int minbin, int maxbin,
-                                     int max0, const float *d_psd, size_t nframes, int bins, unsigned char *d_rgb, short *d_lev,
-                                     float *d_stats, void *hip_stream) {
-  if (nstreams == 0) return GLFER_OK;
-  if (!disps) return GLFER_E_ARG;
-  for (size_t b = 1; b < nstreams; b++)                  // one plan, many streams
-    if (!same_display_options(disps[0], disps[b])) return GLFER_E_ARG;
-  const glfer_hip_display &d0 = disps[0];
-  const int pitch = d0.psd_pitch == 0 ? bins : d0.psd_pitch;
-  if (bins < 1 || bins > 32769 || pitch < bins) return GLFER_E_ARG;     // (waterfall_columns' rules)
-  const bool averaging = avg_mode != 0;
-  if (averaging && (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME || depth < 1 || minbin < 0 ||
-                    maxbin <= minbin || maxbin > bins))
-    return GLFER_E_ARG;
-  if (nframes == 0) return GLFER_OK;
-  if (!d_psd || !d_rgb) return GLFER_E_ARG;
-  if (d0.scale_type < GLFER_SCALE_LIN || d0.scale_type > GLFER_SCALE_LOG_MAX0) return GLFER_E_ARG;   // (display_columns')
-  if (nframes > (SIZE_MAX / sizeof(double) / (size_t)pitch) / nstreams) return GLFER_E_ARG;
-  hipStream_t st = (hipStream_t)hip_stream;
-  DeviceGuard guard(data_device(d_psd));
-  HIP_TRY(guard.error());
-  bool fused = false;
-  size_t tile = 0;
-  waterfall_route(avg_mode, depth, minbin, maxbin, bins, pitch, nframes, &fused, &tile);
-  const bool staged = averaging && !fused;
-  const bool autoscale = d0.autoscale != 0;
-  const int scale_log = d0.scale_type == GLFER_SCALE_LOG || d0.scale_type == GLFER_SCALE_LOG_MAX0;
-  const size_t back = averaging ? (size_t)depth : 0;
-  const size_t bins_z = (size_t)bins, rows_bs = nframes * (size_t)pitch, cols = nframes * bins_z;
-  const size_t chunk = 65535;                            // streams per launch: the grid's y limit
-  // staged: streams per group, the averaged rows of a group within the single-stream entry's 4 GiB per tile
-  size_t group = chunk;
-  if (staged) group = std::max<size_t>(1, std::min(group, ((size_t)4 << 30) / ((tile + back) * bins_z * sizeof(double))));
-
-  // one small allocation: palette, dB table, the carried states [nstreams][3]; one upload
-  const size_t thr_bytes = (2 * glfer::kLogThrK + 1) * sizeof(double);
-  const size_t small_bytes = 768 + thr_bytes + nstreams * 3 * sizeof(float);
-  std::vector<unsigned char> host(small_bytes);
-  glfer::make_palette(d0.palette, host.data());
-  memcpy(host.data() + 768, glfer::log_thresholds(), thr_bytes);
-  float *h_state = reinterpret_cast<float *>(host.data() + 768 + thr_bytes);
-  for (size_t b = 0; b < nstreams; b++) {
-    h_state[b * 3 + 0] = disps[b].first_buffer != 0 ? 1.0f : 0.0f;
-    h_state[b * 3 + 1] = disps[b].display_max_lvl;
-    h_state[b * 3 + 2] = disps[b].display_min_lvl;
-  }
-  unsigned char *small = nullptr;
-  HIP_TRY(glfer::scratch_malloc((void **)&small, small_bytes, st));
-  const unsigned char *d_tab = small;
-  const double *d_thr = reinterpret_cast<const double *>(small + 768);
-  float *d_state = reinterpret_cast<float *>(small + 768 + thr_bytes);
-  int rc = GLFER_OK;
-  auto fail = [&](hipError_t err, const char *what) {
-    if (rc == GLFER_OK) rc = hip_fail(err, what);
-  };
-  // pageable source: hipMemcpyAsync stages it before returning
-  hipError_t e = hipMemcpyAsync(small, host.data(), small_bytes, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) fail(e, "glfer_hip_waterfall_batch_device (upload)");
-
-  // scratch: statistics of all rows (without d_stats), a tile's levels and chunk states, a group's averaged rows (staged)
-  const size_t st_floats = autoscale ? glfer_levels_scratch_floats(tile) : 0;
-  float *stats = d_stats, *levels = nullptr;
-  double *avg = nullptr, *ret = nullptr;
-  if (rc == GLFER_OK && !d_stats) {
-    e = glfer::scratch_malloc((void **)&stats, nstreams * nframes * 4 * sizeof(float), st);
-    if (e != hipSuccess) { stats = nullptr; fail(e, "scratch (waterfall statistics, batch)"); }
-  }
-  if (rc == GLFER_OK) {
-    e = glfer::scratch_malloc((void **)&levels, nstreams * (tile * 4 + st_floats) * sizeof(float), st);
-    if (e != hipSuccess) { levels = nullptr; fail(e, "scratch (waterfall levels, batch)"); }
-  }
-  float *chunk_state = levels ? levels + nstreams * tile * 4 : nullptr;
-  if (rc == GLFER_OK && staged) {
-    const size_t gb = std::min(group, nstreams);
-    e = glfer::scratch_malloc((void **)&avg, gb * (tile + back) * bins_z * sizeof(double), st);
-    if (e == hipSuccess) e = glfer::scratch_malloc((void **)&ret, gb * (tile + back) * 4 * sizeof(double), st);
-    if (e != hipSuccess) fail(e, "hipMallocAsync(waterfall tile, batch)");
-  }
-
-  // compute_floor of every row: the streams' rows are one run of nstreams x nframes rows (pieces: the grid's x limit)
-  const int m = bins - (int)(bins * 0.95);                           // fft.c:271 (glfer_hip_floor_device_pitched)
-  const size_t all_rows = nstreams * nframes, piece = (size_t)1 << 22;
-  for (size_t r0 = 0; rc == GLFER_OK && r0 < all_rows; r0 += piece) {
-    e = glfer_launch_floor(d_psd + r0 * (size_t)pitch, std::min(piece, all_rows - r0), bins, pitch, m, stats + r0 * 4, st);
-    if (e != hipSuccess) fail(e, "compute_floor launch (batch)");
-  }
-
-  const float thr_level = d0.thr_level / 100.0;                                // g_main.c:1099
-  const double thr255 = 255.0 * thr_level, one_m_thr = 1.0 - thr_level;
-  float mx = 0.0f, mn = 0.0f;
-  if (!autoscale) {                                                            // g_main.c:1125-1139
-    mx = pow(10.0, d0.max_level_db / 10.0);
-    mn = pow(10.0, d0.min_level_db / 10.0);
-    mn = (mx > mn ? mn : mx / 10.0);
-  }
-  for (size_t f0 = 0; rc == GLFER_OK && f0 < nframes; f0 += tile) {
-    const size_t nf = std::min(tile, nframes - f0);
-    // the tile's levels, [nstreams][nf][4]
-    if (autoscale) {
-      for (size_t c0 = 0; rc == GLFER_OK && c0 < nstreams; c0 += chunk) {
-        const unsigned nb = (unsigned)std::min(nstreams - c0, chunk);
-        e = glfer_launch_levels_batch(stats + (c0 * nframes + f0) * 4, nf, scale_log, d0.overlap, d_state + c0 * 3,
-                                      (long long)(nframes * 4), (long long)(nf * 4), levels + c0 * nf * 4,
-                                      chunk_state + c0 * glfer_levels_scratch_floats(nf), nb, st);
-        if (e != hipSuccess) fail(e, "level tracking launch (batch)");
-      }
-    } else {
-      const float dmax = scale_log ? (float)(10.0 * log10(mx)) : mx;
-      const float dmin = scale_log ? (float)(10.0 * log10(mn)) : mn;
-      e = glfer_launch_levels_fixed(nstreams * nf, dmax, dmin, mx, mn, levels, st);
-      if (e != hipSuccess) fail(e, "levels launch (batch)");
-    }
-    if (rc != GLFER_OK) break;
-    if (fused) {
-      // the sliding sums of the tile's first rows reach back into the stream's rows before it by themselves
-      for (size_t c0 = 0; rc == GLFER_OK && c0 < nstreams; c0 += chunk) {
-        const unsigned nb = (unsigned)std::min(nstreams - c0, chunk);
-        e = glfer_launch_avgmap_batch(avg_mode, d_psd + c0 * rows_bs, f0, f0 + nf, bins, depth, minbin, maxbin, max0 ? 1 : 0, scale_log,
-                                      thr255, one_m_thr, levels + c0 * nf * 4, d_tab, d_thr, d_rgb + (c0 * cols + f0 * bins_z) * 3,
-                                      d_lev ? d_lev + c0 * cols + f0 * bins_z : nullptr, nb, (long long)rows_bs, (long long)nf,
-                                      (long long)nframes, st);
-        if (e != hipSuccess) fail(e, "average-and-map launch (batch)");
-      }
-      continue;
-    }
-    if (!averaging) {
-      for (size_t c0 = 0; rc == GLFER_OK && c0 < nstreams; c0 += chunk) {
-        const unsigned nb = (unsigned)std::min(nstreams - c0, chunk);
-        e = glfer_launch_map_batch(d_psd + c0 * rows_bs + f0 * (size_t)pitch, nullptr, nf, bins, pitch, scale_log, thr255, one_m_thr,
-                                   levels + c0 * nf * 4, d_tab, d_thr, d_rgb + (c0 * cols + f0 * bins_z) * 3,
-                                   d_lev ? d_lev + c0 * cols + f0 * bins_z : nullptr, nb, (long long)rows_bs, (long long)(nf * 4),
-                                   (long long)(cols * 3), (long long)cols, st);
-        if (e != hipSuccess) fail(e, "map launch (batch)");
-      }
-      continue;
-    }
-    // staged: the sums of the tile's first rows reach `depth` rows back -- run from there (from an empty state at the stream's
-    // row 0, as update_avg does after alloc_avg) and map the tile's rows
-    const size_t lead = std::min(back, f0), arows = nf + lead;
-    for (size_t c0 = 0; rc == GLFER_OK && c0 < nstreams; c0 += group) {
-      const unsigned nb = (unsigned)std::min(nstreams - c0, group);
-      e = glfer_launch_avg_batch(avg_mode, d_psd + c0 * rows_bs + (f0 - lead) * (size_t)pitch, arows, pitch, bins, depth, minbin, maxbin,
-                                 max0 ? 1 : 0, avg, ret, nb, (long long)rows_bs, (long long)(arows * bins_z), (long long)(arows * 4), st);
-      if (e != hipSuccess) fail(e, "update_avg launch (waterfall, batch)");
-      if (rc == GLFER_OK) {
-        e = glfer_launch_map_batch(nullptr, avg + lead * bins_z, nf, bins, bins, scale_log, thr255, one_m_thr, levels + c0 * nf * 4,
-                                   d_tab, d_thr, d_rgb + (c0 * cols + f0 * bins_z) * 3, d_lev ? d_lev + c0 * cols + f0 * bins_z : nullptr,
-                                   nb, (long long)(arows * bins_z), (long long)(nf * 4), (long long)(cols * 3), (long long)cols, st);
-        if (e != hipSuccess) fail(e, "map launch (waterfall, batch)");
-      }
-    }
-  }
-  std::vector<float> back_state(autoscale ? nstreams * 3 : 0);
-  if (rc == GLFER_OK && autoscale) {
-    e = hipMemcpyAsync(back_state.data(), d_state, nstreams * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) fail(e, "glfer_hip_waterfall_batch_device (state download)");
-  }
-  if (avg) glfer::scratch_free(avg, st);
-  if (ret) glfer::scratch_free(ret, st);
-  if (levels) glfer::scratch_free(levels, st);
-  if (!d_stats && stats) glfer::scratch_free(stats, st);
-  glfer::scratch_free(small, st);
-  e = hipStreamSynchronize(st);              // the carried states come back to the host
-  if (e != hipSuccess) fail(e, "glfer_hip_waterfall_batch_device");
-  if (rc == GLFER_OK) {
-    for (size_t b = 0; b < nstreams; b++) {
-      if (autoscale) {
-        disps[b].display_max_lvl = back_state[b * 3 + 1];
-        disps[b].display_min_lvl = back_state[b * 3 + 2];
-        disps[b].first_buffer = 0;                                             // g_main.c:1120
-      } else {
-        disps[b].display_max_lvl = mx;
-        disps[b].display_min_lvl = mn;
-      }
-    }
-  }
-  return rc;
-}
-
-}  // extern "C"
-
-// ---- ragged rows: the per-column stages over streams of unequal length (glfer_hip.h)
-// true where `st` is being captured into a graph: the per-stream tables are uploaded from host memory that is gone when the call
-// returns, which a captured copy would read at every replay
-static bool stream_is_capturing(hipStream_t st) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (st != hipStreamPerThread && hipStreamIsCapturing(st, &cs) == hipSuccess) return cs != hipStreamCaptureStatusNone;
-  (void)hipGetLastError();
-  return false;
-}
-// row_starts of nstreams streams: non-decreasing, at most 2^31 - 1 rows a stream
-static bool ragged_rows_ok(const size_t *row_starts, size_t nstreams) {
-  if (nstreams > 0x7fffffffu) return false;
-  for (size_t b = 0; b < nstreams; b++)
-    if (row_starts[b + 1] < row_starts[b] || row_starts[b + 1] - row_starts[b] > 0x7fffffffu) return false;
-  return true;
-}
-// the streams that have rows, as the ragged launchers take them (out0 = row0: outputs packed as the rows are)
-static std::vector<glfer::RaggedColsEntry> ragged_streams(const size_t *row_starts, size_t nstreams) {
-  std::vector<glfer::RaggedColsEntry> s;
-  for (size_t b = 0; b < nstreams; b++)
-    if (row_starts[b + 1] > row_starts[b])
-      s.push_back(glfer::RaggedColsEntry{(long long)row_starts[b], (long long)row_starts[b], (long long)(row_starts[b + 1] - row_starts[b]), 0, 0, (int)b});
-  return s;
-}
-
-extern "C" {
-
-// glfer_hip_waterfall_batch_device for packed rows of streams of unequal length (glfer_hip.h).  Every stream takes the route
-// glfer_hip_waterfall_device takes for its own frame count (waterfall_route): the per-row stages -- compute_floor, the plain
-// map, the fixed levels -- run over the packed rows as one run; the autoscale walk, the average-and-map kernel and the staged
-// average read a per-stream table (ragged_cols.hpp).  Streams whose route is the fused one and streams whose route is staged are
-// two classes with a launch set each.  A stream its route would cut into tiles sends the whole call through the single entry.
-int glfer_hip_waterfall_ragged_device(glfer_hip_display *disps, size_t nstreams, int avg_mode, int depth, int minbin, int maxbin,
-                                      int max0, const float *d_psd, const size_t *row_starts, int bins, unsigned char *d_rgb,
-                                      short *d_lev, float *d_stats, void *hip_stream) {
-  if (nstreams == 0) return GLFER_OK;
-  if (!disps) return GLFER_E_ARG;
-  for (size_t b = 1; b < nstreams; b++)                  // one plan, many streams
-    if (!same_display_options(disps[0], disps[b])) return GLFER_E_ARG;
-  const glfer_hip_display &d0 = disps[0];
-  const int pitch = d0.psd_pitch == 0 ? bins : d0.psd_pitch;
-  if (bins < 1 || bins > 32769 || pitch < bins) return GLFER_E_ARG;     // (waterfall_columns' rules)
-  const bool averaging = avg_mode != 0;
-  if (averaging && (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME || depth < 1 || minbin < 0 ||
-                    maxbin <= minbin || maxbin > bins))
-    return GLFER_E_ARG;
-  if (d0.scale_type < GLFER_SCALE_LIN || d0.scale_type > GLFER_SCALE_LOG_MAX0) return GLFER_E_ARG;   // (display_columns')
-  if (!row_starts || !ragged_rows_ok(row_starts, nstreams)) return GLFER_E_ARG;
-  const size_t rows_lo = row_starts[0], rows_hi = row_starts[nstreams];
-  if (rows_hi > SIZE_MAX / sizeof(double) / (size_t)pitch) return GLFER_E_ARG;
-  if (rows_hi == rows_lo) return GLFER_OK;
-  if (!d_psd || !d_rgb) return GLFER_E_ARG;
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (stream_is_capturing(st)) return GLFER_E_ARG;
-  DeviceGuard guard(data_device(d_psd));
-  HIP_TRY(guard.error());
-  const size_t bins_z = (size_t)bins;
-
-  // every stream's own route
-  std::vector<glfer::RaggedColsEntry> all = ragged_streams(row_starts, nstreams), fused_s, staged_s;
-  bool tiled = false;
-  for (const glfer::RaggedColsEntry &e : all) {
-    bool fused = false;
-    size_t tile = 0;
-    waterfall_route(avg_mode, depth, minbin, maxbin, bins, pitch, (size_t)e.nframes, &fused, &tile);
-    if (tile < (size_t)e.nframes) tiled = true;
-    if (averaging) (fused ? fused_s : staged_s).push_back(e);
-  }
-  if (tiled) {
-    // stream by stream through the single entry (on copies: an error leaves disps as it was)
-    std::vector<glfer_hip_display> copy(disps, disps + nstreams);
-    for (const glfer::RaggedColsEntry &e : all) {
-      const size_t r = (size_t)e.row0;
-      const int rc = waterfall_columns(&copy[e.stream], avg_mode, depth, minbin, maxbin, max0, d_psd + r * (size_t)pitch, 0, (size_t)e.nframes,
-                                       bins, d_rgb + r * bins_z * 3, d_lev ? d_lev + r * bins_z : nullptr, d_stats ? d_stats + r * 4 : nullptr,
-                                       st, nullptr, pitch);
-      if (rc != GLFER_OK) return rc;
-    }
-    std::copy(copy.begin(), copy.end(), disps);
-    return GLFER_OK;
-  }
-  const bool autoscale = d0.autoscale != 0;
-  const int scale_log = d0.scale_type == GLFER_SCALE_LOG || d0.scale_type == GLFER_SCALE_LOG_MAX0;
-
-  // one small allocation: palette, dB table, the carried states [nstreams][3]; one upload
-  const size_t thr_bytes = (2 * glfer::kLogThrK + 1) * sizeof(double);
-  const size_t small_bytes = 768 + thr_bytes + nstreams * 3 * sizeof(float);
-  std::vector<unsigned char> host(small_bytes);
-  glfer::make_palette(d0.palette, host.data());
-  memcpy(host.data() + 768, glfer::log_thresholds(), thr_bytes);
-  float *h_state = reinterpret_cast<float *>(host.data() + 768 + thr_bytes);
-  for (size_t b = 0; b < nstreams; b++) {
-    h_state[b * 3 + 0] = disps[b].first_buffer != 0 ? 1.0f : 0.0f;
-    h_state[b * 3 + 1] = disps[b].display_max_lvl;
-    h_state[b * 3 + 2] = disps[b].display_min_lvl;
-  }
-  unsigned char *small = nullptr;
-  HIP_TRY(glfer::scratch_malloc((void **)&small, small_bytes, st));
-  const unsigned char *d_tab = small;
-  const double *d_thr = reinterpret_cast<const double *>(small + 768);
-  float *d_state = reinterpret_cast<float *>(small + 768 + thr_bytes);
-  int rc = GLFER_OK;
-  auto fail = [&](hipError_t err, const char *what) {
-    if (rc == GLFER_OK) rc = hip_fail(err, what);
-  };
-  hipError_t e = hipMemcpyAsync(small, host.data(), small_bytes, hipMemcpyHostToDevice, st);   // (pageable source: staged before it returns)
-  if (e != hipSuccess) fail(e, "glfer_hip_waterfall_ragged_device (upload)");
-
-  // scratch, indexed by packed row: statistics (without d_stats), levels; the chunk states of the walks; a group's averaged rows
-  size_t st_floats = 0;
-  if (autoscale)
-    for (const glfer::RaggedColsEntry &s : all) st_floats += glfer_levels_scratch_floats((size_t)s.nframes);
-  // staged: groups of streams whose averaged rows stay within the single entry's 4 GiB (one stream alone always goes)
-  const size_t group_rows_max = std::max<size_t>(1, ((size_t)4 << 30) / (bins_z * sizeof(double)));
-  std::vector<size_t> group_end;                          // staged_s[group_end[g-1] .. group_end[g])
-  size_t scratch_rows = 0;
-  for (size_t i = 0, in_group = 0; i < staged_s.size(); i++) {
-    const size_t n = (size_t)staged_s[i].nframes;
-    if (in_group && in_group + n > group_rows_max) {
-      group_end.push_back(i);
-      in_group = 0;
-    }
-    staged_s[i].out0 = (long long)in_group;               // the averaged rows of a group are packed on their own
-    in_group += n;
-    scratch_rows = std::max(scratch_rows, in_group);
-    if (i + 1 == staged_s.size()) group_end.push_back(i + 1);
-  }
-  float *stats = d_stats, *levels = nullptr;
-  double *avg = nullptr, *ret = nullptr;
-  if (rc == GLFER_OK && !d_stats) {
-    e = glfer::scratch_malloc((void **)&stats, rows_hi * 4 * sizeof(float), st);
-    if (e != hipSuccess) { stats = nullptr; fail(e, "scratch (waterfall statistics, ragged)"); }
-  }
-  if (rc == GLFER_OK) {
-    e = glfer::scratch_malloc((void **)&levels, (rows_hi * 4 + st_floats) * sizeof(float), st);
-    if (e != hipSuccess) { levels = nullptr; fail(e, "scratch (waterfall levels, ragged)"); }
-  }
-  float *chunk_state = levels ? levels + rows_hi * 4 : nullptr;
-  if (rc == GLFER_OK && scratch_rows) {
-    e = glfer::scratch_malloc((void **)&avg, scratch_rows * bins_z * sizeof(double), st);
-    if (e == hipSuccess) e = glfer::scratch_malloc((void **)&ret, scratch_rows * 4 * sizeof(double), st);
-    if (e != hipSuccess) fail(e, "scratch (averaged rows, ragged waterfall)");
-  }
-
-  // compute_floor of every row: the packed rows are one run (pieces: the grid's x limit)
-  const int m = bins - (int)(bins * 0.95);                           // fft.c:271 (glfer_hip_floor_device_pitched)
-  const size_t piece = (size_t)1 << 22;
-  for (size_t r0 = rows_lo; rc == GLFER_OK && r0 < rows_hi; r0 += piece) {
-    e = glfer_launch_floor(d_psd + r0 * (size_t)pitch, std::min(piece, rows_hi - r0), bins, pitch, m, stats + r0 * 4, st);
-    if (e != hipSuccess) fail(e, "compute_floor launch (ragged)");
-  }
-  const float thr_level = d0.thr_level / 100.0;                                // g_main.c:1099
-  const double thr255 = 255.0 * thr_level, one_m_thr = 1.0 - thr_level;
-  float mx = 0.0f, mn = 0.0f;
-  if (rc == GLFER_OK) {
-    if (autoscale) {
-      e = glfer_launch_levels_ragged(stats, all.data(), all.size(), scale_log, d0.overlap, d_state, levels, chunk_state, st);
-      if (e != hipSuccess) fail(e, "level tracking launch (ragged)");
-    } else {                                                                   // g_main.c:1125-1139
-      mx = pow(10.0, d0.max_level_db / 10.0);
-      mn = pow(10.0, d0.min_level_db / 10.0);
-      mn = (mx > mn ? mn : mx / 10.0);
-      const float dmax = scale_log ? (float)(10.0 * log10(mx)) : mx;
-      const float dmin = scale_log ? (float)(10.0 * log10(mn)) : mn;
-      e = glfer_launch_levels_fixed(rows_hi - rows_lo, dmax, dmin, mx, mn, levels + rows_lo * 4, st);
-      if (e != hipSuccess) fail(e, "levels launch (ragged)");
-    }
-  }
-  if (rc == GLFER_OK && !averaging) {
-    const size_t map_piece = (size_t)1 << 30;
-    for (size_t r0 = rows_lo; rc == GLFER_OK && r0 < rows_hi; r0 += map_piece) {
-      e = glfer_launch_map(d_psd + r0 * (size_t)pitch, nullptr, std::min(map_piece, rows_hi - r0), bins, pitch, scale_log, thr255, one_m_thr,
-                           levels + r0 * 4, d_tab, d_thr, d_rgb + r0 * bins_z * 3, d_lev ? d_lev + r0 * bins_z : nullptr, st);
-      if (e != hipSuccess) fail(e, "map launch (ragged)");
-    }
-  }
-  if (rc == GLFER_OK && !fused_s.empty()) {
-    e = glfer_launch_avgmap_ragged(avg_mode, d_psd, fused_s.data(), fused_s.size(), bins, depth, minbin, maxbin, max0 ? 1 : 0, scale_log,
-                                   thr255, one_m_thr, levels, d_tab, d_thr, d_rgb, d_lev, st);
-    if (e != hipSuccess) fail(e, "average-and-map launch (ragged)");
-  }
-  for (size_t g = 0, i0 = 0; rc == GLFER_OK && g < group_end.size(); i0 = group_end[g++]) {
-    const glfer::RaggedColsEntry *gs = staged_s.data() + i0;
-    const size_t gn = group_end[g] - i0;
-    // (update_avg's `bins` is its rows' stride; the band is minbin..maxbin, the averaged rows are dense)
-    e = glfer_launch_avg_ragged(avg_mode, d_psd, gs, gn, pitch, bins, depth, minbin, maxbin, max0 ? 1 : 0, avg, ret, st);
-    if (e != hipSuccess) fail(e, "update_avg launch (ragged waterfall)");
-    if (rc == GLFER_OK) {
-      e = glfer_launch_map_ragged(avg, gs, gn, bins, scale_log, thr255, one_m_thr, levels, d_tab, d_thr, d_rgb, d_lev, st);
-      if (e != hipSuccess) fail(e, "map launch (ragged waterfall)");
-    }
-  }
-  std::vector<float> back_state(autoscale ? nstreams * 3 : 0);
-  if (rc == GLFER_OK && autoscale) {
-    e = hipMemcpyAsync(back_state.data(), d_state, nstreams * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) fail(e, "glfer_hip_waterfall_ragged_device (state download)");
-  }
-  if (avg) glfer::scratch_free(avg, st);
-  if (ret) glfer::scratch_free(ret, st);
-  if (levels) glfer::scratch_free(levels, st);
-  if (!d_stats && stats) glfer::scratch_free(stats, st);
-  glfer::scratch_free(small, st);
-  e = hipStreamSynchronize(st);              // the carried states come back to the host
-  if (e != hipSuccess) fail(e, "glfer_hip_waterfall_ragged_device");
-  if (rc == GLFER_OK) {
-    for (const glfer::RaggedColsEntry &s : all) {        // (a stream without rows keeps its display as it is)
-      glfer_hip_display &d = disps[s.stream];
-      if (autoscale) {
-        d.display_max_lvl = back_state[(size_t)s.stream * 3 + 1];
-        d.display_min_lvl = back_state[(size_t)s.stream * 3 + 2];
-        d.first_buffer = 0;                                                    // g_main.c:1120
-      } else {
-        d.display_max_lvl = mx;
-        d.display_min_lvl = mn;
-      }
-    }
-  }
-  return rc;
 }
 
 }  // extern "C"
@@ -2693,7 +1980,7 @@ int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *p, const void *d_samples
   hipStream_t st = (hipStream_t)hip_stream;
   // the per-stream tables are uploaded from host memory that is gone when the call returns: a copy node of a captured graph
   // would read it at every replay, so a capturing stream is refused
-  if (stream_is_capturing(st)) return GLFER_E_ARG;
+  if (glfer::stream_is_capturing(st)) return GLFER_E_ARG;
   const char *base = static_cast<const char *>(d_samples);
   auto single = [&](size_t b) {
     if (!s[b].frames) return (int)GLFER_OK;
@@ -3089,10 +2376,9 @@ int glfer_hip_submean_exact_device(const void *d_in, float *d_out, int hop, size
 
 int glfer_hip_floor_device_pitched(const float *d_psd, size_t nframes, int bins, int pitch, float *d_stats, void *hip_stream) {
   if (!d_psd || !d_stats || bins < 1 || bins > 32769 || pitch < bins) return GLFER_E_ARG;
-  const int m = bins - (int)(bins * 0.95);                       // fft.c:271: i = N2*0.95 .. N2-1
   DeviceGuard guard(data_device(d_psd));
   HIP_TRY(guard.error());
-  HIP_TRY(glfer_launch_floor(d_psd, nframes, bins, pitch, m, d_stats, (hipStream_t)hip_stream));
+  HIP_TRY(glfer::floor_rows(d_psd, nframes, bins, pitch, d_stats, (hipStream_t)hip_stream));
   return GLFER_OK;
 }
 
@@ -3103,9 +2389,7 @@ int glfer_hip_floor_device(const float *d_psd, size_t nframes, int bins, float *
 int glfer_hip_avg_device(int avg_mode, const float *d_psd, size_t nframes, int bins, int n_out, int depth,
                          int minbin, int maxbin, int max0, double *d_avg, double *d_ret, void *hip_stream) {
   if (!d_psd || !d_avg || !d_ret) return GLFER_E_ARG;
-  if (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME) return GLFER_E_ARG;
-  if (depth < 1 || minbin < 0 || maxbin <= minbin || maxbin > bins || maxbin > n_out || n_out < 1)
-    return GLFER_E_ARG;
+  if (!glfer::update_avg_args_ok(avg_mode, depth, minbin, maxbin, bins, n_out)) return GLFER_E_ARG;
   DeviceGuard guard(data_device(d_psd));
   HIP_TRY(guard.error());
   HIP_TRY(glfer_launch_avg(avg_mode, d_psd, nframes, bins, n_out, depth, minbin, maxbin, max0 ? 1 : 0, d_avg,
@@ -3143,8 +2427,7 @@ int glfer_hip_spectrogram_avg_device(glfer_hip_plan *p, const void *d_stream, si
                                      double *d_avg, double *d_ret, void *hip_stream) {
   if (!p || !d_stream || (!d_avg && nframes)) return GLFER_E_ARG;
   if (p->cfg.mode == GLFER_MODE_HPARMA || p->pitch != p->bins) return GLFER_E_ARG;       // (HP-ARMA rows are not averaged by the reference's callers; rows dense)
-  if (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME) return GLFER_E_ARG;
-  if (depth < 1 || minbin < 0 || maxbin <= minbin || maxbin > p->bins || n_out < p->bins) return GLFER_E_ARG;
+  if (!glfer::update_avg_args_ok(avg_mode, depth, minbin, maxbin, p->bins, n_out) || n_out < p->bins) return GLFER_E_ARG;
   if (nframes == 0) return GLFER_OK;
   if ((first + nframes) > nsamples / (size_t)p->hop || nframes > 0x7fffffffu) return GLFER_E_ARG;
   hipStream_t st = (hipStream_t)hip_stream;
@@ -3230,8 +2513,7 @@ int glfer_hip_spectrogram_avg_device(glfer_hip_plan *p, const void *d_stream, si
 
 int glfer_hip_avg_batch_device(int avg_mode, const float *d_psd, size_t nstreams, size_t nframes, int bins, int n_out, int depth,
                                int minbin, int maxbin, int max0, double *d_avg, double *d_ret, void *hip_stream) {
-  if (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME) return GLFER_E_ARG;
-  if (depth < 1 || minbin < 0 || maxbin <= minbin || maxbin > bins || maxbin > n_out || n_out < 1) return GLFER_E_ARG;
+  if (!glfer::update_avg_args_ok(avg_mode, depth, minbin, maxbin, bins, n_out)) return GLFER_E_ARG;
   if (nstreams == 0 || nframes == 0) return GLFER_OK;
   if (!d_psd || !d_avg || !d_ret) return GLFER_E_ARG;
   if (nframes > (SIZE_MAX / sizeof(double) / (size_t)std::max(bins, n_out)) / nstreams) return GLFER_E_ARG;
@@ -3258,8 +2540,7 @@ int glfer_hip_spectrogram_avg_batch_device(glfer_hip_plan *p, const void *d_stre
                                            void *hip_stream) {
   if (!p) return GLFER_E_ARG;
   if (p->cfg.mode == GLFER_MODE_HPARMA || p->pitch != p->bins) return GLFER_E_ARG;
-  if (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME) return GLFER_E_ARG;
-  if (depth < 1 || minbin < 0 || maxbin <= minbin || maxbin > p->bins || n_out < p->bins) return GLFER_E_ARG;
+  if (!glfer::update_avg_args_ok(avg_mode, depth, minbin, maxbin, p->bins, n_out) || n_out < p->bins) return GLFER_E_ARG;
   const int fmt = p->cfg.sample_format;
   if (fmt != GLFER_FMT_F32 && (stream_pitch & 1)) return GLFER_E_ARG;      // (glfer_hip_spectrogram_batch_device's rule)
   if (nstreams == 0 || nframes == 0) return GLFER_OK;
@@ -3379,19 +2660,18 @@ int glfer_hip_spectrogram_avg_batch_device(glfer_hip_plan *p, const void *d_stre
 // update_avg_* over packed rows of streams of unequal length (glfer_hip.h): glfer_launch_avg_ragged over the streams that have rows
 int glfer_hip_avg_ragged_device(int avg_mode, const float *d_psd, size_t nstreams, const size_t *row_starts, int bins, int n_out,
                                 int depth, int minbin, int maxbin, int max0, double *d_avg, double *d_ret, void *hip_stream) {
-  if (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME) return GLFER_E_ARG;
-  if (depth < 1 || minbin < 0 || maxbin <= minbin || maxbin > bins || maxbin > n_out || n_out < 1) return GLFER_E_ARG;
+  if (!glfer::update_avg_args_ok(avg_mode, depth, minbin, maxbin, bins, n_out)) return GLFER_E_ARG;
   if (nstreams == 0) return GLFER_OK;
-  if (!row_starts || !ragged_rows_ok(row_starts, nstreams)) return GLFER_E_ARG;
+  if (!row_starts || !glfer::ragged_rows_ok(row_starts, nstreams)) return GLFER_E_ARG;
   const size_t rows_hi = row_starts[nstreams];
   if (rows_hi > SIZE_MAX / sizeof(double) / (size_t)std::max(bins, n_out)) return GLFER_E_ARG;
   if (rows_hi == row_starts[0]) return GLFER_OK;
   if (!d_psd || !d_avg) return GLFER_E_ARG;
   hipStream_t st = (hipStream_t)hip_stream;
-  if (stream_is_capturing(st)) return GLFER_E_ARG;
+  if (glfer::stream_is_capturing(st)) return GLFER_E_ARG;
   DeviceGuard guard(data_device(d_psd));
   HIP_TRY(guard.error());
-  const std::vector<glfer::RaggedColsEntry> s = ragged_streams(row_starts, nstreams);
+  const std::vector<glfer::RaggedColsEntry> s = glfer::ragged_streams(row_starts, nstreams);
   double *ret = d_ret;                                   // (the kernels always form the return values: without d_ret they land in scratch)
   if (!ret) HIP_TRY(glfer::scratch_malloc((void **)&ret, rows_hi * 4 * sizeof(double), st));
   const hipError_t e = glfer_launch_avg_ragged(avg_mode, d_psd, s.data(), s.size(), bins, n_out, depth, minbin, maxbin, max0 ? 1 : 0, d_avg,
@@ -3408,8 +2688,7 @@ int glfer_hip_spectrogram_avg_ragged_device(glfer_hip_plan *p, const void *d_sam
                                             void *hip_stream) {
   if (!p) return GLFER_E_ARG;
   if (p->cfg.mode == GLFER_MODE_HPARMA || p->pitch != p->bins) return GLFER_E_ARG;       // (glfer_hip_spectrogram_avg_device's rules)
-  if (avg_mode < GLFER_AVG_SUMAVG || avg_mode > GLFER_AVG_SUMEXTREME) return GLFER_E_ARG;
-  if (depth < 1 || minbin < 0 || maxbin <= minbin || maxbin > p->bins || n_out < p->bins) return GLFER_E_ARG;
+  if (!glfer::update_avg_args_ok(avg_mode, depth, minbin, maxbin, p->bins, n_out) || n_out < p->bins) return GLFER_E_ARG;
   if (nstreams == 0) {
     if (row_starts) row_starts[0] = 0;
     return GLFER_OK;
@@ -3433,7 +2712,7 @@ int glfer_hip_spectrogram_avg_ragged_device(glfer_hip_plan *p, const void *d_sam
   hipStream_t st = (hipStream_t)hip_stream;
   if (total != 0) {
     if (!d_samples || !d_avg) return GLFER_E_ARG;
-    if (stream_is_capturing(st)) return GLFER_E_ARG;
+    if (glfer::stream_is_capturing(st)) return GLFER_E_ARG;
   }
   if (row_starts) std::copy(starts.begin(), starts.end(), row_starts);   // (past the last refusal: a refused call writes nothing)
   if (total == 0) return GLFER_OK;
@@ -3453,7 +2732,7 @@ int glfer_hip_spectrogram_avg_ragged_device(glfer_hip_plan *p, const void *d_sam
 int glfer_hip_avg_cum_device(const float *d_psd, size_t nframes, int bins, int n_out, int depth, int minbin,
                              int maxbin, double *d_cum, void *hip_stream) {
   if (!d_psd || !d_cum) return GLFER_E_ARG;
-  if (depth < 1 || minbin < 0 || maxbin <= minbin || maxbin > bins || maxbin > n_out || n_out < 1) return GLFER_E_ARG;
+  if (!glfer::update_avg_args_ok(GLFER_AVG_PLAIN, depth, minbin, maxbin, bins, n_out)) return GLFER_E_ARG;   // (the sums have no mode)
   DeviceGuard guard(data_device(d_psd));
   HIP_TRY(guard.error());
   HIP_TRY(glfer_launch_avg_cum(d_psd, nframes, bins, n_out, depth, minbin, maxbin, d_cum, (hipStream_t)hip_stream));

@@ -2,6 +2,7 @@
 // state, fft.c:168-187, mtm.c:88-151), error plumbing and the device guard.  Internal.
 #pragma once
 #include "../../include/glfer_hip.h"
+#include "ragged_cols.hpp"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,6 +41,8 @@ class DeviceGuard {
 
 // the device a device pointer belongs to (-1: not a device pointer HIP knows)
 int device_of(const void *d_ptr);
+// the device the data of a plan-less entry lives on: the pointer's, else the current one
+int data_device(const void *d_ptr);
 
 // Stream-ordered scratch on the current device: small requests from a pool of their own, middle ones
 // from the default pool (release threshold raised), 16 MiB and more from blocks the library keeps
@@ -53,6 +56,18 @@ size_t scratch_held(int dev);
 void scratch_set_cap(size_t bytes);
 bool scratch_keeping();                        // false with GLFER_SCRATCH_CACHE=0: the library keeps nothing between calls
 size_t scratch_cap();                          // glfer_hip_scratch_limit / GLFER_SCRATCH_CAP_MB
+
+// ---- what the per-column entries share: waterfall.cpp (display and waterfall) and the floor / update_avg entries of glfer_hip.cpp
+// The averaging-argument rule.  The waterfall's: a mode of update_avg_*, a window of at least one frame, a band inside the row.
+inline bool avg_args_ok(int mode, int depth, int minbin, int maxbin, int bins) {
+  return mode >= GLFER_AVG_SUMAVG && mode <= GLFER_AVG_SUMEXTREME && depth >= 1 && minbin >= 0 && maxbin > minbin && maxbin <= bins;
+}
+// update_avg's own: the band also lies inside the n_out values of an averaged row
+inline bool update_avg_args_ok(int mode, int depth, int minbin, int maxbin, int bins, int n_out) {
+  return avg_args_ok(mode, depth, minbin, maxbin, bins) && maxbin <= n_out && n_out >= 1;
+}
+// compute_floor of a contiguous run of rows `pitch` floats apart (the top 5 % of a row, fft.c:271), 2^22 rows a launch.  waterfall.cpp
+hipError_t floor_rows(const float *d_psd, size_t rows, int bins, int pitch, float *d_stats, hipStream_t st);
 
 // Allow `bytes` of dynamic LDS for `kernel` on the current device (hipFuncSetAttribute, once per
 // device, kernel and size class).
@@ -103,6 +118,15 @@ struct glfer_yqueue {
     hipError_t e_ = (call);                                    \
     if (e_ != hipSuccess) return glfer::hip_fail(e_, #call);   \
   } while (0)
+
+// The launchers of aux_kernels.hip that both glfer_hip.cpp (the update_avg entries) and waterfall.cpp (the staged waterfalls) call;
+// every other launcher is declared where its one caller is, or in spectro_params.h.
+extern "C" hipError_t glfer_launch_avg_batch(int mode, const float *psd, size_t nframes, int bins, int n_out, int depth, int minbin,
+                                             int maxbin, int max0, double *avg, double *ret, unsigned nb, long long psd_bs,
+                                             long long avg_bs, long long ret_bs, hipStream_t st);
+extern "C" hipError_t glfer_launch_avg_ragged(int mode, const float *psd, const glfer::RaggedColsEntry *streams, size_t n, int bins,
+                                              int n_out, int depth, int minbin, int maxbin, int max0, double *avg, double *ret,
+                                              hipStream_t st);
 
 struct glfer_hip_plan {
   glfer_hip_config cfg;

@@ -84,6 +84,16 @@ inline hipError_t ragged_upload(std::initializer_list<RaggedTable *> tabs, Ragge
   return err;
 }
 
+
+// ---- the ragged entries' own rules (waterfall.cpp)
+// true where `st` is being captured into a graph: the per-stream tables are uploaded from host memory that is gone when the call
+// returns, which a captured copy would read at every replay
+bool stream_is_capturing(hipStream_t st);
+// row_starts of nstreams streams: non-decreasing, at most 2^31 - 1 rows a stream
+bool ragged_rows_ok(const size_t *row_starts, size_t nstreams);
+// the streams that have rows, as the ragged launchers take them (out0 = row0: outputs packed as the rows are)
+std::vector<RaggedColsEntry> ragged_streams(const size_t *row_starts, size_t nstreams);
+
 }  // namespace glfer
 
 #endif

@@ -5,7 +5,9 @@ when the kernel traces of two runs are (rocprofv3 --kernel-trace -- python tools
     GLFER_LIB_PATH=<other libglfer_hip.so> python tools/launcher_identity.py
 The cases: the cut-edge calls of tests/test_gpu_frame_cuts.py (plans A .. D, sub_mean 0 / 1 / fast, rows and batch at every
 (first, nframes), the ragged call, plan A's F entries), then one 4 096-frame call per plan through the rows, batch, ragged,
-average, average-batch, F and F-batch entries.  Inputs come from fixed seeds on the host; nothing is timed."""
+average, average-batch, F and F-batch entries; then the column entries (column_cases: display, the waterfalls and their two
+multi-GPU halves, the moving averages; `python tools/launcher_identity.py columns` runs these alone).  Inputs come from fixed
+seeds on the host; nothing is timed."""
 import hashlib
 import os
 import sys
@@ -64,7 +66,144 @@ def ragged(sp, x, frames, spare):
     return sp.run_ragged(buf, offs, lens)[0]
 
 
+# ---- the column entries (waterfall.cpp and the update_avg entries): PSD-like rows from fixed seeds, the carried states in the line
+AVERAGES = {0: dict(avg_mode=0), 1: dict(avg_mode=1, depth=4, minbin=10, maxbin=500), 2: dict(avg_mode=2, depth=4, minbin=0, maxbin=513),
+            3: dict(avg_mode=3, depth=7, minbin=3, maxbin=511)}
+DISPLAYS = {"lin auto": dict(scale_type=0, autoscale=1, overlap=0.75, palette=3, thr_level=10.0),
+            "lin fixed": dict(scale_type=1, autoscale=0, max_level_db=-3.0, min_level_db=-40.0, palette=1),
+            "log auto": dict(scale_type=2, autoscale=1, overlap=0.5, palette=0),
+            "log fixed": dict(scale_type=3, autoscale=0, max_level_db=-20.0, min_level_db=-80.0, thr_level=5.0, palette=5)}
+RAGGED_LENGTHS = [0, 1, 255, 256, 257, 1281, 3000]
+
+
+def psd_rows(shape, seed):
+    """non-negative floats with a floor and a few strong bins; the leading dimension (streams) differs in scale"""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    x = torch.rand(shape, generator=g, device="cuda", dtype=torch.float32)
+    x = x * x * x * x * 0.1 + 2e-4
+    if len(shape) == 3:
+        x = x * torch.tensor([10.0 ** ((b * 37) % 7 - 3) for b in range(shape[0])], device="cuda", dtype=torch.float32)[:, None, None]
+    return x.contiguous()
+
+
+def displays(n, **options):
+    """every third one a first buffer, the others carried levels of their own"""
+    out = []
+    for b in range(n):
+        d = G.Display(first_buffer=1 if b % 3 == 0 else 0, **options)
+        if b % 3:
+            d.display_max_lvl, d.display_min_lvl = 0.05 + 0.01 * (b % 5), 0.002 + 0.0005 * (b % 4)
+        out.append(d)
+    return out
+
+
+def states(disps):
+    return "states " + " ".join("%d/%s/%s" % (d.first_buffer, float(d.display_max_lvl).hex(), float(d.display_min_lvl).hex()) for d in disps)
+
+
+def with_env(fn, **env):
+    """fn() with these environment switches set (the library reads them per call)"""
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return fn()
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
+def halves(disp, rows, av, cut):
+    """glfer_hip_levels_host over the whole call's statistics, then glfer_hip_waterfall_map_device over rows [0, cut) and [cut, end)"""
+    import ctypes as C
+    L = G.api.lib()
+    n, bins = rows.shape
+    stats = np.ascontiguousarray(G.compute_floor(rows).cpu().numpy())
+    levels = np.empty((n, 4), np.float32)
+    assert L.glfer_hip_levels_host(C.byref(disp), stats.ctypes.data, n, levels.ctypes.data, 0) == 0
+    d_levels = torch.from_numpy(levels).to("cuda")
+    rgb = torch.zeros((n, bins, 3), dtype=torch.uint8, device="cuda")
+    lev = torch.zeros((n, bins), dtype=torch.int16, device="cuda")
+    for first, count in ((0, cut), (cut, n - cut)):
+        assert L.glfer_hip_waterfall_map_device(C.byref(disp), av["avg_mode"], av.get("depth", 1), av.get("minbin", 0), av.get("maxbin", 1), 0,
+                                                rows.data_ptr(), first, count, bins, d_levels[first:].data_ptr(), rgb[first:].data_ptr(),
+                                                lev[first:].data_ptr(), None) == 0
+    return rgb, lev, d_levels
+
+
+def column_cases():
+    # display: from rows and from averaged rows
+    rows = psd_rows((3000, 513), 21)
+    stats = G.compute_floor(rows)
+    avg = G.update_avg(G.AVG_PLAIN, rows, 4, 0, 513)[0]
+    for dname, opt in sorted(DISPLAYS.items()):
+        for sname, src in (("rows", rows), ("averaged rows", avg)):
+            d = displays(2, **opt)[1]
+            print("display %s, %s: %s %s" % (dname, sname, sha(*G.display(d, src, stats)), states([d])))
+    # waterfall: each mode on lin / log and autoscale / fixed, two shapes, the two switches
+    for shape in ((3000, 513), (300, 2049)):
+        rows = psd_rows(shape, 22)
+        for dname, opt in sorted(DISPLAYS.items()):
+            for mode, av in sorted(AVERAGES.items()):
+                av = dict(av, maxbin=min(av.get("maxbin", 1), shape[1]))
+                for ename, env in (("", {}), (" TILE=1024", dict(GLFER_WATERFALL_TILE="1024")), (" FUSED=0", dict(GLFER_WATERFALL_FUSED="0"))):
+                    d = displays(2, **opt)[1]
+                    out = with_env(lambda: G.waterfall(d, rows, want_stats=True, **av), **env)
+                    print("waterfall %dx%d %s mode %d%s: %s %s" % (shape[0], shape[1], dname, mode, ename, sha(*out), states([d])))
+        sys.stdout.flush()
+    # waterfall_batch: 5 streams x 1 281 rows
+    rows = psd_rows((5, 1281, 513), 23)
+    for dname, opt in sorted(DISPLAYS.items()):
+        for mode, av in sorted(AVERAGES.items()):
+            for ename, env in (("", {}), (" TILE=1024", dict(GLFER_WATERFALL_TILE="1024")), (" FUSED=0", dict(GLFER_WATERFALL_FUSED="0"))):
+                ds = displays(5, **opt)
+                out = with_env(lambda: G.waterfall_batch(ds, rows, want_stats=True, **av), **env)
+                print("waterfall_batch 5x1281x513 %s mode %d%s: %s %s" % (dname, mode, ename, sha(*out), states(ds)))
+    sys.stdout.flush()
+    # waterfall_ragged: the lengths around the level chunk, once more by the stream-by-stream route; then a set whose short
+    # streams take the staged class and whose long one takes the fused (depth 40, tests/test_gpu_waterfall_ragged.py)
+    starts = np.concatenate([[0], np.cumsum(RAGGED_LENGTHS)])
+    rows = psd_rows((int(starts[-1]), 513), 24)
+    for dname, opt in sorted(DISPLAYS.items()):
+        for mode, av in sorted(AVERAGES.items()):
+            for ename, env in (("", {}), (" TILE=1024 (stream by stream)", dict(GLFER_WATERFALL_TILE="1024"))):
+                ds = displays(len(RAGGED_LENGTHS), **opt)
+                out = with_env(lambda: G.waterfall_ragged(ds, rows, starts, want_stats=True, **av)[:3], **env)
+                print("waterfall_ragged %s mode %d%s: %s %s" % (dname, mode, ename, sha(*out), states(ds)))
+    mixed = [100, 0, 3000, 17000, 40000]
+    mstarts = np.concatenate([[0], np.cumsum(mixed)])
+    mrows = psd_rows((int(mstarts[-1]), 129), 27)
+    for dname in ("log auto", "lin fixed"):
+        for mode in (1, 2):
+            ds = displays(len(mixed), **DISPLAYS[dname])
+            out = G.waterfall_ragged(ds, mrows, mstarts, avg_mode=mode, depth=40, minbin=3, maxbin=127, want_stats=True)[:3]
+            print("waterfall_ragged fused and staged streams, %s mode %d depth 40: %s %s" % (dname, mode, sha(*out), states(ds)))
+    del mrows
+    sys.stdout.flush()
+    # the averages, each mode
+    batch = psd_rows((5, 1281, 513), 25)
+    for mode in (G.AVG_SUMAVG, G.AVG_PLAIN, G.AVG_SUMEXTREME):
+        for depth in (4, 7):
+            print("update_avg mode %d depth %d: %s" % (mode, depth, sha(*G.update_avg(mode, rows, depth, 3, 511))))
+            print("update_avg_batch mode %d depth %d: %s" % (mode, depth, sha(*G.update_avg_batch(mode, batch, depth, 3, 511))))
+            print("update_avg_ragged mode %d depth %d: %s" % (mode, depth, sha(*G.update_avg_ragged(mode, rows, starts, depth, 3, 511)[:2])))
+    for depth in (4, 7):
+        print("avg_cum depth %d: %s" % (depth, sha(G.avg_cum(rows, depth, 3, 511))))
+    # the two halves of a waterfall over several GPUs
+    rows = psd_rows((700, 129), 26)
+    for dname, opt in sorted(DISPLAYS.items()):
+        for mode, av in sorted(AVERAGES.items()):
+            av = dict(av, minbin=min(av.get("minbin", 0), 3), maxbin=min(av.get("maxbin", 1), 129))
+            d = displays(2, **opt)[1]
+            print("halves 700x129 cut 300 %s mode %d: %s %s" % (dname, mode, sha(*halves(d, rows, av, 300)), states([d])))
+    sys.stdout.flush()
+
+
 def main():
+    if sys.argv[1:] == ["columns"]:
+        return column_cases()
     for name, (kind, n, overlap, fmt, hm, Gf, fi) in sorted(PLANS.items()):
         for sub in SUB_MEANS:
             sp = plan(name, sub)
@@ -101,6 +240,7 @@ def main():
         x = streams(1, 4096 * sp.hop, 0, 13)
         print("lmp sub_mean %d rows 4096: %s; first 5 nframes 9: %s" % (sub, sha(sp.run(x[0])), sha(sp.run(x[0], first_frame=5, nframes=9))))
         sp.close()
+    column_cases()
 
 
 if __name__ == "__main__":
