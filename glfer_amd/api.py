@@ -59,6 +59,8 @@ EXPORTS = [
     "glfer_hip_spectrogram_ragged_device", "glfer_hip_ragged_frames",
     # their moving average and waterfall
     "glfer_hip_avg_ragged_device", "glfer_hip_spectrogram_avg_ragged_device", "glfer_hip_waterfall_ragged_device",
+    # their harmonic F-test, alone and beside the multitaper rows
+    "glfer_hip_mtm_ftest_ragged_device", "glfer_hip_mtm_rows_ftest_ragged_device",
 ]
 
 
@@ -171,6 +173,10 @@ def lib():
         L.glfer_hip_mtm_rows_ftest_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, C.c_int, vp]
     if hasattr(L, "glfer_hip_spectrogram_ragged_device"):
         L.glfer_hip_spectrogram_ragged_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    if hasattr(L, "glfer_hip_mtm_ftest_ragged_device"):
+        L.glfer_hip_mtm_ftest_ragged_device.argtypes = [vp, vp, sz, vp, vp, vp, C.c_int, vp, vp]
+    if hasattr(L, "glfer_hip_mtm_rows_ftest_ragged_device"):
+        L.glfer_hip_mtm_rows_ftest_ragged_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, C.c_int, vp, vp]
     if hasattr(L, "glfer_hip_ragged_frames"):
         L.glfer_hip_ragged_frames.argtypes = [vp, sz, vp, vp]
         L.glfer_hip_ragged_frames.restype = sz
@@ -452,17 +458,8 @@ class Spectrogram:
         """streams: a list of 1-D torch tensors of the plan's sample dtype on this GPU.  Concatenates them on the device (every
         stream at an even offset, which the integer formats need) and returns the list of per-stream row views
         [frames_b][pitch] of one run_ragged call."""
-        torch = _torch()
-        assert len(streams) > 0
-        offs, at = [], 0
-        for t in streams:
-            assert t.dim() == 1 and t.dtype == self._sample_dtype()
-            offs.append(at)
-            at += t.numel() + (t.numel() & 1)
-        buf = torch.zeros(max(at, 1), dtype=self._sample_dtype(), device=streams[0].device)
-        for o, t in zip(offs, streams):
-            buf[o:o + t.numel()] = t
-        psd, starts = self.run_ragged(buf, offs, [t.numel() for t in streams])
+        buf, offs, lens = self._pack_list(streams)
+        psd, starts = self.run_ragged(buf, offs, lens)
         return [psd[int(starts[b]):int(starts[b + 1])] for b in range(len(streams))]
 
     def run_avg_ragged(self, samples, offsets, lengths, avg_mode, depth, minbin, maxbin, max0=0, n_out=None, want_psd=False,
@@ -639,6 +636,85 @@ class Spectrogram:
                                                            1 if mu_live else 0, st),
                "glfer_hip_mtm_rows_ftest_batch_device")
         return psd, ft
+
+    def _ragged_args(self, what, samples, offsets, lengths):
+        """run_ragged's validation for the ragged F entries: (offsets uint64, lengths uint64, total rows)"""
+        assert samples.is_cuda and samples.dim() == 1 and samples.is_contiguous()
+        assert samples.dtype == self._sample_dtype(), (samples.dtype, self._sample_dtype())
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        lens = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
+        assert offs.size == lens.size
+        total, _ = self.ragged_frames(lens)
+        if total == 2 ** 64 - 1:
+            raise GlferHipError(what + ": the row count overflows")
+        if lens.size:
+            assert max(int(o) + int(n) for o, n in zip(offs, lens)) <= samples.numel(), "a stream reaches past `samples`"
+        return offs, lens, total
+
+    def ftest_ragged(self, samples, offsets, lengths, mu_live=True, out=None):
+        """ftest for streams of unequal length in one call (glfer_hip_mtm_ftest_ragged_device).  samples, offsets and lengths
+        as run_ragged takes them.  Returns (ftest [sum of frames][bins], row_starts): stream b's rows are
+        ftest[row_starts[b] : row_starts[b + 1]] and hold the bits of ftest(samples[offsets[b] : offsets[b] + lengths[b]]);
+        row_starts is a numpy int64 array of len(offsets) + 1.  Launched on torch's current stream."""
+        torch = _torch()
+        offs, lens, total = self._ragged_args("ftest_ragged", samples, offsets, lengths)
+        if out is None:
+            out = torch.empty((total, self.bins), dtype=torch.float32, device=samples.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= total * self.bins
+        starts = np.zeros(lens.size + 1, np.uint64)
+        st = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+        _check(lib().glfer_hip_mtm_ftest_ragged_device(self._h, C.c_void_p(samples.data_ptr()), lens.size, offs.ctypes.data,
+                                                       lens.ctypes.data, C.c_void_p(out.data_ptr()), 1 if mu_live else 0,
+                                                       starts.ctypes.data, st),
+               "glfer_hip_mtm_ftest_ragged_device")
+        return out, starts.astype(np.int64)
+
+    def rows_ftest_ragged(self, samples, offsets, lengths, mu_live=True, out=None):
+        """rows_ftest for streams of unequal length in one call (glfer_hip_mtm_rows_ftest_ragged_device).  Returns
+        (psd [sum of frames][pitch], ftest [sum of frames][bins], row_starts); rows row_starts[b] : row_starts[b + 1] of both
+        hold the bits of rows_ftest(samples[offsets[b] : offsets[b] + lengths[b]]).  out: a (psd, ftest) pair to write into."""
+        torch = _torch()
+        offs, lens, total = self._ragged_args("rows_ftest_ragged", samples, offsets, lengths)
+        if out is None:
+            out = (torch.empty((total, self.pitch), dtype=torch.float32, device=samples.device),
+                   torch.empty((total, self.bins), dtype=torch.float32, device=samples.device))
+        psd, ft = out
+        for o, w in ((psd, self.pitch), (ft, self.bins)):
+            assert o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and o.numel() >= total * w
+        starts = np.zeros(lens.size + 1, np.uint64)
+        st = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+        _check(lib().glfer_hip_mtm_rows_ftest_ragged_device(self._h, C.c_void_p(samples.data_ptr()), lens.size, offs.ctypes.data,
+                                                            lens.ctypes.data, C.c_void_p(psd.data_ptr()), C.c_void_p(ft.data_ptr()),
+                                                            1 if mu_live else 0, starts.ctypes.data, st),
+               "glfer_hip_mtm_rows_ftest_ragged_device")
+        return psd, ft, starts.astype(np.int64)
+
+    def _pack_list(self, streams):
+        """run_list's packing: the streams concatenated on the device at even offsets: (buffer, offsets, lengths)"""
+        torch = _torch()
+        assert len(streams) > 0
+        offs, at = [], 0
+        for t in streams:
+            assert t.dim() == 1 and t.dtype == self._sample_dtype()
+            offs.append(at)
+            at += t.numel() + (t.numel() & 1)
+        buf = torch.zeros(max(at, 1), dtype=self._sample_dtype(), device=streams[0].device)
+        for o, t in zip(offs, streams):
+            buf[o:o + t.numel()] = t
+        return buf, offs, [t.numel() for t in streams]
+
+    def ftest_list(self, streams):
+        """streams: a list of 1-D torch tensors as run_list takes them.  Returns the list of per-stream F row views
+        [frames_b][bins] of one ftest_ragged call."""
+        buf, offs, lens = self._pack_list(streams)
+        ft, starts = self.ftest_ragged(buf, offs, lens)
+        return [ft[int(starts[b]):int(starts[b + 1])] for b in range(len(streams))]
+
+    def rows_ftest_list(self, streams):
+        """As ftest_list, from one rows_ftest_ragged call: the list of per-stream (psd [frames_b][pitch], ftest [frames_b][bins])."""
+        buf, offs, lens = self._pack_list(streams)
+        psd, ft, starts = self.rows_ftest_ragged(buf, offs, lens)
+        return [(psd[int(starts[b]):int(starts[b + 1])], ft[int(starts[b]):int(starts[b + 1])]) for b in range(len(streams))]
 
     def prepare(self, stream, first_frame=0, nframes=None):
         """prepare_audio's inbuf_fft (fft.c:66-165) for every frame: float tensor [nframes][n]."""

@@ -2349,6 +2349,124 @@ static int ftest_batch(glfer_hip_plan *p, const void *d_streams, size_t nstreams
   return GLFER_OK;
 }
 
+// The F entries over streams of unequal length (glfer_hip.h): the launches of ftest_batch with a table in place of the strides.
+// One chunk (2 <= nb <= the grid's y limit, c.d_psd NULL: F alone): every frame of an F entry goes through corrected copies under
+// mean removal, so the copies of hops [0, frames_b) of every stream come from one RaggedChunk::submean -- no head / body / tail --
+// and one launch of the FT form follows, the form chosen by ftest_in_launch.  d_ftest: the call's; the plan's F tables are made.
+static int ftest_ragged_chunk(const RaggedChunk &c, float *d_ftest, int mu_live) {
+  glfer_hip_plan *p = c.p;
+  SpectroParams sp;
+  ftest_params(p, sp);
+  sp.stream = c.base;
+  std::vector<long long> soff(c.nb);
+  float *scratch = nullptr;
+  if (p->cfg.sub_mean) {
+    std::vector<size_t> hlo(c.nb, 0), hhi(c.nb);
+    for (unsigned b = 0; b < c.nb; b++) hhi[b] = c.s[b].frames;
+    const int rc = c.submean(sp.fmt, hlo, hhi, &scratch, soff);
+    if (rc != GLFER_OK || !scratch) return rc;           // (no scratch: no stream of the chunk has a frame)
+    sp.stream = scratch;
+    sp.fmt = GLFER_FMT_F32;
+  } else {
+    for (unsigned b = 0; b < c.nb; b++) soff[b] = (long long)(c.s[b].off * c.esz);
+  }
+  const SpectroParams q = ftest_in_launch(p, sp, 0, 0, d_ftest, mu_live, c.d_psd);
+  std::vector<GlferRaggedEntry> tab(c.nb);
+  for (unsigned b = 0; b < c.nb; b++) {
+    GlferRaggedEntry e = {};
+    if (c.s[b].frames) {
+      e.stream_off = soff[b];
+      e.psd_off = c.d_psd ? (long long)(c.s[b].row * (size_t)p->pitch) : 0;   // (F alone: psd NULL stays NULL in the kernel)
+      e.ftest_off = (long long)(c.s[b].row * (size_t)p->bins);
+      e.nframes = (int)c.s[b].frames;
+    }
+    tab[b] = e;
+  }
+  const int rc = c.launch(q, tab, ROUTE_PACKED);
+  if (scratch) glfer::scratch_free(scratch, c.st);
+  return rc;
+}
+
+// both ragged F entries; want_psd: the rows-and-F one (d_psd required, its rows at the plan's pitch)
+static int ftest_ragged(glfer_hip_plan *p, const void *d_samples, size_t nstreams, const size_t *offsets, const size_t *lengths,
+                        float *d_psd, bool want_psd, float *d_ftest, int mu_live, size_t *row_starts, hipStream_t st) {
+  if (!p) return GLFER_E_ARG;
+  if (p->cfg.mode != GLFER_MODE_MTM || p->n > 16384) return GLFER_E_ARG;
+  if (nstreams == 0) {
+    if (row_starts) row_starts[0] = 0;
+    return GLFER_OK;
+  }
+  if (!offsets || !lengths) return GLFER_E_ARG;
+  const int fmt = p->cfg.sample_format;
+  const size_t esz = glfer_sample_size(fmt);
+  const size_t rowlen = want_psd ? (size_t)p->pitch : (size_t)p->bins;    // (the wider of the two row sizes: pitch >= bins)
+  // glfer_hip_spectrogram_ragged_device's per-stream rules, from the host arrays alone
+  std::vector<RaggedStream> s(nstreams);
+  size_t total = 0;
+  for (size_t b = 0; b < nstreams; b++) {
+    const size_t f = lengths[b] / (size_t)p->hop;
+    if (f > 0x7fffffffu) return GLFER_E_ARG;
+    if (lengths[b] > SIZE_MAX / esz || offsets[b] > SIZE_MAX / esz - lengths[b]) return GLFER_E_ARG;
+    if (fmt != GLFER_FMT_F32 && (offsets[b] & 1)) return GLFER_E_ARG;   // (every stream of a launch must see the same alignment)
+    if (f > SIZE_MAX / sizeof(float) / rowlen - total) return GLFER_E_ARG;
+    s[b] = RaggedStream{offsets[b], f, total};
+    total += f;
+  }
+  if (row_starts) {
+    for (size_t b = 0; b < nstreams; b++) row_starts[b] = s[b].row;
+    row_starts[nstreams] = total;
+  }
+  if (total == 0) return GLFER_OK;
+  if (!d_samples || !d_ftest || (want_psd && !d_psd)) return GLFER_E_ARG;
+  // (the tables are uploaded from host memory that is gone when the call returns: glfer_hip_spectrogram_ragged_device)
+  if (glfer::stream_is_capturing(st)) return GLFER_E_ARG;
+  if (!want_psd) d_psd = nullptr;
+  const char *base = static_cast<const char *>(d_samples);
+  auto single = [&](size_t b) {
+    if (!s[b].frames) return (int)GLFER_OK;
+    return ftest_single(p, base + s[b].off * esz, 0, s[b].frames, d_psd ? d_psd + s[b].row * (size_t)p->pitch : nullptr,
+                        d_ftest + s[b].row * (size_t)p->bins, mu_live, st);
+  };
+  if (p->n < 256 || nstreams == 1) {
+    for (size_t b = 0; b < nstreams; b++) {
+      const int rc = single(b);
+      if (rc != GLFER_OK) return rc;
+    }
+    return GLFER_OK;
+  }
+  DeviceGuard guard(p->cfg.device);
+  HIP_TRY(guard.error());
+  {
+    const int trc = ftest_tables(p);
+    if (trc != GLFER_OK) return trc;
+  }
+  size_t ymax = 0;
+  if (const int yrc = grid_y_limit(2, &ymax); yrc != GLFER_OK) return yrc;
+  for (size_t c0 = 0; c0 < nstreams; c0 += ymax) {      // above the grid's y limit: chunks of it
+    const unsigned nb = (unsigned)std::min(nstreams - c0, ymax);
+    int rc;
+    if (nb == 1) {
+      rc = single(c0);
+    } else {
+      const RaggedChunk c{p, s.data() + c0, nb, base, d_psd, st, esz, 0};   // (esz: the raw samples'; first_inside is not used)
+      rc = ftest_ragged_chunk(c, d_ftest, mu_live);
+    }
+    if (rc != GLFER_OK) return rc;
+  }
+  return GLFER_OK;
+}
+
+int glfer_hip_mtm_ftest_ragged_device(glfer_hip_plan *p, const void *d_samples, size_t nstreams, const size_t *offsets,
+                                      const size_t *lengths, float *d_ftest, int mu_live, size_t *row_starts, void *hip_stream) {
+  return ftest_ragged(p, d_samples, nstreams, offsets, lengths, nullptr, false, d_ftest, mu_live, row_starts, (hipStream_t)hip_stream);
+}
+
+int glfer_hip_mtm_rows_ftest_ragged_device(glfer_hip_plan *p, const void *d_samples, size_t nstreams, const size_t *offsets,
+                                           const size_t *lengths, float *d_psd, float *d_ftest, int mu_live, size_t *row_starts,
+                                           void *hip_stream) {
+  return ftest_ragged(p, d_samples, nstreams, offsets, lengths, d_psd, true, d_ftest, mu_live, row_starts, (hipStream_t)hip_stream);
+}
+
 int glfer_hip_submean_device(const void *d_in, float *d_out, int hop, size_t nhops, int sample_format,
                              void *hip_stream) {
   if (!d_in || !d_out || hop < 1 || sample_format < 0 || sample_format > 2) return GLFER_E_ARG;

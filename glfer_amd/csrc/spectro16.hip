@@ -90,8 +90,13 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16_kernel(S
   // BAT: the instantiations a batch launches (nbatch > 1) -- blockIdx.y is the stream; the single-stream ones are the code as it was
   if constexpr (BAT != 0) {
     GLFER_STREAM_SELECT(p);
+#ifdef GLFER_RAGGED
+    // (packed rows: the stream's first F row comes from its table entry; F alone: psd NULL and psd_off 0, so psd stays NULL)
+    if constexpr (FT != 0) p.ftest += p.ragged[blockIdx.y].ftest_off;
+#else
     // (F alone: psd stays NULL, psd_batch_stride is 0; ROWS: glfer_batch_select has moved psd on by psd_batch_stride)
     if constexpr (FT != 0) p.ftest += (long long)blockIdx.y * p.ftest_batch_stride;
+#endif
   }
   static_assert(ROWS == 0 || FT != 0, "rows beside F: the F forms");
   static_assert(KM == 0 || (!GEN && (KM == 16 || KM == 8 || KM == 4)), "in-kernel mean removal: the plain path");
@@ -640,9 +645,6 @@ static hipError_t launch16_fmt(const SpectroParams &p, hipStream_t st) {
   const long long cap = glfer_batch_cap(4 * resident, p.nbatch);   // (a batch shares it among its streams)
   unsigned grid = (unsigned)(work < cap ? work : cap);
   if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
-#ifdef GLFER_RAGGED
-  if (p.ftest) return hipErrorInvalidValue;          // (the rows entry only)
-#else
   if (p.ftest) {
     // the F statistic: one taper per round (two spill-free wavefronts per SIMD: mu and the sums are 48 more registers)
     if (p.nonlin || p.spec || p.mean_inkernel || !p.ft_U0) return hipErrorInvalidValue;
@@ -658,7 +660,6 @@ static hipError_t launch16_fmt(const SpectroParams &p, hipStream_t st) {
     else hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
     return hipGetLastError();
   }
-#endif
   if (p.mean_inkernel) {
     // frames inside the stream only, history from the stream, a hop of 4, 8 or 16 sixteenths of the block
     if (p.nonlin || p.spec || p.history_mode || p.frame0 * (long long)p.H < (long long)p.R) return hipErrorInvalidValue;

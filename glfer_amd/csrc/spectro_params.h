@@ -8,7 +8,11 @@ enum { GLFER_FMT_F32 = 0, GLFER_FMT_S16 = 1, GLFER_FMT_U8 = 2 };
 
 /* One stream of a ragged launch (glfer_hip_spectrogram_ragged_device): SpectroParams::ragged[blockIdx.y].  The offsets are
    relative to the launch's own stream / psd / means (virtual bases, so they may be negative); frame0 and nframes are the
-   stream's own piece of this launch (its head, its body or its tail frames).  nframes <= 0: nothing for this stream here. */
+   stream's own piece of this launch (its head, its body or its tail frames).  nframes <= 0: nothing for this stream here.
+   ftest_off (glfer_hip_mtm_ftest_ragged_device / _rows_ftest_ragged_device): the stream's first F row of this launch,
+   (R_b + frame0) * (N/2+1) floats from the launch's ftest -- F rows are dense whatever the PSD pitch, so it is not psd_off.
+   Only spectro16_kernel's FT forms read it (appended: the rows kernels load the fields they always did).  F alone leaves
+   psd NULL and psd_off 0, so that the select's psd + psd_off stays NULL. */
 struct GlferRaggedEntry {
   long long stream_off;    /* bytes                                                          */
   long long psd_off;       /* floats                                                         */
@@ -16,6 +20,7 @@ struct GlferRaggedEntry {
   long long frame0;
   int nframes;
   int reserved;
+  long long ftest_off;     /* floats (the F forms)                                            */
 };
 /* One stream of a ragged hop-means / corrected-copy launch (submean_seq.hip, spectro16.hip's submean kernels, RAG forms) */
 struct GlferRaggedHops {
@@ -124,7 +129,8 @@ struct SpectroParams {
   long long avg_batch_stride;   /* doubles from one stream's first averaged row (avg) to the next one's                        */
   long long avg_ret_batch_stride;   /* doubles from one stream's first return values (avg_ret) to the next one's               */
   long long ftest_batch_stride; /* floats from one stream's first F row (ftest) to the next one's (glfer_hip_mtm_ftest_batch_device:
-                                   psd NULL and psd_batch_stride 0 there); spectro16_kernel's FT forms add it at entry          */
+                                   psd NULL and psd_batch_stride 0 there); spectro16_kernel's FT forms add it at entry (their ragged
+                                   instantiations take GlferRaggedEntry::ftest_off instead)                                    */
   /* the multitaper rows beside F (glfer_hip_mtm_rows_ftest_device): psd != NULL with ftest, pitch and psd_batch_stride as for the rows */
   const float *ft_cj;      /* device: [ntap], 1 / (N (1 + sig_j)): the weight of taper j's |y_j|^2 in the row (mtm.c:212-219, fft.c:212-216).
                               The F tables hold the tapers unscaled, so the rows' weights ride here; read by the ROWS forms only.

@@ -234,7 +234,8 @@ int glfer_hip_spectrogram_device(glfer_hip_plan *plan, const void *d_stream, siz
  * waterfalls: glfer_hip_waterfall_batch_device.
  * The harmonic F-test of many streams: glfer_hip_mtm_ftest_batch_device below.
  * Streams of unequal length: glfer_hip_spectrogram_ragged_device below; their moving average and waterfall:
- * glfer_hip_avg_ragged_device, glfer_hip_spectrogram_avg_ragged_device and glfer_hip_waterfall_ragged_device.
+ * glfer_hip_avg_ragged_device, glfer_hip_spectrogram_avg_ragged_device and glfer_hip_waterfall_ragged_device; their F-test:
+ * glfer_hip_mtm_ftest_ragged_device and glfer_hip_mtm_rows_ftest_ragged_device.
  * Not covered: batched host / WAV / workers entries, the halfcomplex-spectrum output, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as they are. */
 int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams,
                                        size_t stream_pitch, size_t nsamples, size_t first_frame,
@@ -270,7 +271,8 @@ int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_strea
  * host memory that is gone when the call returns, which a captured copy would read at every replay).  nstreams == 0 or no frame at all: GLFER_OK, nothing written.
  * Limits: whole streams only (no first_frame / nframes sub-range), device-resident samples only.  The moving average and
  * the waterfall of ragged rows: glfer_hip_avg_ragged_device, glfer_hip_spectrogram_avg_ragged_device and
- * glfer_hip_waterfall_ragged_device below.  Not built: the ragged F-test and rows-and-F, the average taken inside the
+ * glfer_hip_waterfall_ragged_device below; the harmonic F-test and the rows-and-F pair of ragged streams:
+ * glfer_hip_mtm_ftest_ragged_device and glfer_hip_mtm_rows_ftest_ragged_device.  Not built: the average taken inside the
  * estimator launch for ragged calls, host / WAV ragged entries.  Asynchronous on hip_stream. */
 size_t glfer_hip_ragged_frames(const glfer_hip_plan *plan, size_t nstreams, const size_t *lengths, size_t *row_starts);
 int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *plan, const void *d_samples, size_t nstreams,
@@ -327,7 +329,8 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *plan, const void *d_stream, size_
  * epilogue forms the statistic) goes stream by stream inside the call, the single entry's launches per stream.
  * The F-test tables are made by the first F call on a plan, whichever entry it is; the plan is left as the single entry leaves it.
  * The multitaper rows and F from one pass over the samples: glfer_hip_mtm_rows_ftest_device and its batch form below.
- * Not built: LMP / HP-ARMA batches in one launch set, ragged batches (one length per stream), batched host / WAV entries. */
+ * Streams of unequal length (one length per stream): glfer_hip_mtm_ftest_ragged_device below.
+ * Not built: LMP / HP-ARMA batches in one launch set, batched host / WAV entries. */
 int glfer_hip_mtm_ftest_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams, size_t stream_pitch,
                                      size_t nsamples, size_t first_frame, size_t nframes, float *d_ftest, int mu_live,
                                      void *hip_stream);
@@ -361,6 +364,45 @@ int glfer_hip_mtm_rows_ftest_device(glfer_hip_plan *plan, const void *d_stream, 
 int glfer_hip_mtm_rows_ftest_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams, size_t stream_pitch,
                                           size_t nsamples, size_t first_frame, size_t nframes, float *d_psd, float *d_ftest,
                                           int mu_live, void *hip_stream);
+
+/* The F entries for streams of unequal length in one call: glfer_hip_mtm_ftest_device and glfer_hip_mtm_rows_ftest_device over
+ * the streams glfer_hip_spectrogram_ragged_device takes.  d_samples, offsets, lengths and row_starts mean exactly what they mean
+ * there: one device buffer, HOST offsets / lengths in samples consumed before the call returns, any order, gaps and overlaps
+ * free, even offsets with s16 / u8 samples; row_starts (HOST, optional, [nstreams + 1]) receives R_0 .. R_nstreams.
+ * Each stream is processed WHOLE, from its own zero history: stream b yields frames_b = lengths[b] / hop rows, packed from row
+ * R_b = frames_0 + ... + frames_(b-1) on; glfer_hip_ragged_frames sizes both outputs.
+ *   d_ftest : device, [sum of frames][N/2+1] floats, dense whatever cfg.psd_pitch is, as in every F entry
+ *   d_psd   : device (rows-and-F), [sum of frames][cfg.psd_pitch or N/2+1] floats; the floats between N/2+1 and the pitch are
+ *             not touched
+ * Stream b's F rows are bit for bit those glfer_hip_mtm_ftest_device(plan, d_samples + offsets[b], lengths[b], 0, frames_b, ...)
+ * writes, and its F and PSD rows from the rows-and-F entry those of glfer_hip_mtm_rows_ftest_device for the same arguments --
+ * same mu_live, same GLFER_FTEST_PAIRED, the Nyquist column's x/0 included.  history_mode ZERO_FIRST and ZERO_ALWAYS both.
+ * Arguments, in this order (1-8 before any device is touched):
+ *   1. GLFER_E_ARG for a NULL plan;
+ *   2. GLFER_E_ARG for a plan that is not MTM or has N > 16384;
+ *   3. GLFER_OK with row_starts[0] = 0 and nothing launched for nstreams == 0;
+ *   4. GLFER_E_ARG for NULL offsets / lengths;
+ *   5. GLFER_E_ARG for any of the ragged rows entry's per-stream checks: more than 2^31 - 1 frames in a stream, an odd offset
+ *      with integer samples, sizes that overflow size_t (rows sized with the pitch for the rows-and-F entry, with N/2+1 for F);
+ *   6. row_starts is filled;
+ *   7. GLFER_OK with nothing written if no stream has a frame;
+ *   8. GLFER_E_ARG for a NULL d_samples, d_ftest or (rows-and-F) d_psd;
+ *   9. GLFER_E_ARG for a hip_stream under graph capture (the per-stream tables are uploaded from host memory that is gone when
+ *      the call returns, as in glfer_hip_spectrogram_ragged_device).
+ * N = 256 .. 16384 with two or more streams: a launch count that depends neither on nstreams nor on the lengths.  With sub_mean
+ * 1 or 2, one set of hop-means and corrected-copy launches over hops [0, frames_b) of every stream (the F entries correct every
+ * frame through copies, so there is no head / body / tail cut), then ONE launch of the F statistic's kernel; without mean
+ * removal that one launch from the raw samples.  blockIdx.y indexes a per-stream table that carries the stream's samples, its
+ * first PSD row (in units of the pitch) and, separately, its first F row (in units of N/2+1).  The form -- one sequence per
+ * transform or paired -- is chosen as the single entry chooses it.  More than 65 535 streams go in chunks of that many; a chunk
+ * of one stream, a call of one stream and N < 256 go through the single entry, stream by stream inside the call.
+ * The F-test tables are made once per call at most; the plan is left as the single entry leaves it.  Asynchronous on hip_stream.
+ * Not built: sub-ranges of a ragged stream, host / WAV ragged F entries. */
+int glfer_hip_mtm_ftest_ragged_device(glfer_hip_plan *plan, const void *d_samples, size_t nstreams, const size_t *offsets,
+                                      const size_t *lengths, float *d_ftest, int mu_live, size_t *row_starts, void *hip_stream);
+int glfer_hip_mtm_rows_ftest_ragged_device(glfer_hip_plan *plan, const void *d_samples, size_t nstreams, const size_t *offsets,
+                                           const size_t *lengths, float *d_psd, float *d_ftest, int mu_live, size_t *row_starts,
+                                           void *hip_stream);
 
 /* Host-buffer entry: h_stream goes to the device in chunks through a two-deep ring (two pinned
  * sample buffers, two device buffers each way; uploads on one stream, kernels and downloads on two:
