@@ -61,6 +61,8 @@ EXPORTS = [
     "glfer_hip_avg_ragged_device", "glfer_hip_spectrogram_avg_ragged_device", "glfer_hip_waterfall_ragged_device",
     # their harmonic F-test, alone and beside the multitaper rows
     "glfer_hip_mtm_ftest_ragged_device", "glfer_hip_mtm_rows_ftest_ragged_device",
+    # the LMP statistic over rows already on the device: one stream, a batch, ragged
+    "glfer_hip_lmp_device", "glfer_hip_lmp_batch_device", "glfer_hip_lmp_ragged_device",
 ]
 
 
@@ -182,6 +184,10 @@ def lib():
         L.glfer_hip_ragged_frames.restype = sz
     if hasattr(L, "glfer_hip_avg_ragged_device"):
         L.glfer_hip_avg_ragged_device.argtypes = [C.c_int, vp, sz, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    if hasattr(L, "glfer_hip_lmp_device"):
+        L.glfer_hip_lmp_device.argtypes = [vp, sz, sz, sz, C.c_int, C.c_int, vp, vp]
+        L.glfer_hip_lmp_batch_device.argtypes = [vp, sz, sz, sz, sz, sz, C.c_int, C.c_int, vp, sz, vp]
+        L.glfer_hip_lmp_ragged_device.argtypes = [vp, sz, vp, C.c_int, C.c_int, vp, vp]
     if hasattr(L, "glfer_hip_spectrogram_avg_ragged_device"):
         L.glfer_hip_spectrogram_avg_ragged_device.argtypes = [vp, vp, sz, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                               vp, vp, vp, vp, vp]
@@ -1100,6 +1106,85 @@ def update_avg(mode, psd, depth, minbin, maxbin, max0=0, n_out=None):
                                       maxbin, int(max0), avg.data_ptr(), ret.data_ptr(), st),
            "glfer_hip_avg_device")
     return avg, ret
+
+
+def _lmp_rows(rows, dim, avg, first_frame, lead):
+    """the checks lmp_statistic and lmp_statistic_batch share: returns (frames held, frames out, bins)"""
+    torch = _torch()
+    if rows.dim() != dim or rows.dtype != torch.float32:
+        raise ValueError("rows: a %d-D float32 tensor" % dim)
+    if not 1 <= int(avg) <= 4096:
+        raise ValueError("avg: 1 .. 4096")
+    first_frame, lead = int(first_frame), int(lead)
+    if first_frame < 0 or lead < 0 or lead > first_frame:
+        raise ValueError("first_frame >= lead >= 0")
+    if lead < min(int(avg) - 1, first_frame):
+        raise ValueError("lead: the rows must reach back min(avg - 1, first_frame) frames")
+    held, bins = rows.size(dim - 2), rows.size(dim - 1)
+    if held < lead or bins < 1:
+        raise ValueError("rows: at least `lead` rows of at least one bin")
+    if not rows.is_cuda:
+        raise ValueError("rows: on the GPU")
+    return held, held - lead, bins
+
+
+def lmp_statistic(rows, avg, first_frame=0, lead=0):
+    """The LMP detection statistic (lmp.c:132-160, glfer_hip_lmp_device) over rectangular-window periodogram rows already on the
+    GPU: rows [lead + frames][bins] float32 are frames first_frame - lead .. of one stream (FftParams(window_type=rectangular)
+    rows, from run / run_batch / run_ragged), lead >= min(avg - 1, first_frame): the frames the ring still holds at first_frame.
+    Returns [frames][bins] float32: bit for bit Spectrogram(LmpParams(avg=avg, ...)).run(x, first_frame, frames)."""
+    torch = _torch()
+    held, frames, bins = _lmp_rows(rows, 2, avg, first_frame, lead)
+    if not rows.is_contiguous():
+        raise ValueError("rows: contiguous")
+    out = torch.empty((frames, bins), dtype=torch.float32, device=rows.device)
+    st = C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
+    _check(lib().glfer_hip_lmp_device(rows.data_ptr(), int(first_frame) - int(lead), int(first_frame), frames, bins, int(avg),
+                                      out.data_ptr(), st), "glfer_hip_lmp_device")
+    return out
+
+
+def lmp_statistic_batch(rows, avg, first_frame=0, lead=0):
+    """lmp_statistic over B independent streams in one launch set (glfer_hip_lmp_batch_device): rows [B][lead + frames][bins]
+    float32 on the GPU, the same first_frame and lead for every stream, each stream's ring empty before its frame 0.  The
+    streams may be any number of floats apart (rows.stride(0): a slice along the frames of a larger tensor is taken as it is).
+    Returns [B][frames][bins] float32; stream b's rows are lmp_statistic(rows[b], ...)'s."""
+    torch = _torch()
+    held, frames, bins = _lmp_rows(rows, 3, avg, first_frame, lead)
+    nb = rows.size(0)
+    if nb > 1 and held > 0 and not (rows.stride(2) == 1 and (held == 1 or rows.stride(1) == bins) and rows.stride(0) >= held * bins):
+        raise ValueError("rows: each stream's rows dense, the streams at least a stream's rows apart")
+    if nb <= 1 or held == 0:
+        rows = rows.contiguous()
+    out = torch.empty((nb, frames, bins), dtype=torch.float32, device=rows.device)
+    st = C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
+    _check(lib().glfer_hip_lmp_batch_device(rows.data_ptr(), nb, rows.stride(0) if nb > 1 else held * bins, int(first_frame) - int(lead),
+                                            int(first_frame), frames, bins, int(avg), out.data_ptr(), frames * bins, st),
+           "glfer_hip_lmp_batch_device")
+    return out
+
+
+def lmp_statistic_ragged(rows, row_starts, avg, out=None):
+    """lmp_statistic over packed rows of streams of unequal length (glfer_hip_lmp_ragged_device): rows [rows][bins] float32 on
+    the GPU as Spectrogram.run_ragged returns them for a rectangular-window FFT plan, stream b its rows
+    [row_starts[b], row_starts[b + 1]), whole from its frame 0.  Returns ([rows][bins] float32 packed the same way,
+    row_starts); rows outside every stream are left unwritten (out: a tensor like rows to write into)."""
+    torch = _torch()
+    if rows.dim() != 2 or rows.dtype != torch.float32:
+        raise ValueError("rows: a 2-D float32 tensor")
+    if not 1 <= int(avg) <= 4096:
+        raise ValueError("avg: 1 .. 4096")
+    starts = _row_starts(row_starts, rows.size(0))
+    if not (rows.is_cuda and rows.is_contiguous()) or rows.size(1) < 1:
+        raise ValueError("rows: contiguous, on the GPU")
+    if out is None:
+        out = torch.empty_like(rows)
+    elif not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == rows.shape and out.device == rows.device):
+        raise ValueError("out: a contiguous float32 tensor of the shape of rows, on their device")
+    st = C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
+    _check(lib().glfer_hip_lmp_ragged_device(rows.data_ptr(), starts.size - 1, starts.ctypes.data, rows.size(1), int(avg), out.data_ptr(), st),
+           "glfer_hip_lmp_ragged_device")
+    return out, starts.astype(np.int64)
 
 
 def update_avg_batch(mode, psd, depth, minbin, maxbin, max0=0, n_out=None):

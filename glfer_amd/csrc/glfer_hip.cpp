@@ -34,6 +34,10 @@ extern "C" hipError_t glfer_launch_avg_cum(const float *psd, size_t nframes, int
                                            int minbin, int maxbin, double *cum, hipStream_t st);
 extern "C" hipError_t glfer_launch_lmp(const float *rows, long long row0, long long first, size_t nframes, int bins,
                                        int nl, float *out, hipStream_t st);
+extern "C" hipError_t glfer_launch_lmp_batch(const float *rows, long long row0, long long first, size_t nframes, int bins, int nl,
+                                             float *out, unsigned nb, long long row_stride, long long out_stride, hipStream_t st);
+extern "C" hipError_t glfer_launch_lmp_ragged(const float *rows, const size_t *row_starts, size_t nstreams, int bins, int nl, float *out,
+                                              hipStream_t st);
 extern "C" hipError_t glfer_launch_ftest(const float *spec, size_t nframes, int n, int ntap, const double *U0,
                                          float sum_U0_sqr, int mu_live, float *ftest, hipStream_t st);
 extern "C" hipError_t glfer_launch_ftest_rows(const float *spec, size_t nframes, int n, int ntap, const double *U0,
@@ -1616,7 +1620,12 @@ static int grid_y_limit(int floor, size_t *ymax) {
 
 // the plans whose rows a batch computes in the launches of one stream (the others go stream by stream)
 static bool batch_one_launch(const glfer_hip_plan *p) {
-  return (p->cfg.mode == GLFER_MODE_FFT || p->cfg.mode == GLFER_MODE_MTM) && p->n >= 256 && p->n <= 16384;
+  return (p->cfg.mode == GLFER_MODE_FFT || p->cfg.mode == GLFER_MODE_MTM || p->cfg.mode == GLFER_MODE_LMP) && p->n >= 256 && p->n <= 16384;
+}
+// LMP batches keep the periodograms of a chunk of streams in scratch: the streams whose rows (stream_bytes each) take at most
+// half the kept-scratch cap (plan.h scratch_cap: glfer_hip_scratch_limit / GLFER_SCRATCH_CAP_MB, 16 GiB by default), one at least
+static size_t lmp_chunk_streams(size_t stream_bytes) {
+  return std::max<size_t>(1, (glfer::scratch_cap() / 2) / std::max<size_t>(stream_bytes, 1));
 }
 static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams, size_t stream_pitch, size_t nsamples, size_t first,
                       size_t nframes, float *d_psd, size_t psd_bs, hipStream_t st);
@@ -1655,29 +1664,54 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
   HIP_TRY(guard.error());
   size_t ymax = 0;
   if (const int yrc = grid_y_limit(1, &ymax); yrc != GLFER_OK) return yrc;
+  // LMP (lmp.c:101-181): the periodograms of frames [first - back, first + nframes) of every stream go to scratch -- back: the
+  // frames the ring still holds at `first`, recomputed as glfer_run_device recomputes them, the mean-corrected copy reaching
+  // back with them -- and one batched statistic launch set follows (glfer_launch_lmp_batch).  The call is cut into chunks of
+  // streams whose periodograms take at most half the kept-scratch cap (glfer_hip_scratch_limit; 8 GiB by default), one stream
+  // at least: the launch count grows with the bytes, not with the streams.
+  const bool lmp = p->cfg.mode == GLFER_MODE_LMP;
+  const size_t back = lmp ? std::min<size_t>((size_t)p->lmp_av - 1, first) : 0;
+  const size_t nrows = nframes + back, lmp_bs = nrows * (size_t)p->bins;
+  if (lmp) ymax = std::min(ymax, lmp_chunk_streams(lmp_bs * sizeof(float)));
   for (size_t c0 = 0; c0 < nstreams; c0 += ymax) {      // batches above the grid's y limit: chunks of it
     const unsigned nb = (unsigned)std::min(nstreams - c0, ymax);
+    if (lmp && nb == 1) {                               // (a chunk of one stream: the single-stream entry)
+      const int rc = glfer_run_device(p, base + c0 * stream_pitch * esz, nsamples, first, nframes, d_psd + c0 * psd_bs, nullptr, st);
+      if (rc != GLFER_OK) return rc;
+      continue;
+    }
+    float *rows = nullptr;
+    if (lmp) {
+      const hipError_t e = glfer::scratch_malloc((void **)&rows, (size_t)nb * lmp_bs * sizeof(float), st);
+      if (e != hipSuccess) return hip_fail(e, "scratch (lmp rows, batch)");
+    }
     SpectroParams sp;
     fill_params(p, sp);
     sp.stream = base + c0 * stream_pitch * esz;
-    sp.frame0 = (long long)first;
-    sp.nframes = (int)nframes;
-    sp.psd = d_psd + c0 * psd_bs;
+    sp.frame0 = (long long)(first - back);
+    sp.nframes = (int)nrows;
+    sp.psd = lmp ? rows : d_psd + c0 * psd_bs;
     sp.nbatch = (int)nb;
     sp.batch_stride = (long long)(stream_pitch * esz);
-    sp.psd_batch_stride = (long long)psd_bs;
+    sp.psd_batch_stride = (long long)(lmp ? lmp_bs : psd_bs);
     int rc = GLFER_OK;
     if (p->cfg.sub_mean && mean_inkernel_ok(p, sp, nullptr, -1)) {
       rc = launch_mean_inkernel(p, sp, st);
     } else {
       float *scratch = nullptr;
-      if (p->cfg.sub_mean) rc = submean_scratch(p, sp, first, nframes, st, &scratch);
+      if (p->cfg.sub_mean) rc = submean_scratch(p, sp, first - back, nrows, st, &scratch);
       if (rc == GLFER_OK) {
         const hipError_t e = launch_by_n(sp, p->n, st);
         if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch)");
       }
       if (scratch) glfer::scratch_free(scratch, st);
     }
+    if (rc == GLFER_OK && lmp) {
+      const hipError_t e = glfer_launch_lmp_batch(rows, (long long)(first - back), (long long)first, nframes, p->bins, p->lmp_av,
+                                                  d_psd + c0 * psd_bs, nb, (long long)lmp_bs, (long long)psd_bs, st);
+      if (e != hipSuccess) rc = hip_fail(e, "lmp launch (batch)");
+    }
+    if (rows) glfer::scratch_free(rows, st);
     if (rc != GLFER_OK) return rc;
   }
   return GLFER_OK;
@@ -1986,7 +2020,7 @@ int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *p, const void *d_samples
     if (!s[b].frames) return (int)GLFER_OK;
     return glfer_run_device(p, base + s[b].off * esz, lengths[b], 0, s[b].frames, d_psd + s[b].row * (size_t)p->pitch, nullptr, st);
   };
-  if (!batch_one_launch(p) || nstreams == 1) {      // LMP, HP-ARMA, N outside 256 .. 16384: stream by stream, as batch_rows
+  if (!batch_one_launch(p) || nstreams == 1) {      // HP-ARMA, N outside 256 .. 16384: stream by stream, as batch_rows
     for (size_t b = 0; b < nstreams; b++) {
       const int rc = single(b);
       if (rc != GLFER_OK) return rc;
@@ -1997,16 +2031,41 @@ int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *p, const void *d_samples
   HIP_TRY(guard.error());
   size_t ymax = 0;
   if (const int yrc = grid_y_limit(2, &ymax); yrc != GLFER_OK) return yrc;
-  for (size_t c0 = 0; c0 < nstreams; c0 += ymax) {      // above the grid's y limit: chunks of it
-    const unsigned nb = (unsigned)std::min(nstreams - c0, ymax);
-    int rc;
+  // LMP: a chunk's packed periodogram rows go to scratch (the ragged launch set, as for an FFT plan) and the ragged statistic runs
+  // over the same row starts into d_psd (glfer_launch_lmp_ragged).  A chunk takes the streams whose rows fit half the kept-scratch
+  // cap (lmp_chunk_streams), one at least.
+  const bool lmp = p->cfg.mode == GLFER_MODE_LMP;
+  const size_t bins = (size_t)p->bins, lmp_rows_max = lmp_chunk_streams(bins * sizeof(float));
+  for (size_t c0 = 0; c0 < nstreams;) {                 // above the grid's y limit: chunks of it
+    unsigned nb = (unsigned)std::min(nstreams - c0, ymax);
+    if (lmp) {
+      unsigned k = 1;
+      while (k < nb && s[c0 + k].row + s[c0 + k].frames - s[c0].row <= lmp_rows_max) k++;
+      nb = k;
+    }
+    int rc = GLFER_OK;
     if (nb == 1) {
       rc = single(c0);
-    } else {
+    } else if (!lmp) {
       RaggedChunk c{p, s.data() + c0, nb, base, d_psd, st, esz, 0};
       rc = c.run();
+    } else if (const size_t r0 = s[c0].row, nrows = s[c0 + nb - 1].row + s[c0 + nb - 1].frames - r0; nrows != 0) {
+      std::vector<RaggedStream> rel(s.begin() + c0, s.begin() + c0 + nb);      // the chunk's streams, rows counted from its scratch
+      std::vector<size_t> starts(nb + 1, nrows);
+      for (unsigned b = 0; b < nb; b++) starts[b] = rel[b].row -= r0;
+      float *rows = nullptr;
+      const hipError_t e = glfer::scratch_malloc((void **)&rows, nrows * bins * sizeof(float), st);
+      if (e != hipSuccess) return hip_fail(e, "scratch (lmp rows, ragged)");
+      RaggedChunk c{p, rel.data(), nb, base, rows, st, esz, 0};
+      rc = c.run();
+      if (rc == GLFER_OK) {
+        const hipError_t le = glfer_launch_lmp_ragged(rows, starts.data(), nb, p->bins, p->lmp_av, d_psd + r0 * bins, st);
+        if (le != hipSuccess) rc = hip_fail(le, "lmp launch (ragged)");
+      }
+      glfer::scratch_free(rows, st);
     }
     if (rc != GLFER_OK) return rc;
+    c0 += nb;
   }
   return GLFER_OK;
 }
@@ -2854,6 +2913,65 @@ int glfer_hip_avg_cum_device(const float *d_psd, size_t nframes, int bins, int n
   DeviceGuard guard(data_device(d_psd));
   HIP_TRY(guard.error());
   HIP_TRY(glfer_launch_avg_cum(d_psd, nframes, bins, n_out, depth, minbin, maxbin, d_cum, (hipStream_t)hip_stream));
+  return GLFER_OK;
+}
+
+// The LMP statistic (lmp.c:132-160) over rectangular-window periodogram rows the caller holds (glfer_hip.h): what an LMP plan's
+// entries run after their transforms.  The ring size and the row length are checked first, then "nothing to do", then the rest.
+static bool lmp_args_ok(int bins, int lmp_av) { return bins >= 1 && bins <= 65535 * 256 && lmp_av >= 1 && lmp_av <= 4096; }   // (the bin blocks fit a grid dimension)
+// rows from frame row_first on hold everything frames [first, ..) sum over: the ring reaches back min(lmp_av - 1, first) frames
+static bool lmp_rows_reach(size_t row_first, size_t first, int lmp_av) {
+  return row_first <= first - std::min<size_t>((size_t)lmp_av - 1, first);
+}
+
+int glfer_hip_lmp_device(const float *d_rows, size_t row_first, size_t first, size_t nframes, int bins, int lmp_av, float *d_out,
+                         void *hip_stream) {
+  if (!lmp_args_ok(bins, lmp_av)) return GLFER_E_ARG;
+  if (nframes == 0) return GLFER_OK;
+  if (!d_rows || !d_out) return GLFER_E_ARG;
+  if (nframes > 0x7fffffffu || first > (size_t)LLONG_MAX - nframes || !lmp_rows_reach(row_first, first, lmp_av)) return GLFER_E_ARG;
+  DeviceGuard guard(data_device(d_rows));
+  HIP_TRY(guard.error());
+  HIP_TRY(glfer_launch_lmp(d_rows, (long long)row_first, (long long)first, nframes, bins, lmp_av, d_out, (hipStream_t)hip_stream));
+  return GLFER_OK;
+}
+
+int glfer_hip_lmp_batch_device(const float *d_rows, size_t nstreams, size_t row_stride, size_t row_first, size_t first, size_t nframes,
+                               int bins, int lmp_av, float *d_out, size_t out_stride, void *hip_stream) {
+  if (!lmp_args_ok(bins, lmp_av)) return GLFER_E_ARG;
+  if (nstreams == 0 || nframes == 0) return GLFER_OK;
+  if (!d_rows || !d_out) return GLFER_E_ARG;
+  if (nframes > 0x7fffffffu || first > (size_t)LLONG_MAX - nframes || !lmp_rows_reach(row_first, first, lmp_av)) return GLFER_E_ARG;
+  // a stream's rows and outputs lie inside its stride; the strides of all streams inside size_t
+  const size_t held = first - row_first + nframes;
+  if (held > SIZE_MAX / sizeof(float) / (size_t)bins || row_stride < held * (size_t)bins || out_stride < nframes * (size_t)bins)
+    return GLFER_E_ARG;
+  if (row_stride > (SIZE_MAX / sizeof(float)) / nstreams || out_stride > (SIZE_MAX / sizeof(float)) / nstreams) return GLFER_E_ARG;
+  DeviceGuard guard(data_device(d_rows));
+  HIP_TRY(guard.error());
+  const size_t chunk = 65535;                                    // streams per launch: the grid's z limit
+  for (size_t c0 = 0; c0 < nstreams; c0 += chunk) {
+    const unsigned nb = (unsigned)std::min(nstreams - c0, chunk);
+    HIP_TRY(glfer_launch_lmp_batch(d_rows + c0 * row_stride, (long long)row_first, (long long)first, nframes, bins, lmp_av,
+                                   d_out + c0 * out_stride, nb, (long long)row_stride, (long long)out_stride, (hipStream_t)hip_stream));
+  }
+  return GLFER_OK;
+}
+
+int glfer_hip_lmp_ragged_device(const float *d_rows, size_t nstreams, const size_t *row_starts, int bins, int lmp_av, float *d_out,
+                                void *hip_stream) {
+  if (!lmp_args_ok(bins, lmp_av)) return GLFER_E_ARG;
+  if (nstreams == 0) return GLFER_OK;
+  if (!row_starts || !glfer::ragged_rows_ok(row_starts, nstreams)) return GLFER_E_ARG;
+  const size_t rows_hi = row_starts[nstreams];
+  if (rows_hi > SIZE_MAX / sizeof(float) / (size_t)bins) return GLFER_E_ARG;
+  if (rows_hi == row_starts[0]) return GLFER_OK;
+  if (!d_rows || !d_out) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (glfer::stream_is_capturing(st)) return GLFER_E_ARG;
+  DeviceGuard guard(data_device(d_rows));
+  HIP_TRY(guard.error());
+  HIP_TRY(glfer_launch_lmp_ragged(d_rows, row_starts, nstreams, bins, lmp_av, d_out, st));
   return GLFER_OK;
 }
 

@@ -3,6 +3,7 @@
 // the reference IS the contract here (every statement below is the reference's statement with the
 // same operand types).
 //   lmp_kernel      lmp.c:132-160   detection statistic over the ring of the last nl periodograms
+//   lmp_*_streams_kernel            the same over many streams in one launch: a batch (blockIdx.z) or ragged (a block table)
 //   ftest_kernel    mtm.c:203-210, 222-233   harmonic F statistic from the tapered spectra and mu
 //   prepare_kernel  fft.c:98-156    what prepare_audio leaves in inbuf_fft, for a batch of frames
 #include <hip/hip_runtime.h>
@@ -10,7 +11,10 @@
 #include <stdint.h>
 #include <type_traits>
 #include <algorithm>
+#include <vector>
 #include "spectro_params.h"
+#include "ragged_cols.hpp"
+#include "lmp_groups.h"
 
 #ifndef GLFER_LMP_RING
 #define GLFER_LMP_RING 1    /* 0: every frame through lmp_kernel (one thread per frame and bin, nl row reads each) */
@@ -210,6 +214,186 @@ __global__ __launch_bounds__(256) void lmp_ring_any_kernel(const float *__restri
   }
 }
 
+// ---- the statistic over many streams in one launch (glfer_launch_lmp_batch, glfer_launch_lmp_ragged).  The three kernels above
+// stay what they are; these are their siblings with a stream dimension, the sums, the slot order and SmallDivisor statement for
+// statement theirs.  Where a block works is uniform over the block and stays in scalar registers:
+//   batch  : blockIdx.z is the stream (two strides), blockIdx.y the group or frame, blockIdx.x the 256 bins -- every stream has
+//            the same row_first / first / nframes;
+//   ragged : blockIdx.x is the launch's flat list of groups (lmp_groups.h; the entry found by bisection, ragged_cols.hpp: the
+//            stream's first row, its frame count, its first block), blockIdx.y the 256 bins -- every stream whole from frame 0.
+struct LmpStreams {
+  long long row_first, first, nframes;   // batch: rows holds frames row_first ..; out frames [first, first + nframes) of each stream
+  long long origin;                      // batch: the frame block (., 0, .) starts at (<= first with the register ring)
+  long long row_stride, out_stride;      // batch: floats from one stream's rows / outputs to the next's
+  RaggedCols r;                          // ragged
+};
+struct LmpWhere {
+  const float *rows;                     // the stream's row of frame row_first
+  float *out;                            // its output row of frame first
+  long long row_first, first, end, f0;   // f0: the block's first frame; end: one past the stream's last
+  int i;                                 // the thread's bin
+};
+template <bool RAGGED>
+__device__ __forceinline__ LmpWhere lmp_where(const float *rows, float *out, int bins, int G, const LmpStreams &s) {
+  LmpWhere w;
+  if constexpr (RAGGED) {
+    const RaggedColsEntry e = ragged_cols_find(s.r, blockIdx.x);
+    w.rows = rows + (size_t)e.row0 * bins;
+    w.out = out + (size_t)e.row0 * bins;
+    w.row_first = 0;
+    w.first = 0;
+    w.end = e.nframes;
+    w.f0 = ((long long)blockIdx.x - e.blk0) * G;
+    w.i = blockIdx.y * 256 + threadIdx.x;
+  } else {
+    w.rows = rows + (long long)blockIdx.z * s.row_stride;
+    w.out = out + (long long)blockIdx.z * s.out_stride;
+    w.row_first = s.row_first;
+    w.first = s.first;
+    w.end = s.first + s.nframes;
+    w.f0 = s.origin + (long long)blockIdx.y * G;
+    w.i = blockIdx.x * 256 + threadIdx.x;
+  }
+  return w;
+}
+
+// lmp_ring_kernel with the stream dimension and NO head launch: the first group of a stream starts at the multiple of NL at or
+// below `first` (LmpStreams::origin) and the frames before `first` go through the ring without being summed or stored.  Their
+// rows are in the buffer (the caller's rows reach back min(NL - 1, first) frames); what is preloaded from before row_first is
+// zero and is overwritten before frame `first` is summed.
+template <int NL, int G, bool RAGGED>
+__global__ __launch_bounds__(256) void lmp_ring_streams_kernel(const float *__restrict__ rows_all, int bins, double c_neg, double c_den,
+                                                               double recip_nl, double recip_nl1, float *__restrict__ out_all,
+                                                               LmpStreams s) {
+  static_assert(G % NL == 0, "a group is whole turns of the ring");
+  const LmpWhere p = lmp_where<RAGGED>(rows_all, out_all, bins, G, s);
+  const int i = p.i;
+  const long long f0 = p.f0, end = p.end;                          // f0: a multiple of NL
+  if (i >= bins || f0 >= end) return;
+  const float *col = p.rows + (size_t)(f0 - p.row_first) * bins + i;   // row of frame f0; frame f0 + k is k rows down
+  float w[NL], r[G];
+#pragma unroll
+  for (int j = 0; j < NL; j++)     // frame f0 - NL + j sits in slot j; slot 0 is f0's own before it is ever summed
+    w[j] = (j > 0 && f0 - NL + j >= p.row_first) ? *(col - (size_t)(NL - j) * bins) : 0.0f;
+#pragma unroll
+  for (int k = 0; k < G; k++) r[k] = f0 + k < end ? col[(size_t)k * bins] : 0.0f;
+  const SmallDivisor by_nl((double)NL, recip_nl), by_nl1((double)(NL - 1), recip_nl1);
+#pragma unroll
+  for (int k = 0; k < G; k++) {
+    if (f0 + k >= end) return;
+    w[k % NL] = r[k];
+    if (f0 + k < p.first) continue;                                // before the call's first frame: into the ring only
+    float *o = p.out + (size_t)(f0 + k - p.first) * bins;
+    if (i == 0) {                                                  // lmp.c:160
+      o[0] = 1e-3;
+      continue;
+    }
+    double my = 0.0, sy = 0.0;
+#pragma unroll
+    for (int j = 0; j < NL; j++) my += w[j];                       // lmp.c:134-140
+    my = by_nl(my);
+#pragma unroll
+    for (int j = 0; j < NL; j++) {                                 // lmp.c:143-149
+      const double t = w[j] - my;
+      sy += t * t;
+    }
+    sy = by_nl1(sy);
+    double v_hat = my * my - sy;                                   // lmp.c:153-159
+    if (v_hat < 0.0) v_hat = 0.0;
+    v_hat = 0.5 * (my - sqrt(v_hat));
+    float q = c_neg + (NL * my) / (c_den * v_hat);
+    if (q <= 1.0e-3) q = 1e-3;
+    o[i] = q;
+  }
+}
+
+// lmp_ring_any_kernel with the stream dimension: groups of G frames from `first` (batch) or from the stream's frame 0 (ragged)
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void lmp_ring_any_streams_kernel(const float *__restrict__ rows_all, int bins, int nl, int G, double c_neg,
+                                                                   double c_den, double recip_nl, double recip_nl1,
+                                                                   float *__restrict__ out_all, LmpStreams s) {
+  extern __shared__ float ring[];                                  // [nl][256]
+  const LmpWhere p = lmp_where<RAGGED>(rows_all, out_all, bins, G, s);
+  const int i = p.i;
+  const long long f0 = p.f0, row0 = p.row_first, first = p.first;
+  const long long last = p.end, end = f0 + G < last ? f0 + G : last;
+  if (f0 >= last) return;
+  const bool live = i < bins;
+  float *w = ring + threadIdx.x;
+  const float *col = p.rows + (live ? (size_t)i : 0);
+  // what the ring holds when frame f0 arrives: frames f0 - nl + 1 .. f0 - 1 in their slots (zero before the stream), f0's own slot still to come
+  for (int d = 1; d < nl; d++) {
+    const long long f = f0 - d;
+    const int slot = (int)(((f % nl) + nl) % nl);
+    w[slot * 256] = (f >= 0 && live) ? col[(size_t)(f - row0) * bins] : 0.0f;
+  }
+  const SmallDivisor by_nl((double)nl, recip_nl), by_nl1((double)(nl - 1), recip_nl1);
+  int slot = (int)(f0 % nl);
+  for (long long f = f0; f < end; f++) {
+    w[slot * 256] = live ? col[(size_t)(f - row0) * bins] : 0.0f;
+    slot = slot + 1 == nl ? 0 : slot + 1;
+    if (!live) continue;
+    float *o = p.out + (size_t)(f - first) * bins;
+    if (i == 0) {                                                  // lmp.c:160
+      o[0] = 1e-3;
+      continue;
+    }
+    double my = 0.0, sy = 0.0;
+    for (int j = 0; j < nl; j++) my += w[j * 256];                 // lmp.c:134-140
+    my = by_nl(my);
+    for (int j = 0; j < nl; j++) {                                 // lmp.c:143-149
+      const double t = w[j * 256] - my;
+      sy += t * t;
+    }
+    sy = by_nl1(sy);
+    double v_hat = my * my - sy;                                   // lmp.c:153-159
+    if (v_hat < 0.0) v_hat = 0.0;
+    v_hat = 0.5 * (my - sqrt(v_hat));
+    float q = c_neg + (nl * my) / (c_den * v_hat);
+    if (q <= 1.0e-3) q = 1e-3;
+    o[i] = q;
+  }
+}
+
+// lmp_kernel<0> with the stream dimension: one thread per (stream, frame, bin), any nl, by loops (G = 1: a block is a frame)
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void lmp_streams_kernel(const float *__restrict__ rows_all, int bins, int nl, double c_neg, double c_den,
+                                                          double recip_nl, double recip_nl1, float *__restrict__ out_all, LmpStreams s) {
+  const LmpWhere p = lmp_where<RAGGED>(rows_all, out_all, bins, 1, s);
+  const int i = p.i;
+  const long long f = p.f0;
+  if (f >= p.end || i >= bins) return;
+  float *o = p.out + (size_t)(f - p.first) * bins;
+  if (i == 0) {                                                    // lmp.c:160
+    o[0] = 1e-3;
+    return;
+  }
+  const int jl = (int)(f % nl);                                    // f mod nl
+  const float *col = p.rows + (size_t)(f - p.row_first) * bins + i;   // this frame's row; frame f - d is d rows up
+  const SmallDivisor by_nl((double)nl, recip_nl), by_nl1((double)(nl - 1), recip_nl1);
+  double my = 0.0, sy = 0.0;
+  int d = jl;                                                      // slot j holds frame f - ((jl - j) mod nl)
+  for (int j = 0; j < nl; j++) {                                   // lmp.c:134-140
+    const float v = (long long)d <= f ? *(col - (size_t)d * bins) : 0.0f;
+    my += v;
+    d = d == 0 ? nl - 1 : d - 1;
+  }
+  my = by_nl(my);
+  d = jl;
+  for (int j = 0; j < nl; j++) {                                   // lmp.c:143-149
+    const float v = (long long)d <= f ? *(col - (size_t)d * bins) : 0.0f;
+    sy += (v - my) * (v - my);
+    d = d == 0 ? nl - 1 : d - 1;
+  }
+  sy = by_nl1(sy);
+  double v_hat = my * my - sy;                                     // lmp.c:153-159
+  if (v_hat < 0.0) v_hat = 0.0;
+  v_hat = 0.5 * (my - sqrt(v_hat));
+  float r = c_neg + (nl * my) / (c_den * v_hat);
+  if (r <= 1.0e-3) r = 1e-3;
+  o[i] = r;
+}
+
 // One thread per (frame, bin).  spec: [ntap + 1][nframes][n] halfcomplex spectra (fft_radix2.c
 // layout) of the frame under taper j, the last one under hn (mu); mu_live = 0: mu is all zeros (the
 // reference build without FFTW never writes it, mtm.c:173).
@@ -362,6 +546,108 @@ extern "C" hipError_t glfer_launch_lmp(const float *rows, long long row0, long l
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// glfer_launch_lmp over nb <= 65535 streams (blockIdx.z): stream b's rows at rows + b * row_stride floats (frames row0 ..), its
+// outputs at out + b * out_stride.  The forms are glfer_launch_lmp's by ring size; the register ring takes no head launch
+// (lmp_ring_streams_kernel), so a call is ONE launch per 65535 groups or frames, whatever nb is.
+extern "C" hipError_t glfer_launch_lmp_batch(const float *rows, long long row0, long long first, size_t nframes, int bins, int nl,
+                                             float *out, unsigned nb, long long row_stride, long long out_stride, hipStream_t st) {
+  if (nframes == 0 || nb == 0) return hipSuccess;
+  if (nl < 1 || bins < 1 || nb > 65535u || nframes > 65535u * 65535ull) return hipErrorInvalidValue;
+  const double c_neg = -sqrt(nl / 2.0), c_den = 2.0 * sqrt(2.0 * nl), recip_nl = 1.0 / (double)nl, recip_nl1 = 1.0 / (double)(nl - 1);
+  const unsigned bx = (unsigned)((bins + 255) / 256);
+  LmpStreams s{row0, first, (long long)nframes, first, row_stride, out_stride, RaggedCols{nullptr, 0}};
+  const int form = GLFER_LMP_RING ? glfer_lmp_form(nl) : GLFER_LMP_FORM_FRAMES;
+  if (form == GLFER_LMP_FORM_REGISTERS) {
+    const long long origin = first - first % nl;                   // the multiple of nl at or below `first`
+#define GLFER_LMP_RING_BATCH(NLC, GC)                                                                                 \
+  do {                                                                                                                \
+    const size_t groups = ((size_t)(first - origin) + nframes + GC - 1) / GC;                                         \
+    for (size_t g0 = 0; g0 < groups; g0 += 65535) {                                                                   \
+      s.origin = origin + (long long)(g0 * GC);                                                                       \
+      hipLaunchKernelGGL((lmp_ring_streams_kernel<NLC, GC, false>), dim3(bx, (unsigned)std::min<size_t>(65535, groups - g0), nb), \
+                         dim3(256), 0, st, rows, bins, c_neg, c_den, recip_nl, recip_nl1, out, s);                    \
+    }                                                                                                                 \
+  } while (0)
+    if (nl == 2) GLFER_LMP_RING_BATCH(2, 16);
+    else if (nl == 3) GLFER_LMP_RING_BATCH(3, 15);
+    else if (nl == 4) GLFER_LMP_RING_BATCH(4, 16);
+    else GLFER_LMP_RING_BATCH(8, 16);
+#undef GLFER_LMP_RING_BATCH
+    return hipGetLastError();
+  }
+  if (form == GLFER_LMP_FORM_LDS && nframes >= 64) {                // (glfer_launch_lmp's threshold: one stream's frame count)
+    size_t G = 64;
+    while ((nframes + G - 1) / G > 65535) G *= 2;
+    const size_t lds = (size_t)nl * 256 * sizeof(float);
+    hipError_t e = glfer::allow_dynamic_lds((const void *)lmp_ring_any_streams_kernel<false>, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(lmp_ring_any_streams_kernel<false>, dim3(bx, (unsigned)((nframes + G - 1) / G), nb), dim3(256), lds, st, rows, bins, nl,
+                       (int)G, c_neg, c_den, recip_nl, recip_nl1, out, s);
+    return hipGetLastError();
+  }
+  for (size_t done = 0; done < nframes; done += 65535) {           // blockIdx.y carries the frame: at most 65535 per launch
+    s.origin = first + (long long)done;
+    hipLaunchKernelGGL(lmp_streams_kernel<false>, dim3(bx, (unsigned)std::min<size_t>(65535, nframes - done), nb), dim3(256), 0, st, rows, bins,
+                       nl, c_neg, c_den, recip_nl, recip_nl1, out, s);
+  }
+  return hipGetLastError();
+}
+
+// The statistic over packed rows of streams of unequal length, every stream whole from its frame 0: stream b is rows
+// [row_starts[b], row_starts[b + 1]) of `rows`, its outputs the same rows of `out`.  One launch per piece of the block list
+// (lmp_groups.h: one piece up to 2^31 - 1 groups); the group length is the call's, chosen by the ring size alone.
+extern "C" hipError_t glfer_launch_lmp_ragged(const float *rows, const size_t *row_starts, size_t nstreams, int bins, int nl, float *out,
+                                              hipStream_t st) {
+  if (nstreams == 0) return hipSuccess;
+  if (nl < 1 || bins < 1 || !row_starts) return hipErrorInvalidValue;
+  const int form = GLFER_LMP_RING ? glfer_lmp_form(nl) : GLFER_LMP_FORM_FRAMES;
+  const int G = GLFER_LMP_RING ? glfer_lmp_ragged_group(nl) : 1;
+  std::vector<glfer_lmp_group_entry> groups(nstreams);
+  const size_t n = glfer_lmp_group_table(row_starts, nstreams, G, GLFER_LMP_PIECE_BLOCKS, groups.data(), nullptr);
+  if (n == 0) return hipSuccess;
+  RaggedTable tab;
+  for (size_t k = 0; k < n; k++) {
+    const glfer_lmp_group_entry &g = groups[k];
+    if (tab.pieces.size() <= g.piece) tab.pieces.push_back(RaggedPiece{tab.e.size(), 0, 0});
+    RaggedColsEntry e = {};
+    e.row0 = e.out0 = g.row0;
+    e.nframes = g.nframes;
+    e.blk0 = g.blk0;
+    e.stream = (int)g.stream;
+    tab.e.push_back(e);
+    tab.pieces.back().count++;
+    tab.pieces.back().blocks = g.blk0 + (g.nframes + G - 1) / G;
+  }
+  RaggedColsEntry *d_tab = nullptr;
+  hipError_t err = ragged_upload({&tab}, &d_tab, st);
+  if (err != hipSuccess || !d_tab) return err;
+  const double c_neg = -sqrt(nl / 2.0), c_den = 2.0 * sqrt(2.0 * nl), recip_nl = 1.0 / (double)nl, recip_nl1 = 1.0 / (double)(nl - 1);
+  const unsigned by = (unsigned)((bins + 255) / 256);
+  const size_t lds = (size_t)nl * 256 * sizeof(float);
+  if (form == GLFER_LMP_FORM_LDS) err = glfer::allow_dynamic_lds((const void *)lmp_ring_any_streams_kernel<true>, lds);
+  for (const RaggedPiece &pc : tab.pieces) {
+    if (err != hipSuccess) break;
+    LmpStreams s{0, 0, 0, 0, 0, 0, tab.cols(d_tab, pc)};
+    const dim3 grid((unsigned)pc.blocks, by);
+    if (form == GLFER_LMP_FORM_REGISTERS) {
+#define GLFER_LMP_RING_RAGGED(NLC, GC) \
+  hipLaunchKernelGGL((lmp_ring_streams_kernel<NLC, GC, true>), grid, dim3(256), 0, st, rows, bins, c_neg, c_den, recip_nl, recip_nl1, out, s)
+      if (nl == 2) GLFER_LMP_RING_RAGGED(2, 16);
+      else if (nl == 3) GLFER_LMP_RING_RAGGED(3, 15);
+      else if (nl == 4) GLFER_LMP_RING_RAGGED(4, 16);
+      else GLFER_LMP_RING_RAGGED(8, 16);
+#undef GLFER_LMP_RING_RAGGED
+    } else if (form == GLFER_LMP_FORM_LDS) {
+      hipLaunchKernelGGL(lmp_ring_any_streams_kernel<true>, grid, dim3(256), lds, st, rows, bins, nl, G, c_neg, c_den, recip_nl, recip_nl1, out, s);
+    } else {
+      hipLaunchKernelGGL(lmp_streams_kernel<true>, grid, dim3(256), 0, st, rows, bins, nl, c_neg, c_den, recip_nl, recip_nl1, out, s);
+    }
+    err = hipGetLastError();
+  }
+  scratch_free(d_tab, st);
+  return err;
 }
 
 extern "C" hipError_t glfer_launch_ftest(const float *spec, size_t nframes, int n, int ntap, const double *U0,

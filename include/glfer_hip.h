@@ -227,8 +227,12 @@ int glfer_hip_spectrogram_device(glfer_hip_plan *plan, const void *d_stream, siz
  * in the launches one stream takes (the estimator, hop-means and corrected-copy kernels' stream dimension: blockIdx.y), so
  * the launch count does not grow with nstreams; a batch above the device's grid y limit (65 535) is cut into chunks of that
  * many streams.  Scratch: the corrected copies and hop-means tables of all streams at once, what the single-stream entry
- * takes for a stream of nstreams times the hops.  HP-ARMA, LMP and N outside 256 .. 16384 go stream by stream inside the
- * call.  The opt-in in-launch hop-means producers and the piecewise means (GLFER_MEANS_PRODUCERS, GLFER_EXACT_PIECE_MB)
+ * takes for a stream of nstreams times the hops.  LMP plans run the same way: the periodograms of all streams (with the
+ * min(lmp_av - 1, first_frame) frames the ring still holds, recomputed per stream) go to scratch in the batch's launches and one
+ * batched statistic launch set follows (glfer_hip_lmp_batch_device's kernels); the call is cut into chunks of streams whose
+ * periodograms take at most half of glfer_hip_scratch_limit's cap (8 GiB by default; one stream at least), so the launch
+ * count grows with the bytes, not with nstreams.  HP-ARMA and N outside 256 .. 16384 go stream by stream inside the
+ * call, and so does an LMP chunk of one stream.  The opt-in in-launch hop-means producers and the piecewise means (GLFER_MEANS_PRODUCERS, GLFER_EXACT_PIECE_MB)
  * are never taken by this entry.
  * The moving average of many streams: glfer_hip_spectrogram_avg_batch_device and glfer_hip_avg_batch_device below; their
  * waterfalls: glfer_hip_waterfall_batch_device.
@@ -263,8 +267,10 @@ int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_strea
  * kernel launches and copies that does not depend on nstreams or on the lengths: each launch the single-stream entry makes
  * for one stream (first frames, body, frames off the frame groups, hop means, corrected copies) is made once over all
  * streams, blockIdx.y indexing a small per-stream table the call builds and uploads; more than 65 535 streams go in chunks
- * of that many.  HP-ARMA, LMP and N outside 256 .. 16384 go stream by stream inside the call, and so does a call (or a
- * chunk) of one stream.
+ * of that many.  LMP plans: the packed periodograms go to scratch through the same launch set and the ragged statistic
+ * (glfer_hip_lmp_ragged_device's kernels) runs over the same row starts, in chunks of streams whose rows take at most half of
+ * glfer_hip_scratch_limit's cap (one stream at least).  HP-ARMA and N outside 256 .. 16384 go stream by stream inside the
+ * call, and so does a call (or a chunk) of one stream.
  * GLFER_E_ARG: NULL plan; NULL offsets / lengths with nstreams > 0; NULL d_samples or d_psd while any stream has a frame; an
  * odd offset with integer samples; a stream of more than 2^31 - 1 frames; sizes that overflow size_t -- all checked before
  * anything on the device is touched; a hip_stream that is being captured into a graph (the per-stream tables are uploaded from
@@ -283,6 +289,36 @@ int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *plan, const void *d_samp
  * per frame the rectangular-window periodogram of the assembled frame (lmp.c:114-125), then per
  * bin mean and variance over the ring of the last lmp_av periodograms (zeros before the stream,
  * slot order as lmp.c:134-149) and the clamped statistic of lmp.c:151-160. */
+
+/* The statistic alone, over rectangular-window periodogram rows the caller already holds on the device (rows of an FFT plan
+ * with GLFER_WINDOW rectangular and the LMP plan's n / overlap / sub_mean / history_mode, from any of the spectrogram entries:
+ * an LMP plan computes exactly those rows before its statistic).  Dense rows of `bins` floats.
+ *   d_rows    : frames row_first, row_first + 1, ... of one stream
+ *   d_out     : [nframes][bins], the statistic of frames [first_frame, first_frame + nframes)
+ * The sums run over the ring's slots in slot order and a frame's slot is frame mod lmp_av, so the frames' absolute indices are
+ * arguments; the ring is empty before frame 0 and holds the last lmp_av frames: the rows must reach back
+ * min(lmp_av - 1, first_frame) frames (row_first <= first_frame - that), GLFER_E_ARG otherwise.  Every output is bit for bit
+ * what glfer_hip_spectrogram_device writes on the LMP plan for those frames.
+ * glfer_hip_lmp_batch_device: the same over nstreams streams that share row_first, first_frame and nframes; stream b's rows at
+ * d_rows + b * row_stride floats, its outputs at d_out + b * out_stride floats (strides at least a stream's rows / outputs),
+ * each stream's ring empty before its frame 0.  One launch per 65 535 streams (per 65 535 groups of 16 frames), the kernels'
+ * blockIdx.z the stream; ring sizes 2, 3, 4, 8 keep the ring in registers, the others up to 64 in LDS (from 64 frames a
+ * stream), the rest go frame by frame.
+ * glfer_hip_lmp_ragged_device: packed rows of streams of unequal length as glfer_hip_spectrogram_ragged_device writes them,
+ * stream b rows [row_starts[b], row_starts[b + 1]) of d_rows and of d_out (HOST array [nstreams + 1], non-decreasing, at most
+ * 2^31 - 1 rows a stream), every stream whole from its frame 0.  One launch over a flat list of frame groups (a per-stream
+ * table the call builds and uploads; a stream without rows has no entry), whatever nstreams is.
+ * Arguments, in this order: GLFER_E_ARG for lmp_av outside 1 .. 4096 or bins < 1; GLFER_OK with nothing launched for no
+ * stream or no frame; GLFER_E_ARG for NULL row_starts or ones that decrease or hold a stream of more than 2^31 - 1 rows, for
+ * NULL d_rows / d_out, rows that do not reach back far enough, strides shorter than a stream, nframes > 0x7fffffff, sizes that
+ * overflow size_t; the ragged entry refuses a hip_stream that is being captured (its table is uploaded from host memory).
+ * Asynchronous on hip_stream. */
+int glfer_hip_lmp_device(const float *d_rows, size_t row_first, size_t first_frame, size_t nframes, int bins, int lmp_av,
+                         float *d_out, void *hip_stream);
+int glfer_hip_lmp_batch_device(const float *d_rows, size_t nstreams, size_t row_stride, size_t row_first, size_t first_frame,
+                               size_t nframes, int bins, int lmp_av, float *d_out, size_t out_stride, void *hip_stream);
+int glfer_hip_lmp_ragged_device(const float *d_rows, size_t nstreams, const size_t *row_starts, int bins, int lmp_av,
+                                float *d_out, void *hip_stream);
 
 /* Same, also writing the halfcomplex spectrum of each tapered frame in the layout of
  * fft_radix2.c:75-177 (data[k]=Re X_k, data[N-k]=Im X_k).  FFT mode only: this is
@@ -330,7 +366,7 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *plan, const void *d_stream, size_
  * The F-test tables are made by the first F call on a plan, whichever entry it is; the plan is left as the single entry leaves it.
  * The multitaper rows and F from one pass over the samples: glfer_hip_mtm_rows_ftest_device and its batch form below.
  * Streams of unequal length (one length per stream): glfer_hip_mtm_ftest_ragged_device below.
- * Not built: LMP / HP-ARMA batches in one launch set, batched host / WAV entries. */
+ * Not built: HP-ARMA batches in one launch set, batched host / WAV entries. */
 int glfer_hip_mtm_ftest_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams, size_t stream_pitch,
                                      size_t nsamples, size_t first_frame, size_t nframes, float *d_ftest, int mu_live,
                                      void *hip_stream);
@@ -588,7 +624,7 @@ int glfer_hip_avg_batch_device(int avg_mode, const float *d_psd, size_t nstreams
  * Every output of stream b is bit for bit what glfer_hip_spectrogram_avg_device gives for that stream alone: the call
  * routes one stream's frames as that entry does (the average inside the estimator launch, its head frames and 2^24-frame
  * pieces, or the two launches) and makes every resulting launch cover the whole batch, so the launch count does not grow
- * with nstreams.  Where the rows themselves are not batched (LMP; N outside 256 .. 16384) they are computed stream by
+ * with nstreams.  Where the rows themselves are not batched (N outside 256 .. 16384) they are computed stream by
  * stream, then averaged in one batched launch.  The argument rules of both entries apply (HP-ARMA refused, dense rows,
  * the band, n_out >= bins, an even pitch for s16 / u8); nstreams == 0 or nframes == 0: GLFER_OK, nothing launched.
  * Scratch: rows (without d_psd) and return values (without d_ret) of all streams at once on the two-launch route, cut into
