@@ -11,17 +11,31 @@
 
 #define GLFER_LMP_PIECE_BLOCKS 0x7fffffffll   /* blocks of one launch: the grid's x limit */
 
+/* The ring sizes whose ring is kept in registers, each with the frames a block walks (lmp_ring_kernel's G: whole turns of the
+ * ring).  The only list of them: the forms below read it, and the kernels are instantiated from it (stats_kernels.hip). */
+#ifdef __cplusplus
+constexpr      /* (template arguments there) */
+#else
+static const
+#endif
+int glfer_lmp_ring_groups[][2] = {{2, 16}, {3, 15}, {4, 16}, {8, 16}};
+static inline int glfer_lmp_ring_group(int nl) {   /* 0: no register form */
+  for (size_t k = 0; k < sizeof(glfer_lmp_ring_groups) / sizeof(glfer_lmp_ring_groups[0]); k++)
+    if (glfer_lmp_ring_groups[k][0] == nl) return glfer_lmp_ring_groups[k][1];
+  return 0;
+}
+
 /* the three forms of the statistic's kernels, by ring size (glfer_launch_lmp's rule) */
 enum { GLFER_LMP_FORM_FRAMES = 0, GLFER_LMP_FORM_REGISTERS = 1, GLFER_LMP_FORM_LDS = 2 };
 static inline int glfer_lmp_form(int nl) {
-  if (nl == 2 || nl == 3 || nl == 4 || nl == 8) return GLFER_LMP_FORM_REGISTERS;
+  if (glfer_lmp_ring_group(nl)) return GLFER_LMP_FORM_REGISTERS;
   return nl > 1 && nl <= 64 ? GLFER_LMP_FORM_LDS : GLFER_LMP_FORM_FRAMES;
 }
-/* frames per block of a ragged launch: whole turns of the register ring (lmp_ring_kernel's G), 64 with the ring in LDS, one
- * frame a block frame by frame.  One value per call, whatever the streams' lengths. */
+/* frames per block: the table's with the register ring, 64 with the ring in LDS, one frame a block frame by frame.  One value
+ * per call, whatever the streams' lengths. */
 static inline int glfer_lmp_ragged_group(int nl) {
   const int form = glfer_lmp_form(nl);
-  if (form == GLFER_LMP_FORM_REGISTERS) return nl == 3 ? 15 : 16;
+  if (form == GLFER_LMP_FORM_REGISTERS) return glfer_lmp_ring_group(nl);
   return form == GLFER_LMP_FORM_LDS ? 64 : 1;
 }
 

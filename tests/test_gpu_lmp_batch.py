@@ -146,6 +146,32 @@ def test_batch_stage_equals_single_calls(lib, torch, streams33, B):
         assert same(few[b], lib.lmp_statistic(P[b, :5].contiguous(), 7)), b
 
 
+def test_ring_above_64_from_a_later_frame(lib, torch, streams33):
+    """avg = 65 is past the sizes of the ring in LDS: every entry goes frame by frame, and a frame's slot (frame mod avg) is taken
+    in 32 bits from the launch's first frame mod avg, which the host computes.  first = 1 and 66 make that remainder 1 (66: past
+    one whole turn of the ring); AVGS stops at 16, where 70 frames take the ring kernels instead."""
+    n, avg, B, frames = 256, 65, 3, 70
+    xs = streams33[0][:B]
+    P = rect(lib, n).run_batch(xs)                       # [3][70][129]
+    sp = lmp(lib, n, avg)
+    ref = [lmp_float64(P[b].cpu().numpy().astype(np.float64), avg) for b in range(B)]
+    packed, _ = lib.lmp_statistic_ragged(P.reshape(B * frames, 129), np.arange(B + 1) * frames, avg)
+    for first in (0, 1, 66):
+        lead = min(avg - 1, first)
+        view = P[:, first - lead:]
+        batch = lib.lmp_statistic_batch(view, avg, first_frame=first, lead=lead)
+        for b in range(B):
+            want = sp.run(xs[b], first_frame=first)      # the one-stream estimator, started at `first` itself
+            stage = lib.lmp_statistic(view[b].contiguous(), avg, first_frame=first, lead=lead)
+            assert same(stage, want), (first, b)
+            assert same(batch[b], want), (first, b)
+            assert same(packed[b * frames + first:(b + 1) * frames], want), (first, b)
+            got = stage.cpu().numpy()
+            worst = np.nanmax(np.abs(got - ref[b][first:]) / np.abs(ref[b][first:]))
+            print("lmp_statistic avg=65 first=%d stream %d: max rel err vs float64 %.2e" % (first, b, worst))
+            assert np.allclose(got, ref[b][first:], rtol=3e-7, atol=0), (first, b, worst)
+
+
 @pytest.mark.parametrize("sub_mean", [0, 1])
 @pytest.mark.parametrize("B", [3, 33])
 def test_run_batch_equals_loop_of_run(lib, torch, streams33, B, sub_mean):

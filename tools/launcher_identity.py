@@ -6,8 +6,9 @@ when the kernel traces of two runs are (rocprofv3 --kernel-trace -- python tools
 The cases: the cut-edge calls of tests/test_gpu_frame_cuts.py (plans A .. D, sub_mean 0 / 1 / fast, rows and batch at every
 (first, nframes), the ragged call, plan A's F entries), then one 4 096-frame call per plan through the rows, batch, ragged,
 average, average-batch, F and F-batch entries; then the column entries (column_cases: display, the waterfalls and their two
-multi-GPU halves, the moving averages; `python tools/launcher_identity.py columns` runs these alone).  Inputs come from fixed
-seeds on the host; nothing is timed."""
+multi-GPU halves, the moving averages; `python tools/launcher_identity.py columns` runs these alone), and the LMP statistic's
+three entries and LMP plans at every ring size's form (lmp_cases; `python tools/launcher_identity.py lmp` runs these alone).
+Inputs come from fixed seeds on the host; nothing is timed."""
 import hashlib
 import os
 import sys
@@ -201,9 +202,48 @@ def column_cases():
     sys.stdout.flush()
 
 
+LMP_AVGS = (1, 2, 3, 4, 8, 7, 16, 65)
+
+
+def lmp_cases():
+    """the LMP statistic: the stage over one stream, a batch and ragged streams at every ring size's form (registers, LDS from
+    64 frames, frame by frame), then LMP plans through run, run_batch and run_ragged"""
+    for n in (256, 1024):
+        rect = G.Spectrogram(G.FftParams(n=n, window_type=G.WINDOWS["rectangular"], overlap=0.0))
+        x = streams(3, 70 * n, 0, 14)
+        P70 = rect.run_batch(x)                                       # [3][70][bins]
+        for frames in (5, 70):
+            P = P70[:, :frames].contiguous()
+            for avg in LMP_AVGS:
+                for first in uniq([0, 1, avg, avg + 1]):
+                    if first >= frames:
+                        continue
+                    lead = min(avg - 1, first)
+                    view = P[:, first - lead:]
+                    print("lmp stage n %d frames %d avg %d first %d: %s; batch of 3: %s" % (
+                        n, frames, avg, first, sha(G.lmp_statistic(view[1].contiguous(), avg, first_frame=first, lead=lead)),
+                        sha(G.lmp_statistic_batch(view, avg, first_frame=first, lead=lead))))
+        for avg in LMP_AVGS:
+            counts = [0, 1, 2, avg - 1, 15, 16, 17, 70]
+            rows = torch.cat([P70[b % 3, :c] for b, c in enumerate(counts)])
+            print("lmp stage ragged n %d avg %d: %s" % (n, avg, sha(G.lmp_statistic_ragged(rows, np.concatenate([[0], np.cumsum(counts)]), avg)[0])))
+            for sub in (0, 1):
+                sp = G.Spectrogram(G.LmpParams(n=n, overlap=0.0, avg=avg, sub_mean=sub))
+                lens = [c * n + (7 if b % 3 == 0 else 0) for b, c in enumerate(counts)]
+                offs = [(b % 3) * x.size(1) for b in range(len(lens))]
+                print("lmp plan n %d avg %d sub_mean %d: run %s / %s; run_batch %s / %s; run_ragged %s" % (
+                    n, avg, sub, sha(sp.run(x[1])), sha(sp.run(x[1], first_frame=avg + 1)), sha(sp.run_batch(x)),
+                    sha(sp.run_batch(x, first_frame=avg + 1)), sha(sp.run_ragged(x.reshape(-1), offs, lens)[0])))
+                sp.close()
+        sys.stdout.flush()
+        rect.close()
+
+
 def main():
     if sys.argv[1:] == ["columns"]:
         return column_cases()
+    if sys.argv[1:] == ["lmp"]:
+        return lmp_cases()
     for name, (kind, n, overlap, fmt, hm, Gf, fi) in sorted(PLANS.items()):
         for sub in SUB_MEANS:
             sp = plan(name, sub)
@@ -240,6 +280,7 @@ def main():
         x = streams(1, 4096 * sp.hop, 0, 13)
         print("lmp sub_mean %d rows 4096: %s; first 5 nframes 9: %s" % (sub, sha(sp.run(x[0])), sha(sp.run(x[0], first_frame=5, nframes=9))))
         sp.close()
+    lmp_cases()
     column_cases()
 
 

@@ -7,6 +7,9 @@ tools/ragged_ftest_rate.py).  N = 1024, lmp_av = 4, overlap 0 (the bench.py row 
     python tools/lmp_batch_rate.py --loop        the loop of run() alone (also on another build: GLFER_LIB_PATH)
     python tools/lmp_batch_rate.py --single      single-stream run(), 2^20 frames (run in alternating processes, GLFER_LIB_PATH
                                                  at another build)
+    python tools/lmp_batch_rate.py --stage       the statistic alone (lmp_statistic, _batch, _ragged) over 65 536 rows at ring sizes
+                                                 the plans above do not reach: lmp_av = 100 (frame by frame) and 16 (the ring in
+                                                 LDS), one stream, 16 streams as a batch and ragged (alternating processes as --single)
     python tools/lmp_batch_rate.py --launches B --entry batch|ragged [--sub-mean]
                                                  one call of B streams and nothing else (under rocprofv3 --kernel-trace)"""
 import argparse
@@ -112,6 +115,26 @@ def single(reps):
     print("single-stream run, N=%d lmp_av=%d, %d frames: %s %8.2f M frames/s" % (N, AV, frames, show("", t), frames / t[0] / 1e3), flush=True)
 
 
+def stage(reps):
+    frames, nb = 1 << 16, 16
+    g = torch.Generator(device="cuda").manual_seed(5)
+    P = torch.rand((frames, N // 2 + 1), device="cuda", generator=g) * 0.1 + 1e-3
+    starts = np.arange(nb + 1) * (frames // nb)
+    for avg in (100, 16):
+        fns = [("one stream", lambda: G.lmp_statistic(P, avg)), ("batch of %d" % nb, lambda: G.lmp_statistic_batch(P.view(nb, frames // nb, -1), avg)),
+               ("ragged, %d streams" % nb, lambda: G.lmp_statistic_ragged(P, starts, avg))]
+        for _, fn in fns:
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        ts = {name: [] for name, _ in fns}
+        for _ in range(reps):
+            for name, fn in fns:
+                ts[name].append(once(fn))
+        for name, _ in fns:
+            print("stage N=%d lmp_av=%d, %d rows, %s" % (N, avg, frames, show(name, stats(ts[name]))), flush=True)
+
+
 def launches(nb, entry, sub_mean):
     sp = plan(sub_mean)
     if entry == "batch":
@@ -130,6 +153,7 @@ def main():
     ap.add_argument("--reps", type=int, default=6)
     ap.add_argument("--loop", action="store_true")
     ap.add_argument("--single", action="store_true")
+    ap.add_argument("--stage", action="store_true")
     ap.add_argument("--launches", type=int, default=0)
     ap.add_argument("--entry", default="batch", choices=["batch", "ragged"])
     ap.add_argument("--sub-mean", action="store_true")
@@ -138,6 +162,8 @@ def main():
         return launches(args.launches, args.entry, 1 if args.sub_mean else 0)
     if args.single:
         return single(args.reps)
+    if args.stage:
+        return stage(args.reps)
     for c in args.case or ["short", "long"]:
         for sub_mean in (0, 1):
             if c == "short":
