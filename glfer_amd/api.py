@@ -301,8 +301,9 @@ class HparmaParams:
     """What source.c:368-376 sets before hparma_init(): fft.{n,overlap}, t, p_e (q_e = -1)."""
 
     def __init__(self, n=4096, overlap=0.0, t=96, p_e=16, sub_mean=0, history_mode=HISTORY_ZERO_FIRST,
-                 sample_format=SAMPLES_F32):
+                 sample_format=SAMPLES_F32, psd_pitch=0):
         self.mode = MODE_HPARMA
+        self.psd_pitch = psd_pitch
         self.n, self.overlap, self.t, self.p_e = n, overlap, t, p_e
         self.window_type = WINDOWS["rectangular"]       # source.c:369
         self.a, self.limiter, self.sub_mean = 0.0, 0, sub_mean

@@ -20,6 +20,7 @@
 
 #include "frame_cuts.h"
 #include "host_tables.h"
+#include "hparma_frames.h"
 #include "ragged_cols.hpp"
 #include "spectro_params.h"
 
@@ -27,6 +28,11 @@ static_assert(GLFER_FMT_F32 == GLFER_SAMPLES_F32 && GLFER_FMT_S16 == GLFER_SAMPL
 
 extern "C" hipError_t glfer_launch_hparma(const SpectroParams *sp, int n, int t, int ncol, const int *rot_sched, int rot_steps, int rot_width, const uint16_t *lagmap,
                                           const float2 *unit, hipStream_t st);
+extern "C" hipError_t glfer_launch_hparma_batch(const SpectroParams *sp, int n, int t, int ncol, const int *rot_sched, int rot_steps, int rot_width,
+                                                const uint16_t *lagmap, const float2 *unit, hipStream_t st);
+extern "C" hipError_t glfer_launch_hparma_ragged(const SpectroParams *sp, const GlferRaggedEntry *streams, size_t nstreams, int n, int t, int ncol,
+                                                 const int *rot_sched, int rot_steps, int rot_width, const uint16_t *lagmap, const float2 *unit,
+                                                 hipStream_t st);
 extern "C" hipError_t glfer_launch_avg(int mode, const float *psd, size_t nframes, int bins, int n_out,
                                        int depth, int minbin, int maxbin, int max0, double *avg,
                                        double *ret, hipStream_t st);
@@ -487,9 +493,7 @@ int glfer_hip_plan_create(const glfer_hip_config *cfg, glfer_hip_plan **out) {
   if (cfg->mode == GLFER_MODE_HPARMA) {
     const int t = cfg->hparma_t, ncol = cfg->hparma_p_e + 1;
     if (t < 2 || ncol < 2 || ncol > t || t > n || ncol > 256 || t > 65535) return GLFER_E_ARG;   // p_e+1 <= t (hparma.c:107)
-    const size_t xlen = (size_t)n + (t <= 128 ? 128 : 0);          // (glfer_launch_hparma: the frame and its zero tail)
-    const size_t big = xlen > (size_t)t * ncol ? xlen : (size_t)t * ncol;
-    if ((big + (size_t)ncol * ncol + t + 2 * ncol) * sizeof(float) > 160 * 1024) return GLFER_E_ARG;
+    if (glfer_hparma_lds_bytes(n, t, ncol) > 160 * 1024) return GLFER_E_ARG;   // (hparma_frames.h: the frame's LDS, as its launcher asks for it)
   }
   if (cfg->sample_format < 0 || cfg->sample_format > 2) return GLFER_E_ARG;
   if (cfg->mode == GLFER_MODE_MTM && (cfg->mtm_k < 0 || cfg->mtm_k > 31 || !(cfg->mtm_w > 0.0f)))
@@ -1618,8 +1622,11 @@ static int grid_y_limit(int floor, size_t *ymax) {
   return GLFER_OK;
 }
 
-// the plans whose rows a batch computes in the launches of one stream (the others go stream by stream)
+// the plans whose rows a batch computes in the launches of one stream (the others go stream by stream): the estimator kernels'
+// stream dimension at N = 256 .. 16384, and HP-ARMA at every N a plan accepts -- its launch runs over the flat list of all
+// streams' frames (hparma.hip, HpPlace) -- but for a plan built with GLFER_HPARMA_WIDTH=16 (A/B runs: a single-stream kernel)
 static bool batch_one_launch(const glfer_hip_plan *p) {
+  if (p->cfg.mode == GLFER_MODE_HPARMA) return p->rot_width != 16;
   return (p->cfg.mode == GLFER_MODE_FFT || p->cfg.mode == GLFER_MODE_MTM || p->cfg.mode == GLFER_MODE_LMP) && p->n >= 256 && p->n <= 16384;
 }
 // LMP batches keep the periodograms of a chunk of streams in scratch: the streams whose rows (stream_bytes each) take at most
@@ -1669,13 +1676,15 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
   // back with them -- and one batched statistic launch set follows (glfer_launch_lmp_batch).  The call is cut into chunks of
   // streams whose periodograms take at most half the kept-scratch cap (glfer_hip_scratch_limit; 8 GiB by default), one stream
   // at least: the launch count grows with the bytes, not with the streams.
-  const bool lmp = p->cfg.mode == GLFER_MODE_LMP;
+  // HP-ARMA: the corrected copies of a chunk's streams (submean_scratch, as for the other plans), then ONE launch over the chunk's
+  // nb x nframes frames (glfer_launch_hparma_batch); mean_inkernel_ok refuses the mode.
+  const bool lmp = p->cfg.mode == GLFER_MODE_LMP, hparma = p->cfg.mode == GLFER_MODE_HPARMA;
   const size_t back = lmp ? std::min<size_t>((size_t)p->lmp_av - 1, first) : 0;
   const size_t nrows = nframes + back, lmp_bs = nrows * (size_t)p->bins;
   if (lmp) ymax = std::min(ymax, lmp_chunk_streams(lmp_bs * sizeof(float)));
   for (size_t c0 = 0; c0 < nstreams; c0 += ymax) {      // batches above the grid's y limit: chunks of it
     const unsigned nb = (unsigned)std::min(nstreams - c0, ymax);
-    if (lmp && nb == 1) {                               // (a chunk of one stream: the single-stream entry)
+    if ((lmp || hparma) && nb == 1) {                   // (a chunk of one stream: the single-stream entry)
       const int rc = glfer_run_device(p, base + c0 * stream_pitch * esz, nsamples, first, nframes, d_psd + c0 * psd_bs, nullptr, st);
       if (rc != GLFER_OK) return rc;
       continue;
@@ -1701,7 +1710,9 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
       float *scratch = nullptr;
       if (p->cfg.sub_mean) rc = submean_scratch(p, sp, first - back, nrows, st, &scratch);
       if (rc == GLFER_OK) {
-        const hipError_t e = launch_by_n(sp, p->n, st);
+        const hipError_t e = hparma ? glfer_launch_hparma_batch(&sp, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched, p->rot_steps,
+                                                                p->rot_width, p->d_lagmap, p->d_unit, st)
+                                    : launch_by_n(sp, p->n, st);
         if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch)");
       }
       if (scratch) glfer::scratch_free(scratch, st);
@@ -1785,6 +1796,20 @@ struct RaggedChunk {
   // launch_by_n over the streams: frames [from[b], to[b]) of stream b, whose sample 0 is soff[b] bytes from sp.stream
   int by_n(const SpectroParams &sp, const std::vector<long long> &soff, const std::vector<size_t> &from,
            const std::vector<size_t> &to) const {
+    if (p->cfg.mode == GLFER_MODE_HPARMA) {                              // no routes and no frame groups: one launch over all frames
+      std::vector<GlferRaggedEntry> all(nb);
+      for (unsigned b = 0; b < nb; b++) {
+        all[b] = GlferRaggedEntry{};
+        if (to[b] <= from[b]) continue;
+        all[b].stream_off = soff[b];
+        all[b].psd_off = (long long)((s[b].row + from[b]) * (size_t)p->pitch);
+        all[b].frame0 = (long long)from[b];
+        all[b].nframes = (int)(to[b] - from[b]);
+      }
+      const hipError_t e = glfer_launch_hparma_ragged(&sp, all.data(), nb, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched,
+                                                      p->rot_steps, p->rot_width, p->d_lagmap, p->d_unit, st);
+      return e == hipSuccess ? GLFER_OK : hip_fail(e, "estimator launch (HP-ARMA, ragged)");
+    }
     // the route of THESE samples, as launch_by_n reads it: a corrected copy is f32 whatever the raw format, so its frames may
     // take a real-input kernel where the raw stream's alignment (or an odd hop) keeps the raw samples on the packed one
     SpectroParams r0 = sp;
@@ -2020,7 +2045,7 @@ int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *p, const void *d_samples
     if (!s[b].frames) return (int)GLFER_OK;
     return glfer_run_device(p, base + s[b].off * esz, lengths[b], 0, s[b].frames, d_psd + s[b].row * (size_t)p->pitch, nullptr, st);
   };
-  if (!batch_one_launch(p) || nstreams == 1) {      // HP-ARMA, N outside 256 .. 16384: stream by stream, as batch_rows
+  if (!batch_one_launch(p) || nstreams == 1) {      // N outside 256 .. 16384 (but HP-ARMA's): stream by stream, as batch_rows
     for (size_t b = 0; b < nstreams; b++) {
       const int rc = single(b);
       if (rc != GLFER_OK) return rc;

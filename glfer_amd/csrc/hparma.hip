@@ -15,7 +15,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <vector>
 #include "spectro_params.h"
+#include "hparma_frames.h"
 
 namespace glfer {
 hipError_t allow_dynamic_lds(const void *kernel, size_t bytes);   // plan.h / glfer_hip.cpp: once per device, kernel and size class
@@ -181,6 +183,68 @@ struct HparmaParams {
   unsigned *queue;          // frames handed out beyond the first gridDim.x (null: blockIdx.x, + gridDim.x, ...)
 };
 
+// Where a launch's frames lie.  One: frames [frame0, frame0 + nframes) of one stream, the rows from psd on.  Batch: s.nbatch
+// streams batch_stride bytes apart that share frame0 and nframes, flat frame g is frame g mod nframes of stream g / nframes, the
+// rows psd_batch_stride floats apart.  Ragged: streams of unequal length, each with its own samples, rows, frame0 and nframes in a
+// table (glfer_hparma_frame_table's list, hparma_frames.h).
+enum class HpPlace { One, Batch, Ragged };
+struct HparmaRaggedEntry {
+  long long stream_off;     // bytes from s.stream to the stream's sample 0 (a virtual base: may be negative)
+  long long psd_off;        // floats from s.psd to the row of its first frame of the launch
+  long long frame0;         // that frame's index in the stream
+  unsigned g0;              // its place in the launch's flat list
+  int nframes;
+};
+// The kernel's argument block by placement.  One stream: HparmaParams as it is -- a longer block changes the code the compiler
+// makes of the SAME kernel body (the autocorrelation loop's software pipelining went with three appended members, 0.4 % of the
+// single-stream rate), so what the stream placements need rides in a block of their own.
+template <HpPlace P>
+struct HparmaArgs : HparmaParams {
+  long long total;                 // the launch's flat frame list g = 0 .. total - 1, every stream whole, in stream order: < 2^31
+  const HparmaRaggedEntry *rag;    // Ragged: one entry per stream that has frames, g0 strictly increasing from 0
+  int nrag;
+};
+template <>
+struct HparmaArgs<HpPlace::One> : HparmaParams {};
+// a frame of the launch: the stream it belongs to, that stream's first row and first frame of the launch, the frame's place after it
+struct HpFrame {
+  const char *stream;
+  float *psd;
+  long long frame0;
+  long long f;
+};
+// The flat frame g is the same in every lane (blockIdx.x, or the ticket lane 0 drew): it goes through v_readfirstlane so that the
+// division or the bisection, the table reads and the frame's buffer descriptor are scalar work (a descriptor the compiler cannot
+// prove uniform costs a waterfall loop around every sample load).
+template <HpPlace P>
+__device__ __forceinline__ HpFrame hp_frame(const HparmaArgs<P> &hp, long long g) {
+  const SpectroParams &p = hp.s;
+  const char *stream = reinterpret_cast<const char *>(p.stream);
+  if constexpr (P == HpPlace::One) {
+    return HpFrame{stream, p.psd, p.frame0, g};
+  } else {
+    const unsigned gu = (unsigned)__builtin_amdgcn_readfirstlane((int)g);
+    if constexpr (P == HpPlace::Batch) {
+      const unsigned nf = (unsigned)p.nframes, b = gu / nf;
+      return HpFrame{stream + (long long)b * p.batch_stride, p.psd + (long long)b * p.psd_batch_stride, p.frame0, (long long)(gu - b * nf)};
+    } else {
+      // The table is written before the launch and only read by it: read through the constant address space, its entries are
+      // scalar loads (from the global one they are vector loads at a scalar address and a v_readfirstlane each -- the frame loop
+      // stores and draws tickets, so the compiler cannot tell that nothing writes the table).
+      typedef const HparmaRaggedEntry __attribute__((address_space(4))) *ConstTab;
+      const ConstTab tab = (ConstTab)(unsigned long long)hp.rag;
+      int lo = 0, hi = hp.nrag - 1;                      // the last entry with g0 <= g (ragged_cols_find's bisection)
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].g0 <= gu) lo = mid;
+        else hi = mid - 1;
+      }
+      const long long stream_off = tab[lo].stream_off, psd_off = tab[lo].psd_off, frame0 = tab[lo].frame0;
+      return HpFrame{stream + stream_off, p.psd + psd_off, frame0, (long long)(gu - tab[lo].g0)};
+    }
+  }
+}
+
 template <int FMT>
 __device__ __forceinline__ float hp_sample(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
   if constexpr (FMT == GLFER_FMT_F32) return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, 0, 0));
@@ -193,8 +257,9 @@ __device__ __forceinline__ float hp_sample(__amdgpu_buffer_rsrc_t rsrc, unsigned
 // TT, NC: the matrix shape as compile-time constants (BASELINE config 5: t = 128, p_e + 1 = 33), 0 = taken from the parameters.  With the
 // shape known the step is straight-line code: no row tests around the loads and stores of a column, column offsets by shifts instead
 // of v_mul_lo_u32, Q's five row slots instead of eight tested ones.
-template <int FMT, int LPR = 8, int TT = 0, int NC = 0>
-__global__ __launch_bounds__(64) void hparma_kernel(HparmaParams hp) {
+// P: one stream, a batch or ragged streams -- only the top of the frame loop differs (hp_frame)
+template <int FMT, int LPR = 8, int TT = 0, int NC = 0, HpPlace P = HpPlace::One>
+__global__ __launch_bounds__(64) void hparma_kernel(HparmaArgs<P> hp) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const SpectroParams &p = hp.s;
   const int N = hp.n, t = TT ? TT : hp.t, ncol = NC ? NC : hp.ncol;
@@ -209,15 +274,19 @@ __global__ __launch_bounds__(64) void hparma_kernel(HparmaParams hp) {
   // Frames are handed out from a queue when a launch has more of them than wavefronts in flight (hp.queue, zeroed by the launcher):
   // seven one-wavefront workgroups share a CU's four SIMDs 2 + 2 + 2 + 1 (tools/ldsocc), the one alone on its SIMD is half as
   // fast again as the others, and with a fixed stride it sat idle for the last third of the launch.
-  for (long long f = blockIdx.x; f < p.nframes;
-       f = hp.queue ? (long long)gridDim.x + (long long)__builtin_amdgcn_readfirstlane(lane == 0 ? (int)atomicAdd(hp.queue, 1u) : 0)
-                    : f + gridDim.x) {
+  long long total = p.nframes;
+  if constexpr (P != HpPlace::One) total = hp.total;
+  for (long long g = blockIdx.x; g < total;
+       g = hp.queue ? (long long)gridDim.x + (long long)__builtin_amdgcn_readfirstlane(lane == 0 ? (int)atomicAdd(hp.queue, 1u) : 0)
+                    : g + gridDim.x) {
+    const HpFrame w = hp_frame<P>(hp, g);
+    const long long f = w.f;
     // ---- K1: the assembled frame (prepare_audio, fft.c:98-113), unwindowed (source.c:369)
     {
-      const long long s0 = (p.frame0 + f) * (long long)p.H - p.R;
+      const long long s0 = (w.frame0 + f) * (long long)p.H - p.R;
       const long long sbase = s0 > 0 ? s0 : 0;
       const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<char *>(reinterpret_cast<const char *>(p.stream)) + sbase * (long long)esz, 0, 0x7fffffff, 0x00020000);
+          const_cast<char *>(w.stream) + sbase * (long long)esz, 0, 0x7fffffff, 0x00020000);
       const int rel0 = (int)(s0 - sbase);
       // sixteen loads in flight per lane and one wait for them (one load and its wait per iteration, as this loop used to be
       // compiled, is 64 trips to memory a frame -- with two wavefronts on a SIMD at best, nobody covers them)
@@ -569,7 +638,7 @@ __global__ __launch_bounds__(64) void hparma_kernel(HparmaParams hp) {
     wave_fence();
     // ---- |A(f)|^2/N by Horner at z = exp(-2 pi i k/N) (what the zero-padded N-point FFT of
     // hparma.c:140-153 evaluates), reciprocal below Nyquist (hparma.c:154-156)
-    float *o = p.psd + (size_t)f * (size_t)p.pitch;
+    float *o = w.psd + (size_t)f * (size_t)p.pitch;
     for (int k = lane; k <= N / 2; k += 64) {
       const float2 z = hp.unit[k];
       // double Horner: the reciprocal below magnifies evaluation error at the spectral peaks
@@ -591,9 +660,11 @@ __global__ __launch_bounds__(64) void hparma_kernel(HparmaParams hp) {
 
 using namespace glfer;
 
-extern "C" hipError_t glfer_launch_hparma(const SpectroParams *sp, int n, int t, int ncol, const int *rot_sched, int rot_steps, int rot_width,
-                                          const uint16_t *lagmap, const float2 *unit, hipStream_t st) {
-  if (sp->nframes <= 0) return hipSuccess;
+namespace {
+
+// the plan's part of the kernel arguments
+HparmaParams hparma_params(const SpectroParams *sp, int n, int t, int ncol, const int *rot_sched, int rot_steps, int rot_width,
+                           const uint16_t *lagmap, const float2 *unit) {
   HparmaParams hp;
   hp.s = *sp;
   hp.n = n;
@@ -604,39 +675,62 @@ extern "C" hipError_t glfer_launch_hparma(const SpectroParams *sp, int n, int t,
   hp.width = rot_width;
   hp.lagmap = lagmap;
   hp.unit = unit;
-  const int xlen = n + (t <= 128 ? 128 : 0);            // the frame and its zero tail (the autocorrelation's two-lag walk)
-  const int big = xlen > t * ncol ? xlen : t * ncol;
-  size_t shmem = (size_t)(big + ncol * ncol + t + 2 * ncol) * sizeof(float);
+  hp.queue = nullptr;
+  return hp;
+}
+
+// One launch over `total` frames (P == One: hp.s.nframes of them; else the flat list, with Ragged its table): a wavefront per
+// frame in flight, the rest of the frames from the queue.
+template <HpPlace P>
+hipError_t hparma_launch(const HparmaParams &plan, long long total, hipStream_t st, const HparmaRaggedEntry *rag = nullptr, int nrag = 0) {
+  if (total <= 0) return hipSuccess;
+  HparmaArgs<P> hp;
+  static_cast<HparmaParams &>(hp) = plan;
+  if constexpr (P != HpPlace::One) {
+    hp.total = total;
+    hp.rag = rag;
+    hp.nrag = nrag;
+  }
+  if (total > GLFER_HPARMA_PIECE_FRAMES) return hipErrorInvalidValue;
+  const int t = hp.t, ncol = hp.ncol;
+  size_t shmem = glfer_hparma_lds_bytes(hp.n, t, ncol);
   // GLFER_HPARMA_LDS_KB (tools/hparma_occupancy.sh only): ask for more LDS than the frame needs, i.e. fewer frames in flight per CU
   static const long lds_kb = [] { const char *e = getenv("GLFER_HPARMA_LDS_KB"); return e ? atol(e) : 0L; }();
   if (lds_kb > 0 && (size_t)lds_kb * 1024 > shmem && lds_kb <= 64) shmem = (size_t)lds_kb * 1024;
-  const long long resident = 256LL * (shmem ? (160 * 1024) / shmem : 8);
-  const unsigned grid = (unsigned)(sp->nframes < resident ? sp->nframes : resident);
+  const long long resident = glfer_hparma_resident(shmem);
+  const unsigned grid = (unsigned)(total < resident ? total : resident);
   hipError_t e = hipSuccess;
   hp.queue = nullptr;
-  if ((long long)sp->nframes > (long long)grid) {
+  if (total > (long long)grid) {
     e = glfer::scratch_malloc((void **)&hp.queue, 256, st);
     if (e == hipSuccess) e = hipMemsetAsync(hp.queue, 0, sizeof(unsigned), st);
     if (e != hipSuccess) return e;
   }
 #define GLFER_HPARMA_LAUNCH(F, L, TT, NC)                                                                                  \
   do {                                                                                                                      \
-    e = glfer::allow_dynamic_lds((const void *)hparma_kernel<F, L, TT, NC>, shmem);                                         \
-    if (e == hipSuccess) hipLaunchKernelGGL((hparma_kernel<F, L, TT, NC>), dim3(grid), dim3(64), shmem, st, hp);            \
+    e = glfer::allow_dynamic_lds((const void *)hparma_kernel<F, L, TT, NC, P>, shmem);                                      \
+    if (e == hipSuccess) hipLaunchKernelGGL((hparma_kernel<F, L, TT, NC, P>), dim3(grid), dim3(64), shmem, st, hp);         \
   } while (0)
-  const bool wide = rot_width == 16;
+  const bool wide = hp.width == 16;
   // GLFER_HPARMA_GENERIC=1 (A/B runs and the tests): the shape from the parameters even for t = 128, p_e = 32
   const bool generic_only = [] { const char *e = getenv("GLFER_HPARMA_GENERIC"); return e && atoi(e) != 0; }();
-  const bool fixed = !wide && !generic_only && rot_sched != nullptr && rot_steps > 0;
+  const bool fixed = !wide && !generic_only && hp.sched != nullptr && hp.nsteps > 0;
   const bool c5 = fixed && t == 128 && ncol == 33;                 // BASELINE config 5
   const bool dflt = fixed && t == 96 && ncol == 17;                // glfer's own defaults (glfer.c:248-249: t = 96, p_e = 16)
-  switch (sp->fmt) {
-#define GLFER_HPARMA_FMT(F)                                    \
-    case F:                                                    \
-      if (wide) GLFER_HPARMA_LAUNCH(F, 4, 0, 0);               \
-      else if (c5) GLFER_HPARMA_LAUNCH(F, 8, 128, 33);         \
-      else if (dflt) GLFER_HPARMA_LAUNCH(F, 8, 96, 17);        \
-      else GLFER_HPARMA_LAUNCH(F, 8, 0, 0);                    \
+  // (a rotation over 4 lanes -- GLFER_HPARMA_WIDTH=16, A/B runs -- is a single-stream kernel: glfer_hip.cpp keeps its batches stream by stream)
+  if (wide && P != HpPlace::One) e = hipErrorInvalidValue;
+  else switch (hp.s.fmt) {
+#define GLFER_HPARMA_FMT(F)                                                          \
+    case F:                                                                          \
+      if constexpr (P == HpPlace::One) {                                             \
+        if (wide) {                                                                  \
+          GLFER_HPARMA_LAUNCH(F, 4, 0, 0);                                           \
+          break;                                                                     \
+        }                                                                            \
+      }                                                                              \
+      if (c5) GLFER_HPARMA_LAUNCH(F, 8, 128, 33);                                    \
+      else if (dflt) GLFER_HPARMA_LAUNCH(F, 8, 96, 17);                              \
+      else GLFER_HPARMA_LAUNCH(F, 8, 0, 0);                                          \
       break;
     GLFER_HPARMA_FMT(GLFER_FMT_F32)
     GLFER_HPARMA_FMT(GLFER_FMT_S16)
@@ -648,4 +742,61 @@ extern "C" hipError_t glfer_launch_hparma(const SpectroParams *sp, int n, int t,
 #undef GLFER_HPARMA_LAUNCH
   if (e != hipSuccess) return e;
   return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" hipError_t glfer_launch_hparma(const SpectroParams *sp, int n, int t, int ncol, const int *rot_sched, int rot_steps, int rot_width,
+                                          const uint16_t *lagmap, const float2 *unit, hipStream_t st) {
+  return hparma_launch<HpPlace::One>(hparma_params(sp, n, t, ncol, rot_sched, rot_steps, rot_width, lagmap, unit), sp->nframes, st);
+}
+
+// sp->nbatch streams (sp->batch_stride bytes and sp->psd_batch_stride floats apart) that share sp->frame0 and sp->nframes, in one
+// launch over the nbatch x nframes frames; more than 2^31 - 1 of them go in pieces of whole streams
+extern "C" hipError_t glfer_launch_hparma_batch(const SpectroParams *sp, int n, int t, int ncol, const int *rot_sched, int rot_steps,
+                                                int rot_width, const uint16_t *lagmap, const float2 *unit, hipStream_t st) {
+  if (sp->nframes <= 0 || sp->nbatch <= 0) return hipSuccess;
+  HparmaParams hp = hparma_params(sp, n, t, ncol, rot_sched, rot_steps, rot_width, lagmap, unit);
+  const long long per = GLFER_HPARMA_PIECE_FRAMES / sp->nframes;     // streams a launch takes: one at least
+  for (long long b0 = 0; b0 < sp->nbatch; b0 += per) {
+    const long long nb = sp->nbatch - b0 < per ? sp->nbatch - b0 : per;
+    hp.s.stream = reinterpret_cast<const char *>(sp->stream) + b0 * sp->batch_stride;
+    hp.s.psd = sp->psd + b0 * sp->psd_batch_stride;
+    hp.s.nbatch = (int)nb;
+    const hipError_t e = hparma_launch<HpPlace::Batch>(hp, nb * sp->nframes, st);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// Streams of unequal length: streams[b] (HOST, nstreams of them) holds stream b's samples, rows, first frame and frame count as
+// GlferRaggedEntry gives them, relative to sp->stream and sp->psd; nframes <= 0: nothing for this stream.  One launch over the
+// flat list of all frames (glfer_hparma_frame_table), its table in stream-ordered scratch.
+extern "C" hipError_t glfer_launch_hparma_ragged(const SpectroParams *sp, const GlferRaggedEntry *streams, size_t nstreams, int n, int t,
+                                                 int ncol, const int *rot_sched, int rot_steps, int rot_width, const uint16_t *lagmap,
+                                                 const float2 *unit, hipStream_t st) {
+  std::vector<long long> counts(nstreams);
+  for (size_t b = 0; b < nstreams; b++) counts[b] = streams[b].nframes;
+  std::vector<glfer_hparma_frames_entry> ent(nstreams);
+  size_t npieces = 0;
+  const size_t ne = glfer_hparma_frame_table(counts.data(), nstreams, GLFER_HPARMA_PIECE_FRAMES, ent.data(), &npieces);
+  if (ne == 0) return hipSuccess;
+  std::vector<HparmaRaggedEntry> tab(ne);
+  for (size_t k = 0; k < ne; k++) {
+    const GlferRaggedEntry &r = streams[ent[k].stream];
+    tab[k] = HparmaRaggedEntry{r.stream_off, r.psd_off, r.frame0, (unsigned)ent[k].g0, (int)ent[k].nframes};
+  }
+  HparmaRaggedEntry *d_tab = nullptr;
+  hipError_t e = glfer::scratch_malloc((void **)&d_tab, ne * sizeof(HparmaRaggedEntry), st);
+  if (e != hipSuccess) return e;
+  e = hipMemcpyAsync(d_tab, tab.data(), ne * sizeof(HparmaRaggedEntry), hipMemcpyHostToDevice, st);   // (pageable source: staged before it returns)
+  HparmaParams hp = hparma_params(sp, n, t, ncol, rot_sched, rot_steps, rot_width, lagmap, unit);
+  for (size_t k0 = 0; k0 < ne && e == hipSuccess;) {                 // piece by piece
+    size_t k1 = k0;
+    while (k1 < ne && ent[k1].piece == ent[k0].piece) k1++;
+    e = hparma_launch<HpPlace::Ragged>(hp, ent[k1 - 1].g0 + ent[k1 - 1].nframes, st, d_tab + k0, (int)(k1 - k0));
+    k0 = k1;
+  }
+  glfer::scratch_free(d_tab, st);
+  return e;
 }

@@ -231,8 +231,12 @@ int glfer_hip_spectrogram_device(glfer_hip_plan *plan, const void *d_stream, siz
  * min(lmp_av - 1, first_frame) frames the ring still holds, recomputed per stream) go to scratch in the batch's launches and one
  * batched statistic launch set follows (glfer_hip_lmp_batch_device's kernels); the call is cut into chunks of streams whose
  * periodograms take at most half of glfer_hip_scratch_limit's cap (8 GiB by default; one stream at least), so the launch
- * count grows with the bytes, not with nstreams.  HP-ARMA and N outside 256 .. 16384 go stream by stream inside the
- * call, and so does an LMP chunk of one stream.  The opt-in in-launch hop-means producers and the piecewise means (GLFER_MEANS_PRODUCERS, GLFER_EXACT_PIECE_MB)
+ * count grows with the bytes, not with nstreams.  HP-ARMA plans, at every N they accept (32 .. 32768): the corrected copies of
+ * the batch's mean removal as above, then ONE launch of the HP-ARMA kernel over the flat list of all nstreams x nframes frames
+ * (a wavefront per frame, the frames beyond those in flight drawn from the launch's queue across stream boundaries; 2^31 - 1
+ * frames a launch, more go in pieces of whole streams): 1 kernel a call, 3 with sub_mean = 1, 2 with sub_mean = 2.  (A plan
+ * made under GLFER_HPARMA_WIDTH=16 -- A/B runs -- keeps the loop over the streams.)  The other modes at N outside
+ * 256 .. 16384 go stream by stream inside the call, and so does an LMP or HP-ARMA chunk of one stream.  The opt-in in-launch hop-means producers and the piecewise means (GLFER_MEANS_PRODUCERS, GLFER_EXACT_PIECE_MB)
  * are never taken by this entry.
  * The moving average of many streams: glfer_hip_spectrogram_avg_batch_device and glfer_hip_avg_batch_device below; their
  * waterfalls: glfer_hip_waterfall_batch_device.
@@ -269,8 +273,11 @@ int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_strea
  * streams, blockIdx.y indexing a small per-stream table the call builds and uploads; more than 65 535 streams go in chunks
  * of that many.  LMP plans: the packed periodograms go to scratch through the same launch set and the ragged statistic
  * (glfer_hip_lmp_ragged_device's kernels) runs over the same row starts, in chunks of streams whose rows take at most half of
- * glfer_hip_scratch_limit's cap (one stream at least).  HP-ARMA and N outside 256 .. 16384 go stream by stream inside the
- * call, and so does a call (or a chunk) of one stream.
+ * glfer_hip_scratch_limit's cap (one stream at least).  HP-ARMA plans at every N they accept: one launch over the flat list of
+ * all streams' frames, a per-stream table (first flat frame, samples, first row, frame0, frames; streams without frames have
+ * no entry) searched by bisection -- over the raw samples, or with mean removal over corrected copies made once for all
+ * streams (1 kernel a call, 3 with sub_mean = 1, 2 with sub_mean = 2).  The other modes at N outside 256 .. 16384 go stream
+ * by stream inside the call, and so does a call (or a chunk) of one stream.
  * GLFER_E_ARG: NULL plan; NULL offsets / lengths with nstreams > 0; NULL d_samples or d_psd while any stream has a frame; an
  * odd offset with integer samples; a stream of more than 2^31 - 1 frames; sizes that overflow size_t -- all checked before
  * anything on the device is touched; a hip_stream that is being captured into a graph (the per-stream tables are uploaded from
@@ -366,7 +373,7 @@ int glfer_hip_mtm_ftest_device(glfer_hip_plan *plan, const void *d_stream, size_
  * The F-test tables are made by the first F call on a plan, whichever entry it is; the plan is left as the single entry leaves it.
  * The multitaper rows and F from one pass over the samples: glfer_hip_mtm_rows_ftest_device and its batch form below.
  * Streams of unequal length (one length per stream): glfer_hip_mtm_ftest_ragged_device below.
- * Not built: HP-ARMA batches in one launch set, batched host / WAV entries. */
+ * Not built: batched host / WAV entries. */
 int glfer_hip_mtm_ftest_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams, size_t stream_pitch,
                                      size_t nsamples, size_t first_frame, size_t nframes, float *d_ftest, int mu_live,
                                      void *hip_stream);
