@@ -63,6 +63,9 @@ EXPORTS = [
     "glfer_hip_mtm_ftest_ragged_device", "glfer_hip_mtm_rows_ftest_ragged_device",
     # the LMP statistic over rows already on the device: one stream, a batch, ragged
     "glfer_hip_lmp_device", "glfer_hip_lmp_batch_device", "glfer_hip_lmp_ragged_device",
+    # multi-channel recordings: every interleaved channel as a stream of its own
+    "glfer_hip_deinterleave_device", "glfer_hip_spectrogram_channels_device", "glfer_hip_spectrogram_host_channels",
+    "glfer_hip_spectrogram_wav_channels",
 ]
 
 
@@ -194,6 +197,11 @@ def lib():
     if hasattr(L, "glfer_hip_waterfall_ragged_device"):
         L.glfer_hip_waterfall_ragged_device.argtypes = [C.POINTER(Display), sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp,
                                                         vp, vp]
+    if hasattr(L, "glfer_hip_deinterleave_device"):
+        L.glfer_hip_deinterleave_device.argtypes = [vp, sz, C.c_int, C.c_int, vp, C.c_int, vp, sz, vp]
+        L.glfer_hip_spectrogram_channels_device.argtypes = [vp, vp, sz, C.c_int, vp, C.c_int, sz, sz, vp, vp]
+        L.glfer_hip_spectrogram_host_channels.argtypes = [vp, vp, sz, C.c_int, vp, C.c_int, vp, C.POINTER(sz)]
+        L.glfer_hip_spectrogram_wav_channels.argtypes = [vp, C.c_char_p, vp, C.c_int, vp, sz, C.POINTER(sz), sz]
     L.glfer_hip_host_alloc.argtypes = [sz]
     L.glfer_hip_host_alloc.restype = vp
     L.glfer_hip_host_free.argtypes = [vp]
@@ -423,6 +431,65 @@ class Spectrogram:
         _check(lib().glfer_hip_spectrogram_batch_device(self._h, C.c_void_p(streams.data_ptr()), nb, streams.stride(0), total,
                                                         first_frame, nframes, C.c_void_p(out.data_ptr()), st),
                "glfer_hip_spectrogram_batch_device")
+        return out
+
+    def run_channels(self, samples, channels=None, select=None, first_frame=0, nframes=None, out=None):
+        """samples: an interleaved recording on this GPU, of the plan's sample dtype -- a 1-D tensor (`channels` says how many
+        channels it holds) or a contiguous [S][C] tensor (channels = C).  select: channel indices (duplicates allowed; None =
+        all, in order).  Returns psd [nselect][nframes][pitch] -- out[j] is what run() gives on a contiguous copy of channel
+        select[j] -- launched on torch's current stream (glfer_hip_spectrogram_channels_device)."""
+        torch = _torch()
+        assert samples.is_cuda and samples.is_contiguous() and samples.dim() in (1, 2)
+        assert samples.dtype == self._sample_dtype(), (samples.dtype, self._sample_dtype())
+        if samples.dim() == 2:
+            assert channels is None or channels == samples.size(1)
+            channels = samples.size(1)
+        assert channels is not None and channels >= 1 and samples.numel() % channels == 0
+        per = samples.numel() // channels
+        sel, nsel = _selection(channels, select)
+        if nframes is None:
+            nframes = self.num_frames(per) - first_frame
+        if out is None:
+            out = torch.empty((nsel, nframes, self.pitch), dtype=torch.float32, device=samples.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= nsel * nframes * self.pitch
+        st = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+        _check(lib().glfer_hip_spectrogram_channels_device(self._h, C.c_void_p(samples.data_ptr()), per, channels, sel, nsel,
+                                                           first_frame, nframes, C.c_void_p(out.data_ptr()), st),
+               "glfer_hip_spectrogram_channels_device")
+        return out
+
+    def run_host_channels(self, samples, channels, select=None, pinned=False):
+        """samples: an interleaved recording on the host (numpy, 1-D or [S][C]); returns numpy psd [nselect][frames][bins],
+        plane j the rows run_host gives on channel select[j].  One pass through the chunk ring
+        (glfer_hip_spectrogram_host_channels).  pinned=True: the rows come back in pinned memory."""
+        want = {SAMPLES_F32: np.float32, SAMPLES_S16: np.int16, SAMPLES_U8: np.uint8}[self.params.sample_format]
+        samples = np.ascontiguousarray(samples, want)
+        assert samples.size % channels == 0
+        per = samples.size // channels
+        sel, nsel = _selection(channels, select)
+        frames = self.num_frames(per)
+        shape = (nsel, frames, self.bins)
+        out = pinned_empty(shape, np.float32) if pinned and frames else np.empty(shape, np.float32)
+        nf = C.c_size_t(0)
+        _check(lib().glfer_hip_spectrogram_host_channels(self._h, samples.ctypes.data, per, channels, sel, nsel, out.ctypes.data,
+                                                         C.byref(nf)), "glfer_hip_spectrogram_host_channels")
+        assert nf.value == frames
+        return out
+
+    def run_wav_channels(self, path, select=None, chunk_frames=0, max_frames=None):
+        """A multi-channel WAV file -> numpy psd [nselect][frames][bins]: the file's channels (from its header) as streams of
+        their own, one pass over the file (glfer_hip_spectrogram_wav_channels).  run_wav keeps reading such a file as one
+        stream of interleaved samples, as the reference does."""
+        info = wav_probe(path)
+        sel, nsel = _selection(info.channels, select)
+        frames = (info.data_bytes // (info.channels * (info.bits_per_sample // 8))) // self.hop
+        if max_frames is not None:
+            frames = min(frames, max_frames)
+        out = np.empty((nsel, frames, self.bins), np.float32)
+        nf = C.c_size_t(0)
+        _check(lib().glfer_hip_spectrogram_wav_channels(self._h, os.fsencode(path), sel, nsel, out.ctypes.data, frames,
+                                                        C.byref(nf), chunk_frames), "glfer_hip_spectrogram_wav_channels")
+        assert nf.value == frames
         return out
 
     def ragged_frames(self, lengths):
@@ -765,6 +832,34 @@ class Spectrogram:
                "glfer_hip_spectrogram_host")
         assert nf.value == frames
         return out
+
+
+def _selection(channels, select):
+    """(ctypes int array or None, count) of a channel selection for the *_channels entries."""
+    if select is None:
+        return None, channels
+    idx = [int(c) for c in select]
+    return (C.c_int * len(idx))(*idx), len(idx)
+
+
+def deinterleave(samples, channels, select=None, out=None):
+    """samples: interleaved recording on a GPU (1-D or contiguous [S][C]) of dtype float32 / int16 / uint8.  Returns the selected
+    channels as planes, [nselect][S] (out: a 2-D tensor with stride(1) == 1 and stride(0) >= S), on torch's current stream
+    (glfer_hip_deinterleave_device: bytes are moved, never converted)."""
+    torch = _torch()
+    fmt = {torch.float32: SAMPLES_F32, torch.int16: SAMPLES_S16, torch.uint8: SAMPLES_U8}[samples.dtype]
+    assert samples.is_cuda and samples.is_contiguous() and samples.numel() % channels == 0
+    per = samples.numel() // channels
+    sel, nsel = _selection(channels, select)
+    if out is None:
+        out = torch.empty((nsel, per), dtype=samples.dtype, device=samples.device)
+    assert out.is_cuda and out.dtype == samples.dtype and out.dim() == 2 and out.size(0) == nsel and out.size(1) == per
+    assert (out.stride(1) == 1 or per <= 1) and (out.stride(0) >= per or nsel <= 1)
+    st = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+    _check(lib().glfer_hip_deinterleave_device(C.c_void_p(samples.data_ptr()), per, channels, fmt, sel, nsel,
+                                               C.c_void_p(out.data_ptr()), out.stride(0) if nsel > 1 else max(out.stride(0), per), st),
+           "glfer_hip_deinterleave_device")
+    return out
 
 
 def frame_range(total_frames, rank, world):

@@ -19,6 +19,7 @@
 #include <new>
 
 #include "frame_cuts.h"
+#include "channel_cuts.h"
 #include "host_tables.h"
 #include "hparma_frames.h"
 #include "ragged_cols.hpp"
@@ -1724,6 +1725,75 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
     }
     if (rows) glfer::scratch_free(rows, st);
     if (rc != GLFER_OK) return rc;
+  }
+  return GLFER_OK;
+}
+
+// ---- multi-channel recordings (glfer_hip.h): every interleaved channel as a stream of its own ---------------------------------
+
+static bool channels_wide() {                       // GLFER_CHANNELS_WIDE=0: the general form everywhere (A/B runs)
+  const char *e = getenv("GLFER_CHANNELS_WIDE");
+  return !(e && *e == '0');
+}
+
+int glfer_hip_deinterleave_device(const void *d_in, size_t nframes, int channels, int sample_format, const int *select, int nselect,
+                                  void *d_out, size_t out_pitch, void *hip_stream) {
+  unsigned char sel[GLFER_MAX_CHANNELS];
+  const int nsel = glfer_channel_selection(channels, select, nselect, sel);
+  if (!nsel) return GLFER_E_ARG;
+  if (sample_format != GLFER_SAMPLES_F32 && sample_format != GLFER_SAMPLES_S16 && sample_format != GLFER_SAMPLES_U8) return GLFER_E_ARG;
+  if (out_pitch < nframes) return GLFER_E_ARG;
+  if (nframes == 0) return GLFER_OK;
+  if (!d_in || !d_out) return GLFER_E_ARG;
+  const size_t esz = glfer_sample_size(sample_format);
+  if (nframes > (SIZE_MAX / esz) / (size_t)channels || out_pitch > (SIZE_MAX / esz) / (size_t)nsel) return GLFER_E_ARG;
+  DeviceGuard guard(glfer::data_device(d_in));
+  HIP_TRY(guard.error());
+  const hipError_t e = glfer_launch_deinterleave(d_in, nframes, channels, (int)esz, sel, nsel, d_out, out_pitch, channels_wide() ? 1 : 0,
+                                                 (hipStream_t)hip_stream);
+  return e == hipSuccess ? GLFER_OK : hip_fail(e, "deinterleave launch");
+}
+
+int glfer_hip_spectrogram_channels_device(glfer_hip_plan *p, const void *d_samples, size_t nsamples_per_channel, int channels,
+                                          const int *select, int nselect, size_t first, size_t nframes, float *d_psd,
+                                          void *hip_stream) {
+  if (!p) return GLFER_E_ARG;
+  unsigned char sel[GLFER_MAX_CHANNELS];
+  const int nsel = glfer_channel_selection(channels, select, nselect, sel);
+  if (!nsel) return GLFER_E_ARG;
+  if (nframes == 0) return GLFER_OK;
+  if (!d_samples || !d_psd) return GLFER_E_ARG;
+  if (first > SIZE_MAX - nframes || (first + nframes) > nsamples_per_channel / (size_t)p->hop) return GLFER_E_ARG;   // frame past the recording
+  if (nframes > 0x7fffffffu) return GLFER_E_ARG;
+  const size_t esz = glfer_sample_size(p->cfg.sample_format), hop = (size_t)p->hop, rows = (size_t)p->pitch;
+  if (nsamples_per_channel > (SIZE_MAX / esz) / (size_t)channels || nframes > (SIZE_MAX / sizeof(float) / rows) / (size_t)nsel)
+    return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  // one channel, the default selection: the recording is the stream
+  if (channels == 1 && !select) return glfer_run_device(p, d_samples, nsamples_per_channel, first, nframes, d_psd, nullptr, st);
+  DeviceGuard guard(p->cfg.device);
+  HIP_TRY(guard.error());
+  // The hops frames [at, end) read go to scratch planes and the batch entry's body runs on the planes' virtual base, the frame
+  // indices left global.  Planes of more than half the scratch cap: pieces of frames (channel_cuts.h), each with its own halo.
+  const size_t halo = glfer_channel_halo((size_t)p->keep, hop, p->cfg.mode == GLFER_MODE_LMP ? (size_t)p->lmp_av : 0);
+  const size_t budget = glfer::scratch_cap() / 2, end = first + nframes;
+  const char *src = static_cast<const char *>(d_samples);
+  for (size_t at = first; at < end;) {
+    const size_t to = glfer_channel_piece_end(at, end, halo, hop, esz, (size_t)nsel, budget);
+    const glfer_hop_span h = glfer_channel_hops(at, to - at, halo);
+    const size_t plane = h.n * hop, pitch = glfer_plane_pitch(plane, esz);
+    char *planes = nullptr;
+    hipError_t e = glfer::scratch_malloc((void **)&planes, (size_t)nsel * pitch * esz, st);
+    if (e != hipSuccess) return hip_fail(e, "scratch (channel planes)");
+    e = glfer_launch_deinterleave(src + h.lo * hop * (size_t)channels * esz, plane, channels, (int)esz, sel, nsel, planes, pitch,
+                                  channels_wide() ? 1 : 0, st);
+    int rc = e == hipSuccess ? GLFER_OK : hip_fail(e, "deinterleave launch");
+    if (rc == GLFER_OK)
+      rc = batch_rows(p, planes - h.lo * hop * esz, (size_t)nsel, pitch, nsamples_per_channel, at, to - at, d_psd + (at - first) * rows,
+                      nframes * rows, st);
+    glfer::scratch_free(planes, st);
+    if (rc != GLFER_OK) return rc;
+    at = to;
   }
   return GLFER_OK;
 }

@@ -12,6 +12,7 @@
 // (glfer_hip_host_alloc), otherwise through the pinned row buffers and a host copy.
 #include "plan.h"
 #include "frame_cuts.h"
+#include "channel_cuts.h"
 
 #include <algorithm>
 #include <cctype>
@@ -46,7 +47,7 @@ static size_t ring_bytes(const IngestRing *r) {
   size_t b = 0;
   for (int i = 0; i < 2; i++)
     for (int k = 0; k < 8; k++) b += r->cap[i][k];
-  return b;
+  return b + r->cap_planes[0] + r->cap_planes[1];
 }
 IngestRing *ingest_ring_take(int dev) {
   if (dev < 0 || dev >= 64) return nullptr;
@@ -102,6 +103,7 @@ static void ingest_ring_destroy(IngestRing *r) {
     if (r->d_stats[i]) (void)hipFree(r->d_stats[i]);
     if (r->d_rgb[i]) (void)hipFree(r->d_rgb[i]);
     if (r->d_lev[i]) (void)hipFree(r->d_lev[i]);
+    if (r->d_planes[i]) (void)hipFree(r->d_planes[i]);
     if (r->st[i]) (void)hipStreamDestroy(r->st[i]);
   }
   delete r;
@@ -359,6 +361,12 @@ struct Job {
   const unsigned char *pinned_src = nullptr;   // the whole stream in pinned host memory (hop 0 at this address): uploaded
                                                // from where it lies, no staging copy
   Sink sink;                             // rows of frame f go to index f - frame_lo
+  // A multi-channel recording (the *_channels entries; PSD sink to the host only): the reader's hop is `channels` interleaved
+  // hops, the chunk is de-interleaved on the device and run as a batch of nselect streams; selection j's rows go to
+  // sink.h_psd + (j * plane_frames + f - frame_lo) * bins.  channels <= 1: the single stream of every other job.
+  int channels = 1, nselect = 0;
+  unsigned char select[GLFER_MAX_CHANNELS] = {};
+  size_t plane_frames = 0;
   glfer_hip_phases *phases = nullptr;    // optional: where this job's time went (glfer_hip_workers_*)
 };
 
@@ -368,8 +376,8 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 // streams run at the link's rate there); a SHORT job -- a worker's share of a 1-hour WAV is 1 300 frames of 32 KB -- is cut into at
 // least sixteen chunks of at least ~2 MiB, so that reading chunk c + 1, uploading it, and bringing chunk c - 1's rows home overlap
 // instead of happening once each, one after the other.
-size_t pick_chunk(const glfer_hip_plan *p, size_t frames, size_t asked) {
-  const size_t esz = sample_bytes(p->cfg.sample_format), hop = (size_t)p->hop;
+size_t pick_chunk(const glfer_hip_plan *p, size_t frames, size_t asked, size_t channels = 1) {
+  const size_t esz = sample_bytes(p->cfg.sample_format) * channels, hop = (size_t)p->hop;   // (a hop of a recording: every channel's)
   size_t chunk = asked;
   if (chunk == 0) {
     chunk = 16384;
@@ -393,14 +401,19 @@ int run_job(const Job &job, size_t *frames_done) {
   // rows go home through a dense ring: a pitched plan (cfg.psd_pitch) or display belongs to the device entries
   if (p->pitch != p->bins || (job.sink.disp && job.sink.disp->psd_pitch)) return GLFER_E_ARG;
   if (job.frames == 0) return GLFER_OK;
-  const size_t esz = sample_bytes(p->cfg.sample_format);
+  // a multi-channel job: only rows to host memory (the *_channels entries build nothing else)
+  const bool multi = job.channels > 1 || job.nselect > 0;
+  if (multi && (job.sink.disp || job.sink.d_rows || job.tail_fresh >= 0 || job.nselect < 1)) return GLFER_E_ARG;
+  const size_t ns = multi ? (size_t)job.nselect : 1;
+  const size_t sample = sample_bytes(p->cfg.sample_format);
+  const size_t esz = multi ? sample * (size_t)job.channels : sample;   // bytes of a sample FRAME: what the reader, the halo copy and the upload move per sample of a hop
   const size_t hop = (size_t)p->hop, bins = (size_t)p->bins;
   // history in front of every chunk: whole hops covering the N-H overlap (per-hop means need
   // complete hops), plus the frames the LMP ring reaches back
   const size_t halo_hops = glfer_first_inside((size_t)p->keep, (size_t)p->hop) +
                            (p->cfg.mode == GLFER_MODE_LMP ? (size_t)p->lmp_av - 1 : 0);
   const double t_job = now_s();
-  const size_t chunk = pick_chunk(p, job.frames, job.chunk_frames);
+  const size_t chunk = multi ? pick_chunk(p, job.frames, job.chunk_frames, (size_t)job.channels) : pick_chunk(p, job.frames, job.chunk_frames);
   // chunk boundaries sit on GLOBAL multiples of GLFER_FRAME_ALIGN: the first chunk of a job that
   // starts off the grid is shortened to reach it
   const bool waterfall = job.sink.disp != nullptr;
@@ -438,6 +451,7 @@ int run_job(const Job &job, size_t *frames_done) {
   hipStream_t *st = R.st;
   const size_t in_bytes = (halo_hops + chunk + 1) * hop * esz;       // + 1: a trailing partial block rides on the last chunk
   const size_t rows_cap = chunk + 1;
+  const size_t plane_pitch = multi ? glfer_plane_pitch((halo_hops + chunk + 1) * hop, sample) : 0;   // samples between a chunk's planes
   hipError_t e = hipSuccess;
   // a buffer of at least `bytes`: the one the ring has, or a new one (kind: 0 pinned host, 1 device)
   std::unique_ptr<NodeBinding> near_gpu;
@@ -461,8 +475,9 @@ int run_job(const Job &job, size_t *frames_done) {
     if (!st[b]) e = hipStreamCreateWithFlags(&st[b], hipStreamNonBlocking);
     if (!job.pinned_src) ensure((void **)&h_in[b], &R.cap[b][0], in_bytes, 0);
     ensure((void **)&d_in[b], &R.cap[b][1], in_bytes, 1);
-    if (!dev_sink) ensure((void **)&d_psd[b], &R.cap[b][2], rows_cap * bins * sizeof(float), 1);
-    if (!direct_out && !dev_sink) ensure((void **)&h_out[b], &R.cap[b][3], rows_cap * row_bytes, 0);
+    if (!dev_sink) ensure((void **)&d_psd[b], &R.cap[b][2], ns * rows_cap * bins * sizeof(float), 1);
+    if (!direct_out && !dev_sink) ensure((void **)&h_out[b], &R.cap[b][3], ns * rows_cap * row_bytes, 0);
+    if (multi) ensure((void **)&R.d_planes[b], &R.cap_planes[b], ns * plane_pitch * sample, 1);
     if (waterfall) {
       ensure((void **)&d_stats[b], &R.cap[b][4], rows_cap * 4 * sizeof(float), 1);
       ensure((void **)&d_rgb[b], &R.cap[b][5], rows_cap * bins * 3, 1);
@@ -502,6 +517,9 @@ int run_job(const Job &job, size_t *frames_done) {
       if (waterfall) {
         copy_wide(job.sink.h_rgb + off * bins * 3, h_out[b], nf * bins * 3);
         if (job.sink.h_lev) copy_wide(job.sink.h_lev + off * bins, h_lev[b], nf * bins * sizeof(short));
+      } else if (multi) {
+        for (size_t j = 0; j < ns; j++)
+          copy_wide(job.sink.h_psd + (j * job.plane_frames + off) * bins, h_out[b] + j * nf * bins * sizeof(float), nf * bins * sizeof(float));
       } else {
         copy_wide(job.sink.h_psd + off * bins, h_out[b], nf * bins * sizeof(float));
       }
@@ -576,7 +594,14 @@ int run_job(const Job &job, size_t *frames_done) {
     }
     const unsigned char *vbase = d_in[b] - lo_hop * hop * esz;       // virtual address of stream sample 0
     float *rows = dev_sink ? job.sink.d_rows + (cf - job.frame_lo) * bins : d_psd[b];
-    rc = glfer_run_device(p, vbase, (cf + nf) * hop, cf, nf, rows, nullptr, st[b], has_tail ? job.tail_fresh : -1);
+    if (multi) {
+      // the chunk's hops of every selected channel side by side, then the batch entry on the planes' virtual base
+      e = glfer_launch_deinterleave(d_in[b], up_hops * hop, job.channels, (int)sample, job.select, job.nselect, R.d_planes[b], plane_pitch, 1, st[b]);
+      if (e != hipSuccess) { rc = hip_fail(e, "ingest: deinterleave"); break; }
+      rc = glfer_hip_spectrogram_batch_device(p, R.d_planes[b] - lo_hop * hop * sample, ns, plane_pitch, (cf + nf) * hop, cf, nf, rows, st[b]);
+    } else {
+      rc = glfer_run_device(p, vbase, (cf + nf) * hop, cf, nf, rows, nullptr, st[b], has_tail ? job.tail_fresh : -1);
+    }
     if (rc) break;
     if (timed) (void)hipEventRecord(R.ev_t[b][2], st[b]);
     if (dev_sink) {
@@ -595,6 +620,11 @@ int run_job(const Job &job, size_t *frames_done) {
       if (e == hipSuccess && job.sink.h_lev) {
         short *ldst = direct_out ? job.sink.h_lev + (cf - job.frame_lo) * bins : h_lev[b];
         e = hipMemcpyAsync(ldst, d_lev[b], nf * bins * sizeof(short), hipMemcpyDeviceToHost, st[b]);
+      }
+    } else if (multi) {
+      for (size_t j = 0; j < ns && e == hipSuccess; j++) {          // plane by plane: the caller's planes lie plane_frames rows apart
+        float *dst = direct_out ? job.sink.h_psd + (j * job.plane_frames + cf - job.frame_lo) * bins : reinterpret_cast<float *>(h_out[b]) + j * nf * bins;
+        e = hipMemcpyAsync(dst, d_psd[b] + j * nf * bins, nf * bins * sizeof(float), hipMemcpyDeviceToHost, st[b]);
       }
     } else {
       float *dst = direct_out ? job.sink.h_psd + (cf - job.frame_lo) * bins : reinterpret_cast<float *>(h_out[b]);
@@ -1493,6 +1523,72 @@ int glfer_hip_spectrogram_wav_ex(glfer_hip_plan *p, const char *path, float *h_p
 int glfer_hip_spectrogram_wav(glfer_hip_plan *p, const char *path, float *h_psd, size_t max_frames,
                               size_t *nframes_out, size_t chunk_frames) {
   return glfer_hip_spectrogram_wav_ex(p, path, h_psd, max_frames, nframes_out, chunk_frames, 0);
+}
+
+// Multi-channel recordings through the chunk ring, one pass over the data: a chunk goes up interleaved, is de-interleaved on the
+// device and runs as a batch of the selected channels (run_job's multi-channel job); selection j's rows land at
+// h_psd + j * plane_frames * bins.
+static int channels_job(glfer_hip_plan *p, int channels, const unsigned char *sel, int nsel, size_t frames, size_t plane_frames,
+                        size_t chunk_frames, HopReader read, const unsigned char *pinned_src, float *h_psd, size_t *nframes_out) {
+  Job job;
+  job.p = p;
+  job.frames = frames;
+  job.chunk_frames = chunk_frames;
+  job.channels = channels;
+  job.nselect = nsel;
+  memcpy(job.select, sel, (size_t)nsel);
+  job.plane_frames = plane_frames;
+  job.sink.h_psd = h_psd;
+  job.read = std::move(read);
+  job.pinned_src = pinned_src;
+  if (!job.read) return GLFER_E_ARG;
+  return run_job(job, nframes_out);
+}
+
+int glfer_hip_spectrogram_host_channels(glfer_hip_plan *p, const void *h_samples, size_t nsamples_per_channel, int channels,
+                                        const int *select, int nselect, float *h_psd, size_t *nframes_out) {
+  if (!p || !nframes_out) return GLFER_E_ARG;
+  unsigned char sel[GLFER_MAX_CHANNELS];
+  const int nsel = glfer_channel_selection(channels, select, nselect, sel);
+  if (!nsel) return GLFER_E_ARG;
+  if (p->pitch != p->bins) return GLFER_E_ARG;                 // host rows are dense (cfg.psd_pitch: the device entries)
+  if (channels == 1 && !select) return glfer_hip_spectrogram_host(p, h_samples, nsamples_per_channel, h_psd, nframes_out);
+  const size_t frames = nsamples_per_channel / (size_t)p->hop;
+  *nframes_out = frames;
+  if (frames == 0) return GLFER_OK;
+  if (!h_samples || !h_psd) return GLFER_E_ARG;
+  const size_t esz = sample_bytes(p->cfg.sample_format);
+  if (nsamples_per_channel > (SIZE_MAX / esz) / (size_t)channels || frames > (SIZE_MAX / sizeof(float) / (size_t)p->bins) / (size_t)nsel)
+    return GLFER_E_ARG;
+  const size_t hop_bytes = (size_t)p->hop * esz * (size_t)channels;
+  return channels_job(p, channels, sel, nsel, frames, frames, 0, array_reader(h_samples, hop_bytes),
+                      is_pinned_host(h_samples) ? (const unsigned char *)h_samples : nullptr, h_psd, nframes_out);
+}
+
+int glfer_hip_spectrogram_wav_channels(glfer_hip_plan *p, const char *path, const int *select, int nselect, float *h_psd,
+                                       size_t max_frames, size_t *nframes_out, size_t chunk_frames) {
+  if (!p || !path || !nframes_out) return GLFER_E_ARG;
+  glfer_wav_info wi;
+  const int prc = glfer_hip_wav_probe(path, &wi);
+  if (prc) return prc;
+  if (p->cfg.sample_format != (wi.bits_per_sample == 8 ? GLFER_SAMPLES_U8 : GLFER_SAMPLES_S16)) return GLFER_E_ARG;
+  unsigned char sel[GLFER_MAX_CHANNELS];
+  const int nsel = glfer_channel_selection(wi.channels, select, nselect, sel);
+  if (!nsel) return GLFER_E_ARG;
+  if (p->pitch != p->bins) return GLFER_E_ARG;                 // host rows are dense
+  if (wi.channels == 1 && !select) return glfer_hip_spectrogram_wav(p, path, h_psd, max_frames, nframes_out, chunk_frames);
+  // the planes of h_psd lie max_frames rows apart: the caller's allocation, so it must be a real size with more than one plane
+  if (nsel > 1 && max_frames > (SIZE_MAX / sizeof(float) / (size_t)p->bins) / (size_t)nsel) return GLFER_E_ARG;
+  WavLayout w;
+  w.esz = (size_t)wi.bits_per_sample / 8;
+  w.hop_bytes = (size_t)p->hop * w.esz * (size_t)wi.channels;
+  w.data_offset = wi.data_offset;
+  w.whole = (wi.data_bytes / (w.esz * (size_t)wi.channels)) / (size_t)p->hop;     // whole hops of whole sample frames
+  const size_t frames = std::min(w.whole, max_frames);
+  *nframes_out = frames;
+  if (frames == 0) return GLFER_OK;
+  if (!h_psd) return GLFER_E_ARG;
+  return channels_job(p, wi.channels, sel, nsel, frames, max_frames, chunk_frames, wav_reader(path, w), nullptr, h_psd, nframes_out);
 }
 
 // BASELINE config 4 as worded -- "1-hour 48 kHz WAV, frame-batch sharded across 8 x MI355X": the file's

@@ -81,6 +81,8 @@ struct IngestRing {
   unsigned char *d_rgb[2] = {nullptr, nullptr};
   short *h_lev[2] = {nullptr, nullptr}, *d_lev[2] = {nullptr, nullptr};
   float *d_psd[2] = {nullptr, nullptr}, *d_stats[2] = {nullptr, nullptr};
+  unsigned char *d_planes[2] = {nullptr, nullptr};   // the channel entries' de-interleaved chunk (cap_planes bytes); never made by a one-channel job
+  size_t cap_planes[2] = {0, 0};
   hipStream_t st[2] = {nullptr, nullptr};
   hipStream_t up = nullptr;                       // every chunk's upload (round 4): uploads queue behind one another, so that chunk c + 1 goes up while chunk c's rows come down
   hipEvent_t ev_up[2] = {nullptr, nullptr};       // chunk b's upload done: its stream's kernels wait for it
@@ -127,6 +129,11 @@ extern "C" hipError_t glfer_launch_avg_batch(int mode, const float *psd, size_t 
 extern "C" hipError_t glfer_launch_avg_ragged(int mode, const float *psd, const glfer::RaggedColsEntry *streams, size_t n, int bins,
                                               int n_out, int depth, int minbin, int maxbin, int max0, double *avg, double *ret,
                                               hipStream_t st);
+
+// channels.hip: out[j * out_pitch + i] = in[i * channels + select[j]] over nframes sample frames of esz bytes a sample; select holds
+// nselect checked channel indices.  wide = 0 keeps the general form where the stereo form could run (A/B runs).
+extern "C" hipError_t glfer_launch_deinterleave(const void *in, size_t nframes, int channels, int esz, const unsigned char *select,
+                                                int nselect, void *out, size_t out_pitch, int wide, hipStream_t st);
 
 struct glfer_hip_plan {
   glfer_hip_config cfg;

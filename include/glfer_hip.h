@@ -244,7 +244,9 @@ int glfer_hip_spectrogram_device(glfer_hip_plan *plan, const void *d_stream, siz
  * Streams of unequal length: glfer_hip_spectrogram_ragged_device below; their moving average and waterfall:
  * glfer_hip_avg_ragged_device, glfer_hip_spectrogram_avg_ragged_device and glfer_hip_waterfall_ragged_device; their F-test:
  * glfer_hip_mtm_ftest_ragged_device and glfer_hip_mtm_rows_ftest_ragged_device.
- * Not covered: batched host / WAV / workers entries, the halfcomplex-spectrum output, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as they are. */
+ * The channels of ONE interleaved recording as the streams of a batch: glfer_hip_spectrogram_channels_device, and from host memory
+ * or a WAV file glfer_hip_spectrogram_host_channels / glfer_hip_spectrogram_wav_channels ("Multi-channel recordings" below).
+ * Not covered: batched host / WAV / workers entries for independent streams, the halfcomplex-spectrum output, several GPUs.  glfer_hip_floor_device takes the nstreams x nframes rows as they are. */
 int glfer_hip_spectrogram_batch_device(glfer_hip_plan *plan, const void *d_streams, size_t nstreams,
                                        size_t stream_pitch, size_t nsamples, size_t first_frame,
                                        size_t nframes, float *d_psd, void *hip_stream);
@@ -493,13 +495,15 @@ int glfer_hip_spectrogram_host_workers(const glfer_hip_config *cfg, const int *d
  * The canonical 44-byte RIFF/WAVE header of wav_fmt.h:34-52, read with fixed-width fields
  * (the reference's struct uses u_long and mis-parses every file on LP64 hosts).  As in the
  * reference only PCM (format 1) with 8 or 16 bits per sample is accepted and the channel
- * count is not interpreted: interleaved channels are treated as one sample stream.  The RIFF
+ * count is not interpreted by glfer_hip_spectrogram_wav and its _ex / _range / _multi / _workers forms: interleaved channels are
+ * treated as one sample stream (wav_fmt.c ignores `modus`).  glfer_hip_spectrogram_wav_channels reads `channels` and gives every
+ * channel its own rows ("Multi-channel recordings" below).  The RIFF
  * chunks are walked ("fmt ", then "data"; "LIST" / "fact" / ... skipped), so a file with other
  * chunks before or after its samples is read correctly -- the reference's fixed 44-byte struct
  * (wav_fmt.h:34-52) would play them as samples; a file that cannot be walked is read its way. */
 typedef struct glfer_wav_info {
   int format;            /* 1 = PCM                                  wav_fmt.h:42 */
-  int channels;          /* "modus": 1 mono, 2 stereo                wav_fmt.h:43 */
+  int channels;          /* "modus": 1 mono, 2 stereo                wav_fmt.h:43; read by glfer_hip_spectrogram_wav_channels only */
   int sample_rate;       /* sample_fq                                wav_fmt.h:44 */
   int bits_per_sample;   /* bit_p_spl: 8 or 16                       wav_fmt.h:47 */
   size_t data_offset;    /* first byte of the "data" chunk's payload (44 in the reference's fixed layout) */
@@ -530,6 +534,75 @@ int glfer_hip_spectrogram_wav_ex(glfer_hip_plan *plan, const char *path, float *
  * (The per-hop shims' read-ahead walks a file in such windows, glfer_compat.h.) */
 int glfer_hip_spectrogram_wav_range(glfer_hip_plan *plan, const char *path, size_t first_frame, size_t max_frames,
                                     float *h_psd, size_t *nframes_out, size_t chunk_frames, unsigned flags);
+
+/* ---- Multi-channel recordings: every interleaved channel as its own stream -----------------------------------------------------
+ * A recording of C channels holds sample frames: sample i of channel c is element i * C + c.  Every entry above reads such a
+ * buffer or file as ONE stream L R L R ... (the reference's behaviour, and still theirs); the entries here take the channel count
+ * and give each selected channel the rows the single-stream entries give on a contiguous copy of it.
+ * In all of them: channels is 1 .. 64; select is a HOST array of nselect (1 .. 64) channel indices, each < channels, duplicates
+ * allowed, consumed before the call returns; select == NULL means all channels in order (nselect is then ignored and the number
+ * selected is `channels`).  channels == 1 with select == NULL calls the single-stream entry directly: no copy is made.
+ *
+ * glfer_hip_deinterleave_device: the kernel alone (channels.hip), for callers who feed the other batch entries themselves (the
+ * F-test, the averages, the waterfall, rows-and-F):  d_out[j * out_pitch + i] = d_in[i * channels + select[j]]  for i < nframes
+ * sample frames.  Samples are moved as bytes, never converted.  out_pitch, in samples, must be >= nframes; d_in and d_out may
+ * have any alignment the sample size allows and must not overlap.  ONE launch, no table upload: legal on a hip_stream that is
+ * being captured.  Stereo (channels == 2) runs a form with 16-byte loads and 8-byte stores per lane over the longest run for which
+ * d_in and every plane written are aligned for it (chosen on the host from the pointers and the pitch: the source on whole sample
+ * frames from a 16-byte boundary, the planes 8-byte aligned there), and a lane-per-sample-frame form over the rest; every other
+ * channel count runs the latter.  GLFER_CHANNELS_WIDE=0 in the environment keeps the general form everywhere (A/B runs).
+ * Arguments, in this order, nothing on the device touched before they pass: GLFER_E_ARG for channels outside 1 .. 64, nselect
+ * outside 1 .. 64 with a non-NULL select or an index >= channels; for an unknown sample_format; for out_pitch < nframes; then
+ * GLFER_OK with nothing launched for nframes == 0; then GLFER_E_ARG for a NULL d_in or d_out, or sizes that overflow size_t.
+ * Asynchronous on hip_stream. */
+int glfer_hip_deinterleave_device(const void *d_in, size_t nframes, int channels, int sample_format, const int *select, int nselect,
+                                  void *d_out, size_t out_pitch, void *hip_stream);
+
+/* Frames [first_frame, first_frame + nframes) of every selected channel of a device-resident interleaved recording.
+ *   d_samples            : sample frame 0 of the recording (format = cfg.sample_format), under the virtual-base convention of
+ *                          the other device entries ("Cutting a stream": a piece is passed as d_piece - begin * channels *
+ *                          sample_size with the frame indices left global)
+ *   nsamples_per_channel : sample frames in the recording
+ *   d_psd                : device, [nselect][nframes][pitch] floats (cfg.psd_pitch honoured); row i of selection j at
+ *                          d_psd + (j * nframes + i) * pitch
+ * The rows of selection j are float for float the rows glfer_hip_spectrogram_device writes for the same frames of a contiguous
+ * copy of channel select[j] in the same sample format -- for every plan glfer_hip_spectrogram_batch_device takes (FFT, MTM and LMP
+ * at every N, HP-ARMA at every N it accepts), every sub_mean value, both history modes, f32 / s16 / u8.
+ * Only the hops those frames read are de-interleaved -- their own and the left halo of "Cutting a stream", ceil((N-H)/H) hops plus
+ * lmp_av - 1 for an LMP plan, none below hop 0 -- into stream-ordered scratch planes, each starting 16-byte aligned, a multiple
+ * of 16 bytes apart; the body of glfer_hip_spectrogram_batch_device then runs on the planes' virtual base with the frame indices
+ * left global: its kernels plus one.  Planes of more than half of glfer_hip_scratch_limit's cap: the call is cut into pieces of
+ * frames that end on GLOBAL multiples of GLFER_FRAME_ALIGN (at least GLFER_FRAME_ALIGN frames each while the call has that many
+ * left), each with its own halo, so the rows do not depend on the cut (glfer_amd/csrc/channel_cuts.h).
+ * Arguments, in this order, nothing on the device touched before they pass: GLFER_E_ARG for a NULL plan; for channels outside
+ * 1 .. 64, nselect outside 1 .. 64 with a non-NULL select or an index >= channels; then GLFER_OK with nothing launched for
+ * nframes == 0; then GLFER_E_ARG for a NULL d_samples or d_psd, a frame past the recording, nframes > 0x7fffffff, sizes that
+ * overflow size_t.  Asynchronous on hip_stream. */
+int glfer_hip_spectrogram_channels_device(glfer_hip_plan *plan, const void *d_samples, size_t nsamples_per_channel, int channels,
+                                          const int *select, int nselect, size_t first_frame, size_t nframes, float *d_psd,
+                                          void *hip_stream);
+
+/* The same from host memory and from a WAV file, through the chunk ring of glfer_hip_spectrogram_host in ONE pass over the data:
+ * a chunk of whole hops of sample frames is read and uploaded interleaved (a hop is hop * channels * sample_size bytes for the
+ * reader, the chunk's 256 MiB cap, the halo kept from the previous chunk and the upload), de-interleaved on the device into a
+ * second device buffer of the ring, run as a batch of the selected channels and downloaded plane by plane.  Blocking.
+ *   h_psd        : host, [nselect][F][N/2+1] floats, plane j the rows of channel select[j]; F = the frame count for the host
+ *                  entry (glfer_hip_num_frames(nsamples_per_channel)), max_frames for the file entry -- the caller's allocation,
+ *                  so it must be a real size when more than one channel is selected
+ *   *nframes_out : frames per channel: for a file (its size in whole sample frames) / hop, clipped to max_frames; a trailing
+ *                  incomplete sample frame or hop is dropped
+ * The file's channel count comes from its header.  Plane j equals glfer_hip_spectrogram_host's rows on the extracted channel.
+ * Limits: rows only (no waterfall), one plan on one GPU, whole hops only (GLFER_WAV_PARTIAL_TAIL is defined for one stream), dense
+ * rows (a plan with cfg.psd_pitch is refused, as by every host entry).
+ * Arguments, in this order, nothing on the device touched before they pass: GLFER_E_ARG for a NULL plan (path, nframes_out); [file:
+ * the probe's error for a file that is no PCM WAV, GLFER_E_ARG for a bit depth that does not match the plan;] GLFER_E_ARG for
+ * channels outside 1 .. 64, nselect outside 1 .. 64 with a non-NULL select or an index >= channels; for a pitched plan; then
+ * GLFER_OK with *nframes_out = 0 for a recording shorter than a hop; then GLFER_E_ARG for NULL buffers or sizes that overflow
+ * size_t. */
+int glfer_hip_spectrogram_host_channels(glfer_hip_plan *plan, const void *h_samples, size_t nsamples_per_channel, int channels,
+                                        const int *select, int nselect, float *h_psd, size_t *nframes_out);
+int glfer_hip_spectrogram_wav_channels(glfer_hip_plan *plan, const char *path, const int *select, int nselect, float *h_psd,
+                                       size_t max_frames, size_t *nframes_out, size_t chunk_frames);
 
 /* BASELINE config 4 as worded ("1-hour 48 kHz WAV, frame-batch sharded across 8 x MI355X"): the
  * file's frames dealt out over the GPUs named in device_mask (glfer_hip_frame_range: contiguous
