@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("GLFER_LIB_PATH") or os.path.join(_HERE, "lib", "libgl
 
 MODE_FFT, MODE_MTM, MODE_HPARMA, MODE_LMP = 0, 1, 2, 3
 WAV_PARTIAL_TAIL = 1
+IQ_CENTERED, IQ_SWAP = 1, 2                            # flags of the complex I/Q entries
 WINDOWS = {"hanning": 0, "blackman": 1, "gaussian": 2, "welch": 3,
            "bartlett": 4, "rectangular": 5, "hamming": 6, "kaiser": 7}
 SAMPLES_F32, SAMPLES_S16, SAMPLES_U8 = 0, 1, 2
@@ -66,6 +67,8 @@ EXPORTS = [
     # multi-channel recordings: every interleaved channel as a stream of its own
     "glfer_hip_deinterleave_device", "glfer_hip_spectrogram_channels_device", "glfer_hip_spectrogram_host_channels",
     "glfer_hip_spectrogram_wav_channels",
+    # complex I/Q input: two-sided rows
+    "glfer_hip_iq_supported", "glfer_hip_iq_tables", "glfer_hip_spectrogram_iq_device", "glfer_hip_spectrogram_iq_batch_device",
 ]
 
 
@@ -202,6 +205,11 @@ def lib():
         L.glfer_hip_spectrogram_channels_device.argtypes = [vp, vp, sz, C.c_int, vp, C.c_int, sz, sz, vp, vp]
         L.glfer_hip_spectrogram_host_channels.argtypes = [vp, vp, sz, C.c_int, vp, C.c_int, vp, C.POINTER(sz)]
         L.glfer_hip_spectrogram_wav_channels.argtypes = [vp, C.c_char_p, vp, C.c_int, vp, sz, C.POINTER(sz), sz]
+    if hasattr(L, "glfer_hip_spectrogram_iq_device"):
+        L.glfer_hip_iq_supported.argtypes = [C.POINTER(Config)]
+        L.glfer_hip_iq_tables.argtypes = [C.POINTER(Config), vp]
+        L.glfer_hip_spectrogram_iq_device.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_uint, vp]
+        L.glfer_hip_spectrogram_iq_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, sz, C.c_uint, vp]
     L.glfer_hip_host_alloc.argtypes = [sz]
     L.glfer_hip_host_alloc.restype = vp
     L.glfer_hip_host_free.argtypes = [vp]
@@ -277,6 +285,25 @@ def make_dpss(n, kmax, nw):
     s = np.empty(kmax + 1, np.float64)
     _check(lib().glfer_hip_make_dpss(n, kmax, float(nw), v.ctypes.data, s.ctypes.data), "make_dpss")
     return v, s
+
+
+def iq_supported(params):
+    """Whether a plan of these parameters takes complex I/Q input (glfer_hip_iq_supported; host only)."""
+    cfg = make_config(params)
+    return lib().glfer_hip_iq_supported(C.byref(cfg)) == 0
+
+
+def iq_tables(params):
+    """The scaled float table [tapers][n] of the complex I/Q rows (glfer_hip_iq_tables; host only)."""
+    cfg = make_config(params)
+    nt = lib().glfer_hip_iq_tables(C.byref(cfg), None)
+    if nt < 0:
+        _check(nt, "glfer_hip_iq_tables")
+    tab = np.empty((nt, params.n), np.float32)
+    rc = lib().glfer_hip_iq_tables(C.byref(cfg), tab.ctypes.data)
+    if rc < 0:
+        _check(rc, "glfer_hip_iq_tables")
+    return tab
 
 
 class FftParams:
@@ -431,6 +458,67 @@ class Spectrogram:
         _check(lib().glfer_hip_spectrogram_batch_device(self._h, C.c_void_p(streams.data_ptr()), nb, streams.stride(0), total,
                                                         first_frame, nframes, C.c_void_p(out.data_ptr()), st),
                "glfer_hip_spectrogram_batch_device")
+        return out
+
+    def _iq_view(self, iq, lead):
+        """The interleaved parts of a complex input as [lead dims..., S, 2] of the plan's sample dtype: complex64 [.., S] or
+        [.., S, 2] float32 / int16 / uint8 with a contiguous inner part."""
+        torch = _torch()
+        assert iq.is_cuda, "complex I/Q input lives on the GPU"
+        if iq.is_complex():
+            assert iq.dtype == torch.complex64, iq.dtype
+            iq = torch.view_as_real(iq)
+        assert iq.dim() == lead + 2 and iq.size(-1) == 2, tuple(iq.shape)
+        assert iq.dtype == self._sample_dtype(), (iq.dtype, self._sample_dtype())
+        assert iq.stride(-1) == 1 and (iq.stride(-2) == 2 or iq.size(-2) <= 1), iq.stride()
+        return iq
+
+    def _iq_out(self, out, shape, device):
+        torch = _torch()
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=device), self.n
+        assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == tuple(shape), (tuple(out.shape), shape)
+        assert out.stride(-1) == 1 or out.size(-1) <= 1
+        pitch = out.stride(-2) if out.size(-2) > 1 else self.n          # a pitched view: its row stride is the row pitch
+        assert pitch >= self.n
+        if len(shape) == 3 and out.size(0) > 1:
+            assert out.stride(0) == shape[1] * pitch, "batch rows lie (b * nframes + i) * row_pitch floats from the first"
+        return out, pitch
+
+    def run_iq(self, iq, first_frame=0, nframes=None, out=None, centered=False, swap=False):
+        """iq: complex64 [S] or [S, 2] float32 / int16 / uint8 (I, Q pairs; the dtype is the plan's sample format) on this GPU.
+        Returns the two-sided rows [nframes][n] float32 -- bin k of exp(+2 pi i k n / N) in column k, or column (k + n/2) mod n
+        with centered=True; swap=True: the first value of a pair is Q -- launched on torch's current stream
+        (glfer_hip_spectrogram_iq_device).  out: [nframes][n], its row stride may be larger than n."""
+        torch = _torch()
+        v = self._iq_view(iq, 0)
+        ns = v.size(0)
+        if nframes is None:
+            nframes = self.num_frames(ns) - first_frame
+        out, pitch = self._iq_out(out, (nframes, self.n), v.device)
+        st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+        flags = (IQ_CENTERED if centered else 0) | (IQ_SWAP if swap else 0)
+        _check(lib().glfer_hip_spectrogram_iq_device(self._h, C.c_void_p(v.data_ptr()), ns, first_frame, nframes,
+                                                     C.c_void_p(out.data_ptr()), pitch, flags, st), "glfer_hip_spectrogram_iq_device")
+        return out
+
+    def run_iq_batch(self, iqs, first_frame=0, nframes=None, out=None, centered=False, swap=False):
+        """iqs: complex64 [B, S] or [B, S, 2] with a contiguous inner part; stride(0) is the distance between streams (in
+        complex samples once divided by two for the [B, S, 2] form).  Returns [B][nframes][n] float32: out[b] is what
+        run_iq(iqs[b]) gives (glfer_hip_spectrogram_iq_batch_device)."""
+        torch = _torch()
+        v = self._iq_view(iqs, 1)
+        nb, ns = v.size(0), v.size(1)
+        assert nb <= 1 or v.stride(0) % 2 == 0, v.stride()
+        spitch = v.stride(0) // 2 if nb > 1 else ns
+        if nframes is None:
+            nframes = self.num_frames(ns) - first_frame
+        out, pitch = self._iq_out(out, (nb, nframes, self.n), v.device)
+        st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+        flags = (IQ_CENTERED if centered else 0) | (IQ_SWAP if swap else 0)
+        _check(lib().glfer_hip_spectrogram_iq_batch_device(self._h, C.c_void_p(v.data_ptr()), nb, spitch, ns, first_frame, nframes,
+                                                           C.c_void_p(out.data_ptr()), pitch, flags, st),
+               "glfer_hip_spectrogram_iq_batch_device")
         return out
 
     def run_channels(self, samples, channels=None, select=None, first_frame=0, nframes=None, out=None):

@@ -24,6 +24,7 @@
 #include "hparma_frames.h"
 #include "ragged_cols.hpp"
 #include "spectro_params.h"
+#include "spectro_iq_params.h"
 
 static_assert(GLFER_FMT_F32 == GLFER_SAMPLES_F32 && GLFER_FMT_S16 == GLFER_SAMPLES_S16 && GLFER_FMT_U8 == GLFER_SAMPLES_U8, "glfer_sample_size");
 
@@ -715,6 +716,23 @@ int glfer_hip_plan_create(const glfer_hip_config *cfg, glfer_hip_plan **out) {
     }
   }
 
+  // --- complex I/Q rows (spectro16c.hip): one scaled float per sample and taper, in the order a lane's four 16-byte loads take them
+  // ([taper][m/4][t][4] for sample t + T m); made with the plan so that the entries allocate and copy nothing (stream capture)
+  std::vector<float> iqtaps;
+  if (glfer_hip_iq_supported(&p->cfg) == GLFER_OK) {
+    std::vector<float> flat((size_t)p->ntapers * n);
+    const bool mt = cfg->mode == GLFER_MODE_MTM;
+    glfer::make_iq_table(n, p->ntapers, (mt || p->cfg.window_type == GLFER_WIN_RECTANGULAR) ? nullptr : p->window.data(),
+                         mt ? p->tapers.data() : nullptr, mt ? p->sig.data() : nullptr, flat.data());
+    iqtaps.resize(flat.size());
+    const int T = n / 16;
+    for (int j = 0; j < p->ntapers; j++)
+      for (int i = 0; i < n; i++) {
+        const int t = i % T, m = i / T;
+        iqtaps[(size_t)j * n + ((size_t)(m / 4) * T + t) * 4 + (size_t)(m & 3)] = flat[(size_t)j * n + i];
+      }
+  }
+
   // --- HP-ARMA tables: which lag each cell of the t x (p_e+1) matrix holds after the
   // reference's fill (hparma.c:89-102).  r_xx is matrix(0,t,0,p_e) (hparma.c:64): its rows
   // are contiguous (util.c:153-160), lags 0..t-1 are written into row 0 past its p_e+1
@@ -834,6 +852,10 @@ int glfer_hip_plan_create(const glfer_hip_config *cfg, glfer_hip_plan **out) {
     e = hipMalloc((void **)&p->d_ytaps, ytaps.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(p->d_ytaps, ytaps.data(), ytaps.size() * sizeof(float), hipMemcpyHostToDevice);
   }
+  if (e == hipSuccess && !iqtaps.empty()) {
+    e = hipMalloc((void **)&p->d_iqtaps, iqtaps.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(p->d_iqtaps, iqtaps.data(), iqtaps.size() * sizeof(float), hipMemcpyHostToDevice);
+  }
   if (e == hipSuccess && !xtaps.empty() && n == 4096) {
     p->yq = new glfer_yqueue;
     const size_t bytes = (size_t)glfer_yqueue::SLOTS * glfer_yqueue::PITCH * sizeof(unsigned);
@@ -883,6 +905,7 @@ void glfer_hip_plan_destroy(glfer_hip_plan *p) {
   if (p->d_bigtw) (void)hipFree(p->d_bigtw);
   if (p->d_ltaps) (void)hipFree(p->d_ltaps);
   if (p->d_ytaps) (void)hipFree(p->d_ytaps);
+  if (p->d_iqtaps) (void)hipFree(p->d_iqtaps);
   if (p->yq) {
     if (p->yq->d_counters) (void)hipFree(p->yq->d_counters);
     delete p->yq;
@@ -934,6 +957,35 @@ int glfer_hip_y_half_tables(int n, int kmax, double nw, float *half, float *pair
   if (pairs) memcpy(pairs, taps.data(), (size_t)4 * n * sizeof(float));
   if (last) memcpy(last, xtaps.data(), (size_t)n * sizeof(float));
   return build_y_half_table(n, taps.data(), xtaps.data(), half) ? 1 : 0;
+}
+
+int glfer_hip_iq_supported(const glfer_hip_config *cfg) {
+  if (!cfg) return GLFER_E_ARG;
+  if (cfg->mode != GLFER_MODE_FFT && cfg->mode != GLFER_MODE_MTM) return GLFER_E_ARG;
+  if (!is_pow2(cfg->n) || cfg->n < 256 || cfg->n > 16384) return GLFER_E_ARG;
+  if (cfg->sub_mean != 0 || cfg->limiter_a > 0.0f || cfg->enable_limiter != 0) return GLFER_E_ARG;
+  if (cfg->sample_format < 0 || cfg->sample_format > 2) return GLFER_E_ARG;
+  return GLFER_OK;
+}
+
+int glfer_hip_iq_tables(const glfer_hip_config *cfg, float *table) {
+  if (glfer_hip_iq_supported(cfg) != GLFER_OK) return GLFER_E_ARG;
+  const int n = cfg->n;
+  if (cfg->mode == GLFER_MODE_FFT) {
+    if (cfg->window_type < 0 || cfg->window_type > 7) return GLFER_E_ARG;
+    if (!table) return 1;
+    std::vector<float> w(n);
+    glfer::make_window(cfg->window_type, n, w.data());
+    glfer::make_iq_table(n, 1, cfg->window_type == GLFER_WIN_RECTANGULAR ? nullptr : w.data(), nullptr, nullptr, table);
+    return 1;
+  }
+  if (cfg->mtm_k < 0 || cfg->mtm_k > 31 || !(cfg->mtm_w > 0.0f)) return GLFER_E_ARG;
+  const int nt = cfg->mtm_k + 1;
+  if (!table) return nt;
+  std::vector<double> tapers((size_t)nt * n), sig(nt);
+  if (!glfer::make_dpss(n, cfg->mtm_k, (double)cfg->mtm_w, tapers.data(), sig.data())) return GLFER_E_NUMERIC;
+  glfer::make_iq_table(n, nt, nullptr, tapers.data(), sig.data(), table);
+  return nt;
 }
 
 void glfer_hip_y_queue_shape(int *blocks, int *chunk) {
@@ -1727,6 +1779,73 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
     if (rc != GLFER_OK) return rc;
   }
   return GLFER_OK;
+}
+
+// ---- complex I/Q input (glfer_hip.h): two-sided rows of N bins, spectro16c.hip ---------------------------------------------------
+
+static hipError_t launch_iq(const IqParams &q, int n, hipStream_t st) {
+  switch (n) {
+    case 256: return glfer_launch_spectro16c_n8(&q, st);
+    case 512: return glfer_launch_spectro16c_n9(&q, st);
+    case 1024: return glfer_launch_spectro16c_n10(&q, st);
+    case 2048: return glfer_launch_spectro16c_n11(&q, st);
+    case 4096: return glfer_launch_spectro16c_n12(&q, st);
+    case 8192: return glfer_launch_spectro16c_n13(&q, st);
+    case 16384: return glfer_launch_spectro16c_n14(&q, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+int glfer_hip_spectrogram_iq_batch_device(glfer_hip_plan *p, const void *d_iq, size_t nstreams, size_t stream_pitch, size_t nsamples,
+                                          size_t first, size_t nframes, float *d_psd, size_t row_pitch, unsigned flags,
+                                          void *hip_stream) {
+  if (!p || !p->d_iqtaps || glfer_hip_iq_supported(&p->cfg) != GLFER_OK) return GLFER_E_ARG;
+  if (flags & ~(GLFER_IQ_CENTERED | GLFER_IQ_SWAP)) return GLFER_E_ARG;
+  const size_t n = (size_t)p->n, pitch = row_pitch ? row_pitch : n;
+  if (pitch < n) return GLFER_E_ARG;
+  if (nstreams == 0 || nframes == 0) return GLFER_OK;
+  if (!d_iq || !d_psd) return GLFER_E_ARG;
+  const size_t csz = 2 * glfer_sample_size(p->cfg.sample_format);       // bytes of a complex sample
+  if (reinterpret_cast<uintptr_t>(d_iq) & (csz - 1)) return GLFER_E_ARG;
+  if (first + nframes < first || (first + nframes) > nsamples / (size_t)p->hop) return GLFER_E_ARG;   // wraps, or a frame past the stream
+  if (nframes > 0x7fffffffu) return GLFER_E_ARG;
+  if (nsamples > SIZE_MAX / csz || stream_pitch > (SIZE_MAX / csz) / nstreams) return GLFER_E_ARG;
+  if (pitch > SIZE_MAX / sizeof(float) / nframes || nframes * pitch > (SIZE_MAX / sizeof(float)) / nstreams) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  DeviceGuard guard(p->cfg.device);
+  HIP_TRY(guard.error());
+  size_t ymax = 1;
+  if (nstreams > 1)
+    if (const int yrc = grid_y_limit(1, &ymax); yrc != GLFER_OK) return yrc;
+  IqParams q;
+  memset(&q, 0, sizeof q);
+  q.frame0 = (long long)first;
+  q.nframes = (int)nframes;
+  q.H = p->hop;
+  q.R = p->keep;
+  q.ntap = p->ntapers;
+  q.history_mode = p->cfg.history_mode ? 1 : 0;
+  q.fmt = p->cfg.sample_format;
+  q.flags = flags;
+  q.taps = p->d_iqtaps;
+  q.tw = p->d_tw;
+  q.pitch = (long long)pitch;
+  q.batch_stride = (long long)(stream_pitch * csz);
+  q.psd_batch_stride = (long long)(nframes * pitch);
+  for (size_t c0 = 0; c0 < nstreams; c0 += ymax) {      // batches above the grid's y limit: chunks of it
+    const size_t nb = std::min(nstreams - c0, ymax);
+    q.stream = static_cast<const char *>(d_iq) + c0 * stream_pitch * csz;
+    q.psd = d_psd + c0 * nframes * pitch;
+    q.nbatch = (int)nb;
+    const hipError_t e = launch_iq(q, p->n, st);
+    if (e != hipSuccess) return hip_fail(e, "estimator launch (iq)");
+  }
+  return GLFER_OK;
+}
+
+int glfer_hip_spectrogram_iq_device(glfer_hip_plan *p, const void *d_iq, size_t nsamples, size_t first, size_t nframes, float *d_psd,
+                                    size_t row_pitch, unsigned flags, void *hip_stream) {
+  return glfer_hip_spectrogram_iq_batch_device(p, d_iq, 1, 0, nsamples, first, nframes, d_psd, row_pitch, flags, hip_stream);
 }
 
 // ---- multi-channel recordings (glfer_hip.h): every interleaved channel as a stream of its own ---------------------------------

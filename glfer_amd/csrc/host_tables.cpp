@@ -200,6 +200,19 @@ void make_twiddles(int n, int lanes, float *tw_re_im) {
     }
 }
 
+// The scaled table of the complex I/Q rows: P[k] = |Z[k]|^2 / N (fft.c:212-216 over all N bins) and
+// sum_j |Z_j[k]|^2 / (N (1 + sig_j)) (mtm.c:212-219) with the factor's root folded into the window / taper.  The product in
+// double, rounded once.
+void make_iq_table(int n, int ntap, const float *window, const double *tapers, const double *sig, float *table) {
+  for (int j = 0; j < ntap; j++) {
+    const double scale = std::sqrt(1.0 / ((double)n * (tapers ? 1.0 + sig[j] : 1.0)));
+    for (int i = 0; i < n; i++) {
+      const double w = tapers ? tapers[(size_t)j * n + i] : (window ? (double)window[i] : 1.0);
+      table[(size_t)j * n + i] = (float)(w * scale);
+    }
+  }
+}
+
 // Radix schedule of spectro16.hip (Plan16): 16, 16, then N/256 (N <= 4096) or 16, N/4096.
 int plan16_passes(int logn, int radix[4]) {
   const int n = 1 << logn;

@@ -9,6 +9,9 @@ void make_twiddles(int n, int lanes, float *tw_re_im);                     // [6
 void make_palette(int palette, unsigned char colortab[768]);               // g_main.c:651-762
 constexpr int kLogThrK = 400;                                               // |10 log10 x| <= 400: every normal float, with room
 const double *log_thresholds();                                             // [2 K + 1]: where (short)(10.0*log10(x)) steps, g_main.c:1192-1196
+// complex I/Q rows (spectro16c.hip): table[j][i] = w_j[i] * sqrt(1 / (n (1 + sig_j))), one float per sample and taper.  window: the
+// periodogram's [n] (NULL: rectangular, which the reference never applies -- ones), with tapers NULL; else tapers [ntap][n], sig [ntap]
+void make_iq_table(int n, int ntap, const float *window, const double *tapers, const double *sig, float *table);
 int plan16_passes(int logn, int radix[4]);                                  // spectro16.hip schedule
 int make_twiddles16(int logn, float *tw_re_im);                            // returns slots per lane; [slot][N/16] (cos,sin)
 }  // namespace glfer

@@ -604,6 +604,53 @@ int glfer_hip_spectrogram_host_channels(glfer_hip_plan *plan, const void *h_samp
 int glfer_hip_spectrogram_wav_channels(glfer_hip_plan *plan, const char *path, const int *select, int nselect, float *h_psd,
                                        size_t max_frames, size_t *nframes_out, size_t chunk_frames);
 
+/* ---- Complex I/Q input: two-sided rows -----------------------------------------------------------------------------------------
+ * A complex-baseband recording (an SDR receiver's stereo WAV or raw buffer, I in one channel and Q in the other) holds complex
+ * samples z[n] = I[n] + i Q[n], interleaved I, Q, I, Q, ... in cfg.sample_format: f32 pairs, s16 pairs (x / 32768), u8 pairs
+ * ((x - 128) / 128) -- the conversions of wav_fmt.c:104-117 on each part.  Its spectrum is two-sided, N bins per frame, and is not
+ * the pair of one-sided spectra the channel entries above give for I and Q.  With a plan in GLFER_MODE_FFT or GLFER_MODE_MTM:
+ *   frame f            : complex samples [f H - (N - H), f H + H), H = glfer_hip_hop(plan); the history modes mean what they mean
+ *                        for real streams (ZERO_FIRST: zeros before sample 0; ZERO_ALWAYS: zeros in the first N - H positions of
+ *                        every frame); nsamples / H frames; the virtual-base convention and frame ranges of
+ *                        glfer_hip_spectrogram_device ("Cutting a stream", in complex samples)
+ *   Z_j[k]             = sum_n w_j[n] z_f[n] exp(-2 pi i k n / N),  k = 0 .. N-1
+ *   periodogram        : P[k] = |Z[k]|^2 / N, w the plan's window (fft.c:212-216 over all N bins; rectangular: no window, as there)
+ *   multitaper         : P[k] = sum_j |Z_j[k]|^2 / (N (1 + sig_j)) over the plan's kmax + 1 tapers (mtm.c:212-219)
+ * With Q = 0 bins 0 .. N/2 are the real entry's row to rounding; a tone exp(+2 pi i k0 n / N) lands in bin k0 alone.
+ * One kernel per call (spectro16c.hip; a batch above the grid's y limit: one per chunk of streams), no host synchronisation, no
+ * allocation: legal on a hip_stream that is being captured.  The table [taper][N] of w_j with the scale folded in is made with
+ * the plan; glfer_hip_iq_tables gives the same floats without a device.
+ *   flags : GLFER_IQ_CENTERED  bin k is stored at column (k + N/2) mod N: negative frequencies left of the carrier, as a waterfall
+ *                              shows it
+ *           GLFER_IQ_SWAP      the first value of each pair is Q (the usual cure for a mirrored spectrum): the rows of the stream
+ *                              with the two values exchanged in memory, float for float
+ *   nsamples, stream_pitch : complex samples
+ *   row_pitch : floats from one row to the next; 0 means N, any other value must be >= N.  cfg.psd_pitch is NOT read here
+ *   d_psd     : [nframes][row_pitch]; a batch: row i of stream b at d_psd + (b * nframes + i) * row_pitch
+ *   d_iq (and d_iq + b * stream_pitch) must be aligned to one complex sample: 8, 4 or 2 bytes
+ * Supported (glfer_hip_iq_supported, host only: GLFER_OK or GLFER_E_ARG): FFT or MTM mode, N = 256 .. 16384, every window, every
+ * taper count the plan accepts, every overlap, both history modes, the three sample formats; sub_mean must be 0 and the limiter
+ * off (limiter_a <= 0, enable_limiter == 0).
+ * Arguments, nothing on the device touched before they pass: GLFER_E_ARG for a NULL plan or one that is not supported, unknown
+ * flag bits, a row_pitch below N; then GLFER_OK with nothing launched for nframes == 0 (nstreams == 0); then GLFER_E_ARG for NULL
+ * buffers, a misaligned d_iq (stream_pitch counts complex samples, so every stream of a batch is then aligned), first_frame +
+ * nframes wrapping or reaching past the stream, nframes > 0x7fffffff, sizes that overflow size_t.  Asynchronous on hip_stream.
+ * Downstream: glfer_hip_floor_device, the glfer_hip_avg_* entries and the waterfall entries take a `bins` argument and work up to
+ * 32769 bins, so they take these rows (bins = N <= 16384, pitch = row_pitch) as they are.
+ * Not built: mean removal and the limiter / RA9MB on I/Q, N outside 256 .. 16384, ragged / host / WAV / workers / multi-GPU forms,
+ * the F-test, LMP and HP-ARMA on complex input. */
+#define GLFER_IQ_CENTERED 1u
+#define GLFER_IQ_SWAP     2u
+int glfer_hip_iq_supported(const glfer_hip_config *cfg);
+/* table: host, [taper count][cfg->n] floats, w_j[n] sqrt(1 / N) (periodogram) or v_j[n] sqrt(1 / (N (1 + sig_j))), the product taken in
+ * double and rounded once; NULL: the count alone.  Returns the taper count (1 for the periodogram), or a negative GLFER_E_*. */
+int glfer_hip_iq_tables(const glfer_hip_config *cfg, float *table);
+int glfer_hip_spectrogram_iq_device(glfer_hip_plan *plan, const void *d_iq, size_t nsamples, size_t first_frame, size_t nframes,
+                                    float *d_psd, size_t row_pitch, unsigned flags, void *hip_stream);
+int glfer_hip_spectrogram_iq_batch_device(glfer_hip_plan *plan, const void *d_iq, size_t nstreams, size_t stream_pitch,
+                                          size_t nsamples, size_t first_frame, size_t nframes, float *d_psd, size_t row_pitch,
+                                          unsigned flags, void *hip_stream);
+
 /* BASELINE config 4 as worded ("1-hour 48 kHz WAV, frame-batch sharded across 8 x MI355X"): the
  * file's frames dealt out over the GPUs named in device_mask (glfer_hip_frame_range: contiguous
  * ranges, boundaries on multiples of GLFER_FRAME_ALIGN), one host thread + plan + pinned ring per
