@@ -352,7 +352,9 @@ __global__ __launch_bounds__(256) void prepare_kernel(SpectroParams p, int n, co
       y = x;
     }
     if (p.limiter) {                                               // fft.c:151-156
-      const float ftmp = log(fabs(y));
+      // (the reference's log is C's: double.  In device C++ log(float) is the float overload, up to an ulp of ftmp away,
+      // which exp(0.1 ftmp) turns into several units in the last place of a small |y|^0.1: stockham16.hpp limiter_value)
+      const float ftmp = (float)log((double)fabsf(y));
       y = (y > 0 ? exp(ftmp * 0.1) : -exp(ftmp * 0.1));
     }
     out[(size_t)fi * n + i] = y;

@@ -14,6 +14,7 @@ Signals, all seeded:
   bin      a 0.5 tone exactly on bin n/4 + 1 (rectangular window, overlap 0: every other bin is pure rounding);
   bin_lo / bin_hi: the same on bins 1 and n/2 - 1;   alt: +-0.5 alternating (all power at Nyquist)
   lsb1 / lsb2   integer streams of one / two LSBs of dither;   zero: digital silence
+  full / tiny   (tests/_nonlin_cases.py's, no case of this module uses them) a +-0.99 tone; a 0.7e-4 tone over 0.3e-4 sigma noise
 """
 import functools
 from collections import namedtuple
@@ -199,6 +200,10 @@ def signal(c, count, seed=None):
         x = 0.25 * rng.standard_normal(count)
     elif c.signal == "synth":
         return synth(count, fs=8000.0, seed=seed_of(c) if seed is None else seed)
+    elif c.signal == "full":                                  # (tests/_nonlin_cases.py: RA9MB's 1/x regime)
+        x = 0.99 * np.sin(2 * np.pi * (0.11 * n + 0.29) * t / n + 0.5)
+    elif c.signal == "tiny":                                  # (tests/_nonlin_cases.py: RA9MB's x/a regime, the limiter's log near -10)
+        x = 0.7e-4 * np.sin(2 * np.pi * (0.19 * n + 0.41) * t / n + 0.9) + 0.3e-4 * rng.standard_normal(count)
     elif c.signal == "impulse":
         x = np.zeros(count)
         for j in range(count // h):

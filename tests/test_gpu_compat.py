@@ -84,6 +84,33 @@ def test_fft_do_hop_by_hop(compat, oracle, autoscale):
     assert not p.window and not p.inbuf_audio
 
 
+@pytest.mark.parametrize("autoscale", [1, 0])
+def test_fft_do_hop_by_hop_with_ra9mb_and_the_limiter(compat, oracle, autoscale):
+    """fft_do / fft_psd with a = 0.001 and limiter = 1 (fft.c:127-156), which no other call of the shim sets: hop by hop against
+    the oracle over the same stream, with and without the per-hop mean removal that opt.autoscale switches on."""
+    n, ovl, win, a = 1024, 0.5, 0, 0.001
+    h = oracle.hop(n, ovl)
+    x = synth(12 * h, fs=8000.0, seed=5) + np.float32(0.05)
+    _set(compat, "glfer_compat_autoscale", autoscale)
+    _set(compat, "glfer_compat_first_buffer", 1)
+    p = FftParams(n=n, window_type=win, overlap=ovl, a=a, limiter=1)
+    compat.fft_init(C.byref(p))
+    assert p.sub_mean == autoscale and p.limiter == 1 and p.a == np.float32(a)
+    psd = np.empty(n // 2 + 1, np.float32)
+    got = []
+    for f in range(12):
+        hop = x[f * h:(f + 1) * h].copy()
+        compat.fft_do(_fp(hop), C.byref(p))
+        compat.fft_psd(_fp(psd), None, C.byref(p))
+        got.append(psd.copy())
+        if autoscale:
+            _set(compat, "glfer_compat_first_buffer", 0)
+    want = oracle.spectrogram_fft(x, n, ovl, win, a, 1, sub_mean=autoscale, history_mode=0 if autoscale else 1)
+    worst = max(max(rel_err(g, w)) for g, w in zip(got, want))
+    assert worst < TOL, worst
+    compat.fft_close(C.byref(p))
+
+
 def test_mtm_do_hop_by_hop(compat, oracle):
     n, ovl, nw, kmax = 4096, 0.75, 2.5, 4
     h = oracle.hop(n, ovl)

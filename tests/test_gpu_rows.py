@@ -25,8 +25,8 @@ Which case reaches which kernel file (glfer_hip.cpp, launch_by_n):
   spectro16y.hip      odd taper counts at N = 4096: five tapers NW 2.5 the half-table form, GLFER_Y_TAPERS=full and 3 / 9 tapers the full
   spectro16w.hip      the multitaper at N = 16384, GLFER_FORM=w from N = 2048, spectrum=True at N = 32768
   spectro_big.hip     the periodogram from N = 32768, the two-level combine from N = 131072
-Not here: limiter / RA9MB (non-linear: they keep the oracle tests), HP-ARMA, LMP, the F-test (own rules), the host / WAV /
-worker entries (the same kernels).
+Not here: limiter / RA9MB (non-linear: tests/test_gpu_nonlin.py holds them to the same rule), HP-ARMA, LMP, the F-test (own
+rules), the host / WAV / worker entries (the same kernels).
 
 Lines starting with 'rows-bin-by-bin' (run with -s) are the record kept in profiles/rows_bin_by_bin.txt.
 """
