@@ -247,8 +247,9 @@ class _GoFftState(C.Structure):
                 ("inbuf_audio", C.c_void_p), ("inbuf_fft", C.c_void_p)]
 
 
-def hparma_frames(stream, n, overlap, t, p_e, sub_mean=0):
-    """Per frame: (psd[n/2+1], AR vector a[p_e+1], rank p) -- hparma_do with its intermediates."""
+def hparma_frames(stream, n, overlap, t, p_e, sub_mean=0, history_mode=0):
+    """Per frame: (psd[n/2+1], AR vector a[p_e+1], rank p) -- hparma_do with its intermediates.  history_mode = 1: the
+    history is zeroed in every frame, as go_spectrogram_hparma does it."""
     stream = np.ascontiguousarray(stream, np.float32)
     h = hop(n, overlap)
     frames = num_frames(stream.size, n, overlap)
@@ -260,7 +261,7 @@ def hparma_frames(stream, n, overlap, t, p_e, sub_mean=0):
         psd = np.empty(n // 2 + 1, np.float32)
         a = np.empty(p_e + 1, np.float32)
         rank = C.c_int(0)
-        _lib.go_hparma_frame(C.byref(st), t, p_e, hopbuf, 1 if f == 0 else 0, psd, a, C.byref(rank))
+        _lib.go_hparma_frame(C.byref(st), t, p_e, hopbuf, 1 if f == 0 or history_mode == 1 else 0, psd, a, C.byref(rank))
         out.append((psd, a, rank.value))
     _lib.go_fft_state_free(C.byref(st))
     return out
