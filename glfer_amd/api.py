@@ -69,6 +69,9 @@ EXPORTS = [
     "glfer_hip_spectrogram_wav_channels",
     # complex I/Q input: two-sided rows
     "glfer_hip_iq_supported", "glfer_hip_iq_tables", "glfer_hip_spectrogram_iq_device", "glfer_hip_spectrogram_iq_batch_device",
+    # zoom: the digital down-converter and the I/Q rows of its output
+    "glfer_hip_ddc_phase_word", "glfer_hip_ddc_design", "glfer_hip_ddc_supported", "glfer_hip_ddc_tables", "glfer_hip_ddc_create",
+    "glfer_hip_ddc_destroy", "glfer_hip_ddc_device", "glfer_hip_ddc_batch_device", "glfer_hip_spectrogram_zoom_device",
 ]
 
 
@@ -83,6 +86,12 @@ class Config(C.Structure):
                 ("sub_mean", C.c_int), ("history_mode", C.c_int), ("mtm_w", C.c_float),
                 ("mtm_k", C.c_int), ("sample_format", C.c_int), ("device", C.c_int),
                 ("hparma_t", C.c_int), ("hparma_p_e", C.c_int), ("lmp_av", C.c_int), ("psd_pitch", C.c_int)]
+
+
+class DdcConfig(C.Structure):
+    """glfer_hip_ddc_config (include/glfer_hip.h)."""
+    _fields_ = [("decim", C.c_int), ("ntaps", C.c_int), ("freq", C.c_double), ("complex_in", C.c_int),
+                ("sample_format", C.c_int), ("device", C.c_int)]
 
 
 class Display(C.Structure):
@@ -210,6 +219,18 @@ def lib():
         L.glfer_hip_iq_tables.argtypes = [C.POINTER(Config), vp]
         L.glfer_hip_spectrogram_iq_device.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_uint, vp]
         L.glfer_hip_spectrogram_iq_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, sz, C.c_uint, vp]
+    if hasattr(L, "glfer_hip_ddc_device"):
+        L.glfer_hip_ddc_phase_word.argtypes = [C.c_double]
+        L.glfer_hip_ddc_phase_word.restype = C.c_ulonglong
+        L.glfer_hip_ddc_design.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, vp]
+        L.glfer_hip_ddc_supported.argtypes = [C.POINTER(DdcConfig)]
+        L.glfer_hip_ddc_tables.argtypes = [C.POINTER(DdcConfig), vp, vp]
+        L.glfer_hip_ddc_create.argtypes = [C.POINTER(DdcConfig), vp, C.POINTER(vp)]
+        L.glfer_hip_ddc_destroy.argtypes = [vp]
+        L.glfer_hip_ddc_destroy.restype = None
+        L.glfer_hip_ddc_device.argtypes = [vp, vp, sz, sz, sz, vp, vp]
+        L.glfer_hip_ddc_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, sz, vp]
+        L.glfer_hip_spectrogram_zoom_device.argtypes = [vp, vp, vp, sz, sz, sz, vp, sz, C.c_uint, vp]
     L.glfer_hip_host_alloc.argtypes = [sz]
     L.glfer_hip_host_alloc.restype = vp
     L.glfer_hip_host_free.argtypes = [vp]
@@ -304,6 +325,141 @@ def iq_tables(params):
     if rc < 0:
         _check(rc, "glfer_hip_iq_tables")
     return tab
+
+
+def ddc_phase_word(freq):
+    """W = round(freq 2^64) mod 2^64 (glfer_hip_ddc_phase_word; host only)."""
+    return int(lib().glfer_hip_ddc_phase_word(float(freq)))
+
+
+def ddc_design(decim, ntaps=0, cutoff=0.0, beta=0.0):
+    """The Kaiser-windowed sinc low-pass of the down-converter as float32 taps (glfer_hip_ddc_design; host only).  Arguments <= 0
+    take the defaults: ntaps = min(8 decim + 1, 8192), cutoff = 0.4 / decim cycles per input sample, beta = 8."""
+    nt = lib().glfer_hip_ddc_design(int(decim), int(ntaps), float(cutoff), float(beta), None)
+    if nt < 0:
+        _check(nt, "glfer_hip_ddc_design")
+    taps = np.empty(nt, np.float32)
+    rc = lib().glfer_hip_ddc_design(int(decim), int(ntaps), float(cutoff), float(beta), taps.ctypes.data)
+    if rc < 0:
+        _check(rc, "glfer_hip_ddc_design")
+    return taps
+
+
+def ddc_supported(decim, ntaps, freq, complex_in=False, sample_format=SAMPLES_F32):
+    """Whether a down-converter of this shape can be made (glfer_hip_ddc_supported; host only)."""
+    cfg = DdcConfig(int(decim), int(ntaps), float(freq), int(complex_in), int(sample_format), 0)
+    return lib().glfer_hip_ddc_supported(C.byref(cfg)) == 0
+
+
+def ddc_tables(freq, taps):
+    """The complex taps g[t] = taps[t] exp(+2 pi i phi(t)) as complex64 (glfer_hip_ddc_tables; host only)."""
+    taps = np.ascontiguousarray(taps, np.float32)
+    cfg = DdcConfig(1, len(taps), float(freq), 0, SAMPLES_F32, 0)
+    g = np.empty((len(taps), 2), np.float32)
+    _check(lib().glfer_hip_ddc_tables(C.byref(cfg), taps.ctypes.data, g.ctypes.data), "glfer_hip_ddc_tables")
+    return g.view(np.complex64)[:, 0]
+
+
+class Ddc:
+    """A digital down-converter (glfer_hip_ddc, include/glfer_hip.h "Zoom"): y[m] = exp(-2 pi i phi(n0)) sum_t g[t] x[n0 - t],
+    n0 = (m + 1) decim - 1 -- the band around `freq` (cycles per input sample) moved to 0 Hz, low-passed by `taps` (float32;
+    None: ddc_design(decim, ntaps)) and decimated.  Real input: 1-D tensors of the sample format's dtype; complex input
+    (complex_in=True): complex64 [S], or [S, 2] pairs of the sample format's dtype.  Output: complex64."""
+
+    def __init__(self, decim, freq, taps=None, ntaps=0, complex_in=False, sample_format=SAMPLES_F32, device=0):
+        self._h = None
+        if taps is None:
+            taps = ddc_design(decim, ntaps)
+        self.taps = np.ascontiguousarray(taps, np.float32)
+        assert self.taps.ndim == 1
+        self.decim, self.freq, self.complex_in, self.sample_format, self.device = int(decim), float(freq), bool(complex_in), sample_format, device
+        self.cfg = DdcConfig(self.decim, len(self.taps), self.freq, int(self.complex_in), sample_format, device)
+        if lib().glfer_hip_ddc_supported(C.byref(self.cfg)) != 0:
+            raise GlferHipError("unsupported down-converter: decim %d, %d taps, freq %r" % (self.decim, len(self.taps), self.freq))
+        self.phase_word = ddc_phase_word(self.freq)
+        self._destroy = lib().glfer_hip_ddc_destroy
+        h = C.c_void_p()
+        _check(lib().glfer_hip_ddc_create(C.byref(self.cfg), self.taps.ctypes.data, C.byref(h)), "glfer_hip_ddc_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._destroy(self._h)
+            self._h.value = None
+
+    __del__ = close
+
+    def tables(self):
+        """The complex taps g[T] as complex64 (glfer_hip_ddc_tables; host only)."""
+        g = np.empty((len(self.taps), 2), np.float32)
+        _check(lib().glfer_hip_ddc_tables(C.byref(self.cfg), self.taps.ctypes.data, g.ctypes.data), "glfer_hip_ddc_tables")
+        return g.view(np.complex64)[:, 0]
+
+    def num_out(self, nsamples):
+        return nsamples // self.decim
+
+    def _dtype(self):
+        torch = _torch()
+        return {SAMPLES_F32: torch.float32, SAMPLES_S16: torch.int16, SAMPLES_U8: torch.uint8}[self.sample_format]
+
+    def _view(self, x, lead):
+        """(tensor whose data_ptr is sample 0 of stream 0, samples per stream, stream pitch in input samples)"""
+        torch = _torch()
+        assert x.is_cuda, "the input lives on the GPU"
+        if self.complex_in:
+            if x.is_complex():
+                assert x.dtype == torch.complex64, x.dtype
+                x = torch.view_as_real(x)
+            assert x.dim() == lead + 2 and x.size(-1) == 2, tuple(x.shape)
+            assert x.dtype == self._dtype(), (x.dtype, self._dtype())
+            assert x.stride(-1) == 1 and (x.stride(-2) == 2 or x.size(-2) <= 1), x.stride()
+            ns = x.size(-2)
+            if lead and x.size(0) > 1:
+                assert x.stride(0) % 2 == 0, x.stride()
+                return x, ns, x.stride(0) // 2
+            return x, ns, ns
+        assert x.dim() == lead + 1 and x.dtype == self._dtype(), (tuple(x.shape), x.dtype, self._dtype())
+        assert x.stride(-1) == 1 or x.size(-1) <= 1, x.stride()
+        ns = x.size(-1)
+        return x, ns, (x.stride(0) if lead and x.size(0) > 1 else ns)
+
+    def _out(self, out, shape, device):
+        torch = _torch()
+        if out is None:
+            return torch.empty(shape, dtype=torch.complex64, device=device), shape[-1]
+        assert out.is_cuda and out.dtype == torch.complex64 and tuple(out.shape) == tuple(shape), (tuple(out.shape), shape)
+        assert out.stride(-1) == 1 or out.size(-1) <= 1
+        pitch = out.stride(0) if len(shape) == 2 and out.size(0) > 1 else shape[-1]
+        assert pitch >= shape[-1]
+        return out, pitch
+
+    def run(self, x, first_out=0, nout=None, out=None):
+        """Outputs [first_out, first_out + nout) of the stream x as complex64 [nout], launched on torch's current stream
+        (glfer_hip_ddc_device)."""
+        torch = _torch()
+        v, ns, _ = self._view(x, 0)
+        if nout is None:
+            nout = self.num_out(ns) - first_out
+        out, _ = self._out(out, (nout,), v.device)
+        st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+        _check(lib().glfer_hip_ddc_device(self._h, C.c_void_p(v.data_ptr()), ns, first_out, nout, C.c_void_p(out.data_ptr()), st),
+               "glfer_hip_ddc_device")
+        return out
+
+    def run_batch(self, xs, first_out=0, nout=None, out=None):
+        """xs: [B, S] with stride(1) == 1 (complex input: complex64 [B, S] or [B, S, 2]); stride(0) is the distance between streams.
+        Returns complex64 [B][nout]: out[b] is what run(xs[b]) gives; `out` may be a view with a row stride above nout
+        (glfer_hip_ddc_batch_device)."""
+        torch = _torch()
+        v, ns, spitch = self._view(xs, 1)
+        nb = v.size(0)
+        if nout is None:
+            nout = self.num_out(ns) - first_out
+        out, opitch = self._out(out, (nb, nout), v.device)
+        st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+        _check(lib().glfer_hip_ddc_batch_device(self._h, C.c_void_p(v.data_ptr()), nb, spitch, ns, first_out, nout,
+                                                C.c_void_p(out.data_ptr()), opitch, st), "glfer_hip_ddc_batch_device")
+        return out
 
 
 class FftParams:
@@ -519,6 +675,21 @@ class Spectrogram:
         _check(lib().glfer_hip_spectrogram_iq_batch_device(self._h, C.c_void_p(v.data_ptr()), nb, spitch, ns, first_frame, nframes,
                                                            C.c_void_p(out.data_ptr()), pitch, flags, st),
                "glfer_hip_spectrogram_iq_batch_device")
+        return out
+
+    def run_zoom(self, ddc, x, first_frame=0, nframes=None, out=None, centered=False):
+        """The two-sided rows of run_iq over ddc.run(x), bit for bit, without the caller holding the baseband: x is what ddc.run
+        takes, the plan has the f32 sample format, frames count the ddc.num_out(len(x)) baseband samples.  Two kernels, the
+        baseband in stream-ordered scratch; not under graph capture (glfer_hip_spectrogram_zoom_device)."""
+        torch = _torch()
+        v, ns, _ = ddc._view(x, 0)
+        if nframes is None:
+            nframes = self.num_frames(ddc.num_out(ns)) - first_frame
+        out, pitch = self._iq_out(out, (nframes, self.n), v.device)
+        st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+        _check(lib().glfer_hip_spectrogram_zoom_device(self._h, ddc._h, C.c_void_p(v.data_ptr()), ns, first_frame, nframes,
+                                                       C.c_void_p(out.data_ptr()), pitch, IQ_CENTERED if centered else 0, st),
+               "glfer_hip_spectrogram_zoom_device")
         return out
 
     def run_channels(self, samples, channels=None, select=None, first_frame=0, nframes=None, out=None):

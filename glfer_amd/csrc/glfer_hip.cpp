@@ -25,6 +25,7 @@
 #include "ragged_cols.hpp"
 #include "spectro_params.h"
 #include "spectro_iq_params.h"
+#include "ddc_params.h"
 
 static_assert(GLFER_FMT_F32 == GLFER_SAMPLES_F32 && GLFER_FMT_S16 == GLFER_SAMPLES_S16 && GLFER_FMT_U8 == GLFER_SAMPLES_U8, "glfer_sample_size");
 
@@ -1846,6 +1847,163 @@ int glfer_hip_spectrogram_iq_batch_device(glfer_hip_plan *p, const void *d_iq, s
 int glfer_hip_spectrogram_iq_device(glfer_hip_plan *p, const void *d_iq, size_t nsamples, size_t first, size_t nframes, float *d_psd,
                                     size_t row_pitch, unsigned flags, void *hip_stream) {
   return glfer_hip_spectrogram_iq_batch_device(p, d_iq, 1, 0, nsamples, first, nframes, d_psd, row_pitch, flags, hip_stream);
+}
+
+// ---- digital down-converter and zoom (glfer_hip.h): ddc.hip, then the I/Q rows of its output ----------------------------------
+
+struct glfer_hip_ddc {
+  glfer_hip_ddc_config cfg;
+  unsigned long long W = 0;
+  float2 *d_taps = nullptr;         // [min(D, T)][jpad]: g[j D + r] at [r][j] (ddc_params.h)
+};
+
+unsigned long long glfer_hip_ddc_phase_word(double freq) { return glfer::ddc_phase_word(freq); }
+
+int glfer_hip_ddc_design(int decim, int ntaps, double cutoff, double beta, float *taps) {
+  if (decim < 1 || decim > 1024 || ntaps > 8192) return GLFER_E_ARG;
+  glfer::ddc_design_defaults(decim, &ntaps, &cutoff, &beta);
+  if (!(cutoff <= 0.5) || !(beta < 700.0)) return GLFER_E_ARG;
+  if (taps) glfer::ddc_design(ntaps, cutoff, beta, taps);
+  return ntaps;
+}
+
+int glfer_hip_ddc_supported(const glfer_hip_ddc_config *cfg) {
+  if (!cfg) return GLFER_E_ARG;
+  if (cfg->decim < 1 || cfg->decim > 1024 || cfg->ntaps < 1 || cfg->ntaps > 8192) return GLFER_E_ARG;
+  if (!(cfg->freq >= -0.5 && cfg->freq < 0.5)) return GLFER_E_ARG;
+  if (cfg->sample_format < 0 || cfg->sample_format > 2) return GLFER_E_ARG;
+  if (cfg->complex_in != 0 && cfg->complex_in != 1) return GLFER_E_ARG;
+  return GLFER_OK;
+}
+
+int glfer_hip_ddc_tables(const glfer_hip_ddc_config *cfg, const float *taps, float *g) {
+  if (glfer_hip_ddc_supported(cfg) != GLFER_OK || !taps || !g) return GLFER_E_ARG;
+  glfer::ddc_tables(glfer::ddc_phase_word(cfg->freq), cfg->ntaps, taps, g);
+  return GLFER_OK;
+}
+
+int glfer_hip_ddc_create(const glfer_hip_ddc_config *cfg, const float *taps, glfer_hip_ddc **out) {
+  if (!out) return GLFER_E_ARG;
+  *out = nullptr;
+  if (glfer_hip_ddc_supported(cfg) != GLFER_OK || !taps) return GLFER_E_ARG;
+  const int D = cfg->decim, T = cfg->ntaps, rows = std::min(D, T), jpad = ddc_jpad(D, T);
+  std::vector<float> g((size_t)2 * T), perm((size_t)2 * rows * jpad, 0.0f);
+  const unsigned long long W = glfer::ddc_phase_word(cfg->freq);
+  glfer::ddc_tables(W, T, taps, g.data());
+  for (int t = 0; t < T; t++) {
+    const size_t at = (size_t)(t % D) * jpad + (size_t)(t / D);
+    perm[2 * at] = g[2 * t];
+    perm[2 * at + 1] = g[2 * t + 1];
+  }
+  glfer_hip_ddc *d = new (std::nothrow) glfer_hip_ddc;
+  if (!d) return GLFER_E_NOMEM;
+  d->cfg = *cfg;
+  d->W = W;
+  DeviceGuard guard(cfg->device);
+  hipError_t e = guard.error();
+  if (e == hipSuccess) e = glfer_ddc_prepare();
+  if (e == hipSuccess) e = hipMalloc((void **)&d->d_taps, perm.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d->d_taps, perm.data(), perm.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    const int rc = hip_fail(e, "ddc tables");
+    (void)hipGetLastError();
+    glfer_hip_ddc_destroy(d);
+    return rc;
+  }
+  *out = d;
+  return GLFER_OK;
+}
+
+void glfer_hip_ddc_destroy(glfer_hip_ddc *d) {
+  if (!d) return;
+  DeviceGuard guard(d->cfg.device);
+  if (d->d_taps) (void)hipFree(d->d_taps);
+  delete d;
+}
+
+int glfer_hip_ddc_batch_device(glfer_hip_ddc *d, const void *d_in, size_t nstreams, size_t stream_pitch, size_t nsamples, size_t first,
+                               size_t nout, void *d_out, size_t out_pitch, void *hip_stream) {
+  if (!d) return GLFER_E_ARG;
+  const size_t opitch = out_pitch ? out_pitch : nout;
+  if (opitch < nout) return GLFER_E_ARG;
+  if (nstreams == 0 || nout == 0) return GLFER_OK;
+  if (!d_in || !d_out) return GLFER_E_ARG;
+  const size_t D = (size_t)d->cfg.decim, T = (size_t)d->cfg.ntaps;
+  const size_t esz = glfer_sample_size(d->cfg.sample_format) * (d->cfg.complex_in ? 2 : 1);   // bytes of one input sample
+  if (first + nout < first || first + nout > nsamples / D) return GLFER_E_ARG;                // wraps, or an output past the stream
+  if (nout > 0x7fffffffu) return GLFER_E_ARG;
+  if (reinterpret_cast<uintptr_t>(d_in) & (esz - 1)) return GLFER_E_ARG;
+  if (nsamples > ((size_t)1 << 62) / esz || stream_pitch > (((size_t)1 << 62) / esz) / nstreams) return GLFER_E_ARG;
+  if (opitch > (((size_t)1 << 62) / sizeof(float2)) / nstreams) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  DeviceGuard guard(d->cfg.device);
+  HIP_TRY(guard.error());
+  size_t ymax = 1;
+  if (nstreams > 1)
+    if (const int yrc = grid_y_limit(1, &ymax); yrc != GLFER_OK) return yrc;
+  DdcParams q;
+  memset(&q, 0, sizeof q);
+  q.taps = d->d_taps;
+  q.W = d->W;
+  q.first_out = (long long)first;
+  q.end_out = (long long)(first + nout);
+  q.lo_sample = first * D > T - 1 ? (long long)(first * D - (T - 1)) : 0;
+  q.in_stride = (long long)(stream_pitch * esz);
+  q.out_stride = (long long)opitch;
+  q.D = (int)D;
+  q.T = (int)T;
+  q.jmax = ddc_jmax((int)D, (int)T);
+  q.jpad = ddc_jpad((int)D, (int)T);
+  q.cols = ddc_cols((int)D, (int)T);
+  q.rows = (int)std::min(D, T);
+  q.rc = ddc_rows_per_chunk((int)D, (int)T);
+  q.plane = q.rc * q.cols;
+  q.rlast = (int)((T - 1) % D);
+  q.ntiles = (int)((nout + kDdcTile - 1) / kDdcTile);
+  q.fmt = d->cfg.sample_format;
+  q.complex_in = d->cfg.complex_in;
+  for (size_t c0 = 0; c0 < nstreams; c0 += ymax) {      // batches above the grid's y limit: chunks of it
+    q.in = static_cast<const char *>(d_in) + c0 * stream_pitch * esz;
+    q.out = static_cast<float2 *>(d_out) + c0 * opitch;
+    q.nbatch = (int)std::min(nstreams - c0, ymax);
+    const hipError_t e = glfer_launch_ddc(&q, st);
+    if (e != hipSuccess) return hip_fail(e, "ddc launch");
+  }
+  return GLFER_OK;
+}
+
+int glfer_hip_ddc_device(glfer_hip_ddc *d, const void *d_in, size_t nsamples, size_t first, size_t nout, void *d_out, void *hip_stream) {
+  return glfer_hip_ddc_batch_device(d, d_in, 1, 0, nsamples, first, nout, d_out, 0, hip_stream);
+}
+
+int glfer_hip_spectrogram_zoom_device(glfer_hip_plan *p, glfer_hip_ddc *d, const void *d_in, size_t nsamples, size_t first, size_t nframes,
+                                      float *d_psd, size_t row_pitch, unsigned flags, void *hip_stream) {
+  if (!p || !d || !p->d_iqtaps || glfer_hip_iq_supported(&p->cfg) != GLFER_OK || p->cfg.sample_format != GLFER_SAMPLES_F32) return GLFER_E_ARG;
+  if (p->cfg.device != d->cfg.device) return GLFER_E_ARG;
+  if (flags & ~GLFER_IQ_CENTERED) return GLFER_E_ARG;
+  const size_t n = (size_t)p->n, H = (size_t)p->hop, pitch = row_pitch ? row_pitch : n;
+  if (pitch < n) return GLFER_E_ARG;
+  if (nframes == 0) return GLFER_OK;
+  if (!d_in || !d_psd) return GLFER_E_ARG;
+  const size_t nbase = nsamples / (size_t)d->cfg.decim;                  // complex samples of the baseband stream
+  if (first + nframes < first || first + nframes > nbase / H) return GLFER_E_ARG;
+  if (nframes > 0x7fffffffu) return GLFER_E_ARG;
+  const size_t hi = (first + nframes) * H, lo = first * H > n - H ? first * H - (n - H) : 0;
+  if (hi - lo > 0x7fffffffu) return GLFER_E_ARG;                         // (one DDC launch: its outputs count in 31 bits)
+  hipStream_t st = (hipStream_t)hip_stream;
+  DeviceGuard guard(p->cfg.device);
+  HIP_TRY(guard.error());
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (st != hipStreamPerThread && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return GLFER_E_ARG;
+  (void)hipGetLastError();
+  void *base = nullptr;
+  HIP_TRY(glfer::scratch_malloc(&base, (hi - lo) * sizeof(float2), st));
+  int rc = glfer_hip_ddc_device(d, d_in, nsamples, lo, hi - lo, base, st);
+  if (rc == GLFER_OK)                                                    // the baseband's virtual base: its sample 0 lies lo samples below the scratch
+    rc = glfer_hip_spectrogram_iq_device(p, static_cast<const char *>(base) - lo * sizeof(float2), nbase, first, nframes, d_psd, pitch,
+                                         flags, st);
+  glfer::scratch_free(base, st);
+  return rc;
 }
 
 // ---- multi-channel recordings (glfer_hip.h): every interleaved channel as a stream of its own ---------------------------------

@@ -341,4 +341,58 @@ const double *log_thresholds() {
   return thr;
 }
 
+// ---- the digital down-converter (ddc.hip) -----------------------------------------------------------------------------------
+
+// W = round(freq 2^64) mod 2^64: the scaling is exact, the rounding is to nearest (even)
+unsigned long long ddc_phase_word(double freq) {
+  const double v = std::nearbyint(std::ldexp(freq, 64));            // [-2^63, 2^63) for freq in [-0.5, 0.5)
+  return (unsigned long long)(long long)v;
+}
+
+// I0 by its power series, every term positive: to a few ulps of double for the arguments a Kaiser window takes
+static double bessel_i0_series(double x) {
+  const double q = 0.25 * x * x;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 1000; k++) {
+    term *= q / ((double)k * (double)k);
+    sum += term;
+    if (term < sum * 1e-18) break;
+  }
+  return sum;
+}
+
+void ddc_design_defaults(int decim, int *ntaps, double *cutoff, double *beta) {
+  if (*ntaps <= 0) *ntaps = decim == 1 ? 1 : (8 * decim + 1 < 8192 ? 8 * decim + 1 : 8192);   // (no decimation: nothing to low-pass)
+  if (!(*cutoff > 0.0)) *cutoff = 0.4 / (double)decim;
+  if (!(*beta > 0.0)) *beta = 8.0;
+}
+
+// h[t] = 2c sinc(2c (t - (T-1)/2)) kaiser_beta(t), unit sum: the lower half is computed, the upper half is its mirror image
+void ddc_design(int ntaps, double cutoff, double beta, float *taps) {
+  const int T = ntaps;
+  std::vector<double> h(T);
+  const double mid = 0.5 * (double)(T - 1), i0b = bessel_i0_series(beta);
+  for (int t = 0; t < (T + 1) / 2; t++) {
+    const double u = 2.0 * cutoff * ((double)t - mid), a = kPiD * u;
+    const double sinc = u == 0.0 ? 1.0 : std::sin(a) / a;
+    const double z = T > 1 ? ((double)t - mid) / mid : 0.0;
+    const double arg = 1.0 - z * z;
+    h[t] = h[T - 1 - t] = 2.0 * cutoff * sinc * bessel_i0_series(beta * std::sqrt(arg > 0.0 ? arg : 0.0)) / i0b;
+  }
+  double sum = 0.0;
+  for (int t = 0; t < T / 2; t++) sum += h[t] + h[T - 1 - t];       // (pairs: the same sum read from either end)
+  if (T & 1) sum += h[T / 2];
+  for (int t = 0; t < T; t++) taps[t] = (float)(h[t] / sum);
+}
+
+// g[t] = h[t] exp(+2 pi i phi(t)), phi(t) = (W t mod 2^64) / 2^64 taken in [-1/2, 1/2) turns; each part rounded once
+void ddc_tables(unsigned long long W, int ntaps, const float *taps, float *g) {
+  for (int t = 0; t < ntaps; t++) {
+    const double turns = std::ldexp((double)(long long)(W * (unsigned long long)t), -64);
+    const double ang = 2.0 * kPiD * turns;
+    g[2 * t] = (float)((double)taps[t] * std::cos(ang));
+    g[2 * t + 1] = (float)((double)taps[t] * std::sin(ang));
+  }
+}
+
 }  // namespace glfer

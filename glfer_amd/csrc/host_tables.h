@@ -12,6 +12,13 @@ const double *log_thresholds();                                             // [
 // complex I/Q rows (spectro16c.hip): table[j][i] = w_j[i] * sqrt(1 / (n (1 + sig_j))), one float per sample and taper.  window: the
 // periodogram's [n] (NULL: rectangular, which the reference never applies -- ones), with tapers NULL; else tapers [ntap][n], sig [ntap]
 void make_iq_table(int n, int ntap, const float *window, const double *tapers, const double *sig, float *table);
+// the digital down-converter (ddc.hip, include/glfer_hip.h): the phase word round(freq 2^64) mod 2^64; the defaults of the design
+// (applied where an argument is <= 0); the Kaiser-windowed sinc low-pass, exactly symmetric, unit sum; the complex taps
+// g[t][2] = h[t] exp(+2 pi i (W t mod 2^64) / 2^64)
+unsigned long long ddc_phase_word(double freq);
+void ddc_design_defaults(int decim, int *ntaps, double *cutoff, double *beta);
+void ddc_design(int ntaps, double cutoff, double beta, float *taps);
+void ddc_tables(unsigned long long W, int ntaps, const float *taps, float *g);
 int plan16_passes(int logn, int radix[4]);                                  // spectro16.hip schedule
 int make_twiddles16(int logn, float *tw_re_im);                            // returns slots per lane; [slot][N/16] (cos,sin)
 }  // namespace glfer

@@ -651,6 +651,76 @@ int glfer_hip_spectrogram_iq_batch_device(glfer_hip_plan *plan, const void *d_iq
                                           size_t nsamples, size_t first_frame, size_t nframes, float *d_psd, size_t row_pitch,
                                           unsigned flags, void *hip_stream);
 
+/* ---- Zoom: a digital down-converter, and the two-sided rows of its output -------------------------------------------------------
+ * A few tens of hertz around one carrier of a 48 kHz recording: instead of a block of a million samples whose transform covers the
+ * whole band, the band is moved to 0 Hz, low-passed and decimated by D (a frequency-translating FIR, "DDC"), and the I/Q rows above
+ * run at fs / D: D = 64 with N = 16384 has the resolution of N = 1048576, in rows of N bins that every per-column stage takes.
+ * Definition (ddc.hip; tests/_ddc_exact.py is its float64 restatement):
+ *   x[n]    the input, real or complex (interleaved I/Q as above), f32 / s16 (x / 32768) / u8 ((x - 128) / 128); x[n] = 0 for n < 0
+ *   W       = round(freq 2^64) mod 2^64, freq in cycles per input sample, [-0.5, 0.5); phi(n) = (W n mod 2^64) / 2^64 turns, in
+ *           64-bit integers: no drift at any stream length.  glfer_hip_ddc_phase_word(freq) returns W
+ *   g[t]    = h[t] exp(+2 pi i phi(t)), t = 0 .. T-1, h the real float32 taps; the product in double, each part rounded once
+ *   y[m]    = exp(-2 pi i phi(n0)) sum_t g[t] x[n0 - t],  n0 = (m + 1) D - 1,  m = 0 .. nsamples / D - 1
+ *           = sum_t h[t] (x e^(-2 pi i phi))[n0 - t]: a tone at +freq goes to 0 Hz; one rotation per output, none per input sample
+ * Outputs are complex64, interleaved float pairs: what glfer_hip_spectrogram_iq_device reads with an f32 plan.  The bits of y[m] do
+ * not depend on the launch, range, tile or batch that computes it: the sum runs over t in an order t and D alone fix.
+ * Host only, no device touched:
+ *   glfer_hip_ddc_design     a Kaiser-windowed sinc low-pass in double, h[t] = 2 c sinc(2 c (t - (T-1)/2)) kaiser_beta(t), exactly
+ *                            symmetric, normalised to unit sum, rounded to float.  Defaults where an argument is <= 0: ntaps =
+ *                            min(8 decim + 1, 8192) -- 1 for decim = 1: the single tap 1.0, a pure mixer --, cutoff c = 0.4 / decim
+ *                            (cycles per input sample), beta = 8.  Returns the tap count (taps NULL: the count alone)
+ *                            or GLFER_E_ARG (decim outside 1 .. 1024, ntaps > 8192, cutoff > 0.5)
+ *   glfer_hip_ddc_supported  GLFER_OK or GLFER_E_ARG: decim 1 .. 1024 and ntaps 1 .. 8192 in any combination, freq in [-0.5, 0.5),
+ *                            the three sample formats, complex_in 0 or 1
+ *   glfer_hip_ddc_tables     g[T][2] floats as defined above
+ * The handle: glfer_hip_ddc_create uploads g once (the rotation needs no table: the negated 64-bit phase goes through one double
+ * sincospi per output, each part rounded once to float); calls through it upload and allocate nothing and are legal on a stream
+ * under graph capture.  One handle, one device (cfg.device).
+ *   glfer_hip_ddc_device        outputs [first_out, first_out + nout) to d_out[0 .. nout).  d_in is the address of sample 0 by the
+ *                               virtual-base convention of "Cutting a stream"; only samples [max(0, first_out D - (T-1)),
+ *                               (first_out + nout) D) are read.  The batch of one
+ *   glfer_hip_ddc_batch_device  stream b at d_in + b * stream_pitch (input samples; complex samples for complex input), its outputs
+ *                               at d_out + b * out_pitch (complex samples; 0 means nout, else >= nout).  One launch (the stream is
+ *                               the grid's y; more than 65535 streams: one launch per chunk of that many)
+ *   glfer_hip_spectrogram_zoom_device
+ *                               rows [first_frame, first_frame + nframes) of the I/Q entry over the DDC's output, a stream of
+ *                               nsamples / D complex samples: the DDC outputs [first_frame H - (N - H) clipped at 0,
+ *                               (first_frame + nframes) H) go to stream-ordered scratch, the I/Q kernel runs on that scratch's
+ *                               virtual base.  Two kernels a call; rows bit for bit those of glfer_hip_spectrogram_iq_device over
+ *                               glfer_hip_ddc_device's output.  The plan: one glfer_hip_iq_supported accepts, f32 sample format (the
+ *                               baseband is f32; the handle's format is the recording's), on the handle's device.  flags:
+ *                               GLFER_IQ_CENTERED only.  It takes scratch, so a hip_stream that is being captured is REFUSED
+ *                               (GLFER_E_ARG); capture glfer_hip_ddc_device and the I/Q entry with a buffer of the caller's instead.
+ *                               More than 2^31 - 1 DDC outputs in one call: GLFER_E_ARG (cut the frame range)
+ * Arguments, in this order, nothing on the device touched before they pass: GLFER_E_ARG for a NULL handle (zoom: a NULL or
+ * unsupported plan, unknown flags), an out_pitch (row_pitch) below nout (N); then GLFER_OK with nothing launched for nout == 0,
+ * nstreams == 0 (nframes == 0); then GLFER_E_ARG for NULL buffers, first_out + nout wrapping or past nsamples / D (a frame past the
+ * baseband), nout (nframes) > 0x7fffffff, a d_in not aligned to one input sample (one complex sample for complex input), sizes that
+ * overflow.  Asynchronous on hip_stream.
+ * Not built: ragged / host / WAV / workers / multi-GPU forms, zoom batches, swapped I/Q input, rational resampling, a fused
+ * DDC-plus-transform kernel. */
+typedef struct glfer_hip_ddc_config {
+  int decim;           /* D: 1 .. 1024                                                        */
+  int ntaps;           /* T: 1 .. 8192                                                        */
+  double freq;         /* cycles per input sample, [-0.5, 0.5): what is moved to 0 Hz         */
+  int complex_in;      /* 0: real samples; 1: interleaved I/Q pairs                           */
+  int sample_format;   /* GLFER_SAMPLES_*                                                     */
+  int device;          /* HIP device ordinal                                                  */
+} glfer_hip_ddc_config;
+typedef struct glfer_hip_ddc glfer_hip_ddc;
+unsigned long long glfer_hip_ddc_phase_word(double freq);
+int glfer_hip_ddc_design(int decim, int ntaps, double cutoff, double beta, float *taps);
+int glfer_hip_ddc_supported(const glfer_hip_ddc_config *cfg);
+int glfer_hip_ddc_tables(const glfer_hip_ddc_config *cfg, const float *taps, float *g);
+int glfer_hip_ddc_create(const glfer_hip_ddc_config *cfg, const float *taps, glfer_hip_ddc **ddc);
+void glfer_hip_ddc_destroy(glfer_hip_ddc *ddc);
+int glfer_hip_ddc_device(glfer_hip_ddc *ddc, const void *d_in, size_t nsamples, size_t first_out, size_t nout, void *d_out,
+                         void *hip_stream);
+int glfer_hip_ddc_batch_device(glfer_hip_ddc *ddc, const void *d_in, size_t nstreams, size_t stream_pitch, size_t nsamples,
+                               size_t first_out, size_t nout, void *d_out, size_t out_pitch, void *hip_stream);
+int glfer_hip_spectrogram_zoom_device(glfer_hip_plan *plan, glfer_hip_ddc *ddc, const void *d_in, size_t nsamples, size_t first_frame,
+                                      size_t nframes, float *d_psd, size_t row_pitch, unsigned flags, void *hip_stream);
+
 /* BASELINE config 4 as worded ("1-hour 48 kHz WAV, frame-batch sharded across 8 x MI355X"): the
  * file's frames dealt out over the GPUs named in device_mask (glfer_hip_frame_range: contiguous
  * ranges, boundaries on multiples of GLFER_FRAME_ALIGN), one host thread + plan + pinned ring per
