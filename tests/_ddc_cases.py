@@ -79,21 +79,25 @@ def signal(c, seed):
 
 def make_input(c, seed=None):
     """(raw, x): the piece in the case's format (complex: [S][2] pairs) and the complex64 values the device must see."""
-    z = signal(c, seed_of(c) if seed is None else seed)
+    return convert(signal(c, seed_of(c) if seed is None else seed), c.cplx, c.fmt)
+
+
+def convert(z, cplx, fmt):
+    """make_input's clipping and conversion of the complex128 signal z (real input: its real part); tests/_zoom_cases.py shares it."""
     lim = np.nextafter(1.0, 0.0)
     parts = np.stack([np.clip(z.real, -1.0, lim), np.clip(z.imag, -1.0, lim)], axis=1)
-    if not c.cplx:
+    if not cplx:
         parts[:, 1] = 0.0
-    if c.fmt == "s16":
+    if fmt == "s16":
         raw = np.clip(np.round(parts * 20000), -32768, 32767).astype(np.int16)
         v = raw.astype(np.float32) / np.float32(32768.0)
-    elif c.fmt == "u8":
+    elif fmt == "u8":
         raw = np.clip(np.round(parts * 100 + 128), 0, 255).astype(np.uint8)
         v = (raw.astype(np.float32) - np.float32(128.0)) / np.float32(128.0)
     else:
         raw = np.ascontiguousarray(parts.astype(np.float32))
         v = raw
-    if not c.cplx:
+    if not cplx:
         return np.ascontiguousarray(raw[:, 0]), v[:, 0].astype(np.complex64)
     return np.ascontiguousarray(raw), (v[:, 0] + 1j * v[:, 1]).astype(np.complex64)
 

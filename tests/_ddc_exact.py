@@ -6,7 +6,9 @@
 
 `exact` takes the float tables and the phase word and does the rest in float64 / complex128.  `standin32` is the same case in
 float32: a sequential sum over t = 0, 1, ... of complex64 products, then a rotation whose angle is accurate to double and rounded
-to complex64.  Its switches build the WRONG outputs tests/test_ddc_criterion.py must see rejected.
+to complex64.  Its switches build the WRONG outputs tests/test_ddc_criterion.py must see rejected.  `order` keeps the arithmetic and
+changes the sequence of the sum alone: "taps" (t ascending, the default), "rows" (the order ddc.hip documents: t = r, r + D, r + 2D, ...
+for r = 0 .. min(D, T) - 1, one accumulator throughout) and "down" (t descending, the order tests/test_zoom_criterion.py holds out).
 
 A piece of a long stream: `x` holds samples [base, base + len(x)) and outputs [first, first + nout) are asked for; every sample they
 read (n0 - t >= base, or below 0) must be in the piece.
@@ -82,9 +84,20 @@ def exact(x, g, W, D, first, nout, base=0):
     return (w @ g64) * rotation(W, D, first, nout), np.abs(w) @ np.abs(g64)
 
 
-def standin32(x, g, W, D, first, nout, base=0, conj_taps=False, delay=0, rot_at=0, reverse_taps=False, float_phase=None):
+def tap_order(D, T, order="taps"):
+    """The sequence in which the T products of one output are added."""
+    if order == "taps":
+        return list(range(T))
+    if order == "rows":
+        return [t for r in range(min(D, T)) for t in range(r, T, D)]
+    if order == "down":
+        return list(range(T - 1, -1, -1))
+    raise ValueError(order)
+
+
+def standin32(x, g, W, D, first, nout, base=0, conj_taps=False, delay=0, rot_at=0, reverse_taps=False, float_phase=None, order="taps"):
     """The float32 computation; the keyword switches make the wrong variants.  float_phase: a freq whose float32 product with
-    float32(n0) replaces the integer phase."""
+    float32(n0) replaces the integer phase.  order: the sequence of the sum (tap_order), no wrong variant."""
     g = np.asarray(g, np.complex64)
     if conj_taps:
         g = np.conj(g)
@@ -95,7 +108,7 @@ def standin32(x, g, W, D, first, nout, base=0, conj_taps=False, delay=0, rot_at=
         x = np.concatenate([np.zeros(delay, np.complex64), x[:-delay]])
     w = windows(x, D, len(g), first, nout, base)
     acc = np.zeros(nout, np.complex64)
-    for t in range(len(g)):
+    for t in tap_order(D, len(g), order):
         acc = acc + g[t] * w[:, t]
     if float_phase is None:
         rot = rotation(W, D, first, nout, rot_at)
