@@ -116,3 +116,82 @@ def multitaper32(x, n, overlap, tapers, sig, sub_mean=0, history_mode=0):
         wj = np.float32(1.0 / (1.0 + sig[j]))
         out += _power32(_rfft32(fr * np.asarray(tapers[j], np.float32)), n) * wj
     return out
+
+
+# ---- the harmonic F statistic in float32 (tests/_ftest_rows_check.py takes its bounds from these) ---------------------------
+def _ftest32_tables(tapers, kmax):
+    """The float32 tapers and, formed in double from them and rounded once, U0_j, sum(U0^2) and hn."""
+    v32 = np.asarray(tapers, np.float32)[:kmax + 1]
+    v = v32.astype(np.float64)
+    U0 = v.sum(axis=1)
+    s2 = (U0 * U0).sum()
+    hn = (U0[:, None] * v).sum(axis=0) / s2
+    return v32, U0.astype(np.float32), np.float32(s2), hn.astype(np.float32)
+
+
+def _ftest32_quotient(mu, ys, U0, s2, kmax, order):
+    """num, den and F in float32 from the float32 spectra: the residuals, their squares, the taper sum (in `order`) and
+    the quotient each rounded to float32.  The Nyquist column is num / 0, as the reference leaves it (mtm.c:206)."""
+    num = np.float32(kmax) * (mu.real * mu.real + mu.imag * mu.imag) * s2
+    den = np.zeros_like(num)
+    for j in order:
+        rr = ys[j].real - mu.real * U0[j]
+        ri = ys[j].imag - mu.imag * U0[j]
+        den += rr * rr + ri * ri
+    assert num.dtype == den.dtype == np.float32
+    low = den.copy()
+    low[:, -1] = 0.0
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        return num / low, num, den
+
+
+def ftest32(x, n, overlap, tapers, kmax, sub_mean=0, history_mode=0, reverse=False):
+    """ftest64's frames, one float32 transform (_rfft32) per sequence -- hn, then each taper --, float32 from there on:
+    (F, num, den), each [frames][n/2+1] float32.  reverse: the taper sum taken from the last taper to the first."""
+    fr = frames64(x, n, overlap, sub_mean, history_mode).astype(np.float32)
+    v32, U0, s2, hn = _ftest32_tables(tapers, kmax)
+    mu = _rfft32(fr * hn)
+    ys = [_rfft32(fr * v32[j]) for j in range(kmax + 1)]
+    order = range(kmax, -1, -1) if reverse else range(kmax + 1)
+    return _ftest32_quotient(mu, ys, U0, s2, kmax, order)
+
+
+def _fft32(rows):
+    """Complex float32 transforms row by row (see _rfft32)."""
+    import torch
+    rows = np.ascontiguousarray(rows, np.complex64)
+    out = np.empty_like(rows)
+    for f in range(rows.shape[0]):
+        out[f] = torch.fft.fft(torch.from_numpy(rows[f])).numpy()
+    return out
+
+
+def ftest32_paired(x, n, overlap, tapers, kmax, sub_mean=0, history_mode=0):
+    """The same statistic with TWO real sequences per complex transform, separated through the mirror bins: the sequences hn
+    (brought to a taper's size by a power of two, taken out of mu again), taper 0 ... kmax go two at a time as the real and the
+    imaginary part of z, each halved, and X_a = Z[k] + conj Z[N-k], X_b = (Z[k] - conj Z[N-k]) / i, in float32.  An odd count
+    leaves the last transform's imaginary part zero."""
+    fr = frames64(x, n, overlap, sub_mean, history_mode).astype(np.float32)
+    v32, U0, s2, hn = _ftest32_tables(tapers, kmax)
+    ex = int(np.frexp(np.sqrt(s2))[1])
+    scale = np.float32(2.0 ** (ex - 1)) if s2 > 0 and 0 < ex < 64 else np.float32(1.0)
+    seqs = [hn * scale] + [v32[j] for j in range(kmax + 1)]
+    if len(seqs) % 2:
+        seqs.append(np.zeros(n, np.float32))
+    half = n // 2
+    k = np.arange(half + 1)
+    spectra = []
+    for i in range(0, len(seqs), 2):
+        z = np.empty(fr.shape, np.complex64)
+        z.real = fr * (np.float32(0.5) * seqs[i])
+        z.imag = fr * (np.float32(0.5) * seqs[i + 1])
+        Z = _fft32(z)
+        Zk, Zm = Z[:, k], Z[:, (n - k) % n]
+        xa = np.empty((fr.shape[0], half + 1), np.complex64)
+        xb = np.empty_like(xa)
+        xa.real, xa.imag = Zk.real + Zm.real, Zk.imag - Zm.imag
+        xb.real, xb.imag = Zk.imag + Zm.imag, Zm.real - Zk.real
+        spectra += [xa, xb]
+    mu = np.empty_like(spectra[0])
+    mu.real, mu.imag = spectra[0].real * (np.float32(1.0) / scale), spectra[0].imag * (np.float32(1.0) / scale)
+    return _ftest32_quotient(mu, spectra[1:kmax + 2], U0, s2, kmax, range(kmax + 1))
