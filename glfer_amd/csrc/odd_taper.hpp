@@ -133,7 +133,9 @@ __device__ __forceinline__ void separate_and_store(const SpectroParams &p, const
     constexpr int r = rho_of(m);
     xb[t + T * (m - 8)] = v2f32{zr[r], zi[r]};
   });
+  GLFER_STAMP(12);                                    // mirror entries issued
   frame_sync<T>();
+  GLFER_STAMP(13);                                    // through the barrier behind them
   const unsigned ROWB = (unsigned)p.pitch * 4u;            // bytes from row to row (cfg.psd_pitch)
   const long long leftA = p.nframes - fblk, leftB = p.nframes - (fblk + FPB);
   const unsigned recA = (unsigned)((leftA > FPB ? FPB : leftA) * (long long)ROWB);
@@ -162,6 +164,65 @@ __device__ __forceinline__ void separate_and_store(const SpectroParams &p, const
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(__builtin_fmaf(4.0f * zr[r] * zr[r], uA, sumA(nyq))), ra, voff, (unsigned)(N / 2) * 4u, GLFER_PSD_STORE_AUX);
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(__builtin_fmaf(4.0f * zi[r] * zi[r], uB, sumB(nyq))), rb, voff, (unsigned)(N / 2) * 4u, GLFER_PSD_STORE_AUX);
   }
+  GLFER_STAMP(14);                                    // mirror entries read, rows issued
+  frame_sync<T>();                                    // mirror entries read: xb is free again
+}
+
+// The separation with the mirror fold of the frames' sums in the same LDS pass (spectro16y.hip's half-table forms, one frame
+// pair per workgroup): a lane's upper-half bins travel as 16-byte entries {Re Z, Im Z, accA, accB}[k], entry k - N/2 of xb,
+// so the one read that brings Z[N-k] brings the unfolded sums acc[N-k] of both frames with it.
+// mirror_entry_write: one upper-half bin t + T*m (m = 8..15) of the lane, as soon as the last butterfly stage has it.
+// separate_fold_and_store: the barrier behind those writes, then per bin k = t + T*m < N/2 the fold psd = acc[k] + acc[N-k]
+// (k = 0 pairs with itself and k = N/2 is doubled, on lane 0) and separate_and_store's arithmetic on it, operation for
+// operation: fma(|E|^2, uA, psd).  acc[r]: the sums in transform register order (register r of the lane).
+typedef float v4f32_lds __attribute__((ext_vector_type(4)));
+template <int LOGN, int M>
+__device__ __forceinline__ void mirror_entry_write(v2f32 *xb, unsigned t, float re, float im, float sa, float sb) {
+  constexpr int T = Plan16<LOGN>::T;
+  static_assert(M >= 8 && M < 16, "an upper-half bin");
+  reinterpret_cast<v4f32_lds *>(xb)[t + T * (M - 8)] = v4f32_lds{re, im, sa, sb};
+}
+template <int LOGN>
+__device__ __forceinline__ void separate_fold_and_store(const SpectroParams &p, const float (&zr)[16], const float (&zi)[16],
+                                                        const float (&accA)[16], const float (&accB)[16], v2f32 *xb, unsigned t,
+                                                        long long fblk, int hxA, int hxB) {
+  using C = Plan16<LOGN>;
+  constexpr int N = C::N, T = C::T, RL = C::radix(C::NPASS - 1), BL = 16 / RL;
+  static_assert((N / 2 + 1) * 16 <= (N + N / 16) * 8, "the mirror entries fit one exchange buffer");
+  auto rho_of = [](int m) constexpr { return (m % BL) + BL * brev(m / BL, RL); };
+  GLFER_STAMP(12);                                    // mirror entries issued
+  frame_sync<T>();
+  GLFER_STAMP(13);                                    // through the barrier behind them
+  const unsigned ROWB = (unsigned)p.pitch * 4u;            // bytes from row to row (cfg.psd_pitch)
+  const long long leftA = p.nframes - fblk, leftB = p.nframes - (fblk + 1);
+  const unsigned recA = (unsigned)((leftA > 1 ? 1 : leftA) * (long long)ROWB);
+  const unsigned recB = leftB > 0 ? ROWB : 0u;
+  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(p.psd + (size_t)fblk * (size_t)p.pitch, 0, recA, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(p.psd + (size_t)(fblk + (leftB > 0 ? 1 : 0)) * (size_t)p.pitch, 0, recB, 0x00020000);
+  const unsigned voff = t * 4u;
+  const float uA = scale_out(hxA), uB = scale_out(hxB);
+  const v4f32_lds *xe = reinterpret_cast<const v4f32_lds *>(xb);
+  static_for<0, 8>([&](auto mc) {
+    constexpr int m = decltype(mc)::value;
+    constexpr int r = rho_of(m);
+    const int k = (int)t + T * m;
+    v4f32_lds b = xe[N / 2 - k];                      // {Z, accA, accB}[N-k]; entry N/2 (k = 0) is never written
+    const float ar = zr[r], ai = zi[r];
+    if constexpr (m == 0) {
+      if (t == 0) b = v4f32_lds{ar, ai, accA[r], accB[r]};   // k = 0 pairs with itself
+    }
+    const float sa = accA[r] + b.z, sb = accB[r] + b.w;
+    const float er = ar + b.x, ei = ai - b.y, orr = ar - b.x, oi = ai + b.y;
+    const float pa = __builtin_fmaf(er, er, ei * ei), pb = __builtin_fmaf(orr, orr, oi * oi);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(__builtin_fmaf(pa, uA, sa)), ra, voff, (unsigned)(T * m) * 4u, GLFER_PSD_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(__builtin_fmaf(pb, uB, sb)), rb, voff, (unsigned)(T * m) * 4u, GLFER_PSD_STORE_AUX);
+  });
+  if (t == 0) {                                       // k = N/2 pairs with itself: E = 2 Re Z, O = 2i Im Z
+    constexpr int r = rho_of(8);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(__builtin_fmaf(4.0f * zr[r] * zr[r], uA, 2.0f * accA[r])), ra, voff, (unsigned)(N / 2) * 4u, GLFER_PSD_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(__builtin_fmaf(4.0f * zi[r] * zi[r], uB, 2.0f * accB[r])), rb, voff, (unsigned)(N / 2) * 4u, GLFER_PSD_STORE_AUX);
+  }
+  GLFER_STAMP(14);                                    // mirror entries read, rows issued
   frame_sync<T>();                                    // mirror entries read: xb is free again
 }
 

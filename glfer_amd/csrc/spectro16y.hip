@@ -34,6 +34,17 @@
 // iteration in flight; a workgroup draws exactly one ticket per chunk it takes, so a launch of P chunks draws P tickets
 // whatever the order (P - gridDim.x that succeed, gridDim.x that fail), and the host passes the counter's value before the
 // launch as p.yq_base instead of zeroing it.  Which workgroup takes a pair changes nothing that is computed for it.
+//
+// SEG (the half-table forms outside the ragged build): behind the second dual round an iteration has one transform left and
+// nothing to hide its LDS latency under, so that third of the iteration makes as few LDS round trips as it can.  The sums
+// accA / accB stay in registers through the shared round (32 transform registers there against 64 in a dual round); in front
+// of it only the wavefronts' power totals and the queue ticket cross a barrier (where the other forms also fold the mirror
+// bins through both buffers, "the barrier of the mirror fold" above).  The shared round goes through both exchange buffers
+// (stockham16_passes_pp: no barrier that only releases a buffer), its last butterfly stage writes the upper-half bins as
+// 16-byte entries {Re Z, Im Z, accA, accB}, and the separation folds psd = acc[k] + acc[N-k] from the mirror entry it reads
+// anyway (separate_fold_and_store).  13 barriers per iteration instead of 16, one LDS round trip fewer; per frame the same
+// operations on the same values in the same order, so the rows are bit-identical to every other form's
+// (profiles/y_shared_segment.txt).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "odd_taper.hpp"
@@ -67,6 +78,16 @@
 #define spectro16y_kernel spectro16y_ragged_kernel
 #define glfer_launch_spectro16y_n12 glfer_launch_spectro16y_ragged_n12
 #endif
+// The half-table forms' single-stream third: the mirror fold inside the separation's LDS pass and the shared round through
+// both exchange buffers (see the kernel's SEG; profiles/y_shared_segment.txt).  0 keeps the fold in front of the shared round
+// and the one-buffer passes, as the full-table and mean forms do; the ragged instantiations stay with that.
+#ifndef GLFER16Y_ONE_MIRROR_PASS
+#ifdef GLFER_RAGGED
+#define GLFER16Y_ONE_MIRROR_PASS 0
+#else
+#define GLFER16Y_ONE_MIRROR_PASS 1
+#endif
+#endif
 
 namespace glfer {
 
@@ -95,6 +116,8 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
   // (the hop sums of the mean forms reduce across lanes in lane order: a lane permutation would change their bits)
   static_assert(HALF == 0 || (KM == 0 && GLFER16_X0_ROWS != 0 && GLFER16_BARRIER_AFTER_READS != 0), "half tables: the plain forms, row layout of exchange 0");
   static_assert(QUEUE == 0 || (KM == 0 && BAT == 0 && ABL == 0), "frame queue: the plain single-stream forms");
+  constexpr bool SEG = HALF != 0 && GLFER16Y_ONE_MIRROR_PASS != 0;
+  static_assert(!SEG || ABL == 0, "the ablation reads the folded sums in front of the shared round");
   constexpr int NH = KM > 0 ? 16 / KM : 1;
   __shared__ float mred[KM > 0 ? 4 * (NH + 1) : 1];
   using C = Plan16<12>;
@@ -104,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
   constexpr int NT = C::NTW - TW1;
   constexpr unsigned esz = FMT == GLFER_FMT_F32 ? 4 : (FMT == GLFER_FMT_S16 ? 2 : 1);
   typedef float v4f32 __attribute__((ext_vector_type(4)));
-  extern __shared__ v2f32 lds[];                    // L::LDS_WORDS entries (72 KB: above the static limit)
+  extern __shared__ __attribute__((aligned(16))) v2f32 lds[];   // L::LDS_WORDS entries (72 KB: above the static limit); 16 bytes: the mirror entries of the half-table forms
 
   const unsigned t = threadIdx.x;
   const unsigned rc = HALF ? glfer_yhalf_residue(t) : t;   // the lane's residue in pass 0: samples rc + T*m, column rc of exchange 0
@@ -286,10 +309,10 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
     if constexpr (QUEUE != 0) {
       if (fresh && t == 0) ticket = __hip_atomic_fetch_add(p.yq_counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    float psdA[8], psdB[8], nyqA, nyqB;
+    float psdA[8], psdB[8], nyqA, nyqB;               // (SEG: the fold happens in the separation, these stay unused)
     int hxA, hxB;
+    float accA[16], accB[16];                         // (SEG: live through the shared round)
     {
-      float accA[16], accB[16];
 #pragma unroll
       for (int r = 0; r < 16; r++) accA[r] = accB[r] = 0.0f;     // (dead when NP >= 1: pair 0 overwrites)
       if constexpr (HALF != 0) {
@@ -381,12 +404,15 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
         eB += __shfl_xor(eB, w);
       }
 #endif
-      float *foldA = reinterpret_cast<float *>(xbA), *foldB = reinterpret_cast<float *>(xbB);
-      static_for<8, 16>([&](auto mc) {               // the buffers are free: barrier after the last reads
+      GLFER_SEG_STAMP(0);                            // fold start (sums over the wavefront done)
+      [[maybe_unused]] float *foldA = reinterpret_cast<float *>(xbA), *foldB = reinterpret_cast<float *>(xbB);
+      if constexpr (!SEG) static_for<8, 16>([&](auto mc) {   // the buffers are free: barrier after the last reads
         constexpr int m = decltype(mc)::value;
         foldA[t + T * (m - 8)] = accA[rho_of(m)];
         foldB[t + T * (m - 8)] = accB[rho_of(m)];
       });
+      // (SEG: the mirror fold rides in the separation's LDS pass, separate_fold_and_store; only the scales' power totals and
+      // the queue ticket cross this barrier)
       if ((t & 63) == 0) {
         red[t >> 6] = eA;
         red[4 + (t >> 6)] = eB;
@@ -394,7 +420,9 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
       if constexpr (QUEUE != 0) {
         if (fresh && t == 0) *qword = ticket - p.yq_base;
       }
+      GLFER_SEG_STAMP(1);                            // fold writes / power partials issued
       __syncthreads();
+      GLFER_SEG_STAMP(2);                            // through the barrier behind them
       if constexpr (QUEUE != 0) {
         if (fresh) next_chunk = ((long long)gridDim.x + (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)*qword)) * span;
         nfA = fA + 2 < fEnd ? fA + 2 : next_chunk;
@@ -404,6 +432,7 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
       eB = (red[4] + red[5]) + (red[6] + red[7]);
       hxA = scale_exponent(eA);
       hxB = scale_exponent(eB);
+      if constexpr (!SEG) {
       static_for<0, 8>([&](auto mc) {
         constexpr int m = decltype(mc)::value;
         const int k = T * m + (int)t;
@@ -419,7 +448,9 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
       });
       nyqA = 2.0f * accA[rho_of(8)];
       nyqB = 2.0f * accB[rho_of(8)];
+      GLFER_SEG_STAMP(3);                            // fold reads issued
       __syncthreads();                               // fold buffers read: free for the next writes
+      }
     }
 
     if constexpr (ABL == 1) {
@@ -465,6 +496,15 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
           load_x(xB, nfA + 1);
         }
       };
+      if constexpr (SEG) {
+        // exchange 0 through xbA, exchange 1 through xbB, the mirror entries of the separation through xbA again.  Both
+        // buffers are free here: their last readers were the second dual round's exchange-1 reads, in front of that round's
+        // buffer-release barrier (and the power totals' barrier above).
+        stockham16_passes_pp<12, NT>(zr, zi, xbA, xbB, t, rc, tw1sel, twr, twi, hook, [&](auto qc, auto regc) {
+          constexpr int q = decltype(qc)::value, reg = decltype(regc)::value;
+          if constexpr (q >= 8) mirror_entry_write<12, q>(xbA, t, zr[reg], zi[reg], accA[reg], accB[reg]);
+        });
+      } else
       if constexpr (GLFER16Y_SKEW >= 2) stockham16_passes1s<12, NT>(zr, zi, xbA, t, rc, tw1sel, twr, twi, hook);
       else stockham16_passes<12, NT>(zr, zi, xbA, t, rc, tw1sel, twr, twi, hook);
     };
@@ -473,6 +513,11 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
     if constexpr (KM > 0) {
       if (has_next && !p.means) publish_hop_sums();  // the next iteration's samples are in registers (requested during the passes above)
     }
+    // The barrier that ends either routine is the iteration's last.  SEG: it frees xbA (the mirror entries' readers) for the
+    // next iteration's pass-0 writes; xbB's last readers were the shared round's exchange-1 reads, which every wavefront had in
+    // registers before it arrived at the barrier behind the mirror entries -- two barriers in front of those writes.
+    if constexpr (SEG) separate_fold_and_store<12>(p, zr, zi, accA, accB, xbA, t, fA, hxA, hxB);
+    else
     separate_and_store<12, 1>(p, zr, zi, xbA, t, 0u, fA, hxA, hxB,
                               [&](auto mc) { if constexpr (decltype(mc)::value == 8) return nyqA; else return psdA[decltype(mc)::value]; },
                               [&](auto mc) { if constexpr (decltype(mc)::value == 8) return nyqB; else return psdB[decltype(mc)::value]; });

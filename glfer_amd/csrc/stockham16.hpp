@@ -12,6 +12,11 @@
 #ifndef GLFER_STAMP
 #define GLFER_STAMP(id)
 #endif
+// Further marks for tools/ysegbench only (the single-stream third of spectro16y.hip's iteration): 0..3 the mirror fold,
+// 4 + i exchange i's reads landed, 6 + i through the barrier that releases exchange i's buffer.
+#ifndef GLFER_SEG_STAMP
+#define GLFER_SEG_STAMP(id)
+#endif
 // 1: the barrier that frees the exchange buffer sits right after an exchange's reads; 0: in front
 // of the next exchange's writes
 // inter-pass twiddles folded into the first butterfly stage (fft_inreg.hpp: dit_tw)
@@ -346,7 +351,9 @@ __device__ __forceinline__ void stockham16_passes(float (&zr)[16], float (&zi)[1
       // of in front of the next writes, those writes are not fenced off from the butterflies
       // that produce them and can be issued as their data becomes ready.  The buffer is then
       // free for ANY writer after this point, including the caller's fold / mirror steps.
+      GLFER_SEG_STAMP(4 + i);              // exchange i's reads landed
       if constexpr (GLFER16_BARRIER_AFTER_READS != 0) frame_sync<T>();
+      GLFER_SEG_STAMP(6 + i);              // through the buffer-release barrier
     }
   });
 }
@@ -654,6 +661,75 @@ __device__ __forceinline__ void stockham16_passes1s(float (&zr)[16], float (&zi)
         __builtin_amdgcn_sched_barrier(0);
         frame_sync<T>();                       // the writes are in LDS
       }
+    }
+  });
+}
+
+// One stream through TWO exchange buffers: exchange 0 goes through xb0, exchange 1 through xb1, and the last butterfly
+// stage hands its outputs to last_emit(q, reg) (bin t + T*q sits in register reg), which may write xb0 again.  The two
+// barriers of stockham16_passes that only release its one buffer for the next writes are not needed then; the argument for
+// each reuse stands where the barrier was.  The caller guarantees that nobody reads xb0 or xb1 when the passes start, and
+// puts a barrier between last_emit's writes and their readers.  Same operations in the same order as stockham16_passes.
+// Radix-16 passes only (N = 4096).
+template <int LOGM, int NT, class Tw1, class Hook, class Emit>
+__device__ __forceinline__ void stockham16_passes_pp(float (&zr)[16], float (&zi)[16], v2f32 *xb0, v2f32 *xb1, unsigned t, unsigned col0,
+                                                     const Tw1 &tw1row, const float (&twr)[NT], const float (&twi)[NT],
+                                                     Hook &&after_first_write, Emit &&last_emit) {
+  using C = Plan16<LOGM>;
+  constexpr int T = C::T, NPASS = C::NPASS;
+  static_assert(NPASS == 3 && GLFER16_FOLD_TW != 0 && GLFER16_BARRIER_AFTER_READS != 0 && GLFER16_X0_ROWS != 0 && T >= 32 && T % 32 == 0 && !(GLFER_ABL & 7),
+                "the product configuration, three passes");
+  static_for<0, NPASS>([&](auto ic) {
+    constexpr int i = decltype(ic)::value;
+    constexpr int R = C::radix(i), Ls = C::ls(i);
+    static_assert(R == 16, "radix-16 passes");
+    const PassTwiddles<C, i, NT, Tw1> twf{tw1row, twr, twi};
+    if constexpr (i == 0) dit_head<R, 1, 0, 16>(zr, zi);
+    else dit_head_tw<R, 1, 0, 16>(zr, zi, twf);
+    if constexpr (i == NPASS - 1) {
+      // (stockham16_passes has its second buffer-release barrier in front of this stage.)  last_emit may write xb0: its
+      // last readers were exchange 0's reads, and every wavefront had those in registers (the s_waitcnt that ends
+      // lds_read16_strided) before it arrived at the write-to-read barrier of exchange 1, which this wavefront has passed.
+      // Exchange 1's own readers are not touched by a write to xb0; the caller's barrier behind last_emit's writes is the
+      // next one every wavefront meets, and it has its exchange-1 reads in registers by then.
+      dit_tail<R, 1, 0, 16>(zr, zi, last_emit);
+      GLFER_STAMP(4 * i + 1);              // pass i butterflies done
+    } else {
+      v2f32 *xb = i == 0 ? xb0 : xb1;
+      const int k = (int)t & (Ls - 1);
+      const int a0 = ((int)t - k) * R + k;
+      constexpr bool kRows = i == 0;
+      v2f32 *wbase = kRows ? xb + col0 : xb + a0 + (a0 >> xpad_shift(i));
+      // i == 1 (stockham16_passes has its first buffer-release barrier in front of this stage): these writes go to xb1
+      // while other wavefronts may still be reading exchange 0 from xb0 -- another buffer.  xb1's last readers are the
+      // caller's, fenced off before the passes start.
+      dit_tail<R, 1, 0, 16>(zr, zi, [&](auto qc, auto rc) {
+        constexpr int q = decltype(qc)::value, reg = decltype(rc)::value;
+        wbase[kRows ? q * (T + 2) : xpad_offset(i, q * Ls)] = v2f32{zr[reg], zi[reg]};
+      });
+      GLFER_STAMP(4 * i + 1);              // pass i butterflies done
+      if constexpr (i == 0) {
+        after_first_write();
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      GLFER_STAMP(4 * i + 3);              // writes (and the hook's loads) issued
+      frame_sync<T>();                     // the writes are in LDS
+      GLFER_STAMP(4 * i + 4);              // through the post-write barrier
+      v2f32 v[16];
+      if constexpr (i == 0) {
+        lds_read16_strided<T / 16>(xb + (t & 15) * (T + 2) + (t >> 4), v);
+      } else {
+        constexpr int STRIDE = xpad_offset(i, T);
+        static_assert(15 * STRIDE * 8 < 65536 && xpad_offset(i, 15 * T) == 15 * STRIDE, "one stride");
+        lds_read16_strided<STRIDE>(xb + t + (t >> xpad_shift(i)), v);
+      }
+#pragma unroll
+      for (int m = 0; m < 16; m++) {
+        zr[m] = v[m].x;
+        zi[m] = v[m].y;
+      }
+      GLFER_SEG_STAMP(4 + i);              // exchange i's reads landed
+      // (no barrier here: this buffer is not written again before every wavefront has met the next write-to-read barrier)
     }
   });
 }
