@@ -9,6 +9,7 @@ Names follow the reference's estimator interface (fft.h:77-83, mtm.h:47-49, avg.
 (source.c:320-325, 343-350) and `Spectrogram` is the per-hop loop of source.c:130-158
 run over a whole stream.
 """
+import collections
 import ctypes as C
 import os
 
@@ -21,6 +22,8 @@ LIB_PATH = os.environ.get("GLFER_LIB_PATH") or os.path.join(_HERE, "lib", "libgl
 MODE_FFT, MODE_MTM, MODE_HPARMA, MODE_LMP = 0, 1, 2, 3
 WAV_PARTIAL_TAIL = 1
 IQ_CENTERED, IQ_SWAP = 1, 2                            # flags of the complex I/Q entries
+CROSS_FIELDS = ("sxx", "syy", "sxy", "coh")
+Cross = collections.namedtuple("Cross", CROSS_FIELDS)  # what Spectrogram.cross returns: None for what was not asked
 WINDOWS = {"hanning": 0, "blackman": 1, "gaussian": 2, "welch": 3,
            "bartlett": 4, "rectangular": 5, "hamming": 6, "kaiser": 7}
 SAMPLES_F32, SAMPLES_S16, SAMPLES_U8 = 0, 1, 2
@@ -72,6 +75,8 @@ EXPORTS = [
     # zoom: the digital down-converter and the I/Q rows of its output
     "glfer_hip_ddc_phase_word", "glfer_hip_ddc_design", "glfer_hip_ddc_supported", "glfer_hip_ddc_tables", "glfer_hip_ddc_create",
     "glfer_hip_ddc_destroy", "glfer_hip_ddc_device", "glfer_hip_ddc_batch_device", "glfer_hip_spectrogram_zoom_device",
+    # two channels: multitaper auto- and cross-spectra and coherence in one pass
+    "glfer_hip_cross_supported", "glfer_hip_mtm_cross_device", "glfer_hip_mtm_cross_batch_device",
 ]
 
 
@@ -219,6 +224,10 @@ def lib():
         L.glfer_hip_iq_tables.argtypes = [C.POINTER(Config), vp]
         L.glfer_hip_spectrogram_iq_device.argtypes = [vp, vp, sz, sz, sz, vp, sz, C.c_uint, vp]
         L.glfer_hip_spectrogram_iq_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, sz, C.c_uint, vp]
+    if hasattr(L, "glfer_hip_mtm_cross_device"):
+        L.glfer_hip_cross_supported.argtypes = [C.POINTER(Config)]
+        L.glfer_hip_mtm_cross_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, sz, vp]
+        L.glfer_hip_mtm_cross_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, sz, vp, sz, vp]
     if hasattr(L, "glfer_hip_ddc_device"):
         L.glfer_hip_ddc_phase_word.argtypes = [C.c_double]
         L.glfer_hip_ddc_phase_word.restype = C.c_ulonglong
@@ -312,6 +321,12 @@ def iq_supported(params):
     """Whether a plan of these parameters takes complex I/Q input (glfer_hip_iq_supported; host only)."""
     cfg = make_config(params)
     return lib().glfer_hip_iq_supported(C.byref(cfg)) == 0
+
+
+def cross_supported(params):
+    """Whether a plan of these parameters gives cross-spectra and coherence (glfer_hip_cross_supported; host only)."""
+    cfg = make_config(params)
+    return lib().glfer_hip_cross_supported(C.byref(cfg)) == 0
 
 
 def iq_tables(params):
@@ -676,6 +691,72 @@ class Spectrogram:
                                                            C.c_void_p(out.data_ptr()), pitch, flags, st),
                "glfer_hip_spectrogram_iq_batch_device")
         return out
+
+    def _cross_outs(self, want, out, lead, nframes, device):
+        """The four outputs of a cross call as (tensors by name, row pitch, sxy pitch): made here, or the caller's (out: a
+        mapping or a Cross tuple of tensors [lead..., nframes, n/2+1] whose row stride may be larger; the float rows share one)."""
+        torch = _torch()
+        want = tuple(want)
+        assert want and all(w in CROSS_FIELDS for w in want), want
+        bins = self.n // 2 + 1
+        shape = tuple(lead) + (nframes, bins)
+        if out is not None and not isinstance(out, dict):
+            out = out._asdict()
+        ts, pitches = {}, {}
+        for name in want:
+            dt = torch.complex64 if name == "sxy" else torch.float32
+            o = None if out is None else out.get(name)
+            if o is None:
+                ts[name], pitches[name] = torch.empty(shape, dtype=dt, device=device), bins
+                continue
+            assert o.is_cuda and o.dtype == dt and tuple(o.shape) == shape, (name, tuple(o.shape), shape)
+            assert o.stride(-1) == 1 or o.size(-1) <= 1
+            pitches[name] = o.stride(-2) if o.size(-2) > 1 else bins
+            assert pitches[name] >= bins
+            if lead and o.size(0) > 1:
+                assert o.stride(0) == nframes * pitches[name], "batch rows lie (b * nframes + i) rows from the first"
+            ts[name] = o
+        rp = {pitches[k] for k in want if k != "sxy"}
+        assert len(rp) <= 1, "sxx, syy and coh share one row pitch"
+        return ts, (rp.pop() if rp else 0), pitches.get("sxy", 0)
+
+    @staticmethod
+    def _cross_ptr(ts, name):
+        return C.c_void_p(ts[name].data_ptr()) if name in ts else None
+
+    def cross(self, xy, first_frame=0, nframes=None, want=("coh", "sxy"), out=None):
+        """xy: [S, 2] float32 / int16 / uint8 (x, y pairs; the dtype is the plan's sample format) or complex64 [S] (x in the real
+        part) on this GPU; the plan is a multitaper one with kmax >= 1.  Returns Cross(sxx, syy, sxy, coh) with None for what
+        `want` does not name: sxx, syy, coh float32 [nframes][n/2+1], sxy complex64 [nframes][n/2+1]; y lagging x by d samples
+        gives angle(sxy[k]) = +2 pi k d / n.  One launch on torch's current stream (glfer_hip_mtm_cross_device)."""
+        torch = _torch()
+        v = self._iq_view(xy, 0)
+        ns = v.size(0)
+        if nframes is None:
+            nframes = self.num_frames(ns) - first_frame
+        ts, pitch, xpitch = self._cross_outs(want, out, (), nframes, v.device)
+        st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+        _check(lib().glfer_hip_mtm_cross_device(self._h, C.c_void_p(v.data_ptr()), ns, first_frame, nframes, self._cross_ptr(ts, "sxx"),
+                                                self._cross_ptr(ts, "syy"), self._cross_ptr(ts, "coh"), pitch,
+                                                self._cross_ptr(ts, "sxy"), xpitch, st), "glfer_hip_mtm_cross_device")
+        return Cross(*(ts.get(k) for k in CROSS_FIELDS))
+
+    def cross_batch(self, xys, first_frame=0, nframes=None, want=("coh", "sxy"), out=None):
+        """xys: [B, S, 2] (or complex64 [B, S]) with a contiguous inner part; stride(0) is the distance between streams.  Returns
+        Cross of [B][nframes][n/2+1] tensors: entry b is what cross(xys[b]) gives (glfer_hip_mtm_cross_batch_device)."""
+        torch = _torch()
+        v = self._iq_view(xys, 1)
+        nb, ns = v.size(0), v.size(1)
+        assert nb <= 1 or v.stride(0) % 2 == 0, v.stride()
+        spitch = v.stride(0) // 2 if nb > 1 else ns
+        if nframes is None:
+            nframes = self.num_frames(ns) - first_frame
+        ts, pitch, xpitch = self._cross_outs(want, out, (nb,), nframes, v.device)
+        st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+        _check(lib().glfer_hip_mtm_cross_batch_device(self._h, C.c_void_p(v.data_ptr()), nb, spitch, ns, first_frame, nframes,
+                                                      self._cross_ptr(ts, "sxx"), self._cross_ptr(ts, "syy"), self._cross_ptr(ts, "coh"),
+                                                      pitch, self._cross_ptr(ts, "sxy"), xpitch, st), "glfer_hip_mtm_cross_batch_device")
+        return Cross(*(ts.get(k) for k in CROSS_FIELDS))
 
     def run_zoom(self, ddc, x, first_frame=0, nframes=None, out=None, centered=False):
         """The two-sided rows of run_iq over ddc.run(x), bit for bit, without the caller holding the baseband: x is what ddc.run

@@ -1,0 +1,42 @@
+/* spectro_cross_params.h -- kernel argument block of spectro16cx.hip (two real channels: multitaper auto- and cross-spectra and
+   their coherence), shared by its launchers and the C-ABI layer.  A block of its own: SpectroParams and IqParams stay as they are,
+   so no other kernel's arguments move. */
+#ifndef GLFER_SPECTRO_CROSS_PARAMS_H
+#define GLFER_SPECTRO_CROSS_PARAMS_H
+
+#include <hip/hip_runtime.h>
+
+struct CrossParams {
+  const void *stream;      /* device: pair 0 of the stream (virtual base), x and y interleaved, f32 / s16 / u8 pairs        */
+  long long frame0;        /* index of this launch's first frame in the whole stream                                       */
+  int nframes;             /* frames in this launch                                                                        */
+  int H;                   /* hop, in sample pairs                                                                         */
+  int R;                   /* N - H pairs of history per frame                                                             */
+  int ntap;                /* tapers: one packed transform each                                                            */
+  int history_mode;        /* 0: zeros before pair 0 only; 1: history zeroed every frame                                   */
+  int fmt;                 /* GLFER_FMT_* of each channel                                                                  */
+  const float *taps;       /* device: the plan's I/Q table (IqParams::taps): v_j sqrt(1 / (N (1 + sig_j))), [ntap][4][N/16][4] */
+  const float2 *tw;        /* device: the plan's per-lane inter-pass twiddles (SpectroParams::tw)                          */
+  float *sxx, *syy, *coh;  /* device: [nframes][row_pitch], the first N/2 + 1 floats of a row are its bins; NULL: not wanted */
+  float2 *sxy;             /* device: [nframes][sxy_pitch] (re, im), N/2 + 1 bins a row; NULL: not wanted                  */
+  long long row_pitch;     /* floats from one row of sxx / syy / coh to the next, >= N/2 + 1                               */
+  long long sxy_pitch;     /* float2 from one row of sxy to the next, >= N/2 + 1                                           */
+  int nbatch;              /* streams in this launch (gridDim.y); 0 or 1: one                                              */
+  long long batch_stride;  /* bytes from one stream's pair 0 to the next one's                                             */
+  long long row_batch_stride;   /* floats from one stream's first row of sxx / syy / coh to the next one's                 */
+  long long sxy_batch_stride;   /* float2 from one stream's first row of sxy to the next one's                             */
+};
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+hipError_t glfer_launch_spectro16cx_n8(const struct CrossParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16cx_n9(const struct CrossParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16cx_n10(const struct CrossParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16cx_n11(const struct CrossParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16cx_n12(const struct CrossParams *p, hipStream_t st);
+hipError_t glfer_launch_spectro16cx_n13(const struct CrossParams *p, hipStream_t st);
+#ifdef __cplusplus
+}
+#endif
+#endif

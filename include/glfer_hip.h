@@ -651,6 +651,49 @@ int glfer_hip_spectrogram_iq_batch_device(glfer_hip_plan *plan, const void *d_iq
                                           size_t nsamples, size_t first_frame, size_t nframes, float *d_psd, size_t row_pitch,
                                           unsigned flags, void *hip_stream);
 
+/* ---- Two channels: multitaper cross-spectrum and coherence in one pass ---------------------------------------------------------
+ * How two receivers relate, bin by bin (two antennas, a loop and a noise probe, the halves of a diversity set-up).  The input is
+ * real samples of two channels, interleaved x[0], y[0], x[1], y[1], ... in cfg.sample_format: the memory layout the I/Q entries
+ * read, and a stereo WAV's.  The plan is GLFER_MODE_MTM with kmax >= 1; frames, hop, history modes, the virtual base and frame
+ * ranges are those of glfer_hip_spectrogram_iq_device, counted in sample pairs.  With X_j = FFT(v_j x_f), Y_j = FFT(v_j y_f) over
+ * the plan's kmax + 1 tapers and c_j = 1 / (N (1 + sig_j)), for k = 0 .. N/2:
+ *   Sxx[k] = sum_j c_j |X_j[k]|^2           the real entry's multitaper row of channel x, to rounding
+ *   Syy[k] = sum_j c_j |Y_j[k]|^2
+ *   Sxy[k] = sum_j c_j X_j[k] conj(Y_j[k])  complex; y lagging x by d samples gives angle(Sxy[k]) = +2 pi k d / N
+ *   coh[k] = |Sxy[k]|^2 / (Sxx[k] Syy[k])   the magnitude-squared coherence: clamped to [0, 1], and exactly 0 where Sxx[k] Syy[k]
+ *                                           is 0 (silence gives zero rows, never NaN); the quotient is formed in double, so
+ *                                           spectra anywhere in float range neither underflow the product nor overflow the square
+ * Im Sxy is exactly 0 at k = 0 and k = N/2.  Thomson's K tapers are what makes coh an estimate from a single frame: with one
+ * window it is identically 1, so GLFER_MODE_FFT plans and kmax = 0 are refused.
+ * Outputs, any subset (NULL: not wanted, not computed for the store; all four NULL is refused), P = N/2 + 1 bins a row:
+ *   d_sxx, d_syy, d_coh : [nframes][row_pitch] floats; row_pitch 0 means P, any other value must be >= P
+ *   d_sxy               : [nframes][sxy_pitch] float pairs (re, im), complex64's layout; sxy_pitch counts pairs, 0 means P
+ *   a batch             : row i of stream b at + (b * nframes + i) rows of each output; stream b's pair 0 at d_xy + b * stream_pitch
+ *                         pairs; d_xy must be aligned to one pair (8, 4 or 2 bytes)
+ * One kernel per call (spectro16cx.hip: one packed transform per taper carries both channels, which are taken apart through the
+ * mirror bins; a batch above the grid's y limit: one per chunk of streams), no allocation, no host synchronisation: legal on a
+ * hip_stream that is being captured.  cfg.psd_pitch is NOT read here.
+ * ACCURACY: both channels ride one transform, so a channel's separated spectrum carries the rounding of the PAIR, not its own.  If
+ * one channel is tens of dB louder, the weaker one's Sxx floor sits at the louder one's rounding level (some 2^-24 of the louder
+ * amplitude per bin) -- the effect README.md records for hn in the paired F-test.  Bring the channels to like level first.
+ * Supported (glfer_hip_cross_supported, host only: GLFER_OK or GLFER_E_ARG): MTM mode, kmax >= 1, N = 256 .. 8192, every overlap,
+ * both history modes, the three sample formats; sub_mean must be 0, the limiter and RA9MB off.
+ * Arguments, nothing on the device touched before they pass: GLFER_E_ARG for a NULL plan or one that is not supported, a pitch
+ * below P; then GLFER_OK with nothing launched for nframes == 0 (nstreams == 0); then GLFER_E_ARG for a NULL d_xy or all four
+ * outputs NULL, a misaligned d_xy, first_frame + nframes wrapping or reaching past the stream, nframes > 0x7fffffff, sizes that
+ * overflow size_t.  Asynchronous on hip_stream.
+ * Not built: N = 16384 (its 1024 lanes a frame leave 128 registers a lane: the twiddles, the transform and the 36 sums do not
+ * fit without spilling), Welch-style averaging of Sxy over frames for FFT plans, a phase row (atan2 of d_sxy gives it), two
+ * separate plane pointers, mean removal, ragged / host / WAV / workers forms, more than two channels (pairs of a C-channel
+ * recording). */
+int glfer_hip_cross_supported(const glfer_hip_config *cfg);
+int glfer_hip_mtm_cross_device(glfer_hip_plan *plan, const void *d_xy, size_t nsamples, size_t first_frame, size_t nframes,
+                               float *d_sxx, float *d_syy, float *d_coh, size_t row_pitch, void *d_sxy, size_t sxy_pitch,
+                               void *hip_stream);
+int glfer_hip_mtm_cross_batch_device(glfer_hip_plan *plan, const void *d_xy, size_t nstreams, size_t stream_pitch, size_t nsamples,
+                                     size_t first_frame, size_t nframes, float *d_sxx, float *d_syy, float *d_coh, size_t row_pitch,
+                                     void *d_sxy, size_t sxy_pitch, void *hip_stream);
+
 /* ---- Zoom: a digital down-converter, and the two-sided rows of its output -------------------------------------------------------
  * A few tens of hertz around one carrier of a 48 kHz recording: instead of a block of a million samples whose transform covers the
  * whole band, the band is moved to 0 Hz, low-passed and decimated by D (a frequency-translating FIR, "DDC"), and the I/Q rows above
