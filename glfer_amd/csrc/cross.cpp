@@ -16,15 +16,8 @@ using glfer::hip_fail;
 static_assert(GLFER_FMT_F32 == GLFER_SAMPLES_F32 && GLFER_FMT_S16 == GLFER_SAMPLES_S16 && GLFER_FMT_U8 == GLFER_SAMPLES_U8, "CrossParams::fmt");
 
 static hipError_t launch_cross(const CrossParams &q, int n, hipStream_t st) {
-  switch (n) {
-    case 256: return glfer_launch_spectro16cx_n8(&q, st);
-    case 512: return glfer_launch_spectro16cx_n9(&q, st);
-    case 1024: return glfer_launch_spectro16cx_n10(&q, st);
-    case 2048: return glfer_launch_spectro16cx_n11(&q, st);
-    case 4096: return glfer_launch_spectro16cx_n12(&q, st);
-    case 8192: return glfer_launch_spectro16cx_n13(&q, st);
-  }
-  return hipErrorInvalidValue;
+  const auto f = launcher16_cx(glfer_logn(n));
+  return f ? f(&q, st) : hipErrorInvalidValue;
 }
 
 extern "C" {

@@ -1000,37 +1000,22 @@ int glfer_hip_make_dpss(int n, int kmax, double nw, double *tapers, double *sig)
 }
 
 extern "C" hipError_t glfer_launch_spectro_small(const SpectroParams *p, int n, const float *staps, hipStream_t st);
-extern "C" hipError_t glfer_launch_spectro16w_n15(const SpectroParams *p, hipStream_t st);
 extern "C" hipError_t glfer_launch_spectro_big(const SpectroParams *p, int n, hipStream_t st);
 
-// a launcher of N = 256 .. 16384 and its ragged twin (the same source compiled with GLFER_RAGGED: the stream from sp.ragged)
-#define GLFER_LAUNCH16(kind, logn, sp) \
-  ((sp).ragged ? glfer_launch_##kind##_ragged_n##logn(&(sp), st) : glfer_launch_##kind##_n##logn(&(sp), st))
+// a launcher of N = 256 .. 16384 out of the table of built launchers (spectro_params.h), or its ragged twin (the same source
+// compiled with GLFER_RAGGED: the stream from sp.ragged); nothing built for this kind and size: hipErrorInvalidValue
+static hipError_t launch16(glfer_kind16 kind, const SpectroParams &sp, int n, hipStream_t st) {
+  const glfer_launcher16_fn f = launcher16(kind, glfer_logn(n), sp.ragged != nullptr);
+  return f ? f(&sp, st) : hipErrorInvalidValue;
+}
 
 static hipError_t launch_packed(const SpectroParams &sp, int n, hipStream_t st) {
   if (n < 256) return glfer_launch_spectro_small(&sp, n, sp.taps, st);   // the same role below the 16-points-per-lane range
-  switch (n) {
-    case 256: return GLFER_LAUNCH16(spectro16, 8, sp);
-    case 512: return GLFER_LAUNCH16(spectro16, 9, sp);
-    case 1024: return GLFER_LAUNCH16(spectro16, 10, sp);
-    case 2048: return GLFER_LAUNCH16(spectro16, 11, sp);
-    case 4096: return GLFER_LAUNCH16(spectro16, 12, sp);
-    case 8192: return GLFER_LAUNCH16(spectro16, 13, sp);
-    case 16384: return GLFER_LAUNCH16(spectro16, 14, sp);
-  }
-  return hipErrorInvalidValue;
+  return launch16(GLFER_KIND_spectro16, sp, n, st);
 }
 
 static hipError_t launch_real_input(const SpectroParams &sp, int n, hipStream_t st) {
-  switch (n) {
-    case 512: return GLFER_LAUNCH16(spectro16h, 9, sp);
-    case 1024: return GLFER_LAUNCH16(spectro16h, 10, sp);
-    case 2048: return GLFER_LAUNCH16(spectro16h, 11, sp);
-    case 4096: return GLFER_LAUNCH16(spectro16h, 12, sp);
-    case 8192: return GLFER_LAUNCH16(spectro16h, 13, sp);
-    case 16384: return GLFER_LAUNCH16(spectro16h, 14, sp);
-  }
-  return hipErrorInvalidValue;
+  return launch16(GLFER_KIND_spectro16h, sp, n, st);
 }
 
 // measured defaults: where spectro16w.hip is the faster form (profiles/r02_form_size_sweep.txt: the
@@ -1043,18 +1028,12 @@ static hipError_t launch_real_input(const SpectroParams &sp, int n, hipStream_t 
 static int form_override();
 
 static hipError_t launch_wave_private(const SpectroParams &sp, int n, hipStream_t st) {
-  switch (n) {
-    case 2048: return GLFER_LAUNCH16(spectro16w, 11, sp);
-    case 4096: return GLFER_LAUNCH16(spectro16w, 12, sp);
-    case 8192: return GLFER_LAUNCH16(spectro16w, 13, sp);
-    case 16384: return GLFER_LAUNCH16(spectro16w, 14, sp);
-    // N = 32768: the two-kernel form is the faster one (profiles/r02_big_blocks.txt); spectro16w.hip's single-kernel
-    // form keeps the halfcomplex spectrum output and GLFER_FORM=w
-    case 32768: return (sp.spec || form_override() == 'w') ? glfer_launch_spectro16w_n15(&sp, st) : glfer_launch_spectro_big(&sp, n, st);
-    case 65536: return glfer_launch_spectro_big(&sp, n, st);
-  }
+  // N = 32768: the two-kernel form is the faster one (profiles/r02_big_blocks.txt); spectro16w.hip's single-kernel
+  // form keeps the halfcomplex spectrum output and GLFER_FORM=w
+  if (n == 32768) return (sp.spec || form_override() == 'w') ? glfer_launch_spectro16w_n15(&sp, st) : glfer_launch_spectro_big(&sp, n, st);
+  if (n == 65536) return glfer_launch_spectro_big(&sp, n, st);
   if (n >= 131072 && n <= (1 << 20)) return glfer_launch_spectro_big(&sp, n, st);   // two-level combine (round 3)
-  return hipErrorInvalidValue;
+  return launch16(GLFER_KIND_spectro16w, sp, n, st);
 }
 
 // Which form takes a configuration is a measured choice (profiles/r02_*): GLFER_FORM=h|w|x in the
@@ -1090,18 +1069,18 @@ static int y_queue_chunk() {
 static hipError_t launch_y(SpectroParams &q, hipStream_t st) {
   q.yq_counter = nullptr;
   glfer_yqueue *yq = q.yq;
-  if (!yq || q.mean_inkernel || q.nbatch > 1 || y_queue_off() || st == hipStreamPerThread) return GLFER_LAUNCH16(spectro16y, 12, q);
+  if (!yq || q.mean_inkernel || q.nbatch > 1 || y_queue_off() || st == hipStreamPerThread) return launch16(GLFER_KIND_spectro16y, q, 4096, st);
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
     (void)hipGetLastError();
-    return GLFER_LAUNCH16(spectro16y, 12, q);
+    return launch16(GLFER_KIND_spectro16y, q, 4096, st);
   }
-  if (cs != hipStreamCaptureStatusNone) return GLFER_LAUNCH16(spectro16y, 12, q);
+  if (cs != hipStreamCaptureStatusNone) return launch16(GLFER_KIND_spectro16y, q, 4096, st);
   std::lock_guard<std::mutex> lock(yq->mu);
   int slot = 0;
   while (slot < yq->used && yq->owner[slot] != st) slot++;
   if (slot == yq->used) {
-    if (slot == glfer_yqueue::SLOTS) return GLFER_LAUNCH16(spectro16y, 12, q);
+    if (slot == glfer_yqueue::SLOTS) return launch16(GLFER_KIND_spectro16y, q, 4096, st);
     yq->owner[yq->used++] = st;
   }
   q.yq_counter = yq->d_counters + (size_t)slot * glfer_yqueue::PITCH;
@@ -1119,19 +1098,9 @@ static hipError_t launch_shared_odd(const SpectroParams &sp, int n, hipStream_t 
     return launch_y(q, st);
   }
   if (sp.ltaps) {                      // taper half tables resident in LDS
-    switch (n) {
-      case 256: return GLFER_LAUNCH16(spectro16xl, 8, sp);
-      case 512: return GLFER_LAUNCH16(spectro16xl, 9, sp);
-      case 1024: return GLFER_LAUNCH16(spectro16xl, 10, sp);
-      case 2048: return GLFER_LAUNCH16(spectro16xl, 11, sp);
-    }
+    if (const glfer_launcher16_fn f = launcher16(GLFER_KIND_spectro16xl, glfer_logn(n), sp.ragged != nullptr)) return f(&sp, st);
   }
-  switch (n) {
-    case 256: return GLFER_LAUNCH16(spectro16x, 8, sp);
-    case 512: return GLFER_LAUNCH16(spectro16x, 9, sp);
-    case 1024: return GLFER_LAUNCH16(spectro16x, 10, sp);
-  }
-  return hipErrorInvalidValue;
+  return launch16(GLFER_KIND_spectro16x, sp, n, st);
 }
 
 // Kernel choice.  spectro16.hip (two tapers packed per N-point transform) does everything; two
@@ -1785,16 +1754,8 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
 // ---- complex I/Q input (glfer_hip.h): two-sided rows of N bins, spectro16c.hip ---------------------------------------------------
 
 static hipError_t launch_iq(const IqParams &q, int n, hipStream_t st) {
-  switch (n) {
-    case 256: return glfer_launch_spectro16c_n8(&q, st);
-    case 512: return glfer_launch_spectro16c_n9(&q, st);
-    case 1024: return glfer_launch_spectro16c_n10(&q, st);
-    case 2048: return glfer_launch_spectro16c_n11(&q, st);
-    case 4096: return glfer_launch_spectro16c_n12(&q, st);
-    case 8192: return glfer_launch_spectro16c_n13(&q, st);
-    case 16384: return glfer_launch_spectro16c_n14(&q, st);
-  }
-  return hipErrorInvalidValue;
+  const auto f = launcher16_iq(glfer_logn(n));
+  return f ? f(&q, st) : hipErrorInvalidValue;
 }
 
 int glfer_hip_spectrogram_iq_batch_device(glfer_hip_plan *p, const void *d_iq, size_t nstreams, size_t stream_pitch, size_t nsamples,

@@ -623,6 +623,7 @@ __global__ __launch_bounds__(256) void submean_tail_kernel(const void *raw_last,
 // host-side launchers (called from glfer_hip.cpp).  One translation unit per LOGN
 // (-DGLFER_LOGN=...) so the size variants compile in parallel.
 #ifndef GLFER_NO_LAUNCHERS
+#include "launch16.hpp"
 using namespace glfer;
 
 #ifndef GLFER_LOGN
@@ -641,10 +642,8 @@ static hipError_t launch16_fmt(const SpectroParams &p, hipStream_t st) {
   // the general path (limiter, RA9MB, spectrum output) at two wavefronts per SIMD whatever the size: at three it spills 113-123 VGPRs
   // (N = 4096) and runs at 30-36 M frames/s against 50 (N = 512: 328 against 425) -- tools/packed_rate.py, round 4
   const int wps = (p.nonlin || p.spec) && !p.ftest && !p.mean_inkernel ? 2 : GLFER16_WAVES_PER_SIMD;
-  const long long resident = 256LL * ((wps * 256) / LC::BLOCK > 0 ? (wps * 256) / LC::BLOCK : 1);
-  const long long cap = glfer_batch_cap(4 * resident, p.nbatch);   // (a batch shares it among its streams)
-  unsigned grid = (unsigned)(work < cap ? work : cap);
-  if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
+  const long long resident = resident_workgroups(wps, LC::BLOCK);
+  const dim3 grid = batch_grid(persistent_grid(work, glfer_batch_cap(4 * resident, p.nbatch)), p), block(LC::BLOCK);
   if (p.ftest) {
     // the F statistic: one taper per round (two spill-free wavefronts per SIMD: mu and the sums are 48 more registers)
     if (p.nonlin || p.spec || p.mean_inkernel || !p.ft_U0) return hipErrorInvalidValue;
@@ -652,82 +651,60 @@ static hipError_t launch16_fmt(const SpectroParams &p, hipStream_t st) {
     if (p.psd) {
       // the multitaper rows beside F (glfer_hip_mtm_rows_ftest_device): nine more registers a lane for the rows' sums
       if (!p.ft_cj) return hipErrorInvalidValue;
-      if (p.ft_nseq > 0) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_ROWS_PAIRED_WPS, GLFER16_STAGGER, 0, 2, BAT, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1, BAT, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      return hipGetLastError();
+      if (p.ft_nseq > 0) return launch(spectro16_kernel<L, FMT, false, GLFER16_ROWS_PAIRED_WPS, GLFER16_STAGGER, 0, 2, BAT, 1>, grid, block, 0, st, p);
+      return launch(spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1, BAT, 1>, grid, block, 0, st, p);
     }
-    if (p.ft_nseq > 0) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 3, GLFER16_STAGGER, 0, 2, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    return hipGetLastError();
+    if (p.ft_nseq > 0) return launch(spectro16_kernel<L, FMT, false, 3, GLFER16_STAGGER, 0, 2, BAT>, grid, block, 0, st, p);
+    return launch(spectro16_kernel<L, FMT, false, 2, GLFER16_STAGGER, 0, 1, BAT>, grid, block, 0, st, p);
   }
   if (p.mean_inkernel) {
     // frames inside the stream only, history from the stream, a hop of 4, 8 or 16 sixteenths of the block
     if (p.nonlin || p.spec || p.history_mode || p.frame0 * (long long)p.H < (long long)p.R) return hipErrorInvalidValue;
-    const int km = (16 * p.H) % (1 << L) == 0 ? (16 * p.H) >> L : 0;
-    if (km == 16) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 16, 0, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else if (km == 8) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 8, 0, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else if (km == 4) hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 4, 0, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_value<16, 8, 4>(hop_sixteenths<L>(p.H), [&](auto K) {
+      return launch(spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, K(), 0, BAT>, grid, block, 0, st, p);
+    });
   }
-  if (p.nonlin || p.spec)
-    hipLaunchKernelGGL((spectro16_kernel<L, FMT, true, 2, GLFER16_STAGGER, 0, 0, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-  else
-    hipLaunchKernelGGL((spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 0, 0, BAT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-  return hipGetLastError();
+  if (p.nonlin || p.spec) return launch(spectro16_kernel<L, FMT, true, 2, GLFER16_STAGGER, 0, 0, BAT>, grid, block, 0, st, p);
+  return launch(spectro16_kernel<L, FMT, false, GLFER16_WAVES_PER_SIMD, GLFER16_STAGGER, 0, 0, BAT>, grid, block, 0, st, p);
 }
 
 extern "C" hipError_t GLFER_CAT(glfer_launch_spectro16_n, GLFER_LOGN)(const SpectroParams *p, hipStream_t st) {
 #ifdef GLFER_RAGGED
   if (!p->ragged || p->nbatch < 2) return hipErrorInvalidValue;
-  switch (p->fmt) {
-    case GLFER_FMT_F32: return launch16_fmt<GLFER_FMT_F32, 1>(*p, st);
-    case GLFER_FMT_S16: return launch16_fmt<GLFER_FMT_S16, 1>(*p, st);
-    case GLFER_FMT_U8: return launch16_fmt<GLFER_FMT_U8, 1>(*p, st);
-  }
-  return hipErrorInvalidValue;
+  return with_fmt(p->fmt, [&](auto F) { return launch16_fmt<F(), 1>(*p, st); });
 #else
-  switch (p->fmt) {
-    case GLFER_FMT_F32: return p->nbatch > 1 ? launch16_fmt<GLFER_FMT_F32, 1>(*p, st) : launch16_fmt<GLFER_FMT_F32, 0>(*p, st);
-    case GLFER_FMT_S16: return p->nbatch > 1 ? launch16_fmt<GLFER_FMT_S16, 1>(*p, st) : launch16_fmt<GLFER_FMT_S16, 0>(*p, st);
-    case GLFER_FMT_U8: return p->nbatch > 1 ? launch16_fmt<GLFER_FMT_U8, 1>(*p, st) : launch16_fmt<GLFER_FMT_U8, 0>(*p, st);
-  }
-  return hipErrorInvalidValue;
+  return with_fmt(p->fmt, [&](auto F) { return p->nbatch > 1 ? launch16_fmt<F(), 1>(*p, st) : launch16_fmt<F(), 0>(*p, st); });
 #endif
 }
 
 #if GLFER_LOGN == 12 && !defined(GLFER_RAGGED)
+// The corrected copy over nb streams, RAG = 0: equal streams on strides; RAG = 1: unequal ones, `in` the device table of
+// GlferRaggedHops and `means` a flag (the entry holds the pointer).  Hops up to 16384 samples are held in registers (a
+// wavefront per hop up to 1024 samples, a workgroup above), E values a lane; longer ones go through submean_kernel.
+template <int RAG>
+static hipError_t launch_submean_any(const void *in, float *out, int H, long long nhops, int fmt, hipStream_t st, const float *means,
+                                     unsigned nb, long long in_bstride, long long out_bstride, long long means_bstride) {
+  return with_fmt(fmt, [&](auto F) {
+    auto reg = [&](auto G, auto E) {
+      const unsigned grid = G() == 64 ? (unsigned)((nhops + 3) / 4) : (unsigned)nhops;
+      return launch(submean_reg_kernel<F(), G(), E(), RAG>, dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride);
+    };
+    using G64 = std::integral_constant<int, 64>;
+    using G256 = std::integral_constant<int, 256>;
+    const int e64 = H <= 64 * 2 ? 2 : H <= 64 * 4 ? 4 : H <= 64 * 8 ? 8 : H <= 64 * 16 ? 16 : 0;
+    if (e64) return with_value<2, 4, 8, 16>(e64, [&](auto E) { return reg(G64{}, E); });
+    const int e256 = H <= 256 * 8 ? 8 : H <= 256 * 16 ? 16 : H <= 256 * 32 ? 32 : H <= 256 * 64 ? 64 : 0;
+    if (e256) return with_value<8, 16, 32, 64>(e256, [&](auto E) { return reg(G256{}, E); });
+    return launch(submean_kernel<F(), RAG>, dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride);
+  });
+}
+
 extern "C" hipError_t glfer_launch_submean_batch(const void *in, float *out, int H, long long nhops, int fmt, hipStream_t st,
                                                  const float *means, unsigned nb, long long in_bstride, long long out_bstride,
                                                  long long means_bstride) {
   if (nhops <= 0 || nb == 0) return hipSuccess;
   if (nb > 65535) return hipErrorInvalidValue;
-  if (fmt != GLFER_FMT_F32 && fmt != GLFER_FMT_S16 && fmt != GLFER_FMT_U8) return hipErrorInvalidValue;
-  // hops up to 16384 samples: held in registers (a wavefront per hop up to 1024 samples, a workgroup above)
-#define GLFER_SUBMEAN_REG(G, E)                                                                                     \
-  do {                                                                                                              \
-    const unsigned grid = G == 64 ? (unsigned)((nhops + 3) / 4) : (unsigned)nhops;                                  \
-    if (fmt == GLFER_FMT_F32) hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_F32, G, E>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); \
-    else if (fmt == GLFER_FMT_S16) hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_S16, G, E>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); \
-    else hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_U8, G, E>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); \
-    return hipGetLastError();                                                                                       \
-  } while (0)
-  if (H <= 64 * 2) GLFER_SUBMEAN_REG(64, 2);
-  if (H <= 64 * 4) GLFER_SUBMEAN_REG(64, 4);
-  if (H <= 64 * 8) GLFER_SUBMEAN_REG(64, 8);
-  if (H <= 64 * 16) GLFER_SUBMEAN_REG(64, 16);
-  if (H <= 256 * 8) GLFER_SUBMEAN_REG(256, 8);
-  if (H <= 256 * 16) GLFER_SUBMEAN_REG(256, 16);
-  if (H <= 256 * 32) GLFER_SUBMEAN_REG(256, 32);
-  if (H <= 256 * 64) GLFER_SUBMEAN_REG(256, 64);
-#undef GLFER_SUBMEAN_REG
-  switch (fmt) {
-    case GLFER_FMT_F32: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_F32>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); break;
-    case GLFER_FMT_S16: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_S16>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); break;
-    case GLFER_FMT_U8: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_U8>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, in_bstride, out_bstride, means_bstride); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return launch_submean_any<0>(in, out, H, nhops, fmt, st, means, nb, in_bstride, out_bstride, means_bstride);
 }
 
 // the same over nb streams of unequal length (tab: device, one entry per stream; max_nhops: the longest): the kernel the hop
@@ -736,34 +713,8 @@ extern "C" hipError_t glfer_launch_submean_ragged(const GlferRaggedHops *tab, un
                                                   int with_means, hipStream_t st) {
   if (max_nhops <= 0 || nb == 0) return hipSuccess;
   if (nb > 65535 || !tab) return hipErrorInvalidValue;
-  if (fmt != GLFER_FMT_F32 && fmt != GLFER_FMT_S16 && fmt != GLFER_FMT_U8) return hipErrorInvalidValue;
-  const void *in = tab;
-  float *const out = nullptr;
   const float *const means = with_means ? reinterpret_cast<const float *>(tab) : nullptr;   // (a flag: the entry holds the pointer)
-  const long long nhops = max_nhops;
-#define GLFER_SUBMEAN_REG(G, E)                                                                                     \
-  do {                                                                                                              \
-    const unsigned grid = G == 64 ? (unsigned)((nhops + 3) / 4) : (unsigned)nhops;                                  \
-    if (fmt == GLFER_FMT_F32) hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_F32, G, E, 1>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); \
-    else if (fmt == GLFER_FMT_S16) hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_S16, G, E, 1>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); \
-    else hipLaunchKernelGGL((submean_reg_kernel<GLFER_FMT_U8, G, E, 1>), dim3(grid, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); \
-    return hipGetLastError();                                                                                       \
-  } while (0)
-  if (H <= 64 * 2) GLFER_SUBMEAN_REG(64, 2);
-  if (H <= 64 * 4) GLFER_SUBMEAN_REG(64, 4);
-  if (H <= 64 * 8) GLFER_SUBMEAN_REG(64, 8);
-  if (H <= 64 * 16) GLFER_SUBMEAN_REG(64, 16);
-  if (H <= 256 * 8) GLFER_SUBMEAN_REG(256, 8);
-  if (H <= 256 * 16) GLFER_SUBMEAN_REG(256, 16);
-  if (H <= 256 * 32) GLFER_SUBMEAN_REG(256, 32);
-  if (H <= 256 * 64) GLFER_SUBMEAN_REG(256, 64);
-#undef GLFER_SUBMEAN_REG
-  switch (fmt) {
-    case GLFER_FMT_F32: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_F32, 1>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); break;
-    case GLFER_FMT_S16: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_S16, 1>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); break;
-    default: hipLaunchKernelGGL((submean_kernel<GLFER_FMT_U8, 1>), dim3((unsigned)nhops, nb), dim3(256), 0, st, in, out, H, nhops, means, 0LL, 0LL, 0LL); break;
-  }
-  return hipGetLastError();
+  return launch_submean_any<1>(tab, nullptr, H, max_nhops, fmt, st, means, nb, 0LL, 0LL, 0LL);
 }
 
 extern "C" hipError_t glfer_launch_submean(const void *in, float *out, int H, long long nhops, int fmt,
@@ -773,13 +724,7 @@ extern "C" hipError_t glfer_launch_submean(const void *in, float *out, int H, lo
 
 extern "C" hipError_t glfer_launch_submean_tail_ex(const void *raw_last, const float *prev, float *out, int H, int fresh, int exact,
                                                 int fmt, hipStream_t st) {
-  switch (fmt) {
-    case GLFER_FMT_F32: hipLaunchKernelGGL((submean_tail_kernel<GLFER_FMT_F32>), dim3(1), dim3(256), 0, st, raw_last, prev, out, H, fresh, exact); break;
-    case GLFER_FMT_S16: hipLaunchKernelGGL((submean_tail_kernel<GLFER_FMT_S16>), dim3(1), dim3(256), 0, st, raw_last, prev, out, H, fresh, exact); break;
-    case GLFER_FMT_U8: hipLaunchKernelGGL((submean_tail_kernel<GLFER_FMT_U8>), dim3(1), dim3(256), 0, st, raw_last, prev, out, H, fresh, exact); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_fmt(fmt, [&](auto F) { return launch(submean_tail_kernel<F()>, dim3(1), dim3(256), 0, st, raw_last, prev, out, H, fresh, exact); });
 }
 #endif
 #endif  // GLFER_NO_LAUNCHERS

@@ -336,6 +336,7 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel
 
 // ---------------------------------------------------------------------------
 // host-side launcher (called from cross.cpp).  One translation unit per LOGN (-DGLFER_LOGN=...).
+#include "launch16.hpp"
 using namespace glfer;
 
 #if !defined(GLFER_LOGN) || GLFER_LOGN < 8 || GLFER_LOGN > 13
@@ -351,20 +352,11 @@ static hipError_t launch16cx_fmt(const CrossParams &p, hipStream_t st) {
   // persistent blocks, spectro16.hip's shape: enough to fill every CU at the kernel's occupancy, never more than the work
   const long long work = ((long long)p.nframes + LC::FPB - 1) / LC::FPB;
   if (work <= 0 || p.ntap <= 0) return hipSuccess;
-  const long long resident = 256LL * ((GLFER16CX_WAVES_PER_SIMD * 256) / LC::BLOCK > 0 ? (GLFER16CX_WAVES_PER_SIMD * 256) / LC::BLOCK : 1);
-  const long long cap = glfer_batch_cap(4 * resident, p.nbatch);   // (a batch shares it among its streams)
-  unsigned grid = (unsigned)(work < cap ? work : cap);
-  if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
-  const unsigned ny = p.nbatch > 1 ? (unsigned)p.nbatch : 1u;
-  hipLaunchKernelGGL((spectro16cx_kernel<L, FMT, BAT>), dim3(grid, ny), dim3(LC::BLOCK), 0, st, p);
-  return hipGetLastError();
+  const long long resident = resident_workgroups(GLFER16CX_WAVES_PER_SIMD, LC::BLOCK);
+  const unsigned grid = persistent_grid(work, glfer_batch_cap(4 * resident, p.nbatch));
+  return launch(spectro16cx_kernel<L, FMT, BAT>, batch_grid(grid, p), dim3(LC::BLOCK), 0, st, p);
 }
 
 extern "C" hipError_t GLFER_CAT(glfer_launch_spectro16cx_n, GLFER_LOGN)(const CrossParams *p, hipStream_t st) {
-  switch (p->fmt) {
-    case GLFER_FMT_F32: return p->nbatch > 1 ? launch16cx_fmt<GLFER_FMT_F32, 1>(*p, st) : launch16cx_fmt<GLFER_FMT_F32, 0>(*p, st);
-    case GLFER_FMT_S16: return p->nbatch > 1 ? launch16cx_fmt<GLFER_FMT_S16, 1>(*p, st) : launch16cx_fmt<GLFER_FMT_S16, 0>(*p, st);
-    case GLFER_FMT_U8: return p->nbatch > 1 ? launch16cx_fmt<GLFER_FMT_U8, 1>(*p, st) : launch16cx_fmt<GLFER_FMT_U8, 0>(*p, st);
-  }
-  return hipErrorInvalidValue;
+  return with_fmt(p->fmt, [&](auto F) { return p->nbatch > 1 ? launch16cx_fmt<F(), 1>(*p, st) : launch16cx_fmt<F(), 0>(*p, st); });
 }

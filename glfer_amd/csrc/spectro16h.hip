@@ -1019,6 +1019,7 @@ __global__ __launch_bounds__(LaunchH<LOGN>::BLOCK, WPS) void spectro16h_kernel(S
 }  // namespace glfer
 
 #ifndef GLFER_NO_LAUNCHERS
+#include "launch16.hpp"
 using namespace glfer;
 
 #ifndef GLFER_LOGN
@@ -1037,27 +1038,33 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
 #ifdef GLFER_RAGGED
   if (!p.ragged || p.nbatch < 2) return hipErrorInvalidValue;
 #endif
-  const long long per_cu = (GLFER16H_WAVES_PER_SIMD * 256) / LC::BLOCK > 0 ? (GLFER16H_WAVES_PER_SIMD * 256) / LC::BLOCK : 1;
-  const long long resident = 256LL * per_cu;
+  const long long resident = resident_workgroups(GLFER16H_WAVES_PER_SIMD, LC::BLOCK);
   const long long cap = glfer_batch_cap(8 * resident, p.nbatch);   // (a batch shares it among its streams)
-  unsigned grid = (unsigned)(work < cap ? work : cap);   // tools/hbench: 8x beats 4x by ~2 % with contiguous ranges
-  if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
+  unsigned grid = persistent_grid(work, cap);      // tools/hbench: 8x beats 4x by ~2 % with contiguous ranges
+  const int k16 = hop_sixteenths<L>(p.H);          // the hop in a lane's 16 sample registers (0: no whole number of them)
+  // every launch of this file: gx workgroups a stream, the argument block q
+  auto go = [&](auto kernel, unsigned gx, const SpectroParams &q) { return launch(kernel, batch_grid(gx, p), dim3(LC::BLOCK), 0, st, q); };
+  // The mean-removal ladders over the hop.  2, 4, 8 sixteenths: SHIFT = the hop, a slot keeps the rest of its registers and walks
+  // consecutive frames on the grid `walk`.  Hop = frame (16): nothing to keep, SHIFT = 0 on the grid `whole`.  Any other: refused.
+  [[maybe_unused]] auto by_hop = [&](unsigned whole, unsigned walk, auto &&f) {
+    return with_value<16, 2, 4, 8>(k16, [&](auto K) {
+      constexpr int SH = K() == 16 ? 0 : K();
+      return f(std::integral_constant<int, SH>{}, SH == 0 ? whole : walk);
+    });
+  };
 #if GLFER_LOGN >= 13
   if (p.htapers > 1) {
     if (p.mean_inkernel) {                          // hop = 16, 8 or 4 of a lane's register pairs (overlap 0, 50, 75 %): the hops' means before the frame's first taper
-      const int km = (16 * p.H) % (1 << L) == 0 ? 16 * p.H / (1 << L) : 0;
       if (p.history_mode) return hipErrorInvalidValue;
       // (two wavefronts per SIMD: at three the hop means push the multitaper loop into spills, 152 B of scratch per lane)
       constexpr int W2 = GLFER16H_WAVES_PER_SIMD > 2 ? 2 : GLFER16H_WAVES_PER_SIMD;
-      if (km == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W2, 1, 1, 0, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W2, 1, 1, 0, 0, 8>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W2, 1, 1, 0, 0, 4>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else return hipErrorInvalidValue;
-      return hipGetLastError();
+      return with_value<16, 8, 4>(k16, [&](auto K) {
+        constexpr int MEAN = K() == 16 ? 1 : K();     // (the whole frame is one hop: plain mean removal)
+        return go(spectro16h_kernel<L, FMT, W2, 1, 1, 0, 0, MEAN>, grid, p);
+      });
     }
-    if (p.history_mode) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, 1, 1, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, 1, 1, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    return hipGetLastError();
+    if (p.history_mode) return go(spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, 1, 1, 1>, grid, p);
+    return go(spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, 1, 1, 0>, grid, p);
   }
 #endif
   if (p.htapers > 1) return hipErrorInvalidValue;      // the multitaper form is built for N >= 8192 only
@@ -1066,47 +1073,22 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
     // update_avg_plain inside the kernel: two wavefronts per SIMD, every slot walks consecutive frames and recomputes the
     // depth-1 frames in front of its range -- so a slot gets >= 32 frames where the launch is long enough (3 lead frames: < 10 %)
     if (p.history_mode || (p.mean_inkernel && !p.means) || p.nprod || p.avg_depth < 1 || p.avg_depth > 4 || p.avg_nout < (1 << (L - 1)) + 1) return hipErrorInvalidValue;
-    const long long per_cu2 = (2 * 256) / LC::BLOCK > 0 ? (2 * 256) / LC::BLOCK : 1;
     static const long long mult = [] { const char *e = getenv("GLFER_AVG_GRID_MULT"); const long v = e && *e ? atol(e) : 4; return (long long)(v < 1 ? 1 : v); }();
-    const long long cap = glfer_batch_cap(mult * 256LL * per_cu2, p.nbatch), want = work / 32 > 0 ? work / 32 : 1;   // (a batch shares the cap)
-    unsigned ga = (unsigned)(want < cap ? want : cap);
-    if (ga >= 64) ga &= ~7u;
-    const int k16 = (16 * p.H) % (1 << L) == 0 ? (16 * p.H) >> L : 0;
-    if (p.nbatch > 1) {                              // a batch (glfer_hip_spectrogram_avg_batch_device): the AVG = 2 instantiations
-      const int mt = p.mean_inkernel ? 1 : 0;
-      if (mt && k16 != 2 && k16 != 4 && k16 != 8 && k16 != 16) return hipErrorInvalidValue;
-      const int sh = (k16 == 2 || k16 == 4 || k16 == 8) ? k16 : 0;
-#define GLFER16H_AVG_BATCH(SH, M)                                                                                              \
-  hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, SH, M, M, 2>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p)
-      if (mt) {
-        if (sh == 2) GLFER16H_AVG_BATCH(2, 1);
-        else if (sh == 4) GLFER16H_AVG_BATCH(4, 1);
-        else if (sh == 8) GLFER16H_AVG_BATCH(8, 1);
-        else GLFER16H_AVG_BATCH(0, 1);
-      } else {
-        if (sh == 2) GLFER16H_AVG_BATCH(2, 0);
-        else if (sh == 4) GLFER16H_AVG_BATCH(4, 0);
-        else if (sh == 8) GLFER16H_AVG_BATCH(8, 0);
-        else GLFER16H_AVG_BATCH(0, 0);
-      }
-#undef GLFER16H_AVG_BATCH
-      return hipGetLastError();
-    }
-    if (p.mean_inkernel) {
-      // the reference's default (sub_mean = opt.autoscale) with the means GIVEN (taken in its own order by hop_means_seq_kernel): the
-      // table form's in-place correction in front of the same averaging block
-      if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 2, 1, 1, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 4, 1, 1, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 8, 1, 1, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 0, 1, 1, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else return hipErrorInvalidValue;
-      return hipGetLastError();
-    }
-    if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 2, 0, 0, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 4, 0, 0, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 8, 0, 0, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 0, 0, 0, 1>), dim3(ga, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);   // any other hop: every frame loaded whole
-    return hipGetLastError();
+    const long long cap = glfer_batch_cap(mult * resident_workgroups(2, LC::BLOCK), p.nbatch);   // (a batch shares the cap)
+    const unsigned ga = persistent_grid(work / 32 > 0 ? work / 32 : 1, cap);
+    // MEAN = MTAB = 1: the reference's default (sub_mean = opt.autoscale) with the means GIVEN (taken in its own order by
+    // hop_means_seq_kernel), the table form's in-place correction in front of the same averaging block -- and then the hop must be
+    // 2, 4, 8 or 16 sixteenths.  Without mean removal any other hop loads every frame whole (SHIFT = 0), as hop = frame does.
+    const int mt = p.mean_inkernel ? 1 : 0;
+    if (mt && k16 != 2 && k16 != 4 && k16 != 8 && k16 != 16) return hipErrorInvalidValue;
+    const int sh = (k16 == 2 || k16 == 4 || k16 == 8) ? k16 : 0;
+    return with_value<2, 4, 8, 0>(sh, [&](auto SH) {
+      return with_value<0, 1>(mt, [&](auto M) {
+        // a batch (glfer_hip_spectrogram_avg_batch_device): the AVG = 2 instantiations
+        if (p.nbatch > 1) return go(spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, SH(), M(), M(), 2>, ga, p);
+        return go(spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, SH(), M(), M(), 1>, ga, p);
+      });
+    });
 #else
     return hipErrorInvalidValue;
 #endif
@@ -1116,8 +1098,7 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
 #else
   if (p.history_mode) {
     if (p.mean_inkernel) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    return hipGetLastError();
+    return go(spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 1>, grid, p);
   }
 #if GLFER16H_SHIFT_BUILDS
   if (p.mean_inkernel) {
@@ -1126,9 +1107,7 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
     // (two wavefronts per SIMD: at three the hop means and their sums push the loop into spills, and the
     // periodogram runs as fast at two -- profiles/r02_register_reuse_ab.txt)
     constexpr int kMeanWps = GLFER16H_WAVES_PER_SIMD > 2 ? 2 : GLFER16H_WAVES_PER_SIMD;
-    const int k16 = (16 * p.H) % (1 << L) == 0 ? (16 * p.H) >> L : 0;
-    unsigned g = (unsigned)(work / 4 < 8 * resident ? (work / 4 ? work / 4 : 1) : 8 * resident);
-    if (g >= 64) g &= ~7u;
+    unsigned g = xcd_slices((unsigned)(work / 4 < 8 * resident ? (work / 4 ? work / 4 : 1) : 8 * resident));
     if (p.means) {                                   // the means are given: the table form, at the plain form's occupancy
       constexpr int W = GLFER16H_WAVES_PER_SIMD;
       if (p.nprod > 0 && p.prod_front_frames < 0) {
@@ -1143,13 +1122,7 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
         q.prod_front_frames = (gc / 8) * per * LC::FPB;
         q.prod_look = 96 * q.prod_block_frames + p.prod_look;       // what a front's resident consumers span (3 workgroups x 32 CUs an XCD) + the margin asked for
         const unsigned gl = (unsigned)(gc + p.nprod);
-        constexpr int WL = GLFER16H_WAVES_PER_SIMD;
-        if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 0, 1, 1>), dim3(gl, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, q);
-        else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 2, 1, 1>), dim3(gl, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, q);
-        else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 4, 1, 1>), dim3(gl, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, q);
-        else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, WL, GLFER16H_VAR, 0, 0, 8, 1, 1>), dim3(gl, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, q);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
+        return by_hop(gl, gl, [&](auto SH, unsigned gx) { return go(spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, SH(), 1, 1>, gx, q); });
       }
       if (p.nprod > 0) {                             // the fused launch: producers in front of the grid as it would have been
         if (p.nprod & 7) return hipErrorInvalidValue;
@@ -1160,28 +1133,12 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
       // GLFER_MTAB_WPS=2 (experiment, profiles/r04_piecewise_means.txt): two wavefronts per SIMD, so that a hop-means launch of the
       // NEXT piece (side stream) finds registers and LDS beside this one
       static const bool two = [] { const char *e = getenv("GLFER_MTAB_WPS"); return e && *e == '2'; }();
-      if (two && W > 2) {
-        if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 0, 1, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-        else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 2, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-        else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 4, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-        else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, 8, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-      }
+      if (two && W > 2)
+        return by_hop(grid, g, [&](auto SH, unsigned gx) { return go(spectro16h_kernel<L, FMT, 2, GLFER16H_VAR, 0, 0, SH(), 1, 1>, gx, p); });
 #endif
-      if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 0, 1, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 2, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 4, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, 8, 1, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else return hipErrorInvalidValue;
-      return hipGetLastError();
+      return by_hop(grid, g, [&](auto SH, unsigned gx) { return go(spectro16h_kernel<L, FMT, W, GLFER16H_VAR, 0, 0, SH(), 1, 1>, gx, p); });
     }
-    if (k16 == 16) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else if (k16 == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 2, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else if (k16 == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 4, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else if (k16 == 8) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, 8, 1>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return by_hop(grid, g, [&](auto SH, unsigned gx) { return go(spectro16h_kernel<L, FMT, kMeanWps, GLFER16H_VAR, 0, 0, SH(), 1>, gx, p); });
   }
 #else
   if (p.mean_inkernel) return hipErrorInvalidValue;
@@ -1190,18 +1147,14 @@ static hipError_t launch16h_fmt(const SpectroParams &p, hipStream_t st) {
   // overlap 87.5 / 75 / 50 %: the hop is 2 / 4 / 8 of a lane's 16 sample registers -- a slot that
   // walks consecutive frames keeps the rest.  Worth it when a slot gets >= 4 frames and the
   // launch still fills the chip.
-  const int shift = (16 * p.H) % (1 << L) == 0 ? (16 * p.H) >> L : 0;
-  if ((shift == 2 || shift == 4 || shift == 8) && work >= 4 * resident) {
-    unsigned g = (unsigned)(work / 4 < cap ? work / 4 : cap);
-    if (g >= 64) g &= ~7u;
-    if (shift == 2) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0, 2>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else if (shift == 4) hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0, 4>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0, 8>), dim3(g, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    return hipGetLastError();
+  if ((k16 == 2 || k16 == 4 || k16 == 8) && work >= 4 * resident) {
+    const unsigned g = persistent_grid(work / 4, cap);
+    return with_value<2, 4, 8>(k16, [&](auto SH) {
+      return go(spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0, SH()>, g, p);
+    });
   }
 #endif
-  hipLaunchKernelGGL((spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-  return hipGetLastError();
+  return go(spectro16h_kernel<L, FMT, GLFER16H_WAVES_PER_SIMD, GLFER16H_VAR, 0, 0>, grid, p);
 #endif
 }
 
@@ -1215,11 +1168,6 @@ extern "C" hipError_t GLFER_CAT(glfer_launch_spectro16h_n, GLFER_LOGN)(const Spe
     const unsigned pair = p->fmt == GLFER_FMT_S16 ? 4u : 2u;
     if ((p->H & 1) || (reinterpret_cast<uintptr_t>(p->stream) & (pair - 1u))) return hipErrorInvalidValue;
   }
-  switch (p->fmt) {
-    case GLFER_FMT_F32: return launch16h_fmt<GLFER_FMT_F32>(*p, st);
-    case GLFER_FMT_S16: return launch16h_fmt<GLFER_FMT_S16>(*p, st);
-    case GLFER_FMT_U8: return launch16h_fmt<GLFER_FMT_U8>(*p, st);
-  }
-  return hipErrorInvalidValue;
+  return with_fmt(p->fmt, [&](auto F) { return launch16h_fmt<F()>(*p, st); });
 }
 #endif  // GLFER_NO_LAUNCHERS

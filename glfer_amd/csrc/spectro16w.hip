@@ -652,6 +652,7 @@ __global__ __launch_bounds__(LaunchW<LOGN>::BLOCK, WPS) void spectro16w_kernel(S
 }  // namespace glfer
 
 #ifndef GLFER_NO_LAUNCHERS
+#include "launch16.hpp"
 using namespace glfer;
 
 #define GLFER_CAT2(a, b) a##b
@@ -670,40 +671,34 @@ static hipError_t launch16w_fmt(const SpectroParams &p, hipStream_t st) {
 #endif
   if (work == 0) return hipSuccess;
   constexpr int WPS = GLFER16W_WAVES_PER_SIMD;
-  const long long per_cu = (WPS * 256) / LC::BLOCK > 0 ? (WPS * 256) / LC::BLOCK : 1;
-  const long long resident = 256LL * per_cu;
-  const long long cap = glfer_batch_cap(8 * resident, p.nbatch);   // (a batch shares it among its streams)
-  unsigned grid = (unsigned)(work < cap ? work : cap);
-  if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
+  const long long resident = resident_workgroups(WPS, LC::BLOCK);
+  const dim3 grid = batch_grid(persistent_grid(work, glfer_batch_cap(8 * resident, p.nbatch)), p), block(LC::BLOCK);
 #if GLFER_LOGN >= 15
   // N = 32768: the only kernel for this size, so also its general form (zero history, unaligned
   // integer pairs, RA9MB / limiter, spectrum output)
   const bool general = p.nonlin || p.spec || p.frame0 * (long long)p.H < (long long)p.R ||
                        (p.fmt != GLFER_FMT_F32 && ((p.H & 1) || (reinterpret_cast<uintptr_t>(p.stream) & (p.fmt == GLFER_FMT_S16 ? 3u : 1u))));
   if (general) {
-    if (p.wtapers > 1) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 0, 1, GLFER16W_SETS, WPS, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    return hipGetLastError();
+    if (p.wtapers > 1) return launch(spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS, 1>, grid, block, 0, st, p);
+    return launch(spectro16w_kernel<L, FMT, 0, 1, GLFER16W_SETS, WPS, 1>, grid, block, 0, st, p);
   }
 #endif
   if (p.wtapers > 1) {                             // the multitaper form keeps its sums in registers: two waves per SIMD
     constexpr int WPS_MT = (WPS > 2 && L < 15) ? 2 : WPS;
     if (p.mean_inkernel) {
-      const int km = (16 * p.H) % (1 << L) == 0 ? 16 * p.H / (1 << L) : 0;
+      const int km = hop_sixteenths<L>(p.H);
       if (p.history_mode) return hipErrorInvalidValue;
-      if (km == 16) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0, 16>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 8) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0, 8>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 4) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0, 4>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else return hipErrorInvalidValue;
-    } else if (p.history_mode) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-  } else {
-    if (p.mean_inkernel) return hipErrorInvalidValue;
-    constexpr int VAR = (L <= 12) ? 2 : 1;         // the window in LDS where it costs no resident workgroup
-    if (p.history_mode) hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 0, VAR, GLFER16W_SETS, WPS, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((spectro16w_kernel<L, FMT, 0, VAR, GLFER16W_SETS, WPS, 0, 0>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
+      return with_value<16, 8, 4>(km, [&](auto K) {
+        return launch(spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0, K()>, grid, block, 0, st, p);
+      });
+    }
+    if (p.history_mode) return launch(spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 1>, grid, block, 0, st, p);
+    return launch(spectro16w_kernel<L, FMT, 1, 1, GLFER16W_SETS, WPS_MT, 0, 0>, grid, block, 0, st, p);
   }
-  return hipGetLastError();
+  if (p.mean_inkernel) return hipErrorInvalidValue;
+  constexpr int VAR = (L <= 12) ? 2 : 1;           // the window in LDS where it costs no resident workgroup
+  if (p.history_mode) return launch(spectro16w_kernel<L, FMT, 0, VAR, GLFER16W_SETS, WPS, 0, 1>, grid, block, 0, st, p);
+  return launch(spectro16w_kernel<L, FMT, 0, VAR, GLFER16W_SETS, WPS, 0, 0>, grid, block, 0, st, p);
 }
 
 #ifdef GLFER16W_STAMPS
@@ -752,11 +747,6 @@ extern "C" hipError_t GLFER_CAT(glfer_launch_spectro16w_n, GLFER_LOGN)(const Spe
     if ((p->H & 1) || (reinterpret_cast<uintptr_t>(p->stream) & (pair - 1u))) return hipErrorInvalidValue;
   }
 #endif
-  switch (p->fmt) {
-    case GLFER_FMT_F32: return launch16w_fmt<GLFER_FMT_F32>(*p, st);
-    case GLFER_FMT_S16: return launch16w_fmt<GLFER_FMT_S16>(*p, st);
-    case GLFER_FMT_U8: return launch16w_fmt<GLFER_FMT_U8>(*p, st);
-  }
-  return hipErrorInvalidValue;
+  return with_fmt(p->fmt, [&](auto F) { return launch16w_fmt<F()>(*p, st); });
 }
 #endif  // GLFER_NO_LAUNCHERS

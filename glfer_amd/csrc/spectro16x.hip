@@ -247,6 +247,7 @@ __global__ __launch_bounds__(LaunchX<LOGN>::BLOCK, WPS) void spectro16x_kernel(S
 }  // namespace glfer
 
 #ifndef GLFER_NO_LAUNCHERS
+#include "launch16.hpp"
 using namespace glfer;
 
 #ifndef GLFER_LOGN
@@ -264,26 +265,19 @@ static hipError_t launch16x_fmt(const SpectroParams &p, hipStream_t st) {
   if (!p.ragged || p.nbatch < 2) return hipErrorInvalidValue;
 #endif
   if (work == 0) return hipSuccess;
-  const long long per_cu = (GLFER16X_WAVES_PER_SIMD * 256) / LC::BLOCK > 0 ? (GLFER16X_WAVES_PER_SIMD * 256) / LC::BLOCK : 1;
-  const long long resident = 256LL * per_cu;
-  const long long cap = glfer_batch_cap(4 * resident, p.nbatch);   // (a batch shares it among its streams)
-  unsigned grid = (unsigned)(work < cap ? work : cap);
-  if (grid >= 64) grid &= ~7u;                     // whole XCD slices: see xcd_block_index()
+  const long long resident = resident_workgroups(GLFER16X_WAVES_PER_SIMD, LC::BLOCK);
+  const unsigned grid = persistent_grid(work, glfer_batch_cap(4 * resident, p.nbatch));
   if (p.mean_inkernel) {
     if constexpr (Plan16<L>::T <= 64) {
       if (p.history_mode) return hipErrorInvalidValue;
-      const int km = (16 * p.H) % (1 << L) == 0 ? (16 * p.H) >> L : 0;
-      if (km == 16) hipLaunchKernelGGL((spectro16x_kernel<L, FMT, GLFER16X_WAVES_PER_SIMD, 16>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 8) hipLaunchKernelGGL((spectro16x_kernel<L, FMT, GLFER16X_WAVES_PER_SIMD, 8>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else if (km == 4) hipLaunchKernelGGL((spectro16x_kernel<L, FMT, GLFER16X_WAVES_PER_SIMD, 4>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-      else return hipErrorInvalidValue;
-      return hipGetLastError();
+      return with_value<16, 8, 4>(hop_sixteenths<L>(p.H), [&](auto K) {
+        return launch(spectro16x_kernel<L, FMT, GLFER16X_WAVES_PER_SIMD, K()>, batch_grid(grid, p), dim3(LC::BLOCK), 0, st, p);
+      });
     } else {
       return hipErrorInvalidValue;
     }
   }
-  hipLaunchKernelGGL((spectro16x_kernel<L, FMT>), dim3(grid, glfer_batch_y(p)), dim3(LC::BLOCK), 0, st, p);
-  return hipGetLastError();
+  return launch(spectro16x_kernel<L, FMT>, batch_grid(grid, p), dim3(LC::BLOCK), 0, st, p);
 }
 
 // odd taper counts >= 3; needs p->xtaps (the last taper alone, glfer_hip.cpp builds it)
@@ -291,11 +285,6 @@ extern "C" hipError_t GLFER_CAT(glfer_launch_spectro16x_n, GLFER_LOGN)(const Spe
   if (!p->xtaps || p->npairs < 2 || p->nonlin || p->spec) return hipErrorInvalidValue;
   // the gather has no zero-history path: every frame must lie wholly inside the stream
   if (p->frame0 * (long long)p->H < (long long)p->R) return hipErrorInvalidValue;
-  switch (p->fmt) {
-    case GLFER_FMT_F32: return launch16x_fmt<GLFER_FMT_F32>(*p, st);
-    case GLFER_FMT_S16: return launch16x_fmt<GLFER_FMT_S16>(*p, st);
-    case GLFER_FMT_U8: return launch16x_fmt<GLFER_FMT_U8>(*p, st);
-  }
-  return hipErrorInvalidValue;
+  return with_fmt(p->fmt, [&](auto F) { return launch16x_fmt<F()>(*p, st); });
 }
 #endif  // GLFER_NO_LAUNCHERS

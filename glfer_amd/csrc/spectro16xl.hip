@@ -247,6 +247,7 @@ __global__ __launch_bounds__(256, 2) void spectro16xl_kernel(SpectroParams p) {
 }  // namespace glfer
 
 #ifndef GLFER_NO_LAUNCHERS
+#include "launch16.hpp"
 using namespace glfer;
 
 #ifndef GLFER_LOGN
@@ -267,37 +268,24 @@ static hipError_t launch16xl_fmt(const SpectroParams &p, hipStream_t st) {
   const long long work = ((long long)p.nframes + 2 * LC::FPB - 1) / (2 * LC::FPB);
   if (work == 0) return hipSuccess;
   const long long resident = 256LL * 2;
-  const long long cap = glfer_batch_cap(4 * resident, p.nbatch);   // (a batch shares it among its streams)
-  unsigned grid = (unsigned)(work < cap ? work : cap);
-  if (grid >= 64) grid &= ~7u;                       // whole XCD slices: see xcd_block_index()
-  auto kern = spectro16xl_kernel<L, FMT>;
+  const unsigned grid = persistent_grid(work, glfer_batch_cap(4 * resident, p.nbatch));
   if (p.mean_inkernel) {
     if constexpr (Plan16<L>::T <= 64) {
       if (p.history_mode) return hipErrorInvalidValue;
-      const int km = (16 * p.H) % (1 << L) == 0 ? (16 * p.H) >> L : 0;
-      if (km == 16) kern = spectro16xl_kernel<L, FMT, 16>;
-      else if (km == 8) kern = spectro16xl_kernel<L, FMT, 8>;
-      else if (km == 4) kern = spectro16xl_kernel<L, FMT, 4>;
-      else return hipErrorInvalidValue;
+      return with_value<16, 8, 4>(hop_sixteenths<L>(p.H), [&](auto K) {
+        return launch_dynamic_lds(spectro16xl_kernel<L, FMT, K()>, batch_grid(grid, p), dim3(256), shmem, st, p);
+      });
     } else {
       return hipErrorInvalidValue;
     }
   }
-  hipError_t e = glfer::allow_dynamic_lds(reinterpret_cast<const void *>(kern), shmem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p);
-  return hipGetLastError();
+  return launch_dynamic_lds(spectro16xl_kernel<L, FMT>, batch_grid(grid, p), dim3(256), shmem, st, p);
 }
 
 // odd taper counts >= 3 whose half tables fit in LDS; needs p->ltaps (glfer_hip.cpp builds it)
 extern "C" hipError_t GLFER_CAT(glfer_launch_spectro16xl_n, GLFER_LOGN)(const SpectroParams *p, hipStream_t st) {
   if (!p->ltaps || p->npairs < 2 || p->nonlin || p->spec) return hipErrorInvalidValue;
   if (p->frame0 * (long long)p->H < (long long)p->R) return hipErrorInvalidValue;   // no zero-history path here
-  switch (p->fmt) {
-    case GLFER_FMT_F32: return launch16xl_fmt<GLFER_FMT_F32>(*p, st);
-    case GLFER_FMT_S16: return launch16xl_fmt<GLFER_FMT_S16>(*p, st);
-    case GLFER_FMT_U8: return launch16xl_fmt<GLFER_FMT_U8>(*p, st);
-  }
-  return hipErrorInvalidValue;
+  return with_fmt(p->fmt, [&](auto F) { return launch16xl_fmt<F()>(*p, st); });
 }
 #endif  // GLFER_NO_LAUNCHERS

@@ -545,6 +545,7 @@ __global__ __launch_bounds__(256, 2) void spectro16y_kernel(SpectroParams p) {
 }  // namespace glfer
 
 #ifndef GLFER_NO_LAUNCHERS
+#include "launch16.hpp"
 using namespace glfer;
 
 // The queue form (p.yq_counter set by the host, which keeps the ticket base: glfer_hip.cpp): one workgroup per resident slot
@@ -554,20 +555,13 @@ static hipError_t launch16y_queue(const SpectroParams &p, hipStream_t st) {
   if (p.mean_inkernel || p.nbatch > 1 || p.yq_chunk < 1) return hipErrorInvalidValue;
   const unsigned grid = glfer_yq_grid(glfer_yq_chunks(p.nframes, p.yq_chunk));
   constexpr size_t shmem = (size_t)LaunchY::LDS_WORDS * 8;
-#define GLFER_Y_QUEUE(HIST, HALF)                                                                                    \
-  do {                                                                                                               \
-    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, HIST, 0, 0, HALF, 1>), shmem); \
-    if (e != hipSuccess) return e;                                                                                   \
-    hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, HIST, 0, 0, HALF, 1>), dim3(grid), dim3(256), shmem, st, p);        \
-    return hipGetLastError();                                                                                        \
-  } while (0)
-  if (GLFER16Y_HALF != 0 && p.ytaps && p.npairs == 3) {
-    if (p.history_mode) GLFER_Y_QUEUE(1, GLFER16Y_HALF);
-    else GLFER_Y_QUEUE(0, GLFER16Y_HALF);
+  constexpr int HALF = GLFER16Y_HALF;
+  if (HALF != 0 && p.ytaps && p.npairs == 3) {
+    if (p.history_mode) return launch_dynamic_lds(spectro16y_kernel<FMT, 0, 1, 0, 0, HALF, 1>, dim3(grid), dim3(256), shmem, st, p);
+    return launch_dynamic_lds(spectro16y_kernel<FMT, 0, 0, 0, 0, HALF, 1>, dim3(grid), dim3(256), shmem, st, p);
   }
-  if (p.history_mode) GLFER_Y_QUEUE(1, 0);
-  else GLFER_Y_QUEUE(0, 0);
-#undef GLFER_Y_QUEUE
+  if (p.history_mode) return launch_dynamic_lds(spectro16y_kernel<FMT, 0, 1, 0, 0, 0, 1>, dim3(grid), dim3(256), shmem, st, p);
+  return launch_dynamic_lds(spectro16y_kernel<FMT, 0, 0, 0, 0, 0, 1>, dim3(grid), dim3(256), shmem, st, p);
 }
 #endif
 
@@ -581,69 +575,35 @@ static hipError_t launch16y_fmt(const SpectroParams &p, hipStream_t st) {
   if (p.yq_counter) return launch16y_queue<FMT>(p, st);
 #endif
   const long long resident = 256LL * 2;
-  const long long cap = glfer_batch_cap(16 * resident, p.nbatch);   // (a batch shares it among its streams)
-  unsigned grid = (unsigned)(work < cap ? work : cap);   // tools/xbench: 16x beats 4x by ~2 %
-  if (grid >= 64) grid &= ~7u;                       // whole XCD slices: see xcd_block_index()
+  const dim3 grid = batch_grid(persistent_grid(work, glfer_batch_cap(16 * resident, p.nbatch)), p);   // tools/xbench: 16x beats 4x by ~2 %
   constexpr size_t shmem = (size_t)LaunchY::LDS_WORDS * 8;
   {
+    // (the plain kernel's limit is asked for whichever form is then chosen)
     hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(p.history_mode ? spectro16y_kernel<FMT, 0, 1> : spectro16y_kernel<FMT, 0, 0>), shmem);
     if (e != hipSuccess) return e;
   }
   if (p.mean_inkernel) {
     if (p.history_mode) return hipErrorInvalidValue;
     const int km = p.H % 256 == 0 ? p.H / 256 : 0;
-#ifdef GLFER_RAGGED                                  /* (always a launch over several streams: the BAT forms) */
-#define GLFER_Y_MEAN(K)                                                                                              \
-  do {                                                                                                               \
-    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, 0, K, 1>), shmem);       \
-    if (e != hipSuccess) return e;                                                                                   \
-    hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0, K, 1>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p); \
-    return hipGetLastError();                                                                                        \
-  } while (0)
-#else
-#define GLFER_Y_MEAN(K)                                                                                              \
-  do {                                                                                                               \
-    const void *k_ = p.nbatch > 1 ? reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, 0, K, 1>)                 \
-                                  : reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, 0, K, 0>);                \
-    hipError_t e = allow_dynamic_lds(k_, shmem);                                                                     \
-    if (e != hipSuccess) return e;                                                                                   \
-    if (p.nbatch > 1) hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0, K, 1>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p); \
-    else hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0, K, 0>), dim3(grid, 1), dim3(256), shmem, st, p);          \
-    return hipGetLastError();                                                                                        \
-  } while (0)
+    return with_value<16, 8, 4>(km, [&](auto K) {
+#ifndef GLFER_RAGGED                                 /* (the ragged build is always a launch over several streams: the BAT forms) */
+      if (!(p.nbatch > 1)) return launch_dynamic_lds(spectro16y_kernel<FMT, 0, 0, K(), 0>, dim3(grid.x, 1), dim3(256), shmem, st, p);
 #endif
-    if (km == 16) GLFER_Y_MEAN(16);
-    if (km == 8) GLFER_Y_MEAN(8);
-    if (km == 4) GLFER_Y_MEAN(4);
-#undef GLFER_Y_MEAN
-    return hipErrorInvalidValue;
+      return launch_dynamic_lds(spectro16y_kernel<FMT, 0, 0, K(), 1>, grid, dim3(256), shmem, st, p);
+    });
   }
   if (GLFER16Y_HALF != 0 && p.ytaps && p.npairs == 3) {   // five tapers, exactly (anti)symmetric tables: the half-table form
-#define GLFER_Y_HALF(HIST)                                                                                           \
-  do {                                                                                                               \
-    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(spectro16y_kernel<FMT, 0, HIST, 0, 0, GLFER16Y_HALF>), shmem); \
-    if (e != hipSuccess) return e;                                                                                   \
-    hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, HIST, 0, 0, GLFER16Y_HALF>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p); \
-    return hipGetLastError();                                                                                        \
-  } while (0)
-    if (p.history_mode) GLFER_Y_HALF(1);
-    else GLFER_Y_HALF(0);
-#undef GLFER_Y_HALF
+    if (p.history_mode) return launch_dynamic_lds(spectro16y_kernel<FMT, 0, 1, 0, 0, GLFER16Y_HALF>, grid, dim3(256), shmem, st, p);
+    return launch_dynamic_lds(spectro16y_kernel<FMT, 0, 0, 0, 0, GLFER16Y_HALF>, grid, dim3(256), shmem, st, p);
   }
-  if (p.history_mode) hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 1>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p);
-  else hipLaunchKernelGGL((spectro16y_kernel<FMT, 0, 0>), dim3(grid, glfer_batch_y(p)), dim3(256), shmem, st, p);
-  return hipGetLastError();
+  if (p.history_mode) return launch(spectro16y_kernel<FMT, 0, 1>, grid, dim3(256), shmem, st, p);
+  return launch(spectro16y_kernel<FMT, 0, 0>, grid, dim3(256), shmem, st, p);
 }
 
 // N = 4096, odd taper counts >= 3; needs p->xtaps (glfer_hip.cpp builds it)
 extern "C" hipError_t glfer_launch_spectro16y_n12(const SpectroParams *p, hipStream_t st) {
   if (!p->xtaps || p->npairs < 2 || p->nonlin || p->spec) return hipErrorInvalidValue;
   if (p->frame0 * (long long)p->H < (long long)p->R) return hipErrorInvalidValue;   // no zero-history path here
-  switch (p->fmt) {
-    case GLFER_FMT_F32: return launch16y_fmt<GLFER_FMT_F32>(*p, st);
-    case GLFER_FMT_S16: return launch16y_fmt<GLFER_FMT_S16>(*p, st);
-    case GLFER_FMT_U8: return launch16y_fmt<GLFER_FMT_U8>(*p, st);
-  }
-  return hipErrorInvalidValue;
+  return with_fmt(p->fmt, [&](auto F) { return launch16y_fmt<F()>(*p, st); });
 }
 #endif  // GLFER_NO_LAUNCHERS

@@ -5,6 +5,7 @@
 #define GLFER_SPECTRO_CROSS_PARAMS_H
 
 #include <hip/hip_runtime.h>
+#include "spectro_params.h"
 
 struct CrossParams {
   const void *stream;      /* device: pair 0 of the stream (virtual base), x and y interleaved, f32 / s16 / u8 pairs        */
@@ -27,16 +28,18 @@ struct CrossParams {
   long long sxy_batch_stride;   /* float2 from one stream's first row of sxy to the next one's                             */
 };
 
+/* the launchers glfer_launch_spectro16cx_n<logn>(const CrossParams *, hipStream_t): declared by spectro_params.h's table of built
+   launchers (its CX entries); the one built for a block size, or nullptr */
 #ifdef __cplusplus
-extern "C" {
-#endif
-hipError_t glfer_launch_spectro16cx_n8(const struct CrossParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16cx_n9(const struct CrossParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16cx_n10(const struct CrossParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16cx_n11(const struct CrossParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16cx_n12(const struct CrossParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16cx_n13(const struct CrossParams *p, hipStream_t st);
-#ifdef __cplusplus
+#define GLFER_LOOKUP16_CX(k, l, t) if (logn == l) return glfer_launch_##k##_n##l;
+#define GLFER_LOOKUP16_S(k, l, t)
+#define GLFER_LOOKUP16_IQ(k, l, t)
+static inline hipError_t (*launcher16_cx(int logn))(const CrossParams *, hipStream_t) {
+  GLFER_LAUNCHERS16(GLFER_LOOKUP16)
+  return nullptr;
 }
+#undef GLFER_LOOKUP16_S
+#undef GLFER_LOOKUP16_IQ
+#undef GLFER_LOOKUP16_CX
 #endif
 #endif

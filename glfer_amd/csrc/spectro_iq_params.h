@@ -4,6 +4,7 @@
 #define GLFER_SPECTRO_IQ_PARAMS_H
 
 #include <hip/hip_runtime.h>
+#include "spectro_params.h"
 
 /* include/glfer_hip.h's flag bits (the kernels do not include the public header) */
 #ifndef GLFER_IQ_CENTERED
@@ -30,17 +31,18 @@ struct IqParams {
   long long psd_batch_stride;   /* floats from one stream's first row to the next one's                  */
 };
 
+/* the launchers glfer_launch_spectro16c_n<logn>(const IqParams *, hipStream_t): declared by spectro_params.h's table of built
+   launchers (its IQ entries); the one built for a block size, or nullptr */
 #ifdef __cplusplus
-extern "C" {
-#endif
-hipError_t glfer_launch_spectro16c_n8(const struct IqParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16c_n9(const struct IqParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16c_n10(const struct IqParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16c_n11(const struct IqParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16c_n12(const struct IqParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16c_n13(const struct IqParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16c_n14(const struct IqParams *p, hipStream_t st);
-#ifdef __cplusplus
+#define GLFER_LOOKUP16_IQ(k, l, t) if (logn == l) return glfer_launch_##k##_n##l;
+#define GLFER_LOOKUP16_S(k, l, t)
+#define GLFER_LOOKUP16_CX(k, l, t)
+static inline hipError_t (*launcher16_iq(int logn))(const IqParams *, hipStream_t) {
+  GLFER_LAUNCHERS16(GLFER_LOOKUP16)
+  return nullptr;
 }
+#undef GLFER_LOOKUP16_S
+#undef GLFER_LOOKUP16_IQ
+#undef GLFER_LOOKUP16_CX
 #endif
 #endif

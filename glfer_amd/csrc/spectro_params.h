@@ -210,60 +210,42 @@ __device__ __forceinline__ void glfer_batch_select_avg(SpectroParams &p) {
 }
 #endif
 
+/* THE TABLE OF BUILT ESTIMATOR LAUNCHERS: X(kind, block, logn, twin), one entry per launcher glfer_launch_<kind>_n<logn> --
+     kind     the source spectro16*.hip and the stem of the launcher's name
+     block    the argument block it takes: S = SpectroParams, IQ = IqParams (spectro_iq_params.h), CX = CrossParams
+              (spectro_cross_params.h)
+     logn     log2 of the block size the source is compiled for (the Makefile's LOGNS lists)
+     twin     1: built once more with -DGLFER_RAGGED as glfer_launch_<kind>_ragged_n<logn> (the stream from SpectroParams::ragged;
+              the Makefile's RAGGED_OBJS); 0: no ragged twin
+   The prototypes and the lookups launcher16() (below), launcher16_iq() and launcher16_cx() (beside their argument blocks) are
+   generated from it; tests/test_launch_table_host.py holds the Makefile's lists and the library's symbols against it. */
+#define GLFER_LAUNCHERS16(X)                                                                                                                  \
+  X(spectro16, S, 8, 1) X(spectro16, S, 9, 1) X(spectro16, S, 10, 1) X(spectro16, S, 11, 1) X(spectro16, S, 12, 1) X(spectro16, S, 13, 1) X(spectro16, S, 14, 1) \
+  X(spectro16h, S, 9, 1) X(spectro16h, S, 10, 1) X(spectro16h, S, 11, 1) X(spectro16h, S, 12, 1) X(spectro16h, S, 13, 1) X(spectro16h, S, 14, 1) \
+  X(spectro16w, S, 11, 1) X(spectro16w, S, 12, 1) X(spectro16w, S, 13, 1) X(spectro16w, S, 14, 1) X(spectro16w, S, 15, 0)                       \
+  X(spectro16x, S, 8, 1) X(spectro16x, S, 9, 1) X(spectro16x, S, 10, 1)                                                                       \
+  X(spectro16xl, S, 8, 1) X(spectro16xl, S, 9, 1) X(spectro16xl, S, 10, 1) X(spectro16xl, S, 11, 1)                                           \
+  X(spectro16y, S, 12, 1)                                                                                                                     \
+  X(spectro16c, IQ, 8, 0) X(spectro16c, IQ, 9, 0) X(spectro16c, IQ, 10, 0) X(spectro16c, IQ, 11, 0) X(spectro16c, IQ, 12, 0) X(spectro16c, IQ, 13, 0) X(spectro16c, IQ, 14, 0) \
+  X(spectro16cx, CX, 8, 0) X(spectro16cx, CX, 9, 0) X(spectro16cx, CX, 10, 0) X(spectro16cx, CX, 11, 0) X(spectro16cx, CX, 12, 0) X(spectro16cx, CX, 13, 0)
+enum glfer_kind16 { GLFER_KIND_spectro16, GLFER_KIND_spectro16h, GLFER_KIND_spectro16w, GLFER_KIND_spectro16x, GLFER_KIND_spectro16xl,
+                    GLFER_KIND_spectro16y };
+#define GLFER_BLOCK16_S SpectroParams
+#define GLFER_BLOCK16_IQ IqParams
+#define GLFER_BLOCK16_CX CrossParams
+#define GLFER_TWIN16_0(...)
+#define GLFER_TWIN16_1(...) __VA_ARGS__
+
 #ifdef __cplusplus
 extern "C" {
 #endif
-hipError_t glfer_launch_spectro16_n8(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_n9(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_n10(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_n11(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_n12(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_n13(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_n14(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16x_n8(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16x_n9(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16x_n10(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16xl_n8(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16xl_n9(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16xl_n10(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16xl_n11(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16y_n12(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_n9(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_n10(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_n11(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_n12(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_n13(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_n14(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16w_n11(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16w_n12(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16w_n13(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16w_n14(const SpectroParams *p, hipStream_t st);
-/* the ragged instantiations (p->ragged != NULL, p->nbatch >= 2) */
-hipError_t glfer_launch_spectro16_ragged_n8(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_ragged_n9(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_ragged_n10(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_ragged_n11(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_ragged_n12(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_ragged_n13(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16_ragged_n14(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16x_ragged_n8(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16x_ragged_n9(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16x_ragged_n10(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16xl_ragged_n8(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16xl_ragged_n9(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16xl_ragged_n10(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16xl_ragged_n11(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16y_ragged_n12(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_ragged_n9(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_ragged_n10(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_ragged_n11(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_ragged_n12(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_ragged_n13(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16h_ragged_n14(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16w_ragged_n11(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16w_ragged_n12(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16w_ragged_n13(const SpectroParams *p, hipStream_t st);
-hipError_t glfer_launch_spectro16w_ragged_n14(const SpectroParams *p, hipStream_t st);
+struct IqParams;
+struct CrossParams;
+#define GLFER_PROTO16(k, b, l, t)                                                        \
+  hipError_t glfer_launch_##k##_n##l(const struct GLFER_BLOCK16_##b *p, hipStream_t st); \
+  GLFER_TWIN16_##t(hipError_t glfer_launch_##k##_ragged_n##l(const struct GLFER_BLOCK16_##b *p, hipStream_t st);)
+GLFER_LAUNCHERS16(GLFER_PROTO16)
+#undef GLFER_PROTO16
 size_t glfer_levels_scratch_floats(size_t nframes);
 hipError_t glfer_launch_levels(const float *stats, size_t nframes, int scale_log, int autoscale,
                                int first_buffer, float overlap, float max_lvl0, float min_lvl0,
@@ -289,5 +271,25 @@ hipError_t glfer_launch_submean_ragged(const GlferRaggedHops *tab, unsigned nb, 
                                        hipStream_t st);
 #ifdef __cplusplus
 }
+/* The lookups.  GLFER_LOOKUP16 hands an entry to GLFER_LOOKUP16_<block>; the header of an argument block defines its own as
+   `if (<kind and logn match>) return <launcher, or its ragged twin>;` and the other two as nothing (this one: S; the IQ and CX
+   entries in spectro_iq_params.h and spectro_cross_params.h).  Nothing built: nullptr, which the routing functions
+   (glfer_hip.cpp, cross.cpp) turn into hipErrorInvalidValue. */
+#define GLFER_PICK16_0(k, l) nullptr
+#define GLFER_PICK16_1(k, l) glfer_launch_##k##_ragged_n##l
+#define GLFER_LOOKUP16_S(k, l, t) if (kind == GLFER_KIND_##k && logn == l) return ragged ? GLFER_PICK16_##t(k, l) : glfer_launch_##k##_n##l;
+#define GLFER_LOOKUP16_IQ(k, l, t)
+#define GLFER_LOOKUP16_CX(k, l, t)
+#define GLFER_LOOKUP16(k, b, l, t) GLFER_LOOKUP16_##b(k, l, t)
+typedef hipError_t (*glfer_launcher16_fn)(const SpectroParams *, hipStream_t);
+static inline glfer_launcher16_fn launcher16(glfer_kind16 kind, int logn, bool ragged) {
+  GLFER_LAUNCHERS16(GLFER_LOOKUP16)
+  return nullptr;
+}
+#undef GLFER_LOOKUP16_S
+#undef GLFER_LOOKUP16_IQ
+#undef GLFER_LOOKUP16_CX
+/* log2 of a block size, -1 when it is no power of two (the lookups then find nothing) */
+static inline int glfer_logn(int n) { return n > 0 && (n & (n - 1)) == 0 ? __builtin_ctz((unsigned)n) : -1; }
 #endif
 #endif

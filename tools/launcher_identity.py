@@ -7,7 +7,10 @@ The cases: the cut-edge calls of tests/test_gpu_frame_cuts.py (plans A .. D, sub
 (first, nframes), the ragged call, plan A's F entries), then one 4 096-frame call per plan through the rows, batch, ragged,
 average, average-batch, F and F-batch entries; then the column entries (column_cases: display, the waterfalls and their two
 multi-GPU halves, the moving averages; `python tools/launcher_identity.py columns` runs these alone), and the LMP statistic's
-three entries and LMP plans at every ring size's form (lmp_cases; `python tools/launcher_identity.py lmp` runs these alone).
+three entries and LMP plans at every ring size's form (lmp_cases; `python tools/launcher_identity.py lmp` runs these alone);
+then the estimator launchers' own branches (launcher_cases: every launch site of spectro16*.hip that the Python API and the
+documented environment switches reach, each at the smallest frame count that takes it; `python tools/launcher_identity.py
+launchers` runs these alone, and `... mtab` the few that need GLFER_MTAB_WPS=2, which the library reads once per process).
 Inputs come from fixed seeds on the host; nothing is timed."""
 import hashlib
 import os
@@ -50,7 +53,10 @@ def plan(name, sub):
 def streams(nb, nsamples, fmt, seed):
     rng = np.random.default_rng(seed)
     x = 0.25 * rng.standard_normal((nb, nsamples)) + np.linspace(-0.1, 0.1, nb)[:, None]
-    x = np.clip(np.round(x * 20000.0), -32768, 32767).astype(np.int16) if fmt == 1 else x.astype(np.float32)
+    if fmt == 2:
+        x = np.clip(np.round(x * 100.0 + 128.0), 0, 255).astype(np.uint8)
+    else:
+        x = np.clip(np.round(x * 20000.0), -32768, 32767).astype(np.int16) if fmt == 1 else x.astype(np.float32)
     return torch.from_numpy(x).to("cuda")
 
 
@@ -239,11 +245,178 @@ def lmp_cases():
         rect.close()
 
 
+FMT_NAMES = {0: "f32", 1: "s16", 2: "u8"}
+
+
+def case(label, fn):
+    """one line: the hashes of what fn returns, or its refusal -- two builds must also refuse alike"""
+    try:
+        out = fn()
+        print("%s: %s" % (label, sha(*(out if isinstance(out, (tuple, list)) else (out,)))))
+    except (G.api.GlferHipError, AssertionError) as e:
+        print("%s: refused (%s)" % (label, (str(e).splitlines() or [type(e).__name__])[0][:100]))
+
+
+def three_ways(tag, sp, frames, fmt, seed, nb=3, batch=True):
+    """the rows, batch and ragged entries over streams of `frames` frames"""
+    x = streams(nb, frames * sp.hop + 2 * (sp.hop // 6) + 8, fmt, seed)
+    case(tag + " rows", lambda: sp.run(x[nb - 1]))
+    if batch:
+        case(tag + " batch", lambda: sp.run_batch(x))
+        case(tag + " ragged", lambda: ragged(sp, x, [frames, max(frames // 3, 1), frames - 6][:nb], [0, 5, 0][:nb]))
+    return x
+
+
+def launcher_cases(mtab=False):
+    """The estimator launchers' branches beyond what main() reaches; profiles/launch_scaffold_identity.txt lists the launch
+    sites with the case that reaches each."""
+    fft = lambda **kw: G.Spectrogram(G.FftParams(window_type=0, **kw))
+    mtm = lambda **kw: G.Spectrogram(G.MtmParams(**kw))
+    produced = (dict(GLFER_FUSED_MIN_FRAMES="64", GLFER_MEANS_PRODUCERS="8"),
+                dict(GLFER_FUSED_MIN_FRAMES="64", GLFER_MEANS_PRODUCERS="8", GLFER_FUSED_BLOCK_FRAMES="16", GLFER_FUSED_LOOK="64"))
+    if mtab:
+        # spectro16h's table form at two wavefronts per SIMD: the means given (reference order), one stream; every hop of the ladder
+        for n in (1024, 4096):
+            for ovl in (0.0, 0.5, 0.75, 0.875, 0.6):
+                sp = fft(n=n, overlap=ovl, sub_mean=G.SUBMEAN_EXACT)
+                three_ways("mtab h n %d overlap %g" % (n, ovl), sp, 300, 0, 31, batch=False)
+                sp.close()
+        sp = fft(n=1024, overlap=0.5, sub_mean=G.SUBMEAN_EXACT)
+        x = streams(1, 300 * sp.hop, 0, 32)
+        for env in produced:
+            case("mtab h produced means %s" % sorted(env.items()), lambda: with_env(lambda: sp.run(x[0]), **env))
+        sp.close()
+        return
+    # spectro16h, the periodogram: every hop of the ladders (16, 8, 4, 2 sixteenths) and one outside them, every sample format,
+    # no mean removal / the means given (reference order) / summed in the kernel (fast); history zeroed in every frame
+    for n in (512, 1024):
+        for ovl in (0.0, 0.5, 0.75, 0.875, 0.6):
+            for fmt in (0, 1, 2):
+                for sub in SUB_MEANS:
+                    for hm in ((0, 1) if sub == 0 and fmt == 0 else (0,)):
+                        sp = fft(n=n, overlap=ovl, sub_mean=sub, sample_format=fmt, history_mode=hm)
+                        three_ways("h n %d overlap %g %s sub_mean %d history %d" % (n, ovl, FMT_NAMES[fmt], sub, hm), sp, 40, fmt, 33)
+                        sp.close()
+        sys.stdout.flush()
+    # ... the means produced inside the launch (GLFER_MEANS_PRODUCERS; the lock-stepped form with GLFER_FUSED_BLOCK_FRAMES)
+    sp = fft(n=1024, overlap=0.5, sub_mean=G.SUBMEAN_EXACT)
+    x = streams(1, 300 * sp.hop, 0, 32)
+    for env in produced:
+        case("h produced means %s" % sorted(env.items()), lambda: with_env(lambda: sp.run(x[0]), **env))
+    sp.close()
+    # ... the register-reuse forms: work >= 4 x resident workgroups (3 072 workgroups of 8, 2 and 1 frames at N = 1024, 4096, 16384)
+    for n, ovl, frames in ((1024, 0.5, 24800), (1024, 0.75, 24800), (1024, 0.875, 24800), (4096, 0.75, 6400), (16384, 0.875, 1100)):
+        for fmt in (0, 1):
+            sp = fft(n=n, overlap=ovl, sample_format=fmt)
+            x = streams(2, frames * sp.hop + 64, fmt, 34)
+            tag = "h shifted n %d overlap %g %s" % (n, ovl, FMT_NAMES[fmt])
+            case(tag + " rows", lambda: sp.run(x[1]))
+            case(tag + " batch", lambda: sp.run_batch(x))
+            case(tag + " ragged", lambda: ragged(sp, x, [frames, 100], [0, 5]))
+            sp.close()
+            del x
+        sys.stdout.flush()
+    # ... the average inside the launch (a launch of >= 256 frames with full windows), single and batch
+    for n in (512, 1024, 4096):
+        for ovl in (0.0, 0.5, 0.75, 0.875, 0.6):
+            for sub in (0, G.SUBMEAN_EXACT):
+                for fmt in ((0, 1) if ovl == 0.5 else (0,)):
+                    sp = fft(n=n, overlap=ovl, sub_mean=sub, sample_format=fmt)
+                    x = streams(2, 600 * sp.hop + 64, fmt, 35)
+                    tag = "h average n %d overlap %g %s sub_mean %d" % (n, ovl, FMT_NAMES[fmt], sub)
+                    for depth in (1, 4):
+                        case("%s depth %d" % (tag, depth), lambda: sp.run_avg(x[0], G.AVG_PLAIN, depth, 3, sp.bins - 5, want_psd=True))
+                        case("%s depth %d batch" % (tag, depth), lambda: sp.run_avg_batch(x, G.AVG_PLAIN, depth, 3, sp.bins - 5, want_psd=True))
+                    sp.close()
+        sys.stdout.flush()
+    # spectro16 (and spectro_small below N = 256), the general path: RA9MB and the limiter, the spectrum output
+    for n in (128, 256, 1024, 4096, 16384):
+        for fmt in (0, 2):
+            sp = G.Spectrogram(G.FftParams(n=n, window_type=0, overlap=0.5, a=0.5, limiter=1, sample_format=fmt))
+            x = three_ways("packed general n %d %s" % (n, FMT_NAMES[fmt]), sp, 24, fmt, 36)
+            sp.close()
+            sp = fft(n=n, overlap=0.5, sample_format=fmt)
+            case("packed spectrum n %d %s" % (n, FMT_NAMES[fmt]), lambda: sp.run(x[0], spectrum=True))
+            sp.close()
+    sys.stdout.flush()
+    # the multitaper: even counts (spectro16), odd ones (spectro16xl's LDS tables; spectro16x with 23 tapers, whose tables do not
+    # fit; spectro16y at N = 4096; packed at 2048 and from 8192), spectro16h's form at N = 8192 and spectro16w's at 16384; the
+    # forms forced with GLFER_FORM, spectro16y's full tables and static stride
+    hops = ((0.0, 0), (0.0, G.SUBMEAN_EXACT), (0.5, G.SUBMEAN_FAST), (0.75, G.SUBMEAN_FAST), (0.5, 0))
+    shapes = [(n, 2.5, k) for n in (256, 512, 1024, 2048, 4096) for k in (3, 4, 6)] + [(1024, 12.0, 22), (8192, 2.5, 4), (16384, 2.5, 4)]
+    for n, w, kmax in shapes:
+        for ovl, sub in (hops if n <= 4096 else hops[:3]):
+            for fmt in ((0, 2) if kmax == 4 else (0,)):
+                for hm in ((0, 1) if (ovl, sub, fmt, kmax) == (0.5, 0, 0, 4) else (0,)):
+                    sp = mtm(n=n, overlap=ovl, w=w, kmax=kmax, sub_mean=sub, sample_format=fmt, history_mode=hm)
+                    tag = "mtm n %d tapers %d overlap %g %s sub_mean %d history %d" % (n, kmax + 1, ovl, FMT_NAMES[fmt], sub, hm)
+                    x = three_ways(tag, sp, 40, fmt, 37)
+                    forms = [dict(GLFER_FORM=f) for f in ("w", "h", "x") if n >= 2048 and kmax == 4]
+                    if n == 4096:
+                        forms += [dict(GLFER_Y_TAPERS="full"), dict(GLFER_Y_QUEUE="0"), dict(GLFER_Y_TAPERS="full", GLFER_Y_QUEUE="0")]
+                    for env in forms:
+                        etag = "%s %s" % (tag, " ".join("%s=%s" % kv for kv in sorted(env.items())))
+                        case(etag + " rows", lambda: with_env(lambda: sp.run(x[1]), **env))
+                        case(etag + " batch", lambda: with_env(lambda: sp.run_batch(x), **env))
+                        case(etag + " ragged", lambda: with_env(lambda: ragged(sp, x, [40, 13, 34], [0, 5, 0]), **env))
+                    sp.close()
+        sys.stdout.flush()
+    # the periodogram through spectro16w (GLFER_FORM=w)
+    for n in (2048, 4096, 8192, 16384):
+        for hm in (0, 1):
+            sp = fft(n=n, overlap=0.5, history_mode=hm)
+            with_env(lambda: three_ways("w periodogram n %d history %d" % (n, hm), sp, 24, 0, 38), GLFER_FORM="w")
+            sp.close()
+    # N = 32768 both ways (the two-kernel form; spectro16w's single kernel with GLFER_FORM=w and for the spectrum), N = 65536
+    for make, name in ((lambda **kw: fft(**kw), "fft"), (lambda **kw: mtm(w=2.5, kmax=4, **kw), "mtm")):
+        for fmt in (0, 1):
+            for ovl in (0.0, 0.5):
+                sp = make(n=32768, overlap=ovl, sample_format=fmt)
+                tag = "n 32768 %s overlap %g %s" % (name, ovl, FMT_NAMES[fmt])
+                x = three_ways(tag, sp, 6, fmt, 39, nb=2)
+                with_env(lambda: three_ways(tag + " GLFER_FORM=w", sp, 6, fmt, 39, nb=2), GLFER_FORM="w")
+                if name == "fft":
+                    case(tag + " spectrum", lambda: sp.run(x[0], spectrum=True))
+                sp.close()
+    sp = fft(n=65536, overlap=0.5)
+    three_ways("n 65536 fft", sp, 4, 0, 40, nb=2)
+    sp.close()
+    sys.stdout.flush()
+    # complex I/Q rows (spectro16c) and the cross-spectrum (spectro16cx): single and batch over their size lists, every format
+    for n in (256, 512, 1024, 2048, 4096, 8192, 16384):
+        for fmt in (0, 1, 2):
+            for name, sp in (("fft", fft(n=n, overlap=0.5, sample_format=fmt)), ("mtm", mtm(n=n, overlap=0.5, w=2.5, kmax=2, sample_format=fmt))):
+                x = streams(3, 2 * (20 * sp.hop + 8), fmt, 41).reshape(3, -1, 2)
+                tag = "n %d %s %s" % (n, name, FMT_NAMES[fmt])
+                case("iq " + tag, lambda: sp.run_iq(x[1], centered=(fmt == 1), swap=(fmt == 2)))
+                case("iq batch " + tag, lambda: sp.run_iq_batch(x))
+                if name == "mtm":
+                    case("cross " + tag, lambda: tuple(sp.cross(x[1], want=("sxx", "syy", "sxy", "coh"))))
+                    case("cross batch " + tag, lambda: tuple(sp.cross_batch(x, want=("sxx", "syy", "sxy", "coh"))))
+                sp.close()
+        sys.stdout.flush()
+    # the F statistic on integer samples (the float forms: main())
+    for fmt in (1, 2):
+        sp = mtm(n=512, overlap=0.5, w=2.5, kmax=4, sample_format=fmt)
+        x = streams(3, 40 * sp.hop + 8, fmt, 42)
+        tag = "F n 512 %s" % FMT_NAMES[fmt]
+        case(tag, lambda: sp.ftest(x[1]))
+        case(tag + " batch", lambda: sp.ftest_batch(x))
+        case(tag + " rows-and-F", lambda: sp.rows_ftest(x[1]))
+        case(tag + " rows-and-F batch", lambda: sp.rows_ftest_batch(x))
+        sp.close()
+
+
 def main():
     if sys.argv[1:] == ["columns"]:
         return column_cases()
     if sys.argv[1:] == ["lmp"]:
         return lmp_cases()
+    if sys.argv[1:] == ["launchers"]:
+        return launcher_cases()
+    if sys.argv[1:] == ["mtab"]:
+        os.environ["GLFER_MTAB_WPS"] = "2"              # (read once, at the first launch that asks)
+        return launcher_cases(mtab=True)
     for name, (kind, n, overlap, fmt, hm, Gf, fi) in sorted(PLANS.items()):
         for sub in SUB_MEANS:
             sp = plan(name, sub)
@@ -282,6 +455,7 @@ def main():
         sp.close()
     lmp_cases()
     column_cases()
+    launcher_cases()
 
 
 if __name__ == "__main__":
