@@ -6,5 +6,5 @@ from .api import (Workers, Phases, AVG_PLAIN, AVG_SUMAVG, AVG_SUMEXTREME, HISTOR
                   GlferHipError, HparmaParams, MtmParams, Spectrogram, compute_floor, display, make_dpss, make_window, palette,
                   lmp_statistic, lmp_statistic_batch, lmp_statistic_ragged,
                   update_avg, update_avg_batch, update_avg_ragged, version, waterfall_ragged, wav_probe, deinterleave,
-                  IQ_CENTERED, IQ_SWAP, iq_supported, iq_tables, Cross, cross_supported,
+                  IQ_CENTERED, IQ_SWAP, iq_supported, iq_tables, Cross, cross_supported, welch_cross_supported,
                   Ddc, DdcConfig, ddc_design, ddc_phase_word, ddc_supported, ddc_tables)

@@ -77,6 +77,8 @@ EXPORTS = [
     "glfer_hip_ddc_destroy", "glfer_hip_ddc_device", "glfer_hip_ddc_batch_device", "glfer_hip_spectrogram_zoom_device",
     # two channels: multitaper auto- and cross-spectra and coherence in one pass
     "glfer_hip_cross_supported", "glfer_hip_mtm_cross_device", "glfer_hip_mtm_cross_batch_device",
+    # the same averaged over L consecutive segments (Welch): FFT plans too
+    "glfer_hip_welch_cross_supported", "glfer_hip_welch_rows", "glfer_hip_welch_cross_device", "glfer_hip_welch_cross_batch_device",
 ]
 
 
@@ -228,6 +230,12 @@ def lib():
         L.glfer_hip_cross_supported.argtypes = [C.POINTER(Config)]
         L.glfer_hip_mtm_cross_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, sz, vp]
         L.glfer_hip_mtm_cross_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, sz, vp, sz, vp]
+    if hasattr(L, "glfer_hip_welch_cross_device"):
+        L.glfer_hip_welch_cross_supported.argtypes = [C.POINTER(Config), sz, sz]
+        L.glfer_hip_welch_rows.argtypes = [vp, sz, sz, sz, sz]
+        L.glfer_hip_welch_rows.restype = sz
+        L.glfer_hip_welch_cross_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, sz, vp, sz, vp]
+        L.glfer_hip_welch_cross_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, sz, sz, vp, vp, vp, sz, vp, sz, vp]
     if hasattr(L, "glfer_hip_ddc_device"):
         L.glfer_hip_ddc_phase_word.argtypes = [C.c_double]
         L.glfer_hip_ddc_phase_word.restype = C.c_ulonglong
@@ -327,6 +335,13 @@ def cross_supported(params):
     """Whether a plan of these parameters gives cross-spectra and coherence (glfer_hip_cross_supported; host only)."""
     cfg = make_config(params)
     return lib().glfer_hip_cross_supported(C.byref(cfg)) == 0
+
+
+def welch_cross_supported(params, segments, step):
+    """Whether a plan of these parameters gives cross-spectra and coherence averaged over `segments` frames, rows `step` frames
+    apart (glfer_hip_welch_cross_supported; host only)."""
+    cfg = make_config(params)
+    return lib().glfer_hip_welch_cross_supported(C.byref(cfg), segments, step) == 0
 
 
 def iq_tables(params):
@@ -756,6 +771,47 @@ class Spectrogram:
         _check(lib().glfer_hip_mtm_cross_batch_device(self._h, C.c_void_p(v.data_ptr()), nb, spitch, ns, first_frame, nframes,
                                                       self._cross_ptr(ts, "sxx"), self._cross_ptr(ts, "syy"), self._cross_ptr(ts, "coh"),
                                                       pitch, self._cross_ptr(ts, "sxy"), xpitch, st), "glfer_hip_mtm_cross_batch_device")
+        return Cross(*(ts.get(k) for k in CROSS_FIELDS))
+
+    def welch_rows(self, nsamples, segments, step=None, first_frame=0):
+        """Rows cross_welch gives for a stream of nsamples pairs: (frames - first_frame - segments) // step + 1, or 0."""
+        return lib().glfer_hip_welch_rows(self._h, nsamples, first_frame, segments, segments if step is None else step)
+
+    def cross_welch(self, xy, segments, step=None, first_frame=0, nrows=None, want=("coh", "sxy"), out=None):
+        """Welch's estimate of what cross gives: row r averages |X|^2, |Y|^2 and X conj(Y) over the `segments` consecutive frames
+        from first_frame + r * step (step=None: segments, the block average; smaller: a moving estimate), then takes the quotient.
+        The plan is an FFT one with any window, or a multitaper one (all its tapers in every segment); xy and the returned
+        Cross([nrows][n/2+1]) as cross.  One launch on torch's current stream (glfer_hip_welch_cross_device)."""
+        torch = _torch()
+        v = self._iq_view(xy, 0)
+        ns = v.size(0)
+        step = segments if step is None else step
+        if nrows is None:
+            nrows = self.welch_rows(ns, segments, step, first_frame)
+        ts, pitch, xpitch = self._cross_outs(want, out, (), nrows, v.device)
+        st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+        _check(lib().glfer_hip_welch_cross_device(self._h, C.c_void_p(v.data_ptr()), ns, first_frame, segments, step, nrows,
+                                                  self._cross_ptr(ts, "sxx"), self._cross_ptr(ts, "syy"), self._cross_ptr(ts, "coh"), pitch,
+                                                  self._cross_ptr(ts, "sxy"), xpitch, st), "glfer_hip_welch_cross_device")
+        return Cross(*(ts.get(k) for k in CROSS_FIELDS))
+
+    def cross_welch_batch(self, xys, segments, step=None, first_frame=0, nrows=None, want=("coh", "sxy"), out=None):
+        """xys as cross_batch takes them.  Returns Cross of [B][nrows][n/2+1] tensors: entry b is what cross_welch(xys[b], ...)
+        gives (glfer_hip_welch_cross_batch_device)."""
+        torch = _torch()
+        v = self._iq_view(xys, 1)
+        nb, ns = v.size(0), v.size(1)
+        assert nb <= 1 or v.stride(0) % 2 == 0, v.stride()
+        spitch = v.stride(0) // 2 if nb > 1 else ns
+        step = segments if step is None else step
+        if nrows is None:
+            nrows = self.welch_rows(ns, segments, step, first_frame)
+        ts, pitch, xpitch = self._cross_outs(want, out, (nb,), nrows, v.device)
+        st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+        _check(lib().glfer_hip_welch_cross_batch_device(self._h, C.c_void_p(v.data_ptr()), nb, spitch, ns, first_frame, segments, step,
+                                                        nrows, self._cross_ptr(ts, "sxx"), self._cross_ptr(ts, "syy"),
+                                                        self._cross_ptr(ts, "coh"), pitch, self._cross_ptr(ts, "sxy"), xpitch, st),
+               "glfer_hip_welch_cross_batch_device")
         return Cross(*(ts.get(k) for k in CROSS_FIELDS))
 
     def run_zoom(self, ddc, x, first_frame=0, nframes=None, out=None, centered=False):

@@ -20,6 +20,11 @@
 // not NULL (a wave-uniform choice).
 //
 // Both channels ride one transform: a channel's separated spectrum carries the rounding of the PAIR, not its own (include/glfer_hip.h).
+//
+// Segment averaging (the WELCH instantiations, glfer_hip_welch_cross_device): the same body with rounds of (row group, segment,
+// taper).  The four sums run on over the L consecutive frames of a row before the one epilogue, so a plan of ONE window (an FFT
+// plan, where a single frame's coherence is identically 1) gives the csd / coherence estimate of L averaged segments from one pass
+// over the samples, with nothing between the frames' transforms and the row but registers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "stockham16.hpp"
@@ -73,8 +78,21 @@ __device__ __forceinline__ void buf_pair_sample(__amdgpu_buffer_rsrc_t rsrc, uns
   }
 }
 
+// The kernel's argument block as the kernel was launched with it, through a pointer the compiler cannot see through: what is read
+// from it is loaded where it is used and not held in scalar registers across the round loop (the scarce kind here)
+__device__ __forceinline__ const __attribute__((address_space(4))) CrossParams *cross_kernarg() {
+  const __attribute__((address_space(4))) CrossParams *kp =
+      (const __attribute__((address_space(4))) CrossParams *)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kp));
+  return kp;
+}
+
 // BAT: the instantiations a batch launches -- blockIdx.y is the stream (the convention of glfer_batch_select)
-template <int LOGN, int FMT, int BAT, int WPS = GLFER16CX_WAVES_PER_SIMD, int STG = GLFER16_STAGGER>
+// WELCH: segment averaging (glfer_hip_welch_cross_device).  p.nframes counts output ROWS; row r sums the frames
+// frame0 + r * step + s, s = 0 .. segments - 1, segments outermost and the tapers inside, and its sums are stored times p.scale.
+// Rounds are (row group, segment, taper): the samples are fetched at every segment's first taper, the sums and the "has a sample"
+// bits run on across the row's segments.  WELCH = 0 is the one-frame-a-row form: one segment, step 1, scale 1/4.
+template <int LOGN, int FMT, int BAT, int WELCH, int WPS = GLFER16CX_WAVES_PER_SIMD, int STG = GLFER16_STAGGER>
 __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel(CrossParams p) {
   if constexpr (BAT != 0) p.stream = reinterpret_cast<const char *>(p.stream) + (long long)blockIdx.y * p.batch_stride;
   using C = Plan16<LOGN>;
@@ -125,17 +143,34 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel
 
   // ---- registers filled ahead of use: the frame's pairs in memory order (once per frame) and the NEXT round's table
   float pa[16], pb[16], pw[16];
-  auto prefetch_x = [&](long long fblk, unsigned t) {
+  auto prefetch_x = [&](long long fblk, int seg, unsigned t) {
     // spectro16c.hip's gather, in pairs: index of frame-relative pair j is sblk + flc*H + j, the descriptor starts at pair
     // max(sblk, 0), pairs before the stream get an offset past the range and read 0
     // (fblk < nframes <= 2^31 - 1 and fl < 16: the sum fits 32 bits unsigned)
+    // WELCH: fblk counts rows, the block's rows lie step frames apart and this is segment seg of each: the descriptor starts at
+    // the first row's frame and a lane's row adds flc * step * H pairs to its offset, which the entry keeps inside the
+    // descriptor's range ((FPB - 1) step H + N pairs are at most 2^31 - 1 bytes: glfer_hip_welch_cross_supported)
     const unsigned flc = FPB == 1 || (unsigned)fblk + fl < (unsigned)p.nframes ? fl : (unsigned)(p.nframes - 1 - fblk);   // clamp: loads stay in range
-    const long long sblk = (p.frame0 + fblk) * (long long)p.H - p.R;
+    const char *stream = reinterpret_cast<const char *>(p.stream);
+    int H = p.H, R = p.R, history_mode = p.history_mode;
+    long long frame = p.frame0 + fblk;
+    unsigned lhop = (unsigned)H;                             // pairs from one lane row's frame to the next one's
+    if constexpr (WELCH != 0) {
+      // once per segment: everything but the row count comes from the argument block here, so that none of it is a scalar
+      // register held across the rounds (four instantiations spilled two to four of them otherwise)
+      const __attribute__((address_space(4))) CrossParams *kp = cross_kernarg();
+      const long long step = kp->step;
+      stream = reinterpret_cast<const char *>(kp->stream) + (BAT != 0 ? (long long)blockIdx.y * kp->batch_stride : 0);
+      H = kp->H, R = kp->R, history_mode = kp->history_mode;
+      frame = kp->frame0 + fblk * step + seg;
+      lhop = FPB == 1 ? 0u : (unsigned)step * (unsigned)H;
+    }
+    const long long sblk = frame * (long long)H - R;
     const long long sbase = sblk > 0 ? sblk : 0;
     const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(p.stream)) + sbase * (long long)csz, 0, 0x7fffffff, 0x00020000);
-    const int lrel = (int)(sblk - sbase) + (int)(flc * (unsigned)p.H + t);   // lane's first pair, relative to sbase
-    if (sblk >= 0 && p.history_mode == 0) {        // wave-uniform: no per-element predicate needed
+        const_cast<char *>(stream) + sbase * (long long)csz, 0, 0x7fffffff, 0x00020000);
+    const int lrel = (int)(sblk - sbase) + (int)(flc * lhop + t);   // lane's first pair, relative to sbase
+    if (sblk >= 0 && history_mode == 0) {          // wave-uniform: no per-element predicate needed
       static_for<0, 16>([&](auto mc) {
         constexpr int m = decltype(mc)::value;
         buf_pair_sample<FMT>(xrsrc, (unsigned)lrel * csz, (unsigned)(T * m) * csz, pa[m], pb[m]);
@@ -146,7 +181,7 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel
         constexpr int m = decltype(mc)::value;
         const int j = T * m + (int)t;
         const int rel = lrel + T * m;
-        const bool ok = p.history_mode ? (j >= p.R) : (rel >= 0);
+        const bool ok = history_mode ? (j >= R) : (rel >= 0);
         float a, b;
         buf_pair_sample<FMT>(xrsrc, ok ? (unsigned)rel * csz : 0x80000000u, 0u, a, b);
         pa[m] = ok ? a : 0.0f;             // raw 0 is not sample 0.0 for u8 ((0-128)/128)
@@ -175,8 +210,8 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel
   }
   long long fblk = (long long)xcd_block_index() * FPB;
   if (fblk >= p.nframes) return;
-  int tap = 0;
-  if constexpr (PF >= 1) prefetch_x(fblk, t);
+  int tap = 0, seg = 0;
+  if constexpr (PF >= 1) prefetch_x(fblk, 0, t);
   if constexpr (PF >= 2) prefetch_taps(0, t);
 
   // the four running sums, by bin register (bins k <= N/2: the registers with b + B q' <= 8; the others stay unused)
@@ -189,13 +224,15 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel
   // coherence: the frame's rows of a channel without a sample are stored as the exact zeros they are.  T <= 64: the frame lives in
   // one wavefront, a ballot answers; else every wavefront leaves its bits in LDS at the frame's first round, in the slots of
   // the frame's parity (the previous frame's epilogue may still be reading the other set), and the epilogue reads them all --
-  // the barriers of the passes lie in between.
+  // the barriers of the passes lie in between.  WELCH: a row's bits are those of its segments OR-ed (a channel is silent when it
+  // is in every one of them); the parity flips per segment, written at the segment's first round and read after its last
+  // round's passes, so the barriers still lie between a write and its read and between a read and the next write of its slots.
   unsigned nz = 0, par = 0;
   asm volatile("" : "+v"(par));                      // (kept in a vector register: the scalar ones are the scarce kind here)
 
   while (true) {
     const unsigned tl = t;
-    if constexpr (PF < 1) prefetch_x(fblk, tl);
+    if constexpr (PF < 1) prefetch_x(fblk, seg, tl);
     if constexpr (PF < 2) prefetch_taps(tap, tl);
     if (tap == 0) {
       bool xnz = false, ynz = false;
@@ -211,7 +248,8 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel
       } else {
         const unsigned sh = (unsigned)(__lane_id() & ~(T - 1));            // the frame's lanes of this wavefront
         const unsigned long long fm = (T == 64 ? ~0ull : ((1ull << T) - 1)) << sh;
-        nz = ((bx & fm) ? 1u : 0u) | ((by & fm) ? 2u : 0u);
+        const unsigned bits = ((bx & fm) ? 1u : 0u) | ((by & fm) ? 2u : 0u);
+        nz = WELCH != 0 && seg != 0 ? nz | bits : bits;
       }
     }
     // ---- z = (x + i y) v_j
@@ -223,20 +261,25 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel
     }
 
     // ---- which round comes next (wave-uniform)
-    int ntap = tap + 1;
+    int ntap = tap + 1, nseg = seg;
     long long nfblk = fblk;
     if (ntap == p.ntap) {
       ntap = 0;
-      nfblk += stride;
+      if constexpr (WELCH != 0) {
+        if (++nseg == cross_kernarg()->segments) nseg = 0;
+      }
+      if (nseg == 0) nfblk += stride;
     }
     const bool has_next = nfblk < p.nframes;
 
     // ---- Stockham passes; the next round's loads go out after the first exchange's writes
     stockham16_passes<LOGN, NT>(zr, zi, xb, tl, tw1row, twr, twi, [&] {
       if (has_next) {
-        if constexpr (PF >= 2) prefetch_taps(ntap, tl);
+        if constexpr (PF >= 2) {
+          if (WELCH == 0 || p.ntap != 1) prefetch_taps(ntap, tl);       // (one window: the table loaded before the loop is kept)
+        }
         if constexpr (PF >= 1) {
-          if (ntap == 0) prefetch_x(nfblk, tl);
+          if (ntap == 0) prefetch_x(nfblk, nseg, tl);
         }
       }
     });
@@ -273,10 +316,19 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel
     // mirror bins read: the barrier that frees the buffer for the next round's first-pass writes
     if constexpr (GLFER16_BARRIER_AFTER_READS != 0) frame_sync<T>();
 
-    if (ntap == 0) {
-      // ---- the frame's last taper: the quotient in double from the unscaled sums, then the stores (1/4: the two halves of the
-      // separation).  Bin N/2 is register b + B q' = 8 of lane 0 alone.
-      if constexpr (T > 64) {
+    if constexpr (WELCH != 0 && T > 64) {
+      if (ntap == 0) {                                   // a segment's last taper: its bits join the row's
+        if (seg == 0) nz = 0;
+#pragma unroll
+        for (int w = 0; w < WPF; w++) nz |= nzslot[par][fl * WPF + w];
+      }
+    }
+    if (ntap == 0 && nseg == 0) {
+      // ---- the row's last taper: the quotient in double from the unscaled sums, then the stores (1/4: the two halves of the
+      // separation; WELCH: p.scale, 1/4 over the segments).  Bin N/2 is register b + B q' = 8 of lane 0 alone.
+      // (the per-frame form collects its bits here, as it always did: merged with the block above, its instantiations at
+      // N >= 2048 come out with other register counts)
+      if constexpr (WELCH == 0 && T > 64) {
         nz = 0;
 #pragma unroll
         for (int w = 0; w < WPF; w++) nz |= nzslot[par][fl * WPF + w];
@@ -285,9 +337,8 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel
         const size_t f = (size_t)fblk + fl;
         // the four output pointers and their pitches are read from the kernel's argument block HERE, once per frame, through a
         // pointer the compiler cannot see through: held across the loop they were the scalar registers that spilled
-        const __attribute__((address_space(4))) CrossParams *kp =
-            (const __attribute__((address_space(4))) CrossParams *)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(kp));
+        const __attribute__((address_space(4))) CrossParams *kp = cross_kernarg();
+        const float scale = WELCH != 0 ? kp->scale : 0.25f;
         const long long rpitch = kp->row_pitch, xpitch = kp->sxy_pitch;
         const long long roff = BAT != 0 ? (long long)blockIdx.y * kp->row_batch_stride : 0;
         float *const o_sxx = kp->sxx ? kp->sxx + roff : nullptr;
@@ -308,9 +359,9 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel
           if constexpr (c <= 8) {
             if (c < 8 || tl == 0) {
               const unsigned k = tl + (unsigned)(T * c);
-              if (o_sxx) o_sxx[f * (size_t)rpitch + k] = 0.25f * sxx[rho];
-              if (o_syy) o_syy[f * (size_t)rpitch + k] = 0.25f * syy[rho];
-              if (o_sxy) o_sxy[f * (size_t)xpitch + k] = float2{0.25f * sre[rho], 0.25f * sim[rho]};
+              if (o_sxx) o_sxx[f * (size_t)rpitch + k] = scale * sxx[rho];
+              if (o_syy) o_syy[f * (size_t)rpitch + k] = scale * syy[rho];
+              if (o_sxy) o_sxy[f * (size_t)xpitch + k] = float2{scale * sre[rho], scale * sim[rho]};
               if (o_coh) {
 #pragma clang fp contract(off)
                 const double den = (double)sxx[rho] * (double)syy[rho];
@@ -329,6 +380,7 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16cx_kernel
     if (!has_next) break;
     fblk = nfblk;
     tap = ntap;
+    seg = nseg;
   }
 }
 
@@ -345,7 +397,7 @@ using namespace glfer;
 #define GLFER_CAT2(a, b) a##b
 #define GLFER_CAT(a, b) GLFER_CAT2(a, b)
 
-template <int FMT, int BAT>
+template <int FMT, int BAT, int WELCH>
 static hipError_t launch16cx_fmt(const CrossParams &p, hipStream_t st) {
   constexpr int L = GLFER_LOGN;
   using LC = Launch16<L>;
@@ -354,9 +406,13 @@ static hipError_t launch16cx_fmt(const CrossParams &p, hipStream_t st) {
   if (work <= 0 || p.ntap <= 0) return hipSuccess;
   const long long resident = resident_workgroups(GLFER16CX_WAVES_PER_SIMD, LC::BLOCK);
   const unsigned grid = persistent_grid(work, glfer_batch_cap(4 * resident, p.nbatch));
-  return launch(spectro16cx_kernel<L, FMT, BAT>, batch_grid(grid, p), dim3(LC::BLOCK), 0, st, p);
+  return launch(spectro16cx_kernel<L, FMT, BAT, WELCH>, batch_grid(grid, p), dim3(LC::BLOCK), 0, st, p);
 }
 
 extern "C" hipError_t GLFER_CAT(glfer_launch_spectro16cx_n, GLFER_LOGN)(const CrossParams *p, hipStream_t st) {
-  return with_fmt(p->fmt, [&](auto F) { return p->nbatch > 1 ? launch16cx_fmt<F(), 1>(*p, st) : launch16cx_fmt<F(), 0>(*p, st); });
+  // segments != 0: the segment-averaging instantiations (p->nframes counts rows)
+  return with_fmt(p->fmt, [&](auto F) {
+    if (p->segments != 0) return p->nbatch > 1 ? launch16cx_fmt<F(), 1, 1>(*p, st) : launch16cx_fmt<F(), 0, 1>(*p, st);
+    return p->nbatch > 1 ? launch16cx_fmt<F(), 1, 0>(*p, st) : launch16cx_fmt<F(), 0, 0>(*p, st);
+  });
 }

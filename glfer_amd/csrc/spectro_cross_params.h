@@ -26,6 +26,11 @@ struct CrossParams {
   long long batch_stride;  /* bytes from one stream's pair 0 to the next one's                                             */
   long long row_batch_stride;   /* floats from one stream's first row of sxx / syy / coh to the next one's                 */
   long long sxy_batch_stride;   /* float2 from one stream's first row of sxy to the next one's                             */
+  /* segment averaging (glfer_hip_welch_cross_device), appended: the offsets above do not move.  segments == 0: the one-frame-a-row
+     form, the three are not read.  Else nframes counts ROWS and row r sums the frames frame0 + r * step + s, s < segments         */
+  int segments;            /* L: frames summed into a row                                                                  */
+  float scale;             /* what the sums are stored times: 0.25 / L rounded once (0.25: the two halves of the separation) */
+  long long step;          /* frames from one row's first frame to the next row's, >= 1                                    */
 };
 
 /* the launchers glfer_launch_spectro16cx_n<logn>(const CrossParams *, hipStream_t): declared by spectro_params.h's table of built

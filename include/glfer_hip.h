@@ -683,9 +683,9 @@ int glfer_hip_spectrogram_iq_batch_device(glfer_hip_plan *plan, const void *d_iq
  * outputs NULL, a misaligned d_xy, first_frame + nframes wrapping or reaching past the stream, nframes > 0x7fffffff, sizes that
  * overflow size_t.  Asynchronous on hip_stream.
  * Not built: N = 16384 (its 1024 lanes a frame leave 128 registers a lane: the twiddles, the transform and the 36 sums do not
- * fit without spilling), Welch-style averaging of Sxy over frames for FFT plans, a phase row (atan2 of d_sxy gives it), two
+ * fit without spilling), a phase row (atan2 of d_sxy gives it), two
  * separate plane pointers, mean removal, ragged / host / WAV / workers forms, more than two channels (pairs of a C-channel
- * recording). */
+ * recording).  Averaging over frames, which is what gives FFT plans a coherence: the Welch entries below. */
 int glfer_hip_cross_supported(const glfer_hip_config *cfg);
 int glfer_hip_mtm_cross_device(glfer_hip_plan *plan, const void *d_xy, size_t nsamples, size_t first_frame, size_t nframes,
                                float *d_sxx, float *d_syy, float *d_coh, size_t row_pitch, void *d_sxy, size_t sxy_pitch,
@@ -693,6 +693,43 @@ int glfer_hip_mtm_cross_device(glfer_hip_plan *plan, const void *d_xy, size_t ns
 int glfer_hip_mtm_cross_batch_device(glfer_hip_plan *plan, const void *d_xy, size_t nstreams, size_t stream_pitch, size_t nsamples,
                                      size_t first_frame, size_t nframes, float *d_sxx, float *d_syy, float *d_coh, size_t row_pitch,
                                      void *d_sxy, size_t sxy_pitch, void *hip_stream);
+
+/* ---- Two channels, Welch's form: the cross-spectrum and coherence of L averaged segments in one pass ------------------------------
+ * The estimate known as csd / coherence: X conj(Y), |X|^2 and |Y|^2 averaged over L consecutive frames, then the quotient.  It is
+ * what gives a plan of ONE window a coherence at all, so GLFER_MODE_FFT plans with any of the eight windows are taken here, and
+ * it is the form that carries a weak line common to two receivers over a long stretch of time.  Input, frames (hop H, N - H pairs
+ * of history, both history modes), outputs, pitches and batches are those of glfer_hip_mtm_cross_device.  With J the plan's
+ * tapers (1 for an FFT plan: the table is the plan's window, c = 1 / N; a rectangular window is all ones), L = segments and
+ * step the frames from one output row to the next, row r averages the frames f = first_frame + r step + s, s = 0 .. L-1:
+ *   Sxx[r][k] = (1/L) sum_s sum_j c_j |X_{f,j}[k]|^2          Syy likewise
+ *   Sxy[r][k] = (1/L) sum_s sum_j c_j X_{f,j}[k] conj(Y_{f,j}[k])
+ *   coh[r][k] = |Sxy|^2 / (Sxx Syy)     in double from the unscaled sums, clamped to [0, 1], exactly 0 where Sxx Syy = 0
+ * step = L is Welch's block average, step < L overlapping rows (a moving estimate), step > L skips frames.  A stream of F frames
+ * has glfer_hip_welch_rows = (F - first_frame - L) / step + 1 rows, none if F - first_frame < L.  The sums run in a fixed order,
+ * segments outermost in increasing s and the tapers inside, in float: a row is a function of its own frames alone, whatever the
+ * range, step or batch that computes it.  They are stored times 0.25 / L rounded once to float, so segments = 1 stores the bits
+ * of glfer_hip_mtm_cross_device.  A channel that holds no non-zero sample in ANY of a row's L segments gets exact zeros in its
+ * spectrum, in Sxy and in coh; Im Sxy is exactly 0 at k = 0 and k = N/2.  The accuracy note above holds for every segment.
+ * One kernel per call (spectro16cx.hip: the running sums stay in registers across a row's segments; a batch above the grid's y
+ * limit: one per chunk of streams), no allocation, no host synchronisation: legal on a hip_stream that is being captured.
+ * Supported (glfer_hip_welch_cross_supported, host only: GLFER_OK or GLFER_E_ARG): FFT and MTM plans that glfer_hip_iq_supported
+ * takes, N = 256 .. 8192; 1 <= segments <= 4096 with segments * J >= 2 (one window and one segment: identically 1, refused);
+ * step >= 1 and, where a block handles FPB = 4096 / N > 1 rows, (FPB - 1) step H + N <= (2^31 - 1) / (bytes of a pair): the
+ * rows of a block read through one buffer descriptor.
+ * Arguments: as glfer_hip_mtm_cross_device, nrows in the place of nframes -- GLFER_E_ARG for a NULL plan or an unsupported plan,
+ * segments or step, a pitch below P; then GLFER_OK with nothing launched for nrows == 0 (nstreams == 0); then GLFER_E_ARG for a
+ * NULL d_xy or all four outputs NULL, a misaligned d_xy, nrows above glfer_hip_welch_rows (a frame past the stream, or
+ * first_frame + segments wrapping), nrows > 0x7fffffff, sizes that overflow size_t.  Asynchronous on hip_stream.
+ * Not built: N = 16384, mean removal, ragged / host / WAV / workers forms, exponential (running) averaging across calls, more
+ * than two channels, a phase row. */
+int glfer_hip_welch_cross_supported(const glfer_hip_config *cfg, size_t segments, size_t step);
+size_t glfer_hip_welch_rows(glfer_hip_plan *plan, size_t nsamples, size_t first_frame, size_t segments, size_t step);
+int glfer_hip_welch_cross_device(glfer_hip_plan *plan, const void *d_xy, size_t nsamples, size_t first_frame, size_t segments,
+                                 size_t step, size_t nrows, float *d_sxx, float *d_syy, float *d_coh, size_t row_pitch, void *d_sxy,
+                                 size_t sxy_pitch, void *hip_stream);
+int glfer_hip_welch_cross_batch_device(glfer_hip_plan *plan, const void *d_xy, size_t nstreams, size_t stream_pitch, size_t nsamples,
+                                       size_t first_frame, size_t segments, size_t step, size_t nrows, float *d_sxx, float *d_syy,
+                                       float *d_coh, size_t row_pitch, void *d_sxy, size_t sxy_pitch, void *hip_stream);
 
 /* ---- Zoom: a digital down-converter, and the two-sided rows of its output -------------------------------------------------------
  * A few tens of hertz around one carrier of a 48 kHz recording: instead of a block of a million samples whose transform covers the
