@@ -118,6 +118,63 @@ def multitaper32(x, n, overlap, tapers, sig, sub_mean=0, history_mode=0):
     return out
 
 
+def _half_exponent(power):
+    """odd_taper.hpp's scale_exponent, from its comment: half the binary exponent of a float32 power (power = m 2^ex with
+    0.5 <= m < 1), the exponent clamped to +-120; None for a power of exactly 0 (the kernels' kSilent)."""
+    power = np.float32(power)
+    if power == 0:
+        return None
+    ex = int(np.frexp(power)[1]) if np.isfinite(power) else 0
+    return max(-120, min(120, ex)) >> 1
+
+
+def multitaper32_paired(x, n, overlap, tapers, sig, sub_mean=0, history_mode=0, pairs=(), scales="own"):
+    """multitaper32 with the LAST taper of the frame pairs (fa, fb) of `pairs` in ONE complex float32 transform, as
+    odd_taper.hpp describes the kernels for odd taper counts (written from its comments, never from device output):
+    tapers 0 ... T-2 go one frame at a time; then z = sA yA + i sB yB with y = frame x last taper / 2 and s = 2^-hx, hx half
+    the binary exponent of the frame's float32 power over the tapers done so far (a power of exactly 0: scale 0); the mirror
+    bins separate them, E = Z[k] + conj Z[N-k] = sA Y_A[k], O = Z[k] - conj Z[N-k] = i sB Y_B[k], and |E|^2 / sA^2, |O|^2 / sB^2
+    join the frames' sums.  A frame in no pair keeps multitaper32's row.
+    scales: 'own' as above; 'unit' both scales 1 (a silent frame's too); 'exchanged' frame A enters and leaves with B's scale and
+    B with A's -- consistent, so exact arithmetic would not notice; only the rounding level each frame sees changes."""
+    assert scales in ("own", "unit", "exchanged")
+    fr = frames64(x, n, overlap, sub_mean, history_mode).astype(np.float32)
+    T = len(sig)
+    half = n // 2
+    k = np.arange(half + 1)
+    w = [np.float32(1.0 / (1.0 + sig[j])) for j in range(T)]
+    paired = sorted({f for p in pairs for f in p})
+    assert len(paired) == 2 * len(pairs) and all(0 <= f < fr.shape[0] for f in paired), "every frame in at most one pair"
+    out = multitaper32(x, n, overlap, tapers, sig, sub_mean, history_mode)
+    if not pairs:
+        return out
+    acc = np.zeros((len(paired), half + 1), np.float32)
+    for j in range(T - 1):
+        acc += _power32(_rfft32(fr[paired] * np.asarray(tapers[j], np.float32)), n) * w[j]
+    slot = {f: i for i, f in enumerate(paired)}
+    last = np.float32(0.5) * np.asarray(tapers[T - 1], np.float32)
+    for fa, fb in pairs:
+        hx = [_half_exponent(acc[slot[f]].sum(dtype=np.float32)) for f in (fa, fb)]
+        if scales == "unit":
+            hx = [0, 0]
+        elif scales == "exchanged":
+            hx = hx[::-1]
+        s_in = [np.float32(0.0) if h is None else np.float32(2.0 ** -h) for h in hx]
+        s_out = [np.float32(0.0) if h is None else np.float32(2.0 ** (2 * h)) for h in hx]
+        z = np.empty((1, n), np.complex64)
+        z.real = fr[fa] * last * s_in[0]
+        z.imag = fr[fb] * last * s_in[1]
+        Z = _fft32(z)[0]
+        Zk, Zm = Z[k], Z[(n - k) % n]
+        er, ei = Zk.real + Zm.real, Zk.imag - Zm.imag
+        orr, oi = Zk.real - Zm.real, Zk.imag + Zm.imag
+        with np.errstate(over="ignore", invalid="ignore"):
+            out[fa] = acc[slot[fa]] + (er * er + ei * ei) / np.float32(n) * w[T - 1] * s_out[0]
+            out[fb] = acc[slot[fb]] + (orr * orr + oi * oi) / np.float32(n) * w[T - 1] * s_out[1]
+    assert out.dtype == np.float32
+    return out
+
+
 # ---- the harmonic F statistic in float32 (tests/_ftest_rows_check.py takes its bounds from these) ---------------------------
 def _ftest32_tables(tapers, kmax):
     """The float32 tapers and, formed in double from them and rounded once, U0_j, sum(U0^2) and hn."""

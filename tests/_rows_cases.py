@@ -14,6 +14,8 @@ Signals, all seeded:
   bin      a 0.5 tone exactly on bin n/4 + 1 (rectangular window, overlap 0: every other bin is pure rounding);
   bin_lo / bin_hi: the same on bins 1 and n/2 - 1;   alt: +-0.5 alternating (all power at Nyquist)
   lsb1 / lsb2   integer streams of one / two LSBs of dither;   zero: digital silence
+  keyed / keyed_noise / keyed_dc   (tests/_pairs_cases.py's, no case of this module uses them) 'weak' / 0.25 sigma noise times a level
+                of KEY_LEVELS per hop; hops of 0.5 DC (exact, or over a 0.7e-6 sigma floor) among hops of 'weak'
   full / tiny   (tests/_nonlin_cases.py's, no case of this module uses them) a +-0.99 tone; a 0.7e-4 tone over 0.3e-4 sigma noise
 """
 import functools
@@ -187,6 +189,18 @@ def seed_of(c):
     return c.n + 7 * c.kmax + c.frames + 13 * len(c.signal) + 1000 * WINDOW_NAMES.index(c.window)
 
 
+KEY_LEVELS = (1.0, 1e-2, 1e-3, 1e-5, 1e-6, 0.0)
+
+
+def key_runs(rng, nhops, span, levels):
+    """One of `levels` per hop, drawn for runs of 1 ... 2 span hops (span: the hops of a frame): under overlap a frame holds
+    onsets and releases, and a run of a frame's length and more leaves whole frames at one level -- digital silence among them."""
+    out = []
+    while len(out) < nhops:
+        out += [levels[int(rng.integers(len(levels)))]] * int(rng.integers(1, 2 * span + 1))
+    return np.asarray(out[:nhops], np.float64)
+
+
 def signal(c, count, seed=None):
     """`count` float samples of the case's signal (before the conversion to its sample format)."""
     n = c.n
@@ -196,6 +210,16 @@ def signal(c, count, seed=None):
     if c.signal == "weak":
         k0, k1 = 0.23 * n + 0.37, 0.37 * n + 0.21
         x = 0.7 * np.sin(2 * np.pi * k0 * t / n + 0.3) + 0.7e-4 * np.sin(2 * np.pi * k1 * t / n + 1.1) + 0.7e-6 * rng.standard_normal(count)
+    elif c.signal in ("keyed", "keyed_noise", "keyed_dc"):    # (tests/_pairs_cases.py: a level per hop)
+        weak = 0.7 * np.sin(2 * np.pi * (0.23 * n + 0.37) * t / n + 0.3) + 0.7e-4 * np.sin(2 * np.pi * (0.37 * n + 0.21) * t / n + 1.1) \
+            + 0.7e-6 * rng.standard_normal(count)
+        nhops = -(-count // h)
+        if c.signal == "keyed_dc":
+            kind = np.repeat(key_runs(rng, nhops, -(-n // h), (0.0, 1.0, 2.0)), h)[:count]
+            x = np.where(kind == 0, weak, np.where(kind == 1, 0.5, 0.5 + 0.7e-6 * rng.standard_normal(count)))
+        else:
+            base = weak if c.signal == "keyed" else 0.25 * rng.standard_normal(count)
+            x = base * np.repeat(key_runs(rng, nhops, -(-n // h), KEY_LEVELS), h)[:count]
     elif c.signal == "noise":
         x = 0.25 * rng.standard_normal(count)
     elif c.signal == "synth":
