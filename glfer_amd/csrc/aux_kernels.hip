@@ -1115,13 +1115,13 @@ extern "C" hipError_t glfer_launch_avg_ragged(int mode, const float *psd, const 
       norm.add(e, e.nframes);
     }
   }
-  RaggedColsEntry *d_tabs = nullptr;
-  hipError_t err = ragged_upload({&fused, &cum, &norm}, &d_tabs, st);
+  Scratch<RaggedColsEntry> d_tabs(st);
+  hipError_t err = ragged_upload({&fused, &cum, &norm}, d_tabs);
   if (err != hipSuccess || !d_tabs) return err;
   const size_t ring_bytes = (size_t)depth * bpt_of(bpt) * 256 * sizeof(float);
   const bool ring = ring_bytes <= 60 * 1024;                   // (launch_avg's rule)
   for (const RaggedPiece &pc : fused.pieces) {
-    const RaggedCols rc = fused.cols(d_tabs, pc);
+    const RaggedCols rc = fused.cols(d_tabs.get(), pc);
     const unsigned blocks = (unsigned)pc.blocks;
 #define GLFER_AVG_FUSED_RAG(B)                                                                                          \
   do {                                                                                                                  \
@@ -1140,15 +1140,14 @@ extern "C" hipError_t glfer_launch_avg_ragged(int mode, const float *psd, const 
   }
   for (const RaggedPiece &pc : cum.pieces) {
     hipLaunchKernelGGL((avg_cum_kernel<false, true>), dim3((unsigned)pc.blocks, (unsigned)((band + 255) / 256)), dim3(256), 0, st, psd, 0ll,
-                       bins, n_out, depth, minbin, maxbin, avg, cum.cols(d_tabs, pc));
+                       bins, n_out, depth, minbin, maxbin, avg, cum.cols(d_tabs.get(), pc));
     if (err == hipSuccess) err = hipGetLastError();
   }
   for (const RaggedPiece &pc : norm.pieces) {
     hipLaunchKernelGGL((avg_norm_kernel<false, true>), dim3((unsigned)pc.blocks), dim3(256), 0, st, psd, bins, n_out, depth, minbin, maxbin,
-                       mode, max0, avg, ret, norm.cols(d_tabs, pc));
+                       mode, max0, avg, ret, norm.cols(d_tabs.get(), pc));
     if (err == hipSuccess) err = hipGetLastError();
   }
-  scratch_free(d_tabs, st);
   return err;
 }
 
@@ -1271,22 +1270,22 @@ extern "C" hipError_t glfer_launch_avgmap_ragged(int mode, const float *psd, con
     e.chunk = shape.chunk;
     tab.add(e, (e.nframes + shape.chunk - 1) / shape.chunk);
   }
-  RaggedColsEntry *d_tabs = nullptr;
-  hipError_t err = ragged_upload({&tab}, &d_tabs, st);
+  Scratch<RaggedColsEntry> d_tabs(st);
+  hipError_t err = ragged_upload({&tab}, d_tabs);
   if (err != hipSuccess || !d_tabs) return err;
   const int bpt = shape.bpt;
   const bool ring = shape.ring;
   const size_t shmem = shape.shmem;
   const AvgMapArgs ma{levels, colortab, log_thr, rgb, lev, scale_log, thr255, one_m_thr, 0};
   for (const RaggedPiece &pc : tab.pieces) {
-    const RaggedCols rc = tab.cols(d_tabs, pc);
+    const RaggedCols rc = tab.cols(d_tabs.get(), pc);
     const unsigned blocks = (unsigned)pc.blocks;
 #define GLFER_AVGMAP_RAG_NT(B, NT)                                                                                      \
   do {                                                                                                                  \
     const void *fn = ring ? reinterpret_cast<const void *>(avg_fused_kernel<B, true, true, NT, false, true>)            \
                           : reinterpret_cast<const void *>(avg_fused_kernel<B, false, true, NT, false, true>);          \
     hipError_t e = allow_dynamic_lds(fn, shmem);                                                                        \
-    if (e != hipSuccess) { scratch_free(d_tabs, st); return e; }                                                        \
+    if (e != hipSuccess) return e;                                                                                      \
     if (ring) hipLaunchKernelGGL((avg_fused_kernel<B, true, true, NT, false, true>), dim3(blocks), dim3(NT), shmem, st, psd, 0ll, 0, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma, rc); \
     else hipLaunchKernelGGL((avg_fused_kernel<B, false, true, NT, false, true>), dim3(blocks), dim3(NT), shmem, st, psd, 0ll, 0, bins, bins, depth, minbin, maxbin, mode, max0, (double *)nullptr, (double *)nullptr, ma, rc); \
   } while (0)
@@ -1310,7 +1309,6 @@ extern "C" hipError_t glfer_launch_avgmap_ragged(int mode, const float *psd, con
 #undef GLFER_AVGMAP_RAG
     if (err == hipSuccess) err = hipGetLastError();
   }
-  scratch_free(d_tabs, st);
   return err;
 }
 

@@ -511,20 +511,19 @@ extern "C" hipError_t glfer_launch_levels_ragged(const float *stats, const Ragge
     if (tab.pieces.size() != pieces) piece_chunk0.push_back(chunks_before);
     chunks_before += nchunks;
   }
-  RaggedColsEntry *d_tabs = nullptr;
-  hipError_t err = ragged_upload({&tab}, &d_tabs, st);
+  Scratch<RaggedColsEntry> d_tabs(st);
+  hipError_t err = ragged_upload({&tab}, d_tabs);
   if (err != hipSuccess || !d_tabs) return err;
   LevelsParams p{scale_log, 1, 0, overlap, 0.0f, 0.0f};
   for (size_t k = 0; k < tab.pieces.size(); k++) {
     const RaggedPiece &pc = tab.pieces[k];
-    const LevelsRagged lr{tab.cols(d_tabs, pc), state};
+    const LevelsRagged lr{tab.cols(d_tabs.get(), pc), state};
     float *cs = chunk_state + piece_chunk0[k] * 4;
     hipLaunchKernelGGL((levels_kernel<false, true>), dim3((unsigned)pc.blocks), dim3(64), 0, st, stats, 0ll, p, levels, cs, lr);
     if (err == hipSuccess) err = hipGetLastError();
     hipLaunchKernelGGL((levels_fixup_kernel<false, true>), dim3((unsigned)pc.count), dim3(64), 0, st, stats, 0ll, p, levels, cs, 0, lr);
     if (err == hipSuccess) err = hipGetLastError();
   }
-  scratch_free(d_tabs, st);
   return err;
 }
 
@@ -537,14 +536,13 @@ extern "C" hipError_t glfer_launch_map_ragged(const double *avg, const RaggedCol
   RaggedTable tab;
   for (size_t i = 0; i < n; i++)
     if (streams[i].nframes > 0) tab.add(streams[i], streams[i].nframes);
-  RaggedColsEntry *d_tabs = nullptr;
-  hipError_t err = ragged_upload({&tab}, &d_tabs, st);
+  Scratch<RaggedColsEntry> d_tabs(st);
+  hipError_t err = ragged_upload({&tab}, d_tabs);
   if (err != hipSuccess || !d_tabs) return err;
   for (const RaggedPiece &pc : tab.pieces) {
     hipLaunchKernelGGL((map_kernel<double, false, true>), dim3((unsigned)pc.blocks), dim3(256), 0, st, avg, bins, bins, scale_log, thr255,
-                       one_m_thr, levels, colortab, log_thr, rgb, lev, tab.cols(d_tabs, pc));
+                       one_m_thr, levels, colortab, log_thr, rgb, lev, tab.cols(d_tabs.get(), pc));
     if (err == hipSuccess) err = hipGetLastError();
   }
-  scratch_free(d_tabs, st);
   return err;
 }

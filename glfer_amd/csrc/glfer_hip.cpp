@@ -88,257 +88,6 @@ int data_device(const void *d_ptr) {
   if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
   return dev;
 }
-// ---- scratch.  Three sources, by size:
-//   * under 1 MiB (statistics, tables, level states): a stream-ordered pool of their own, so that
-//     they never carve a piece out of a large free block of the default pool;
-//   * 1 MiB .. 16 MiB: the device's default stream-ordered pool, release threshold raised (by default
-//     it hands everything back at the next synchronisation);
-//   * 16 MiB and more (averaged rows, a mean-corrected copy of a stream, the big-block scratch,
-//     LMP / F-test spectra: hundreds of MB to GB): blocks this library keeps (plain hipMalloc, size
-//     classes a sixteenth of a power of two apart, at most kBigBlocks per device, never returned
-//     before the process ends).  The stream-ordered pool is not made for these: tools/pooltail on this
-//     stack -- 2.2 GiB malloc + touch + free + sync per call, sizes alternating by 64 KB: median 2.0 ms
-//     a call and ONE CALL IN THREE over 10 ms, up to 4 s (a waterfall call with 2 GiB of averaged
-//     rows: 2.3 ms, one in ~100 taking 4.4 s); the same through one kept block: 17 us, never more than
-//     24.  A kept block is handed out under a mutex; giving it back records an event on the stream
-//     that used it, and the next taker on ANOTHER stream waits for that event first (stream order
-//     preserved, nothing synchronised on the host).  When all kept blocks are out (concurrent calls)
-//     or would not fit, the request falls through to the pool.  GLFER_SCRATCH_CACHE=0 turns it off.
-namespace {
-constexpr int kBigBlocks = 6;
-constexpr size_t kBigMin = (size_t)16 << 20;
-struct BigBlock {
-  void *p = nullptr;
-  size_t cap = 0;
-  bool out = false;
-  hipEvent_t freed = nullptr;
-  hipStream_t last = nullptr;
-  bool used = false;                                 // an event has been recorded on it
-  int dev = -1;                                      // the device it was allocated on
-};
-struct DeviceScratch {
-  bool init = false;
-  hipMemPool_t small_pool = nullptr;
-  BigBlock big[kBigBlocks];
-};
-std::mutex g_scratch_mu;
-DeviceScratch g_scratch[64];
-// Bytes of kept blocks per device above which IDLE blocks are given back before a new one is made
-// (GLFER_SCRATCH_CAP_MB; default 16 GiB of a 288 GB card; glfer_hip_scratch_limit sets it at run time).
-// A single request larger than the cap is still served -- by a kept block that is the only one.
-size_t g_scratch_cap = [] {
-  const char *e = getenv("GLFER_SCRATCH_CAP_MB");
-  return e && *e ? (size_t)strtoull(e, nullptr, 10) << 20 : (size_t)16 << 30;
-}();
-// Frees one idle kept block (after the work recorded on it has completed).  Caller holds the mutex
-// and has the block's device current.
-void drop_block(BigBlock &b) {
-  if (b.used) (void)hipEventSynchronize(b.freed);
-  (void)hipFree(b.p);
-  (void)hipEventDestroy(b.freed);
-  b = BigBlock();
-}
-// Idle kept blocks of a device, smallest first, until at most `keep_bytes` stay (blocks that are out
-// with a call stay and count).  Returns the bytes freed.
-size_t trim_locked(DeviceScratch &ds, size_t keep_bytes) {
-  size_t held = 0, freed = 0;
-  for (BigBlock &b : ds.big)
-    if (b.p) held += b.cap;
-  while (held > keep_bytes) {
-    BigBlock *victim = nullptr;
-    for (BigBlock &b : ds.big)
-      if (b.p && !b.out && (!victim || b.cap < victim->cap)) victim = &b;
-    if (!victim) break;
-    held -= victim->cap;
-    freed += victim->cap;
-    drop_block(*victim);
-  }
-  return freed;
-}
-bool scratch_cache_on() {
-  static const bool on = [] {
-    const char *e = getenv("GLFER_SCRATCH_CACHE");
-    return !(e && atoi(e) == 0 && *e);
-  }();
-  return on;
-}
-}  // namespace
-
-bool scratch_keeping() { return scratch_cache_on(); }
-size_t scratch_cap() {
-  std::lock_guard<std::mutex> lock(g_scratch_mu);
-  return g_scratch_cap;
-}
-
-hipError_t scratch_malloc(void **p, size_t bytes, hipStream_t st) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipMallocAsync(p, bytes, st);
-  std::unique_lock<std::mutex> lock(g_scratch_mu);
-  DeviceScratch &ds = g_scratch[dev];
-  if (!ds.init) {
-    ds.init = true;
-    hipMemPool_t pool = nullptr;
-    uint64_t keep = (uint64_t)8 << 30;
-    if (hipDeviceGetDefaultMemPool(&pool, dev) != hipSuccess ||
-        hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep) != hipSuccess)
-      (void)hipGetLastError();                   // the pool keeps its default: slower, not wrong
-    hipMemPoolProps props = {};
-    props.allocType = hipMemAllocationTypePinned;
-    props.handleTypes = hipMemHandleTypeNone;
-    props.location.type = hipMemLocationTypeDevice;
-    props.location.id = dev;
-    uint64_t keep_small = (uint64_t)64 << 20;
-    if (hipMemPoolCreate(&ds.small_pool, &props) != hipSuccess ||
-        hipMemPoolSetAttribute(ds.small_pool, hipMemPoolAttrReleaseThreshold, &keep_small) != hipSuccess) {
-      (void)hipGetLastError();                   // no second pool: everything from the default one
-      ds.small_pool = nullptr;
-    }
-  }
-  if (bytes < ((size_t)1 << 20) && ds.small_pool) {
-    hipMemPool_t from = ds.small_pool;
-    lock.unlock();
-    return hipMallocFromPoolAsync(p, bytes, from, st);
-  }
-  if (bytes >= kBigMin && scratch_cache_on()) {
-    size_t cls = (size_t)1 << 20;                    // size classes: a batch one row longer finds the block of the last call
-    while (cls * 32 <= bytes) cls <<= 1;
-    const size_t want = (bytes + cls - 1) / cls * cls;
-    BigBlock *best = nullptr, *empty = nullptr;
-    for (BigBlock &b : ds.big) {
-      if (!b.p) {
-        if (!empty) empty = &b;
-      } else if (!b.out && b.cap >= want && (!best || b.cap < best->cap)) {
-        best = &b;
-      }
-    }
-    if (!best && !empty) {                           // every slot taken by smaller blocks: the smallest idle one makes room
-      BigBlock *victim = nullptr;
-      for (BigBlock &b : ds.big)
-        if (!b.out && b.cap < want && (!victim || b.cap < victim->cap)) victim = &b;
-      if (victim) {
-        drop_block(*victim);
-        empty = victim;
-      }
-    }
-    if (!best && empty) {                            // a new kept block (synchronous hipMalloc: once per size class)
-      // the byte cap: idle blocks go first (none of them fits -- `best` would have been one)
-      size_t held = 0;
-      for (BigBlock &b : ds.big)
-        if (b.p) held += b.cap;
-      if (held + want > g_scratch_cap) trim_locked(ds, g_scratch_cap > want ? g_scratch_cap - want : 0);
-      void *q = nullptr;
-      hipEvent_t ev = nullptr;
-      hipError_t me = hipMalloc(&q, want);
-      if (me != hipSuccess) {                        // out of memory: every idle kept block goes back, then once more
-        (void)hipGetLastError();
-        q = nullptr;
-        if (trim_locked(ds, 0) > 0) me = hipMalloc(&q, want);
-        for (BigBlock &b : ds.big)                   // the slot may have moved: any empty one will do
-          if (!b.p) { empty = &b; break; }
-      }
-      if (me == hipSuccess && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) {
-        empty->p = q;
-        empty->cap = want;
-        empty->freed = ev;
-        empty->used = false;
-        empty->dev = dev;
-        best = empty;
-      } else {
-        (void)hipGetLastError();
-        if (q) (void)hipFree(q);
-      }
-    }
-    if (best) {
-      best->out = true;
-      hipError_t e = hipSuccess;
-      if (best->used && best->last != st) e = hipStreamWaitEvent(st, best->freed, 0);
-      if (e != hipSuccess) {
-        best->out = false;
-        return e;
-      }
-      *p = best->p;
-      return hipSuccess;
-    }
-  }
-  lock.unlock();
-  return hipMallocAsync(p, bytes, st);
-}
-
-// gives back what scratch_malloc handed out (stream-ordered either way)
-void scratch_free(void *q, hipStream_t st) {
-  if (!q) return;
-  {
-    std::lock_guard<std::mutex> lock(g_scratch_mu);
-    for (DeviceScratch &ds : g_scratch)
-      for (BigBlock &b : ds.big)
-        if (b.p == q) {
-          // the event is recorded on the stream that used the block -- a stream of the block's own
-          // device, which need not be the caller's current one
-          int cur = -1;
-          const bool moved = hipGetDevice(&cur) == hipSuccess && cur != b.dev && b.dev >= 0 && hipSetDevice(b.dev) == hipSuccess;
-          if (hipEventRecord(b.freed, st) == hipSuccess) {
-            b.used = true;
-            b.last = st;
-          } else {
-            // no event to order the next taker behind: wait here for the work on `st`, after which
-            // the block is free for any stream (used = false: nothing to wait for)
-            (void)hipGetLastError();
-            if (hipStreamSynchronize(st) != hipSuccess) {
-              (void)hipGetLastError();               // not even that: the block leaves the cache for good
-              (void)hipDeviceSynchronize();
-              (void)hipFree(b.p);
-              (void)hipEventDestroy(b.freed);
-              b = BigBlock();
-              if (moved) (void)hipSetDevice(cur);
-              return;
-            }
-            b.used = false;
-            b.last = nullptr;
-          }
-          b.out = false;
-          // the cap bounds what is KEPT, not only what is newly made: a block handed back while the
-          // device holds more than the cap -- a reused block larger than a cap set since, glfer_hip_scratch_limit(0)
-          // -- goes back now (drop_block waits for the event just recorded, then hipFree)
-          if (b.dev >= 0 && b.dev < 64) trim_locked(g_scratch[b.dev], g_scratch_cap);
-          if (moved) (void)hipSetDevice(cur);
-          return;
-        }
-  }
-  (void)hipFreeAsync(q, st);
-}
-
-// glfer_hip_scratch_trim / glfer_hip_scratch_limit (include/glfer_hip.h)
-size_t scratch_trim(int dev, size_t keep_bytes) {
-  if (dev < 0 || dev >= 64) return 0;
-  DeviceGuard guard(dev);
-  std::lock_guard<std::mutex> lock(g_scratch_mu);
-  return trim_locked(g_scratch[dev], keep_bytes);
-}
-size_t scratch_held(int dev) {
-  if (dev < 0 || dev >= 64) return 0;
-  std::lock_guard<std::mutex> lock(g_scratch_mu);
-  size_t held = 0;
-  for (BigBlock &b : g_scratch[dev].big)
-    if (b.p) held += b.cap;
-  return held;
-}
-void scratch_set_cap(size_t bytes) {
-  std::lock_guard<std::mutex> lock(g_scratch_mu);
-  g_scratch_cap = bytes;
-  // idle blocks above the new cap go back at once, on every device that holds any
-  int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-  for (int dev = 0; dev < 64; dev++) {
-    size_t held = 0;
-    for (BigBlock &b : g_scratch[dev].big)
-      if (b.p) held += b.cap;
-    if (held <= bytes) continue;
-    if (dev != cur && hipSetDevice(dev) != hipSuccess) { (void)hipGetLastError(); continue; }
-    trim_locked(g_scratch[dev], bytes);
-    if (dev != cur && cur >= 0) (void)hipSetDevice(cur);
-  }
-}
-
 // Dynamic LDS above the default limit has to be allowed per kernel -- and per DEVICE: a process that
 // drives several GPUs (glfer_hip_spectrogram_host_multi) launches the same kernel on each.  One call
 // per (device, kernel) and size class, not one per launch.
@@ -1256,8 +1005,9 @@ static bool reference_means(const glfer_hip_plan *p) { return p->cfg.sub_mean !=
 // its fresh samples over a copy of the previous hop's RAW samples; what the reference's buffer
 // holds there is the previous hop AFTER its mean removal (wav_fmt.c:102-119 over fft.c:93-95), so
 // the last hop is rebuilt from the corrected previous hop before its own mean is taken.
+// The copy is the caller's to hold until its launches are enqueued: it is left in `copy`, a guard on `st`.
 static int submean_scratch(const glfer_hip_plan *p, SpectroParams &sp, size_t first, size_t nframes, hipStream_t st,
-                           float **scratch_out, long tail_fresh = -1) {
+                           glfer::Scratch<float> &copy, long tail_fresh = -1) {
   // A batch (sp.nbatch streams, sp.batch_stride bytes apart): one copy per stream, side by side in one scratch block, from
   // launches that cover the whole batch; sp leaves with the copy of stream 0 and the copies' stride.
   const unsigned nb = glfer_batch_y(sp);
@@ -1269,35 +1019,33 @@ static int submean_scratch(const glfer_hip_plan *p, SpectroParams &sp, size_t fi
   const size_t hops_back = glfer_hops_back(sp.history_mode, plan_first_inside(p));
   const glfer_hop_span h = glfer_copy_hops(first, nframes, hops_back, tail_fresh >= 0);
   const size_t hop_lo = h.lo, nhops = h.n, per = nhops * (size_t)p->hop;
-  float *scratch = nullptr;
-  HIP_TRY(glfer::scratch_malloc((void **)&scratch, (size_t)nb * per * sizeof(float), st));
+  HIP_TRY(copy.take((size_t)nb * per));
+  float *scratch = copy.get();
   const size_t esz = glfer_sample_size(sp.fmt);
   const char *src = (const char *)sp.stream + hop_lo * (size_t)p->hop * esz;
   // GLFER_SUBMEAN_EXACT: the hop means first, accumulated sample after sample as fft.c:88-92 does
   // (submean_seq.hip: one more read of the stream), then the copy with those means
   const bool exact = reference_means(p);
-  float *means = nullptr;
+  glfer::Scratch<float> means(st);
   hipError_t e = hipSuccess;
   if (exact) {
-    e = glfer::scratch_malloc((void **)&means, (size_t)nb * nhops * sizeof(float), st);
+    e = means.take((size_t)nb * nhops);
     if (e == hipSuccess)
-      e = glfer_launch_hop_means_seq_batch(src, means, p->hop, (long long)nhops, sp.fmt, nb, sp.batch_stride, (long long)nhops, st);
+      e = glfer_launch_hop_means_seq_batch(src, means.get(), p->hop, (long long)nhops, sp.fmt, nb, sp.batch_stride, (long long)nhops, st);
   }
   if (e == hipSuccess)
-    e = glfer_launch_submean_batch(src, scratch, p->hop, (long long)nhops, sp.fmt, st, means, nb, sp.batch_stride, (long long)per,
+    e = glfer_launch_submean_batch(src, scratch, p->hop, (long long)nhops, sp.fmt, st, means.get(), nb, sp.batch_stride, (long long)per,
                                    (long long)nhops);
   if (e == hipSuccess && tail_fresh >= 0)
     e = glfer_launch_submean_tail_ex(src + (nhops - 1) * (size_t)p->hop * esz, nhops > 1 ? scratch + (nhops - 2) * (size_t)p->hop : nullptr,
                                      scratch + (nhops - 1) * (size_t)p->hop, p->hop, (int)tail_fresh, exact ? 1 : 0, sp.fmt, st);
-  if (means) glfer::scratch_free(means, st);
   if (e != hipSuccess) {
-    glfer::scratch_free(scratch, st);
+    copy.release();
     return hip_fail(e, "glfer_launch_submean");
   }
   sp.stream = reinterpret_cast<const char *>(scratch) - hop_lo * (size_t)p->hop * sizeof(float);
   sp.fmt = GLFER_FMT_F32;
   if (nb > 1) sp.batch_stride = (long long)(per * sizeof(float));
-  *scratch_out = scratch;
   return GLFER_OK;
 }
 
@@ -1367,9 +1115,11 @@ static int launch_body_with_reference_means(glfer_hip_plan *p, const SpectroPara
   }
   const size_t npieces = (b1 - b0 + piece - 1) / piece;
   int nstreams = npieces > 1 ? nstreams_env : 1;
-  float *means = nullptr;
-  hipError_t e = glfer::scratch_malloc((void **)&means, nhops * sizeof(float), st);
+  // (on the caller's stream: the piecewise form gives it back below, after the join of the side streams and the failure path's waits)
+  glfer::Scratch<float> means_buf(st);
+  hipError_t e = means_buf.take(nhops);
   if (e != hipSuccess) return hip_fail(e, "scratch (hop means)");
+  float *const means = means_buf.get();
   SpectroParams q = bs;
   q.means = means - hop_lo;                                                    // indexed by GLOBAL hop (= frame) index
   // THE FUSED LAUNCH (round 4, the periodogram's table form, N <= 8192; an EXPERIMENT, off by default): the hop means are
@@ -1394,8 +1144,9 @@ static int launch_body_with_reference_means(glfer_hip_plan *p, const SpectroPara
       const bool lockstep = block_frames > 0;
       const int chunk = lockstep ? 64 : 4096;
       const size_t nchunks = (nhops + chunk - 1) / chunk;
-      unsigned *ready = nullptr;
-      e = glfer::scratch_malloc((void **)&ready, (nchunks + 8) * sizeof(unsigned), st);
+      glfer::Scratch<unsigned> ready_buf(st);
+      e = ready_buf.take(nchunks + 8);
+      unsigned *const ready = ready_buf.get();
       if (e == hipSuccess) e = hipMemsetAsync(ready, 0, (nchunks + 8) * sizeof(unsigned), st);
       if (e == hipSuccess) {
         q.nprod = (int)(producers / 8 * 8);
@@ -1412,8 +1163,6 @@ static int launch_body_with_reference_means(glfer_hip_plan *p, const SpectroPara
         }
         e = launch_by_n(q, p->n, st);
       }
-      if (ready) glfer::scratch_free(ready, st);
-      glfer::scratch_free(means, st);
       return e == hipSuccess ? GLFER_OK : hip_fail(e, "estimator launch (hop means produced in the launch)");
     }
   }
@@ -1450,7 +1199,6 @@ static int launch_body_with_reference_means(glfer_hip_plan *p, const SpectroPara
       q.psd = bs.psd + (f0 - b0) * (size_t)p->pitch;
       if (e == hipSuccess) e = launch_by_n(q, p->n, st);
     }
-    glfer::scratch_free(means, st);
     return e == hipSuccess ? GLFER_OK : hip_fail(e, "estimator launch (given hop means)");
   }
   // means(c) on aux[0]; estimator(c) on the caller's stream (or alternately aux[1]) after means(c); means(c + 2) not before
@@ -1486,7 +1234,7 @@ static int launch_body_with_reference_means(glfer_hip_plan *p, const SpectroPara
     (void)hipStreamSynchronize(sm);
     if (nstreams > 2) (void)hipStreamSynchronize(p->aux[1]);
   }
-  glfer::scratch_free(means, st);
+  means_buf.release();
   if (own_aux) {
     std::lock_guard<std::mutex> lock(aux_mu);
     p->aux_busy = false;
@@ -1513,13 +1261,12 @@ static int launch_mean_inkernel(glfer_hip_plan *p, const SpectroParams &sp, hipS
     hs.frame0 = (long long)from;
     hs.nframes = (int)(to - from);
     hs.psd = sp.psd + (from - first) * (size_t)p->pitch;
-    float *scratch = nullptr;
-    rc = submean_scratch(p, hs, from, to - from, st, &scratch);
+    glfer::Scratch<float> copy(st);
+    rc = submean_scratch(p, hs, from, to - from, st, copy);
     if (rc == GLFER_OK) {
       hipError_t e = launch_by_n(hs, p->n, st);
       if (e != hipSuccess) rc = hip_fail(e, nb > 1 ? "estimator launch (batch, frames through the corrected copies)" : "estimator launch (frames through the corrected copy)");
     }
-    if (scratch) glfer::scratch_free(scratch, st);
   };
   by_copy(first, b0);
   if (rc == GLFER_OK && b1 > b0) {
@@ -1536,15 +1283,14 @@ static int launch_mean_inkernel(glfer_hip_plan *p, const SpectroParams &sp, hipS
       rc = launch_body_with_reference_means(p, bs, b0, b1, st);
     } else {                                                             // a batch: one table per stream, nhops apart, from one launch
       const glfer_hop_span h = glfer_means_hops(b0, b1, 0, first_inside);
-      float *means = nullptr;
-      hipError_t e = glfer::scratch_malloc((void **)&means, (size_t)nb * h.n * sizeof(float), st);
+      glfer::Scratch<float> means(st);
+      hipError_t e = means.take((size_t)nb * h.n);
       if (e == hipSuccess)
-        e = glfer_launch_hop_means_seq_batch((const char *)sp.stream + h.lo * (size_t)p->hop * glfer_sample_size(sp.fmt), means, p->hop,
+        e = glfer_launch_hop_means_seq_batch((const char *)sp.stream + h.lo * (size_t)p->hop * glfer_sample_size(sp.fmt), means.get(), p->hop,
                                              (long long)h.n, sp.fmt, nb, sp.batch_stride, (long long)h.n, st);
-      bs.means = means - h.lo;                                           // indexed by the stream's own hop (= frame) index
+      bs.means = means.get() - h.lo;                                     // indexed by the stream's own hop (= frame) index
       bs.means_batch_stride = (long long)h.n;
       if (e == hipSuccess) e = launch_by_n(bs, p->n, st);
-      if (means) glfer::scratch_free(means, st);
       if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch, mean removal in the kernel)");
     }
   }
@@ -1570,57 +1316,41 @@ int glfer_run_device(glfer_hip_plan *p, const void *d_stream, size_t nsamples, s
   sp.psd = d_psd;
   sp.spec = d_spec;
 
-  float *scratch = nullptr, *rows = nullptr;
-  int rc = GLFER_OK;
+  glfer::Scratch<float> copy(st), rows(st);
   if (tail_fresh >= 0 && (tail_fresh >= (long)p->hop || p->cfg.mode == GLFER_MODE_LMP)) return GLFER_E_ARG;
   const bool inkernel = p->cfg.sub_mean && mean_inkernel_ok(p, sp, d_spec, tail_fresh);
   if (inkernel && p->cfg.mode != GLFER_MODE_LMP) return launch_mean_inkernel(p, sp, st);
-  if (p->cfg.sub_mean && !inkernel) rc = submean_scratch(p, sp, first, nframes, st, &scratch, tail_fresh);
-  if (rc == GLFER_OK && p->cfg.mode == GLFER_MODE_LMP) {
-    // lmp.c:101-181: periodograms of the frames the ring holds when frame first+nframes-1 is done
-    // (lmp_av - 1 frames before `first`, recomputed rather than carried), then the statistic
-    const size_t back = std::min<size_t>((size_t)p->lmp_av - 1, first);
-    const size_t nrows = nframes + back;
-    hipError_t e = glfer::scratch_malloc((void **)&rows, nrows * (size_t)p->bins * sizeof(float), st);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMallocAsync(lmp rows)");
-    if (rc == GLFER_OK && inkernel) {
-      sp.frame0 = (long long)(first - back);
-      sp.nframes = (int)nrows;
-      sp.psd = rows;
-      rc = launch_mean_inkernel(p, sp, st);
-      if (rc == GLFER_OK) {
-        e = glfer_launch_lmp(rows, (long long)(first - back), (long long)first, nframes, p->bins, p->lmp_av, d_psd, st);
-        if (e != hipSuccess) rc = hip_fail(e, "lmp launch");
-      }
-      glfer::scratch_free(rows, st);
-      return rc;
-    }
-    if (rc == GLFER_OK && back && p->cfg.sub_mean) {
-      // the extra frames reach further back than the hops corrected above
-      glfer::scratch_free(scratch, st);
-      scratch = nullptr;
-      sp.stream = d_stream;
-      sp.fmt = p->cfg.sample_format;
-      rc = submean_scratch(p, sp, first - back, nrows, st, &scratch);
-    }
-    if (rc == GLFER_OK) {
-      sp.frame0 = (long long)(first - back);
-      sp.nframes = (int)nrows;
-      sp.psd = rows;
-      e = launch_by_n(sp, p->n, st);
-      if (e == hipSuccess)
-        e = glfer_launch_lmp(rows, (long long)(first - back), (long long)first, nframes, p->bins, p->lmp_av, d_psd, st);
-      if (e != hipSuccess) rc = hip_fail(e, "lmp launch");
-    }
-  } else if (rc == GLFER_OK) {
-    hipError_t e = p->cfg.mode == GLFER_MODE_HPARMA
-                       ? glfer_launch_hparma(&sp, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched, p->rot_steps, p->rot_width, p->d_lagmap, p->d_unit, st)
-                       : launch_by_n(sp, p->n, st);
-    if (e != hipSuccess) rc = hip_fail(e, "estimator launch");
+  if (p->cfg.sub_mean && !inkernel)
+    if (const int rc = submean_scratch(p, sp, first, nframes, st, copy, tail_fresh); rc != GLFER_OK) return rc;
+  if (p->cfg.mode != GLFER_MODE_LMP) {
+    const hipError_t e = p->cfg.mode == GLFER_MODE_HPARMA
+                             ? glfer_launch_hparma(&sp, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched, p->rot_steps, p->rot_width, p->d_lagmap, p->d_unit, st)
+                             : launch_by_n(sp, p->n, st);
+    return e == hipSuccess ? GLFER_OK : hip_fail(e, "estimator launch");
   }
-  if (rows) glfer::scratch_free(rows, st);
-  if (scratch) glfer::scratch_free(scratch, st);
-  return rc;
+  // lmp.c:101-181: periodograms of the frames the ring holds when frame first+nframes-1 is done
+  // (lmp_av - 1 frames before `first`, recomputed rather than carried), then the statistic
+  const size_t back = std::min<size_t>((size_t)p->lmp_av - 1, first);
+  const size_t nrows = nframes + back;
+  hipError_t e = rows.take(nrows * (size_t)p->bins);
+  if (e != hipSuccess) return hip_fail(e, "hipMallocAsync(lmp rows)");
+  if (!inkernel && back && p->cfg.sub_mean) {
+    // the extra frames reach further back than the hops corrected above
+    sp.stream = d_stream;
+    sp.fmt = p->cfg.sample_format;
+    if (const int rc = submean_scratch(p, sp, first - back, nrows, st, copy); rc != GLFER_OK) return rc;
+  }
+  sp.frame0 = (long long)(first - back);
+  sp.nframes = (int)nrows;
+  sp.psd = rows.get();
+  if (inkernel) {
+    if (const int rc = launch_mean_inkernel(p, sp, st); rc != GLFER_OK) return rc;
+  } else {
+    e = launch_by_n(sp, p->n, st);
+    if (e != hipSuccess) return hip_fail(e, "lmp launch");
+  }
+  e = glfer_launch_lmp(rows.get(), (long long)(first - back), (long long)first, nframes, p->bins, p->lmp_av, d_psd, st);
+  return e == hipSuccess ? GLFER_OK : hip_fail(e, "lmp launch");
 }
 
 extern "C" {
@@ -1712,9 +1442,9 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
       if (rc != GLFER_OK) return rc;
       continue;
     }
-    float *rows = nullptr;
+    glfer::Scratch<float> rows(st);
     if (lmp) {
-      const hipError_t e = glfer::scratch_malloc((void **)&rows, (size_t)nb * lmp_bs * sizeof(float), st);
+      const hipError_t e = rows.take((size_t)nb * lmp_bs);
       if (e != hipSuccess) return hip_fail(e, "scratch (lmp rows, batch)");
     }
     SpectroParams sp;
@@ -1722,31 +1452,26 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
     sp.stream = base + c0 * stream_pitch * esz;
     sp.frame0 = (long long)(first - back);
     sp.nframes = (int)nrows;
-    sp.psd = lmp ? rows : d_psd + c0 * psd_bs;
+    sp.psd = lmp ? rows.get() : d_psd + c0 * psd_bs;
     sp.nbatch = (int)nb;
     sp.batch_stride = (long long)(stream_pitch * esz);
     sp.psd_batch_stride = (long long)(lmp ? lmp_bs : psd_bs);
-    int rc = GLFER_OK;
     if (p->cfg.sub_mean && mean_inkernel_ok(p, sp, nullptr, -1)) {
-      rc = launch_mean_inkernel(p, sp, st);
+      if (const int rc = launch_mean_inkernel(p, sp, st); rc != GLFER_OK) return rc;
     } else {
-      float *scratch = nullptr;
-      if (p->cfg.sub_mean) rc = submean_scratch(p, sp, first - back, nrows, st, &scratch);
-      if (rc == GLFER_OK) {
-        const hipError_t e = hparma ? glfer_launch_hparma_batch(&sp, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched, p->rot_steps,
-                                                                p->rot_width, p->d_lagmap, p->d_unit, st)
-                                    : launch_by_n(sp, p->n, st);
-        if (e != hipSuccess) rc = hip_fail(e, "estimator launch (batch)");
-      }
-      if (scratch) glfer::scratch_free(scratch, st);
+      glfer::Scratch<float> copy(st);
+      if (p->cfg.sub_mean)
+        if (const int rc = submean_scratch(p, sp, first - back, nrows, st, copy); rc != GLFER_OK) return rc;
+      const hipError_t e = hparma ? glfer_launch_hparma_batch(&sp, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched, p->rot_steps,
+                                                              p->rot_width, p->d_lagmap, p->d_unit, st)
+                                  : launch_by_n(sp, p->n, st);
+      if (e != hipSuccess) return hip_fail(e, "estimator launch (batch)");
     }
-    if (rc == GLFER_OK && lmp) {
-      const hipError_t e = glfer_launch_lmp_batch(rows, (long long)(first - back), (long long)first, nframes, p->bins, p->lmp_av,
+    if (lmp) {
+      const hipError_t e = glfer_launch_lmp_batch(rows.get(), (long long)(first - back), (long long)first, nframes, p->bins, p->lmp_av,
                                                   d_psd + c0 * psd_bs, nb, (long long)lmp_bs, (long long)psd_bs, st);
-      if (e != hipSuccess) rc = hip_fail(e, "lmp launch (batch)");
+      if (e != hipSuccess) return hip_fail(e, "lmp launch (batch)");
     }
-    if (rows) glfer::scratch_free(rows, st);
-    if (rc != GLFER_OK) return rc;
   }
   return GLFER_OK;
 }
@@ -1957,14 +1682,12 @@ int glfer_hip_spectrogram_zoom_device(glfer_hip_plan *p, glfer_hip_ddc *d, const
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (st != hipStreamPerThread && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return GLFER_E_ARG;
   (void)hipGetLastError();
-  void *base = nullptr;
-  HIP_TRY(glfer::scratch_malloc(&base, (hi - lo) * sizeof(float2), st));
-  int rc = glfer_hip_ddc_device(d, d_in, nsamples, lo, hi - lo, base, st);
-  if (rc == GLFER_OK)                                                    // the baseband's virtual base: its sample 0 lies lo samples below the scratch
-    rc = glfer_hip_spectrogram_iq_device(p, static_cast<const char *>(base) - lo * sizeof(float2), nbase, first, nframes, d_psd, pitch,
-                                         flags, st);
-  glfer::scratch_free(base, st);
-  return rc;
+  glfer::Scratch<float2> base(st);
+  HIP_TRY(base.take(hi - lo));
+  const int rc = glfer_hip_ddc_device(d, d_in, nsamples, lo, hi - lo, base.get(), st);
+  if (rc != GLFER_OK) return rc;
+  // the baseband's virtual base: its sample 0 lies lo samples below the scratch
+  return glfer_hip_spectrogram_iq_device(p, base.get() - lo, nbase, first, nframes, d_psd, pitch, flags, st);
 }
 
 // ---- multi-channel recordings (glfer_hip.h): every interleaved channel as a stream of its own ---------------------------------
@@ -2020,16 +1743,14 @@ int glfer_hip_spectrogram_channels_device(glfer_hip_plan *p, const void *d_sampl
     const size_t to = glfer_channel_piece_end(at, end, halo, hop, esz, (size_t)nsel, budget);
     const glfer_hop_span h = glfer_channel_hops(at, to - at, halo);
     const size_t plane = h.n * hop, pitch = glfer_plane_pitch(plane, esz);
-    char *planes = nullptr;
-    hipError_t e = glfer::scratch_malloc((void **)&planes, (size_t)nsel * pitch * esz, st);
+    glfer::Scratch<char> planes(st);
+    hipError_t e = planes.take((size_t)nsel * pitch * esz);
     if (e != hipSuccess) return hip_fail(e, "scratch (channel planes)");
-    e = glfer_launch_deinterleave(src + h.lo * hop * (size_t)channels * esz, plane, channels, (int)esz, sel, nsel, planes, pitch,
+    e = glfer_launch_deinterleave(src + h.lo * hop * (size_t)channels * esz, plane, channels, (int)esz, sel, nsel, planes.get(), pitch,
                                   channels_wide() ? 1 : 0, st);
-    int rc = e == hipSuccess ? GLFER_OK : hip_fail(e, "deinterleave launch");
-    if (rc == GLFER_OK)
-      rc = batch_rows(p, planes - h.lo * hop * esz, (size_t)nsel, pitch, nsamples_per_channel, at, to - at, d_psd + (at - first) * rows,
-                      nframes * rows, st);
-    glfer::scratch_free(planes, st);
+    if (e != hipSuccess) return hip_fail(e, "deinterleave launch");
+    const int rc = batch_rows(p, planes.get() - h.lo * hop * esz, (size_t)nsel, pitch, nsamples_per_channel, at, to - at,
+                              d_psd + (at - first) * rows, nframes * rows, st);
     if (rc != GLFER_OK) return rc;
     at = to;
   }
@@ -2063,17 +1784,11 @@ struct RaggedChunk {
   size_t esz;
   size_t first_inside;
 
-  // a table to the device: stream-ordered scratch and an async copy (pageable source: hipMemcpyAsync stages it before returning)
+  // a table to the device (Scratch::upload, on st)
   template <typename T>
-  int upload(const std::vector<T> &host, T **dev) const {
-    HIP_TRY(glfer::scratch_malloc((void **)dev, host.size() * sizeof(T), st));
-    const hipError_t e = hipMemcpyAsync(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) {
-      glfer::scratch_free(*dev, st);
-      *dev = nullptr;
-      return hip_fail(e, "ragged table upload");
-    }
-    return GLFER_OK;
+  int upload(const std::vector<T> &host, glfer::Scratch<T> &dev) const {
+    const hipError_t e = dev.upload(host.data(), host.size());
+    return e == hipSuccess ? GLFER_OK : hip_fail(e, "ragged table upload");
   }
 
   // one launch over a table; sp: everything but frame0 / nframes / nbatch / ragged.  r: the kernel (ROUTE_PACKED: the packed one)
@@ -2086,18 +1801,17 @@ struct RaggedChunk {
         longest = std::max(longest, e.nframes);
       }
     if (longest == 0) return GLFER_OK;
-    GlferRaggedEntry *d_tab = nullptr;
-    const int rc = upload(tab, &d_tab);
+    glfer::Scratch<GlferRaggedEntry> d_tab(st);
+    const int rc = upload(tab, d_tab);
     if (rc != GLFER_OK) return rc;
     sp.frame0 = f0;                  // (the launchers check the range and size the grid with these; the kernels read the table)
     sp.nframes = longest;
     sp.nbatch = (int)nb;
-    sp.ragged = d_tab;
+    sp.ragged = d_tab.get();
     hipError_t e;
     if (r == ROUTE_PACKED) e = launch_packed(sp, p->n, st);
     else if (r == ROUTE_WAVE_PRIVATE) e = launch_wave_private(sp, p->n, st);
     else e = r == ROUTE_REAL_INPUT ? launch_real_input(sp, p->n, st) : launch_shared_odd(sp, p->n, st);
-    glfer::scratch_free(d_tab, st);
     return e == hipSuccess ? GLFER_OK : hip_fail(e, "estimator launch (ragged)");
   }
 
@@ -2153,8 +1867,9 @@ struct RaggedChunk {
   }
 
   // submean_scratch over the streams: the corrected copy of hops [hlo[b], hhi[b]) of stream b, side by side in one block;
-  // soff[b] leaves as the copy's virtual sample 0 in bytes from *scratch
-  int submean(int fmt, const std::vector<size_t> &hlo, const std::vector<size_t> &hhi, float **scratch, std::vector<long long> &soff) const {
+  // soff[b] leaves as the copy's virtual sample 0 in bytes from the block, which is left in the caller's `copy` (empty: no hops)
+  int submean(int fmt, const std::vector<size_t> &hlo, const std::vector<size_t> &hhi, glfer::Scratch<float> &copy,
+              std::vector<long long> &soff) const {
     const size_t H = (size_t)p->hop;
     size_t total = 0, longest = 0;
     for (unsigned b = 0; b < nb; b++) {
@@ -2162,36 +1877,31 @@ struct RaggedChunk {
       total += n;
       longest = std::max(longest, n);
     }
-    *scratch = nullptr;
+    copy.release();
     if (total == 0) return GLFER_OK;
-    float *means = nullptr;
-    HIP_TRY(glfer::scratch_malloc((void **)scratch, total * H * sizeof(float), st));
+    glfer::Scratch<float> means(st);
+    HIP_TRY(copy.take(total * H));
     const bool exact = reference_means(p);
-    hipError_t e = exact ? glfer::scratch_malloc((void **)&means, total * sizeof(float), st) : hipSuccess;
+    hipError_t e = exact ? means.take(total) : hipSuccess;
     std::vector<GlferRaggedHops> tab(nb);
     size_t at = 0;
     for (unsigned b = 0; b < nb; b++) {
       const size_t n = hhi[b] > hlo[b] ? hhi[b] - hlo[b] : 0;
       tab[b].in = base + (s[b].off + hlo[b] * H) * esz;
-      tab[b].out = *scratch + at * H;
-      tab[b].means = means ? means + at : nullptr;
+      tab[b].out = copy.get() + at * H;
+      tab[b].means = means ? means.get() + at : nullptr;
       tab[b].nhops = (long long)n;
       soff[b] = ((long long)at - (long long)hlo[b]) * (long long)(H * sizeof(float));
       at += n;
     }
-    GlferRaggedHops *d_tab = nullptr;
-    int rc = e == hipSuccess ? upload(tab, &d_tab) : hip_fail(e, "scratch (hop means, ragged)");
+    glfer::Scratch<GlferRaggedHops> d_tab(st);
+    int rc = e == hipSuccess ? upload(tab, d_tab) : hip_fail(e, "scratch (hop means, ragged)");
     if (rc == GLFER_OK) {
-      if (exact) e = glfer_launch_hop_means_seq_ragged(d_tab, nb, p->hop, (long long)longest, fmt, st);
-      if (e == hipSuccess) e = glfer_launch_submean_ragged(d_tab, nb, p->hop, (long long)longest, fmt, exact ? 1 : 0, st);
+      if (exact) e = glfer_launch_hop_means_seq_ragged(d_tab.get(), nb, p->hop, (long long)longest, fmt, st);
+      if (e == hipSuccess) e = glfer_launch_submean_ragged(d_tab.get(), nb, p->hop, (long long)longest, fmt, exact ? 1 : 0, st);
       if (e != hipSuccess) rc = hip_fail(e, "glfer_launch_submean_ragged");
     }
-    if (d_tab) glfer::scratch_free(d_tab, st);
-    if (means) glfer::scratch_free(means, st);
-    if (rc != GLFER_OK) {
-      glfer::scratch_free(*scratch, st);
-      *scratch = nullptr;
-    }
+    if (rc != GLFER_OK) copy.release();
     return rc;
   }
 
@@ -2205,15 +1915,13 @@ struct RaggedChunk {
       hlo[b] = h.lo;
       hhi[b] = h.lo + h.n;
     }
-    float *scratch = nullptr;
-    int rc = submean(sp.fmt, hlo, hhi, &scratch, soff);
-    if (rc != GLFER_OK || !scratch) return rc;
+    glfer::Scratch<float> copy(st);
+    const int rc = submean(sp.fmt, hlo, hhi, copy, soff);
+    if (rc != GLFER_OK || !copy) return rc;
     SpectroParams hs = sp;
-    hs.stream = scratch;
+    hs.stream = copy.get();
     hs.fmt = GLFER_FMT_F32;
-    rc = by_n(hs, soff, from, to);
-    glfer::scratch_free(scratch, st);
-    return rc;
+    return by_n(hs, soff, from, to);
   }
 
   int run() {
@@ -2250,35 +1958,34 @@ struct RaggedChunk {
       SpectroParams bs = sp;
       bs.mean_inkernel = 1;
       std::vector<GlferRaggedEntry> body(nb);
-      float *means = nullptr;
-      GlferRaggedHops *d_hops = nullptr;
+      glfer::Scratch<float> means(st);
+      glfer::Scratch<GlferRaggedHops> d_hops(st);
       if (reference_means(p)) {                      // the hop means in the reference's order: hops [b0 - first_inside, b1) of each stream
         std::vector<GlferRaggedHops> hops(nb);
         size_t total = 0, longest = 0;
         for (unsigned b = 0; b < nb; b++) total += glfer_means_hops(b0[b], b1[b], 0, first_inside).n;
         if (total) {
-          HIP_TRY(glfer::scratch_malloc((void **)&means, total * sizeof(float), st));
+          HIP_TRY(means.take(total));
           size_t at = 0;
           for (unsigned b = 0; b < nb; b++) {
             const glfer_hop_span h = glfer_means_hops(b0[b], b1[b], 0, first_inside);
             const size_t hop_lo = h.lo, n = h.n;
             hops[b].in = base + (s[b].off + hop_lo * (size_t)p->hop) * esz;
             hops[b].out = nullptr;
-            hops[b].means = means + at;
+            hops[b].means = means.get() + at;
             hops[b].nhops = (long long)n;
             body[b].means_off = (long long)at - (long long)hop_lo;       // indexed by the stream's own hop (= frame) index
             longest = std::max(longest, n);
             at += n;
           }
-          rc = upload(hops, &d_hops);
-          if (rc == GLFER_OK) {
-            const hipError_t e = glfer_launch_hop_means_seq_ragged(d_hops, nb, p->hop, (long long)longest, sp.fmt, st);
-            if (e != hipSuccess) rc = hip_fail(e, "hop means (ragged)");
-          }
-          bs.means = means;
+          rc = upload(hops, d_hops);
+          if (rc != GLFER_OK) return rc;
+          const hipError_t e = glfer_launch_hop_means_seq_ragged(d_hops.get(), nb, p->hop, (long long)longest, sp.fmt, st);
+          if (e != hipSuccess) return hip_fail(e, "hop means (ragged)");
+          bs.means = means.get();
         }
       }
-      for (unsigned b = 0; b < nb && rc == GLFER_OK; b++) {
+      for (unsigned b = 0; b < nb; b++) {
         if (b1[b] <= b0[b]) {
           body[b] = GlferRaggedEntry{};
           continue;
@@ -2288,9 +1995,7 @@ struct RaggedChunk {
         body[b].frame0 = (long long)b0[b];
         body[b].nframes = (int)(b1[b] - b0[b]);
       }
-      if (rc == GLFER_OK) rc = launch(bs, body, route);
-      if (d_hops) glfer::scratch_free(d_hops, st);
-      if (means) glfer::scratch_free(means, st);
+      rc = launch(bs, body, route);
       if (rc != GLFER_OK) return rc;
     }
     return by_copy(sp, b1, end);
@@ -2386,16 +2091,15 @@ int glfer_hip_spectrogram_ragged_device(glfer_hip_plan *p, const void *d_samples
       std::vector<RaggedStream> rel(s.begin() + c0, s.begin() + c0 + nb);      // the chunk's streams, rows counted from its scratch
       std::vector<size_t> starts(nb + 1, nrows);
       for (unsigned b = 0; b < nb; b++) starts[b] = rel[b].row -= r0;
-      float *rows = nullptr;
-      const hipError_t e = glfer::scratch_malloc((void **)&rows, nrows * bins * sizeof(float), st);
+      glfer::Scratch<float> rows(st);
+      const hipError_t e = rows.take(nrows * bins);
       if (e != hipSuccess) return hip_fail(e, "scratch (lmp rows, ragged)");
-      RaggedChunk c{p, rel.data(), nb, base, rows, st, esz, 0};
+      RaggedChunk c{p, rel.data(), nb, base, rows.get(), st, esz, 0};
       rc = c.run();
       if (rc == GLFER_OK) {
-        const hipError_t le = glfer_launch_lmp_ragged(rows, starts.data(), nb, p->bins, p->lmp_av, d_psd + r0 * bins, st);
+        const hipError_t le = glfer_launch_lmp_ragged(rows.get(), starts.data(), nb, p->bins, p->lmp_av, d_psd + r0 * bins, st);
         if (le != hipSuccess) rc = hip_fail(le, "lmp launch (ragged)");
       }
-      glfer::scratch_free(rows, st);
     }
     if (rc != GLFER_OK) return rc;
     c0 += nb;
@@ -2424,18 +2128,14 @@ int glfer_hip_prepare_device(glfer_hip_plan *p, const void *d_stream, size_t nsa
   sp.stream = d_stream;
   sp.frame0 = (long long)first;
   sp.nframes = (int)nframes;
-  float *scratch = nullptr;
-  int rc = GLFER_OK;
-  if (p->cfg.sub_mean) rc = submean_scratch(p, sp, first, nframes, st, &scratch);
-  if (rc == GLFER_OK) {
-    // MTM / HP-ARMA / LMP run prepare_audio with a rectangular window (source.c:344,369,395); a and
-    // the limiter still act on inbuf_fft there, but those estimators overwrite it, so the shims ask
-    // for this only in FFT mode
-    hipError_t e = glfer_launch_prepare(&sp, p->n, p->d_window, d_frames, st);
-    if (e != hipSuccess) rc = hip_fail(e, "glfer_launch_prepare");
-  }
-  if (scratch) glfer::scratch_free(scratch, st);
-  return rc;
+  glfer::Scratch<float> copy(st);
+  if (p->cfg.sub_mean)
+    if (const int rc = submean_scratch(p, sp, first, nframes, st, copy); rc != GLFER_OK) return rc;
+  // MTM / HP-ARMA / LMP run prepare_audio with a rectangular window (source.c:344,369,395); a and
+  // the limiter still act on inbuf_fft there, but those estimators overwrite it, so the shims ask
+  // for this only in FFT mode
+  const hipError_t e = glfer_launch_prepare(&sp, p->n, p->d_window, d_frames, st);
+  return e == hipSuccess ? GLFER_OK : hip_fail(e, "glfer_launch_prepare");
 }
 
 // The F-test's tables, made on the first F call of a plan (either entry) and kept with it.
@@ -2584,29 +2284,26 @@ static int ftest_single(glfer_hip_plan *p, const void *d_stream, size_t first, s
   SpectroParams sp;
   ftest_params(p, sp);
   sp.stream = d_stream;
-  float *scratch = nullptr;
-  int rc = GLFER_OK;
+  glfer::Scratch<float> copy(st);
   if (p->cfg.sub_mean) {
     sp.frame0 = (long long)first;
-    rc = submean_scratch(p, sp, first, nframes, st, &scratch);
+    if (const int rc = submean_scratch(p, sp, first, nframes, st, copy); rc != GLFER_OK) return rc;
   }
-  if (rc == GLFER_OK && n >= 256) {
+  if (n >= 256) {
     const SpectroParams q = ftest_in_launch(p, sp, first, nframes, d_ftest, mu_live, d_psd);
-    hipError_t e = launch_packed(q, n, st);
-    if (e != hipSuccess) rc = hip_fail(e, "ftest launch");
-    if (scratch) glfer::scratch_free(scratch, st);
-    return rc;
+    const hipError_t e = launch_packed(q, n, st);
+    return e == hipSuccess ? GLFER_OK : hip_fail(e, "ftest launch");
   }
   size_t group = ((size_t)256 << 20) / ((size_t)(T + 1) * n * sizeof(float));
   group = std::max<size_t>(1, std::min<size_t>(group, 32768));
-  float *spec = nullptr, *dummy = nullptr;
-  if (rc == GLFER_OK) {
+  glfer::Scratch<float> spec(st), dummy(st);
+  {
     const size_t g = std::min(group, nframes);
-    hipError_t e = glfer::scratch_malloc((void **)&spec, (size_t)(T + 1) * g * n * sizeof(float), st);
-    if (e == hipSuccess) e = glfer::scratch_malloc((void **)&dummy, g * (size_t)p->bins * sizeof(float), st);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMallocAsync(ftest spectra)");
+    hipError_t e = spec.take((size_t)(T + 1) * g * n);
+    if (e == hipSuccess) e = dummy.take(g * (size_t)p->bins);
+    if (e != hipSuccess) return hip_fail(e, "hipMallocAsync(ftest spectra)");
   }
-  for (size_t done = 0; rc == GLFER_OK && done < nframes; done += group) {
+  for (size_t done = 0; done < nframes; done += group) {
     const size_t g = std::min(group, nframes - done);
     hipError_t e = hipSuccess;
     for (int j = 0; j <= T && e == hipSuccess; j++) {
@@ -2615,21 +2312,18 @@ static int ftest_single(glfer_hip_plan *p, const void *d_stream, size_t first, s
       q.frame0 = (long long)(first + done);
       q.nframes = (int)g;
       q.taps = p->d_ftaps + (size_t)j * 2 * n;
-      q.psd = dummy;
-      q.spec = spec + (size_t)j * g * n;
+      q.psd = dummy.get();
+      q.spec = spec.get() + (size_t)j * g * n;
       e = launch_packed(q, n, st);
     }
     if (e == hipSuccess && d_psd)
-      e = glfer_launch_ftest_rows(spec, g, n, T, p->d_U0, p->sum_U0_sqr, mu_live ? 1 : 0, d_ftest + done * (size_t)p->bins,
+      e = glfer_launch_ftest_rows(spec.get(), g, n, T, p->d_U0, p->sum_U0_sqr, mu_live ? 1 : 0, d_ftest + done * (size_t)p->bins,
                                   p->d_rows_cj, d_psd + done * (size_t)p->pitch, p->pitch, st);
     else if (e == hipSuccess)
-      e = glfer_launch_ftest(spec, g, n, T, p->d_U0, p->sum_U0_sqr, mu_live ? 1 : 0, d_ftest + done * (size_t)p->bins, st);
-    if (e != hipSuccess) rc = hip_fail(e, "ftest launch");
+      e = glfer_launch_ftest(spec.get(), g, n, T, p->d_U0, p->sum_U0_sqr, mu_live ? 1 : 0, d_ftest + done * (size_t)p->bins, st);
+    if (e != hipSuccess) return hip_fail(e, "ftest launch");
   }
-  if (spec) glfer::scratch_free(spec, st);
-  if (dummy) glfer::scratch_free(dummy, st);
-  if (scratch) glfer::scratch_free(scratch, st);
-  return rc;
+  return GLFER_OK;
 }
 
 // glfer_hip_mtm_ftest_device over many streams (glfer_hip.h).  N >= 256: the launches of one stream -- the corrected copies under
@@ -2722,21 +2416,16 @@ static int ftest_batch(glfer_hip_plan *p, const void *d_streams, size_t nstreams
     sp.stream = base + c0 * stream_pitch * esz;
     sp.nbatch = (int)nb;
     sp.batch_stride = (long long)(stream_pitch * esz);
-    float *scratch = nullptr;
-    int rc = GLFER_OK;
+    glfer::Scratch<float> copy(st);
     if (p->cfg.sub_mean) {
       sp.frame0 = (long long)first;
-      rc = submean_scratch(p, sp, first, nframes, st, &scratch);
+      if (const int rc = submean_scratch(p, sp, first, nframes, st, copy); rc != GLFER_OK) return rc;
     }
-    if (rc == GLFER_OK) {
-      SpectroParams q = ftest_in_launch(p, sp, first, nframes, d_ftest + c0 * ft_bs, mu_live, d_psd ? d_psd + c0 * psd_bs : nullptr);
-      q.ftest_batch_stride = (long long)ft_bs;                  // (F alone: psd NULL, psd_batch_stride 0)
-      if (d_psd) q.psd_batch_stride = (long long)psd_bs;
-      const hipError_t e = launch_packed(q, n, st);
-      if (e != hipSuccess) rc = hip_fail(e, "ftest launch (batch)");
-    }
-    if (scratch) glfer::scratch_free(scratch, st);
-    if (rc != GLFER_OK) return rc;
+    SpectroParams q = ftest_in_launch(p, sp, first, nframes, d_ftest + c0 * ft_bs, mu_live, d_psd ? d_psd + c0 * psd_bs : nullptr);
+    q.ftest_batch_stride = (long long)ft_bs;                  // (F alone: psd NULL, psd_batch_stride 0)
+    if (d_psd) q.psd_batch_stride = (long long)psd_bs;
+    const hipError_t e = launch_packed(q, n, st);
+    if (e != hipSuccess) return hip_fail(e, "ftest launch (batch)");
   }
   return GLFER_OK;
 }
@@ -2751,13 +2440,13 @@ static int ftest_ragged_chunk(const RaggedChunk &c, float *d_ftest, int mu_live)
   ftest_params(p, sp);
   sp.stream = c.base;
   std::vector<long long> soff(c.nb);
-  float *scratch = nullptr;
+  glfer::Scratch<float> copy(c.st);
   if (p->cfg.sub_mean) {
     std::vector<size_t> hlo(c.nb, 0), hhi(c.nb);
     for (unsigned b = 0; b < c.nb; b++) hhi[b] = c.s[b].frames;
-    const int rc = c.submean(sp.fmt, hlo, hhi, &scratch, soff);
-    if (rc != GLFER_OK || !scratch) return rc;           // (no scratch: no stream of the chunk has a frame)
-    sp.stream = scratch;
+    const int rc = c.submean(sp.fmt, hlo, hhi, copy, soff);
+    if (rc != GLFER_OK || !copy) return rc;              // (no copy: no stream of the chunk has a frame)
+    sp.stream = copy.get();
     sp.fmt = GLFER_FMT_F32;
   } else {
     for (unsigned b = 0; b < c.nb; b++) soff[b] = (long long)(c.s[b].off * c.esz);
@@ -2774,9 +2463,7 @@ static int ftest_ragged_chunk(const RaggedChunk &c, float *d_ftest, int mu_live)
     }
     tab[b] = e;
   }
-  const int rc = c.launch(q, tab, ROUTE_PACKED);
-  if (scratch) glfer::scratch_free(scratch, c.st);
-  return rc;
+  return c.launch(q, tab, ROUTE_PACKED);
 }
 
 // both ragged F entries; want_psd: the rows-and-F one (d_psd required, its rows at the plan's pitch)
@@ -2876,11 +2563,10 @@ int glfer_hip_submean_exact_device(const void *d_in, float *d_out, int hop, size
   hipStream_t st = (hipStream_t)hip_stream;
   DeviceGuard guard(data_device(d_out));
   HIP_TRY(guard.error());
-  float *means = nullptr;
-  HIP_TRY(glfer::scratch_malloc((void **)&means, nhops * sizeof(float), st));
-  hipError_t e = glfer_launch_hop_means_seq(d_in, means, hop, (long long)nhops, sample_format, st);
-  if (e == hipSuccess) e = glfer_launch_submean(d_in, d_out, hop, (long long)nhops, sample_format, st, means);
-  glfer::scratch_free(means, st);
+  glfer::Scratch<float> means(st);
+  HIP_TRY(means.take(nhops));
+  hipError_t e = glfer_launch_hop_means_seq(d_in, means.get(), hop, (long long)nhops, sample_format, st);
+  if (e == hipSuccess) e = glfer_launch_submean(d_in, d_out, hop, (long long)nhops, sample_format, st, means.get());
   return e == hipSuccess ? GLFER_OK : hip_fail(e, "glfer_hip_submean_exact_device");
 }
 
@@ -2944,24 +2630,21 @@ int glfer_hip_spectrogram_avg_device(glfer_hip_plan *p, const void *d_stream, si
   DeviceGuard guard(p->cfg.device);
   HIP_TRY(guard.error());
   const size_t bins = (size_t)p->bins;
-  int rc = GLFER_OK;
   // frames [from, to): the rows (to d_psd, or scratch), then update_avg over them with the state empty at `from`
-  auto two_launches = [&](size_t from, size_t to) {
-    if (rc != GLFER_OK || from >= to) return;
+  auto two_launches = [&](size_t from, size_t to) -> int {
+    if (from >= to) return GLFER_OK;
     const size_t nf = to - from;
-    float *rows = d_psd ? d_psd + (from - first) * bins : nullptr;
-    double *ret = d_ret ? d_ret + (from - first) * 4 : nullptr;
+    glfer::Scratch<float> rows_buf(st);
+    glfer::Scratch<double> ret_buf(st);
     hipError_t e = hipSuccess;
-    if (!d_psd) e = glfer::scratch_malloc((void **)&rows, nf * bins * sizeof(float), st);
-    if (e == hipSuccess && !d_ret) e = glfer::scratch_malloc((void **)&ret, nf * 4 * sizeof(double), st);
-    if (e != hipSuccess) rc = hip_fail(e, "scratch (rows to average)");
-    if (rc == GLFER_OK) rc = glfer_run_device(p, d_stream, nsamples, from, nf, rows, nullptr, st);
-    if (rc == GLFER_OK) {
-      e = glfer_launch_avg(avg_mode, rows, nf, (int)bins, n_out, depth, minbin, maxbin, max0 ? 1 : 0, d_avg + (from - first) * (size_t)n_out, ret, st);
-      if (e != hipSuccess) rc = hip_fail(e, "update_avg launch");
-    }
-    if (!d_psd && rows) glfer::scratch_free(rows, st);
-    if (!d_ret && ret) glfer::scratch_free(ret, st);
+    if (!d_psd) e = rows_buf.take(nf * bins);
+    if (e == hipSuccess && !d_ret) e = ret_buf.take(nf * 4);
+    if (e != hipSuccess) return hip_fail(e, "scratch (rows to average)");
+    float *rows = d_psd ? d_psd + (from - first) * bins : rows_buf.get();
+    double *ret = d_ret ? d_ret + (from - first) * 4 : ret_buf.get();
+    if (const int rc = glfer_run_device(p, d_stream, nsamples, from, nf, rows, nullptr, st); rc != GLFER_OK) return rc;
+    e = glfer_launch_avg(avg_mode, rows, nf, (int)bins, n_out, depth, minbin, maxbin, max0 ? 1 : 0, d_avg + (from - first) * (size_t)n_out, ret, st);
+    return e == hipSuccess ? GLFER_OK : hip_fail(e, "update_avg launch");
   };
   SpectroParams sp;
   fill_params(p, sp);
@@ -2971,54 +2654,45 @@ int glfer_hip_spectrogram_avg_device(glfer_hip_plan *p, const void *d_stream, si
   const bool with_means = p->cfg.sub_mean != 0;
   const size_t end = first + nframes;
   size_t b0 = end;
-  if (!avg_in_launch(p, sp, avg_mode, depth, n_out, first, nframes, &b0)) {
-    two_launches(first, end);
-    return rc;
-  }
+  if (!avg_in_launch(p, sp, avg_mode, depth, n_out, first, nframes, &b0)) return two_launches(first, end);
   // The head's state starts empty at `first`, like the whole call's.  Its rows are also what the body's first slots would need
   // in front of them -- they recompute them instead (frames >= b0 - (depth-1) >= first_inside are all computable).
-  two_launches(first, b0);
+  if (const int rc = two_launches(first, b0); rc != GLFER_OK) return rc;
   const size_t piece = (size_t)1 << 24;                     // frames per launch: keeps a workgroup's rows under the 4 GiB of a buffer descriptor
   // (the kernel always forms the return values -- one code path, no branch per bin: without d_ret they land in scratch)
-  double *ret_scratch = nullptr;
+  glfer::Scratch<double> ret_scratch(st);
   if (!d_ret) {
-    hipError_t e = glfer::scratch_malloc((void **)&ret_scratch, std::min(piece, end - b0) * 4 * sizeof(double), st);
+    hipError_t e = ret_scratch.take(std::min(piece, end - b0) * 4);
     if (e != hipSuccess) return hip_fail(e, "scratch (return values)");
   }
   // the hop means of everything the body touches: its frames, the depth-1 frames a slot recomputes in front of them, their history
-  float *means = nullptr;
+  glfer::Scratch<float> means(st);
   const glfer_hop_span mh = glfer_means_hops(b0, end, (size_t)(depth - 1), plan_first_inside(p));
   if (with_means) {
-    hipError_t e = glfer::scratch_malloc((void **)&means, mh.n * sizeof(float), st);
-    if (e == hipSuccess) e = launch_reference_means(p, sp, mh.lo, mh.n, means, 0, st);
-    if (e != hipSuccess) {
-      if (means) glfer::scratch_free(means, st);
-      if (ret_scratch) glfer::scratch_free(ret_scratch, st);
-      return hip_fail(e, "hop means (average inside the kernel)");
-    }
+    hipError_t e = means.take(mh.n);
+    if (e == hipSuccess) e = launch_reference_means(p, sp, mh.lo, mh.n, means.get(), 0, st);
+    if (e != hipSuccess) return hip_fail(e, "hop means (average inside the kernel)");
   }
-  for (size_t f0 = b0; rc == GLFER_OK && f0 < end; f0 += piece) {
+  for (size_t f0 = b0; f0 < end; f0 += piece) {
     const size_t nf = std::min(piece, end - f0);
     SpectroParams q = sp;
     if (with_means) {
       q.mean_inkernel = 1;
-      q.means = means - mh.lo;                               // indexed by GLOBAL hop (= frame) index
+      q.means = means.get() - mh.lo;                         // indexed by GLOBAL hop (= frame) index
     }
     q.frame0 = (long long)f0;
     q.nframes = (int)nf;
     q.psd = d_psd ? d_psd + (f0 - first) * bins : nullptr;
     q.avg = d_avg + (f0 - first) * (size_t)n_out;
-    q.avg_ret = d_ret ? d_ret + (f0 - first) * 4 : ret_scratch;
+    q.avg_ret = d_ret ? d_ret + (f0 - first) * 4 : ret_scratch.get();
     q.avg_depth = depth;
     q.avg_minbin = minbin;
     q.avg_maxbin = maxbin;
     q.avg_nout = n_out;
     hipError_t e = launch_real_input(q, p->n, st);
-    if (e != hipSuccess) rc = hip_fail(e, "estimator launch (average inside the kernel)");
+    if (e != hipSuccess) return hip_fail(e, "estimator launch (average inside the kernel)");
   }
-  if (means) glfer::scratch_free(means, st);
-  if (ret_scratch) glfer::scratch_free(ret_scratch, st);
-  return rc;
+  return GLFER_OK;
 }
 
 int glfer_hip_avg_batch_device(int avg_mode, const float *d_psd, size_t nstreams, size_t nframes, int bins, int n_out, int depth,
@@ -3078,64 +2752,53 @@ int glfer_hip_spectrogram_avg_batch_device(glfer_hip_plan *p, const void *d_stre
   size_t group = 65535;
   if (!d_psd && scratch_frames > 0)
     group = std::max<size_t>(1, std::min(group, ((size_t)8 << 30) / (scratch_frames * bins * sizeof(float))));
-  int rc = GLFER_OK;
-  for (size_t c0 = 0; rc == GLFER_OK && c0 < nstreams; c0 += group) {
+  for (size_t c0 = 0; c0 < nstreams; c0 += group) {
     const unsigned nb = (unsigned)std::min(nstreams - c0, group);
     const char *sbase = base + c0 * stream_pitch * esz;
     float *psd_c = d_psd ? d_psd + c0 * nframes * bins : nullptr;
     double *avg_c = d_avg + c0 * nframes * (size_t)n_out, *ret_c = d_ret ? d_ret + c0 * nframes * 4 : nullptr;
     // frames [from, to) of every stream of the group: the rows (to d_psd, or scratch), then update_avg over them with the state
     // empty at `from`
-    auto two_launches = [&](size_t from, size_t to) {
-      if (rc != GLFER_OK || from >= to) return;
+    auto two_launches = [&](size_t from, size_t to) -> int {
+      if (from >= to) return GLFER_OK;
       const size_t nf = to - from;
-      float *rows = psd_c ? psd_c + (from - first) * bins : nullptr;
-      double *ret = ret_c ? ret_c + (from - first) * 4 : nullptr;
       const size_t rows_bs = psd_c ? nframes * bins : nf * bins, ret_bs = ret_c ? nframes * 4 : nf * 4;
+      glfer::Scratch<float> rows_buf(st);
+      glfer::Scratch<double> ret_buf(st);
       hipError_t e = hipSuccess;
-      if (!psd_c) e = glfer::scratch_malloc((void **)&rows, (size_t)nb * nf * bins * sizeof(float), st);
-      if (e == hipSuccess && !ret_c) e = glfer::scratch_malloc((void **)&ret, (size_t)nb * nf * 4 * sizeof(double), st);
-      if (e != hipSuccess) rc = hip_fail(e, "scratch (rows to average, batch)");
-      if (rc == GLFER_OK) rc = batch_rows(p, sbase, nb, stream_pitch, nsamples, from, nf, rows, rows_bs, st);
-      if (rc == GLFER_OK) {
-        e = glfer_launch_avg_batch(avg_mode, rows, nf, (int)bins, n_out, depth, minbin, maxbin, max0 ? 1 : 0,
-                                   avg_c + (from - first) * (size_t)n_out, ret, nb, (long long)rows_bs,
-                                   (long long)(nframes * (size_t)n_out), (long long)ret_bs, st);
-        if (e != hipSuccess) rc = hip_fail(e, "update_avg launch (batch)");
-      }
-      if (!psd_c && rows) glfer::scratch_free(rows, st);
-      if (!ret_c && ret) glfer::scratch_free(ret, st);
+      if (!psd_c) e = rows_buf.take((size_t)nb * nf * bins);
+      if (e == hipSuccess && !ret_c) e = ret_buf.take((size_t)nb * nf * 4);
+      if (e != hipSuccess) return hip_fail(e, "scratch (rows to average, batch)");
+      float *rows = psd_c ? psd_c + (from - first) * bins : rows_buf.get();
+      double *ret = ret_c ? ret_c + (from - first) * 4 : ret_buf.get();
+      if (const int rc = batch_rows(p, sbase, nb, stream_pitch, nsamples, from, nf, rows, rows_bs, st); rc != GLFER_OK) return rc;
+      e = glfer_launch_avg_batch(avg_mode, rows, nf, (int)bins, n_out, depth, minbin, maxbin, max0 ? 1 : 0,
+                                 avg_c + (from - first) * (size_t)n_out, ret, nb, (long long)rows_bs,
+                                 (long long)(nframes * (size_t)n_out), (long long)ret_bs, st);
+      return e == hipSuccess ? GLFER_OK : hip_fail(e, "update_avg launch (batch)");
     };
-    if (!in_launch) {
-      two_launches(first, end);
-      continue;
-    }
-    two_launches(first, b0);
-    if (rc != GLFER_OK) break;
+    if (const int rc = two_launches(first, in_launch ? b0 : end); rc != GLFER_OK) return rc;
+    if (!in_launch) continue;
     const size_t piece = (size_t)1 << 24;                   // frames per launch, as the single-stream entry cuts them
     const size_t ret_rows = std::min(piece, end - b0);
-    double *ret_scratch = nullptr;
+    glfer::Scratch<double> ret_scratch(st);
     if (!ret_c) {
-      hipError_t e = glfer::scratch_malloc((void **)&ret_scratch, (size_t)nb * ret_rows * 4 * sizeof(double), st);
+      hipError_t e = ret_scratch.take((size_t)nb * ret_rows * 4);
       if (e != hipSuccess) return hip_fail(e, "scratch (return values, batch)");
     }
     // the hop means of everything the body touches, one table per stream: its frames, the depth-1 frames a slot recomputes in
     // front of them, their history
-    float *means = nullptr;
+    glfer::Scratch<float> means(st);
     const glfer_hop_span mh = glfer_means_hops(b0, end, (size_t)(depth - 1), plan_first_inside(p));
     const size_t hop_lo = mh.lo, nhops = mh.n;
     if (with_means) {
-      hipError_t e = glfer::scratch_malloc((void **)&means, (size_t)nb * nhops * sizeof(float), st);
+      hipError_t e = means.take((size_t)nb * nhops);
       if (e == hipSuccess)
-        e = glfer_launch_hop_means_seq_batch(sbase + hop_lo * (size_t)p->hop * esz, means, p->hop, (long long)nhops, fmt, nb,
+        e = glfer_launch_hop_means_seq_batch(sbase + hop_lo * (size_t)p->hop * esz, means.get(), p->hop, (long long)nhops, fmt, nb,
                                              (long long)(stream_pitch * esz), (long long)nhops, st);
-      if (e != hipSuccess) {
-        if (means) glfer::scratch_free(means, st);
-        if (ret_scratch) glfer::scratch_free(ret_scratch, st);
-        return hip_fail(e, "hop means (average inside the kernel, batch)");
-      }
+      if (e != hipSuccess) return hip_fail(e, "hop means (average inside the kernel, batch)");
     }
-    for (size_t f0 = b0; rc == GLFER_OK && f0 < end; f0 += piece) {
+    for (size_t f0 = b0; f0 < end; f0 += piece) {
       const size_t nf = std::min(piece, end - f0);
       SpectroParams q = sp;
       q.stream = sbase;
@@ -3143,7 +2806,7 @@ int glfer_hip_spectrogram_avg_batch_device(glfer_hip_plan *p, const void *d_stre
       q.batch_stride = (long long)(stream_pitch * esz);
       if (with_means) {
         q.mean_inkernel = 1;
-        q.means = means - hop_lo;                              // indexed by the stream's own hop (= frame) index
+        q.means = means.get() - hop_lo;                        // indexed by the stream's own hop (= frame) index
         q.means_batch_stride = (long long)nhops;
       }
       q.frame0 = (long long)f0;
@@ -3152,19 +2815,17 @@ int glfer_hip_spectrogram_avg_batch_device(glfer_hip_plan *p, const void *d_stre
       q.psd_batch_stride = psd_c ? (long long)(nframes * bins) : 0;    // (0: psd stays NULL in every stream)
       q.avg = avg_c + (f0 - first) * (size_t)n_out;
       q.avg_batch_stride = (long long)(nframes * (size_t)n_out);
-      q.avg_ret = ret_c ? ret_c + (f0 - first) * 4 : ret_scratch;
+      q.avg_ret = ret_c ? ret_c + (f0 - first) * 4 : ret_scratch.get();
       q.avg_ret_batch_stride = (long long)(ret_c ? nframes * 4 : ret_rows * 4);
       q.avg_depth = depth;
       q.avg_minbin = minbin;
       q.avg_maxbin = maxbin;
       q.avg_nout = n_out;
       hipError_t e = launch_real_input(q, p->n, st);
-      if (e != hipSuccess) rc = hip_fail(e, "estimator launch (average inside the kernel, batch)");
+      if (e != hipSuccess) return hip_fail(e, "estimator launch (average inside the kernel, batch)");
     }
-    if (means) glfer::scratch_free(means, st);
-    if (ret_scratch) glfer::scratch_free(ret_scratch, st);
   }
-  return rc;
+  return GLFER_OK;
 }
 
 // update_avg_* over packed rows of streams of unequal length (glfer_hip.h): glfer_launch_avg_ragged over the streams that have rows
@@ -3182,11 +2843,10 @@ int glfer_hip_avg_ragged_device(int avg_mode, const float *d_psd, size_t nstream
   DeviceGuard guard(data_device(d_psd));
   HIP_TRY(guard.error());
   const std::vector<glfer::RaggedColsEntry> s = glfer::ragged_streams(row_starts, nstreams);
-  double *ret = d_ret;                                   // (the kernels always form the return values: without d_ret they land in scratch)
-  if (!ret) HIP_TRY(glfer::scratch_malloc((void **)&ret, rows_hi * 4 * sizeof(double), st));
+  glfer::Scratch<double> ret(st);                        // (the kernels always form the return values: without d_ret they land in scratch)
+  if (!d_ret) HIP_TRY(ret.take(rows_hi * 4));
   const hipError_t e = glfer_launch_avg_ragged(avg_mode, d_psd, s.data(), s.size(), bins, n_out, depth, minbin, maxbin, max0 ? 1 : 0, d_avg,
-                                               ret, st);
-  if (!d_ret) glfer::scratch_free(ret, st);
+                                               d_ret ? d_ret : ret.get(), st);
   return e == hipSuccess ? GLFER_OK : hip_fail(e, "update_avg launch (ragged)");
 }
 
@@ -3228,13 +2888,11 @@ int glfer_hip_spectrogram_avg_ragged_device(glfer_hip_plan *p, const void *d_sam
   if (total == 0) return GLFER_OK;
   DeviceGuard guard(p->cfg.device);
   HIP_TRY(guard.error());
-  float *rows = d_psd;
-  if (!rows) HIP_TRY(glfer::scratch_malloc((void **)&rows, total * bins * sizeof(float), st));
-  int rc = glfer_hip_spectrogram_ragged_device(p, d_samples, nstreams, offsets, lengths, rows, nullptr, st);
-  if (rc == GLFER_OK)
-    rc = glfer_hip_avg_ragged_device(avg_mode, rows, nstreams, starts.data(), (int)bins, n_out, depth, minbin, maxbin, max0, d_avg, d_ret, st);
-  if (!d_psd) glfer::scratch_free(rows, st);
-  return rc;
+  glfer::Scratch<float> rows_buf(st);
+  if (!d_psd) HIP_TRY(rows_buf.take(total * bins));
+  float *rows = d_psd ? d_psd : rows_buf.get();
+  if (const int rc = glfer_hip_spectrogram_ragged_device(p, d_samples, nstreams, offsets, lengths, rows, nullptr, st); rc != GLFER_OK) return rc;
+  return glfer_hip_avg_ragged_device(avg_mode, rows, nstreams, starts.data(), (int)bins, n_out, depth, minbin, maxbin, max0, d_avg, d_ret, st);
 }
 
 // the sliding sums alone (avgdata->cum after each frame, avg.c:114-127); bins outside

@@ -18,11 +18,10 @@
 #include <vector>
 #include "spectro_params.h"
 #include "hparma_frames.h"
+#include "scratch.hpp"
 
 namespace glfer {
 hipError_t allow_dynamic_lds(const void *kernel, size_t bytes);   // plan.h / glfer_hip.cpp: once per device, kernel and size class
-hipError_t scratch_malloc(void **p, size_t bytes, hipStream_t st);   // (stream-ordered scratch of the library)
-void scratch_free(void *q, hipStream_t st);
 }
 
 namespace glfer {
@@ -700,12 +699,13 @@ hipError_t hparma_launch(const HparmaParams &plan, long long total, hipStream_t 
   const long long resident = glfer_hparma_resident(shmem);
   const unsigned grid = (unsigned)(total < resident ? total : resident);
   hipError_t e = hipSuccess;
-  hp.queue = nullptr;
+  glfer::Scratch<unsigned> queue(st);
   if (total > (long long)grid) {
-    e = glfer::scratch_malloc((void **)&hp.queue, 256, st);
-    if (e == hipSuccess) e = hipMemsetAsync(hp.queue, 0, sizeof(unsigned), st);
+    e = queue.take(64);
+    if (e == hipSuccess) e = hipMemsetAsync(queue.get(), 0, sizeof(unsigned), st);
     if (e != hipSuccess) return e;
   }
+  hp.queue = queue.get();
 #define GLFER_HPARMA_LAUNCH(F, L, TT, NC)                                                                                  \
   do {                                                                                                                      \
     e = glfer::allow_dynamic_lds((const void *)hparma_kernel<F, L, TT, NC, P>, shmem);                                      \
@@ -738,7 +738,6 @@ hipError_t hparma_launch(const HparmaParams &plan, long long total, hipStream_t 
 #undef GLFER_HPARMA_FMT
     default: e = hipErrorInvalidValue;
   }
-  if (hp.queue) glfer::scratch_free(hp.queue, st);
 #undef GLFER_HPARMA_LAUNCH
   if (e != hipSuccess) return e;
   return hipGetLastError();
@@ -786,17 +785,14 @@ extern "C" hipError_t glfer_launch_hparma_ragged(const SpectroParams *sp, const 
     const GlferRaggedEntry &r = streams[ent[k].stream];
     tab[k] = HparmaRaggedEntry{r.stream_off, r.psd_off, r.frame0, (unsigned)ent[k].g0, (int)ent[k].nframes};
   }
-  HparmaRaggedEntry *d_tab = nullptr;
-  hipError_t e = glfer::scratch_malloc((void **)&d_tab, ne * sizeof(HparmaRaggedEntry), st);
-  if (e != hipSuccess) return e;
-  e = hipMemcpyAsync(d_tab, tab.data(), ne * sizeof(HparmaRaggedEntry), hipMemcpyHostToDevice, st);   // (pageable source: staged before it returns)
+  glfer::Scratch<HparmaRaggedEntry> d_tab(st);
+  hipError_t e = d_tab.upload(tab.data(), ne);
   HparmaParams hp = hparma_params(sp, n, t, ncol, rot_sched, rot_steps, rot_width, lagmap, unit);
   for (size_t k0 = 0; k0 < ne && e == hipSuccess;) {                 // piece by piece
     size_t k1 = k0;
     while (k1 < ne && ent[k1].piece == ent[k0].piece) k1++;
-    e = hparma_launch<HpPlace::Ragged>(hp, ent[k1 - 1].g0 + ent[k1 - 1].nframes, st, d_tab + k0, (int)(k1 - k0));
+    e = hparma_launch<HpPlace::Ragged>(hp, ent[k1 - 1].g0 + ent[k1 - 1].nframes, st, d_tab.get() + k0, (int)(k1 - k0));
     k0 = k1;
   }
-  glfer::scratch_free(d_tab, st);
   return e;
 }

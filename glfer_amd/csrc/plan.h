@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/glfer_hip.h"
 #include "ragged_cols.hpp"
+#include "scratch.hpp"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,19 +44,6 @@ class DeviceGuard {
 int device_of(const void *d_ptr);
 // the device the data of a plan-less entry lives on: the pointer's, else the current one
 int data_device(const void *d_ptr);
-
-// Stream-ordered scratch on the current device: small requests from a pool of their own, middle ones
-// from the default pool (release threshold raised), 16 MiB and more from blocks the library keeps
-// (glfer_hip.cpp: the stream-ordered pool costs milliseconds, and now and then seconds, per GB-sized
-// request).  Always given back through scratch_free on the stream that used it.
-hipError_t scratch_malloc(void **p, size_t bytes, hipStream_t st);
-void scratch_free(void *p, hipStream_t st);
-// idle kept blocks of `dev` given back until at most keep_bytes stay / bytes kept now / the per-device cap
-size_t scratch_trim(int dev, size_t keep_bytes);
-size_t scratch_held(int dev);
-void scratch_set_cap(size_t bytes);
-bool scratch_keeping();                        // false with GLFER_SCRATCH_CACHE=0: the library keeps nothing between calls
-size_t scratch_cap();                          // glfer_hip_scratch_limit / GLFER_SCRATCH_CAP_MB
 
 // ---- what the per-column entries share: waterfall.cpp (display and waterfall) and the floor / update_avg entries of glfer_hip.cpp
 // The averaging-argument rule.  The waterfall's: a mode of update_avg_*, a window of at least one frame, a band inside the row.

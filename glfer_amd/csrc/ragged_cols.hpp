@@ -14,6 +14,8 @@
 #include <initializer_list>
 #include <vector>
 
+#include "scratch.hpp"
+
 namespace glfer {
 
 struct RaggedColsEntry {
@@ -42,8 +44,6 @@ __device__ __forceinline__ RaggedColsEntry ragged_cols_find(const RaggedCols &r,
 #endif
 
 // ---- host side: the tables of one launcher call
-hipError_t scratch_malloc(void **p, size_t bytes, hipStream_t st);   // plan.h / glfer_hip.cpp
-void scratch_free(void *p, hipStream_t st);
 
 // One launch's entries, in stream order.  The grid's x limit cuts it into pieces of at most 2^31 - 1 blocks (a stream has at
 // most 2^31 - 1 frames, so an entry always fits one); blk0 counts from the piece's first block.
@@ -65,25 +65,16 @@ struct RaggedTable {
   }
   RaggedCols cols(const RaggedColsEntry *d_tabs, const RaggedPiece &p) const { return RaggedCols{d_tabs + base + p.first, (int)p.count}; }
 };
-// the tables of a call into ONE stream-ordered allocation, one copy (pageable source: staged before hipMemcpyAsync returns)
-inline hipError_t ragged_upload(std::initializer_list<RaggedTable *> tabs, RaggedColsEntry **d_tabs, hipStream_t st) {
+// the tables of a call into ONE stream-ordered allocation, one copy, on d_tabs' stream (empty tables: d_tabs stays empty)
+inline hipError_t ragged_upload(std::initializer_list<RaggedTable *> tabs, Scratch<RaggedColsEntry> &d_tabs) {
   std::vector<RaggedColsEntry> all;
   for (RaggedTable *t : tabs) {
     t->base = all.size();
     all.insert(all.end(), t->e.begin(), t->e.end());
   }
-  *d_tabs = nullptr;
-  if (all.empty()) return hipSuccess;
-  hipError_t err = scratch_malloc((void **)d_tabs, all.size() * sizeof(RaggedColsEntry), st);
-  if (err != hipSuccess) return err;
-  err = hipMemcpyAsync(*d_tabs, all.data(), all.size() * sizeof(RaggedColsEntry), hipMemcpyHostToDevice, st);
-  if (err != hipSuccess) {
-    scratch_free(*d_tabs, st);
-    *d_tabs = nullptr;
-  }
-  return err;
+  d_tabs.release();
+  return all.empty() ? hipSuccess : d_tabs.upload(all.data(), all.size());
 }
-
 
 // ---- the ragged entries' own rules (waterfall.cpp)
 // true where `st` is being captured into a graph: the per-stream tables are uploaded from host memory that is gone when the call

@@ -12,6 +12,7 @@
 // periodogram and multitaper.  Very-slow-CW sizes; a correct path, not a tuned one.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "scratch.hpp"   // stream-ordered; large requests from blocks the library keeps
 #include "stockham16.hpp"
 
 namespace glfer {
@@ -310,11 +311,6 @@ __global__ __launch_bounds__(64) void combine2_kernel(SpectroParams p, int ntap,
 
 using namespace glfer;
 
-namespace glfer {
-hipError_t scratch_malloc(void **p, size_t bytes, hipStream_t st);   // plan.h / glfer_hip.cpp: stream-ordered; large requests from blocks the library keeps
-void scratch_free(void *p, hipStream_t st);
-}
-
 // frames [p->frame0 .. +nframes) in groups that keep the scratch under ~512 MiB; p->psd is row 0 of the launch
 extern "C" hipError_t glfer_launch_spectro_big(const SpectroParams *p, int n, hipStream_t st) {
   if (n < 32768 || n > (1 << 20) || (n & (n - 1)) || !p->wtaps || !p->wtw || !p->bigtw || p->spec) return hipErrorInvalidValue;
@@ -328,16 +324,12 @@ extern "C" hipError_t glfer_launch_spectro_big(const SpectroParams *p, int n, hi
   if (group < 1) group = 1;
   if (group > p->nframes) group = p->nframes;
   if (two_level && group > 65535 / ntap) group = 65535 / ntap;   // (grid.z of combine1)
-  v2f32 *scratch = nullptr, *scratch2 = nullptr;
-  hipError_t e = glfer::scratch_malloc((void **)&scratch, (size_t)group * per_frame, st);
+  Scratch<v2f32> buf(st), buf2(st);
+  const size_t group_elems = (size_t)group * per_frame / sizeof(v2f32);
+  hipError_t e = buf.take(group_elems);
+  if (e == hipSuccess && two_level) e = buf2.take(group_elems);
   if (e != hipSuccess) return e;
-  if (two_level) {
-    e = glfer::scratch_malloc((void **)&scratch2, (size_t)group * per_frame, st);
-    if (e != hipSuccess) {
-      glfer::scratch_free(scratch, st);
-      return e;
-    }
-  }
+  v2f32 *const scratch = buf.get(), *const scratch2 = buf2.get();
   for (long long f0 = 0; f0 < p->nframes && e == hipSuccess; f0 += group) {
     const int nf = (int)((p->nframes - f0 < group) ? p->nframes - f0 : group);
     const long long blocks = ((long long)nf * ntap * W + 3) / 4;
@@ -369,7 +361,5 @@ extern "C" hipError_t glfer_launch_spectro_big(const SpectroParams *p, int n, hi
       e = hipGetLastError();
     }
   }
-  glfer::scratch_free(scratch, st);
-  if (scratch2) glfer::scratch_free(scratch2, st);
   return e;
 }

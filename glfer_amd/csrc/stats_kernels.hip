@@ -510,15 +510,14 @@ extern "C" hipError_t glfer_launch_lmp_ragged(const float *rows, const size_t *r
     tab.pieces.back().count++;
     tab.pieces.back().blocks = g.blk0 + (g.nframes + G - 1) / G;
   }
-  RaggedColsEntry *d_tab = nullptr;
-  hipError_t err = ragged_upload({&tab}, &d_tab, st);
+  Scratch<RaggedColsEntry> d_tab(st);
+  hipError_t err = ragged_upload({&tab}, d_tab);
   if (err != hipSuccess || !d_tab) return err;
   for (const RaggedPiece &pc : tab.pieces) {
-    const LmpStreams s{0, 0, 0, 0, 0, 0, 0, tab.cols(d_tab, pc)};
+    const LmpStreams s{0, 0, 0, 0, 0, 0, 0, tab.cols(d_tab.get(), pc)};
     err = lmp_launch<LmpPlace::Ragged>(form, LmpCall{rows, out, bins, nl, st}, s, (size_t)pc.blocks, 1, G);
     if (err != hipSuccess) break;
   }
-  scratch_free(d_tab, st);
   return err;
 }
 

@@ -85,15 +85,16 @@ hipError_t floor_rows(const float *d_psd, size_t rows, int bins, int pitch, floa
 }  // namespace glfer
 
 // The small device table of a batch or ragged call: the palette, the dB steps and the carried states of disps[0..n) as
-// [n][3] floats {first_buffer, display_max_lvl, display_min_lvl}.  One stream-ordered allocation, one upload (pageable
-// source: hipMemcpyAsync stages it before returning).  On an error nothing is left allocated.
+// [n][3] floats {first_buffer, display_max_lvl, display_min_lvl}.  One stream-ordered allocation, one upload
+// (Scratch::upload).  On an error nothing is left allocated.
 struct DisplayTable {
-  unsigned char *block = nullptr;
+  explicit DisplayTable(hipStream_t st) : block(st) {}
+  glfer::Scratch<unsigned char> block;
   const unsigned char *d_tab = nullptr;
   const double *d_thr = nullptr;
   float *d_state = nullptr;
 };
-static hipError_t display_table_upload(const glfer_hip_display *disps, size_t n, hipStream_t st, DisplayTable *t) {
+static hipError_t display_table_upload(const glfer_hip_display *disps, size_t n, DisplayTable *t) {
   const size_t thr_bytes = (2 * glfer::kLogThrK + 1) * sizeof(double), bytes = 768 + thr_bytes + n * 3 * sizeof(float);
   std::vector<unsigned char> host(bytes);
   glfer::make_palette(disps[0].palette, host.data());
@@ -104,14 +105,12 @@ static hipError_t display_table_upload(const glfer_hip_display *disps, size_t n,
     h_state[b * 3 + 1] = disps[b].display_max_lvl;
     h_state[b * 3 + 2] = disps[b].display_min_lvl;
   }
-  hipError_t e = glfer::scratch_malloc((void **)&t->block, bytes, st);
+  const hipError_t e = t->block.upload(host.data(), bytes);
   if (e != hipSuccess) return e;
-  t->d_tab = t->block;
-  t->d_thr = reinterpret_cast<const double *>(t->block + 768);
-  t->d_state = reinterpret_cast<float *>(t->block + 768 + thr_bytes);
-  e = hipMemcpyAsync(t->block, host.data(), bytes, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) glfer::scratch_free(t->block, st);
-  return e;
+  t->d_tab = t->block.get();
+  t->d_thr = reinterpret_cast<const double *>(t->block.get() + 768);
+  t->d_state = reinterpret_cast<float *>(t->block.get() + 768 + thr_bytes);
+  return hipSuccess;
 }
 
 // update_avg_* inside the mapping (avg_fused_kernel<.., MAP>): the PSD batch the columns belong to,
@@ -146,8 +145,9 @@ static int display_columns(glfer_hip_display *d, const float *d_psd, const doubl
   const size_t lev_floats = (d_levels || d_levels_in) ? 0 : nframes * 4;
   const size_t st_floats = (d->autoscale && !d_levels_in) ? glfer_levels_scratch_floats(nframes) : 0;
   const size_t thr_bytes = (2 * glfer::kLogThrK + 1) * sizeof(double);
-  unsigned char *scratch = nullptr;
-  HIP_TRY(glfer::scratch_malloc((void **)&scratch, 768 + thr_bytes + (lev_floats + st_floats) * sizeof(float), st));
+  glfer::Scratch<unsigned char> block(st);
+  HIP_TRY(block.take(768 + thr_bytes + (lev_floats + st_floats) * sizeof(float)));
+  unsigned char *const scratch = block.get();
   unsigned char *d_tab = scratch;
   double *d_thr = reinterpret_cast<double *>(scratch + 768);
   float *fs = reinterpret_cast<float *>(scratch + 768 + thr_bytes);
@@ -186,7 +186,7 @@ static int display_columns(glfer_hip_display *d, const float *d_psd, const doubl
     e = hipMemcpyAsync(last, levels + (nframes - 1) * 4, sizeof last, hipMemcpyDeviceToHost, st);
     if (e != hipSuccess) fail(e);
   }
-  glfer::scratch_free(scratch, st);
+  block.release();                           // (stream-ordered: before the wait, not after it)
   e = hipStreamSynchronize(st);              // the carried state comes back to the host
   if (e != hipSuccess && rc == GLFER_OK) fail(e);
   if (rc == GLFER_OK && !d_levels_in) {
@@ -265,18 +265,18 @@ static int waterfall_columns(glfer_hip_display *d, int avg_mode, int depth, int 
   size_t tile = 0;
   waterfall_route(avg_mode, depth, minbin, maxbin, bins, pitch, nframes, &fused, &tile);
   const size_t back = averaging ? (size_t)depth : 0;       // rows re-read in front of a tile to restart the sliding sums
-  float *stats = d_stats;
-  double *avg = nullptr, *ret = nullptr;
-  if (!stats && !d_levels_in) HIP_TRY(glfer::scratch_malloc((void **)&stats, tile * 4 * sizeof(float), st));
-  int rc = GLFER_OK;
+  glfer::Scratch<float> stats(st);
+  glfer::Scratch<double> avg(st), ret(st);
+  if (!d_stats && !d_levels_in) HIP_TRY(stats.take(tile * 4));
   if (averaging && !fused) {
-    hipError_t e = glfer::scratch_malloc((void **)&avg, (tile + back) * (size_t)bins * sizeof(double), st);
-    if (e == hipSuccess) e = glfer::scratch_malloc((void **)&ret, (tile + back) * 4 * sizeof(double), st);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMallocAsync(waterfall tile)");
+    hipError_t e = avg.take((tile + back) * (size_t)bins);
+    if (e == hipSuccess) e = ret.take((tile + back) * 4);
+    if (e != hipSuccess) return hip_fail(e, "hipMallocAsync(waterfall tile)");
   }
+  int rc = GLFER_OK;
   for (size_t f0 = 0; rc == GLFER_OK && f0 < nframes; f0 += tile) {
     const size_t nf = std::min(tile, nframes - f0);
-    float *tstats = d_stats ? d_stats + f0 * 4 : stats;
+    float *tstats = d_stats ? d_stats + f0 * 4 : stats.get();
     const float *tlevels = d_levels_in ? d_levels_in + f0 * 4 : nullptr;
     unsigned char *trgb = d_rgb + f0 * (size_t)bins * 3;
     short *tlev = d_lev ? d_lev + f0 * (size_t)bins : nullptr;
@@ -295,16 +295,13 @@ static int waterfall_columns(glfer_hip_display *d, int avg_mode, int depth, int 
       const size_t lead = std::min(back, row0 + f0);
       // (update_avg's `bins` is its rows' stride; the band is minbin..maxbin, the averaged rows are dense)
       rc = glfer_hip_avg_device(avg_mode, d_batch + (row0 + f0 - lead) * (size_t)pitch, nf + lead, pitch, bins, depth, minbin, maxbin, max0,
-                                avg, ret, st);
-      src_avg = avg + lead * (size_t)bins;
+                                avg.get(), ret.get(), st);
+      src_avg = avg.get() + lead * (size_t)bins;
     }
     if (rc == GLFER_OK)
       rc = display_columns(d, averaging ? nullptr : d_psd + f0 * (size_t)pitch, src_avg, nullptr, tstats, nf, bins, trgb, tlev,
                            nullptr, st, tlevels, pitch);
   }
-  if (avg) glfer::scratch_free(avg, st);
-  if (ret) glfer::scratch_free(ret, st);
-  if (!d_stats && stats) glfer::scratch_free(stats, st);
   return rc;
 }
 
@@ -331,8 +328,9 @@ int glfer_hip_levels_host(glfer_hip_display *d, const float *h_stats, size_t nfr
   HIP_TRY(guard.error());
   const DisplayOptions o(*d);
   const size_t st_floats = d->autoscale ? glfer_levels_scratch_floats(nframes) : 0;
-  float *buf = nullptr;
-  HIP_TRY(glfer::scratch_malloc((void **)&buf, (nframes * 8 + st_floats) * sizeof(float), nullptr));
+  glfer::Scratch<float> block(nullptr);
+  HIP_TRY(block.take(nframes * 8 + st_floats));
+  float *const buf = block.get();
   float *d_stats = buf, *levels = buf + nframes * 4, *chunk_state = st_floats ? buf + nframes * 8 : nullptr;
   int rc = GLFER_OK;
   hipError_t e = hipMemcpyAsync(d_stats, h_stats, nframes * 4 * sizeof(float), hipMemcpyHostToDevice, nullptr);
@@ -346,7 +344,6 @@ int glfer_hip_levels_host(glfer_hip_display *d, const float *h_stats, size_t nfr
   }
   if (e == hipSuccess) e = hipMemcpyAsync(h_levels, levels, nframes * 4 * sizeof(float), hipMemcpyDeviceToHost, nullptr);
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  glfer::scratch_free(buf, nullptr);
   if (e != hipSuccess) rc = hip_fail(e, "glfer_hip_levels_host");
   if (rc == GLFER_OK) {
     d->display_max_lvl = h_levels[(nframes - 1) * 4 + 2];
@@ -390,42 +387,44 @@ static bool waterfall_batch_opens(const glfer_hip_display *disps, size_t nstream
   return true;
 }
 
-// The stream-ordered scratch of such a call (plain pointers: waterfall_batch_finish gives them back): the statistics of all rows
+// The stream-ordered scratch of such a call (waterfall_batch_finish gives it back before its wait): the statistics of all rows
 // (only without d_stats), the levels with the walks' chunk states behind them, the averaged rows of a staged group and their
 // return values.
 struct WaterfallScratch {
-  float *stats = nullptr, *own_stats = nullptr, *levels = nullptr;
-  double *avg = nullptr, *ret = nullptr;
+  explicit WaterfallScratch(hipStream_t st) : own_stats(st), levels(st), avg(st), ret(st) {}
+  float *stats = nullptr;                                 // the caller's d_stats, or own_stats
+  glfer::Scratch<float> own_stats, levels;
+  glfer::Scratch<double> avg, ret;
+  void release() {
+    avg.release();
+    ret.release();
+    levels.release();
+    own_stats.release();
+  }
 };
-static hipError_t waterfall_scratch_take(WaterfallScratch *s, float *d_stats, size_t rows, size_t level_floats, size_t avg_rows, size_t bins,
-                                         hipStream_t st) {
-  hipError_t e = hipSuccess;
-  auto take = [&](auto **p, size_t bytes) {               // (after a failure nothing more is asked for, and nothing of it is kept)
-    if (e == hipSuccess && (e = glfer::scratch_malloc((void **)p, bytes, st)) != hipSuccess) *p = nullptr;
-  };
-  if (!d_stats) take(&s->own_stats, rows * 4 * sizeof(float));
-  s->stats = d_stats ? d_stats : s->own_stats;
-  take(&s->levels, level_floats * sizeof(float));
-  if (avg_rows) take(&s->avg, avg_rows * bins * sizeof(double));
-  if (avg_rows) take(&s->ret, avg_rows * 4 * sizeof(double));
+// (after a failure nothing more is asked for, and nothing is kept)
+static hipError_t waterfall_scratch_take(WaterfallScratch *s, float *d_stats, size_t rows, size_t level_floats, size_t avg_rows, size_t bins) {
+  hipError_t e = d_stats ? hipSuccess : s->own_stats.take(rows * 4);
+  s->stats = d_stats ? d_stats : s->own_stats.get();
+  if (e == hipSuccess) e = s->levels.take(level_floats);
+  if (e == hipSuccess && avg_rows) e = s->avg.take(avg_rows * bins);
+  if (e == hipSuccess && avg_rows) e = s->ret.take(avg_rows * 4);
+  if (e != hipSuccess) s->release();
   return e;
 }
 
 // The end of such a call: the carried states come down (autoscale), the scratch and the table go back -- stream-ordered, before
 // the synchronisation -- and after it the displays take their states: those of the streams `live` names, or all of them.
 static int waterfall_batch_finish(int rc, glfer_hip_display *disps, size_t nstreams, const std::vector<RaggedColsEntry> *live,
-                                  const DisplayOptions &o, const DisplayTable &t, const WaterfallScratch &s, hipStream_t st,
+                                  const DisplayOptions &o, DisplayTable &t, WaterfallScratch &s, hipStream_t st,
                                   const char *entry) {
   const bool autoscale = disps[0].autoscale != 0;
   std::vector<float> back_state(autoscale ? nstreams * 3 : 0);
   hipError_t e = hipSuccess;
   if (rc == GLFER_OK && autoscale) e = hipMemcpyAsync(back_state.data(), t.d_state, nstreams * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
   if (e != hipSuccess) rc = hip_fail(e, entry);
-  glfer::scratch_free(s.avg, st);
-  glfer::scratch_free(s.ret, st);
-  glfer::scratch_free(s.levels, st);
-  glfer::scratch_free(s.own_stats, st);
-  glfer::scratch_free(t.block, st);
+  s.release();
+  t.block.release();
   e = hipStreamSynchronize(st);              // the carried states come back to the host
   if (e != hipSuccess && rc == GLFER_OK) rc = hip_fail(e, entry);
   if (rc != GLFER_OK) return rc;
@@ -496,18 +495,18 @@ int glfer_hip_waterfall_batch_device(glfer_hip_display *disps, size_t nstreams, 
   size_t group = chunk;
   if (staged) group = std::max<size_t>(1, std::min(group, ((size_t)4 << 30) / ((tile + back) * bins_z * sizeof(double))));
 
-  DisplayTable t;
-  HIP_TRY(display_table_upload(disps, nstreams, st, &t));
+  DisplayTable t(st);
+  HIP_TRY(display_table_upload(disps, nstreams, &t));
   auto fail = [&](hipError_t err, const char *what) {
     if (rc == GLFER_OK) rc = hip_fail(err, what);
   };
   // scratch: statistics of all rows, a tile's levels and chunk states, a group's averaged rows (staged)
   const size_t st_floats = autoscale ? glfer_levels_scratch_floats(tile) : 0;
-  WaterfallScratch s;
+  WaterfallScratch s(st);
   hipError_t e = waterfall_scratch_take(&s, d_stats, nstreams * nframes, nstreams * (tile * 4 + st_floats),
-                                        staged ? std::min(group, nstreams) * (tile + back) : 0, bins_z, st);
+                                        staged ? std::min(group, nstreams) * (tile + back) : 0, bins_z);
   if (e != hipSuccess) fail(e, "scratch (waterfall, batch)");
-  float *stats = s.stats, *levels = s.levels, *chunk_state = s.levels ? s.levels + nstreams * tile * 4 : nullptr;
+  float *stats = s.stats, *levels = s.levels.get(), *chunk_state = levels ? levels + nstreams * tile * 4 : nullptr;
 
   // compute_floor of every row: the streams' rows are one run of nstreams x nframes rows
   if (rc == GLFER_OK) {
@@ -559,10 +558,10 @@ int glfer_hip_waterfall_batch_device(glfer_hip_display *disps, size_t nstreams, 
     for (size_t c0 = 0; rc == GLFER_OK && c0 < nstreams; c0 += group) {
       const unsigned nb = (unsigned)std::min(nstreams - c0, group);
       e = glfer_launch_avg_batch(avg_mode, d_psd + c0 * rows_bs + (f0 - lead) * (size_t)pitch, arows, pitch, bins, depth, minbin, maxbin,
-                                 max0 ? 1 : 0, s.avg, s.ret, nb, (long long)rows_bs, (long long)(arows * bins_z), (long long)(arows * 4), st);
+                                 max0 ? 1 : 0, s.avg.get(), s.ret.get(), nb, (long long)rows_bs, (long long)(arows * bins_z), (long long)(arows * 4), st);
       if (e != hipSuccess) fail(e, "update_avg launch (waterfall, batch)");
       if (rc == GLFER_OK) {
-        e = glfer_launch_map_batch(nullptr, s.avg + lead * bins_z, nf, bins, bins, o.scale_log, o.thr255, o.one_m_thr, levels + c0 * nf * 4,
+        e = glfer_launch_map_batch(nullptr, s.avg.get() + lead * bins_z, nf, bins, bins, o.scale_log, o.thr255, o.one_m_thr, levels + c0 * nf * 4,
                                    t.d_tab, t.d_thr, d_rgb + (c0 * cols + f0 * bins_z) * 3, d_lev ? d_lev + c0 * cols + f0 * bins_z : nullptr,
                                    nb, (long long)(arows * bins_z), (long long)(nf * 4), (long long)(cols * 3), (long long)cols, st);
         if (e != hipSuccess) fail(e, "map launch (waterfall, batch)");
@@ -619,8 +618,8 @@ int glfer_hip_waterfall_ragged_device(glfer_hip_display *disps, size_t nstreams,
     return GLFER_OK;
   }
   const DisplayOptions o(disps[0]);
-  DisplayTable t;
-  HIP_TRY(display_table_upload(disps, nstreams, st, &t));
+  DisplayTable t(st);
+  HIP_TRY(display_table_upload(disps, nstreams, &t));
   auto fail = [&](hipError_t err, const char *what) {
     if (rc == GLFER_OK) rc = hip_fail(err, what);
   };
@@ -644,10 +643,10 @@ int glfer_hip_waterfall_ragged_device(glfer_hip_display *disps, size_t nstreams,
     scratch_rows = std::max(scratch_rows, in_group);
     if (i + 1 == staged_s.size()) group_end.push_back(i + 1);
   }
-  WaterfallScratch s;
-  hipError_t e = waterfall_scratch_take(&s, d_stats, rows_hi, rows_hi * 4 + st_floats, scratch_rows, bins_z, st);
+  WaterfallScratch s(st);
+  hipError_t e = waterfall_scratch_take(&s, d_stats, rows_hi, rows_hi * 4 + st_floats, scratch_rows, bins_z);
   if (e != hipSuccess) fail(e, "scratch (waterfall, ragged)");
-  float *stats = s.stats, *levels = s.levels, *chunk_state = s.levels ? s.levels + rows_hi * 4 : nullptr;
+  float *stats = s.stats, *levels = s.levels.get(), *chunk_state = levels ? levels + rows_hi * 4 : nullptr;
 
   // compute_floor of every row: the packed rows are one run
   if (rc == GLFER_OK) {
@@ -680,10 +679,10 @@ int glfer_hip_waterfall_ragged_device(glfer_hip_display *disps, size_t nstreams,
     const RaggedColsEntry *gs = staged_s.data() + i0;
     const size_t gn = group_end[g] - i0;
     // (update_avg's `bins` is its rows' stride; the band is minbin..maxbin, the averaged rows are dense)
-    e = glfer_launch_avg_ragged(avg_mode, d_psd, gs, gn, pitch, bins, depth, minbin, maxbin, max0 ? 1 : 0, s.avg, s.ret, st);
+    e = glfer_launch_avg_ragged(avg_mode, d_psd, gs, gn, pitch, bins, depth, minbin, maxbin, max0 ? 1 : 0, s.avg.get(), s.ret.get(), st);
     if (e != hipSuccess) fail(e, "update_avg launch (ragged waterfall)");
     if (rc == GLFER_OK) {
-      e = glfer_launch_map_ragged(s.avg, gs, gn, bins, o.scale_log, o.thr255, o.one_m_thr, levels, t.d_tab, t.d_thr, d_rgb, d_lev, st);
+      e = glfer_launch_map_ragged(s.avg.get(), gs, gn, bins, o.scale_log, o.thr255, o.one_m_thr, levels, t.d_tab, t.d_thr, d_rgb, d_lev, st);
       if (e != hipSuccess) fail(e, "map launch (ragged waterfall)");
     }
   }
