@@ -7,4 +7,5 @@ from .api import (Workers, Phases, AVG_PLAIN, AVG_SUMAVG, AVG_SUMEXTREME, HISTOR
                   lmp_statistic, lmp_statistic_batch, lmp_statistic_ragged,
                   update_avg, update_avg_batch, update_avg_ragged, version, waterfall_ragged, wav_probe, deinterleave,
                   IQ_CENTERED, IQ_SWAP, iq_supported, iq_tables, Cross, cross_supported, welch_cross_supported,
+                  Adaptive, adaptive_supported, adaptive_weights,
                   Ddc, DdcConfig, ddc_design, ddc_phase_word, ddc_supported, ddc_tables)

@@ -24,6 +24,8 @@ WAV_PARTIAL_TAIL = 1
 IQ_CENTERED, IQ_SWAP = 1, 2                            # flags of the complex I/Q entries
 CROSS_FIELDS = ("sxx", "syy", "sxy", "coh")
 Cross = collections.namedtuple("Cross", CROSS_FIELDS)  # what Spectrogram.cross returns: None for what was not asked
+ADAPTIVE_FIELDS = ("psd", "dof")
+Adaptive = collections.namedtuple("Adaptive", ADAPTIVE_FIELDS)  # what Spectrogram.adaptive returns: None for what was not asked
 WINDOWS = {"hanning": 0, "blackman": 1, "gaussian": 2, "welch": 3,
            "bartlett": 4, "rectangular": 5, "hamming": 6, "kaiser": 7}
 SAMPLES_F32, SAMPLES_S16, SAMPLES_U8 = 0, 1, 2
@@ -79,6 +81,8 @@ EXPORTS = [
     "glfer_hip_cross_supported", "glfer_hip_mtm_cross_device", "glfer_hip_mtm_cross_batch_device",
     # the same averaged over L consecutive segments (Welch): FFT plans too
     "glfer_hip_welch_cross_supported", "glfer_hip_welch_rows", "glfer_hip_welch_cross_device", "glfer_hip_welch_cross_batch_device",
+    # adaptive multitaper weights: leakage-resistant rows and their degrees of freedom in one pass
+    "glfer_hip_adaptive_supported", "glfer_hip_adaptive_weights", "glfer_hip_mtm_adaptive_device", "glfer_hip_mtm_adaptive_batch_device",
 ]
 
 
@@ -236,6 +240,11 @@ def lib():
         L.glfer_hip_welch_rows.restype = sz
         L.glfer_hip_welch_cross_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, sz, vp, sz, vp]
         L.glfer_hip_welch_cross_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, sz, sz, vp, vp, vp, sz, vp, sz, vp]
+    if hasattr(L, "glfer_hip_mtm_adaptive_device"):
+        L.glfer_hip_adaptive_supported.argtypes = [C.POINTER(Config)]
+        L.glfer_hip_adaptive_weights.argtypes = [C.POINTER(Config), vp, vp]
+        L.glfer_hip_mtm_adaptive_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, sz, C.c_int, vp]
+        L.glfer_hip_mtm_adaptive_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, sz, C.c_int, vp]
     if hasattr(L, "glfer_hip_ddc_device"):
         L.glfer_hip_ddc_phase_word.argtypes = [C.c_double]
         L.glfer_hip_ddc_phase_word.restype = C.c_ulonglong
@@ -342,6 +351,24 @@ def welch_cross_supported(params, segments, step):
     apart (glfer_hip_welch_cross_supported; host only)."""
     cfg = make_config(params)
     return lib().glfer_hip_welch_cross_supported(C.byref(cfg), segments, step) == 0
+
+
+def adaptive_supported(params):
+    """Whether a plan of these parameters gives adaptively weighted rows (glfer_hip_adaptive_supported; host only)."""
+    cfg = make_config(params)
+    return lib().glfer_hip_adaptive_supported(C.byref(cfg)) == 0
+
+
+def adaptive_weights(params):
+    """(lambda, beta): the float32 weights the adaptive kernel gets for a plan of these parameters, one per taper
+    (glfer_hip_adaptive_weights; host only)."""
+    cfg = make_config(params)
+    k = params.kmax + 1
+    lam, beta = np.empty(k, np.float32), np.empty(k, np.float32)
+    rc = lib().glfer_hip_adaptive_weights(C.byref(cfg), lam.ctypes.data, beta.ctypes.data)
+    if rc != k:
+        _check(rc if rc < 0 else -1, "glfer_hip_adaptive_weights")
+    return lam, beta
 
 
 def iq_tables(params):
@@ -772,6 +799,67 @@ class Spectrogram:
                                                       self._cross_ptr(ts, "sxx"), self._cross_ptr(ts, "syy"), self._cross_ptr(ts, "coh"),
                                                       pitch, self._cross_ptr(ts, "sxy"), xpitch, st), "glfer_hip_mtm_cross_batch_device")
         return Cross(*(ts.get(k) for k in CROSS_FIELDS))
+
+    def _adaptive_outs(self, want, out, lead, nframes, device):
+        """The outputs of an adaptive call as (tensors by name, row pitch): made here, or the caller's (out: a mapping or an
+        Adaptive tuple of float32 tensors [lead..., nframes, n/2+1] whose row stride may be larger; they share one)."""
+        torch = _torch()
+        want = tuple(want)
+        assert want and all(w in ADAPTIVE_FIELDS for w in want), want
+        bins = self.n // 2 + 1
+        shape = tuple(lead) + (nframes, bins)
+        if out is not None and not isinstance(out, dict):
+            out = out._asdict()
+        ts, pitches = {}, set()
+        for name in want:
+            o = None if out is None else out.get(name)
+            if o is None:
+                ts[name] = torch.empty(shape, dtype=torch.float32, device=device)
+                pitches.add(bins)
+                continue
+            assert o.is_cuda and o.dtype == torch.float32 and tuple(o.shape) == shape, (name, tuple(o.shape), shape)
+            assert o.stride(-1) == 1 or o.size(-1) <= 1
+            pitch = o.stride(-2) if o.size(-2) > 1 else bins
+            assert pitch >= bins
+            if lead and o.size(0) > 1:
+                assert o.stride(0) == nframes * pitch, "batch rows lie (b * nframes + i) rows from the first"
+            pitches.add(pitch)
+            ts[name] = o
+        assert len(pitches) == 1, "psd and dof share one row pitch"
+        return ts, pitches.pop()
+
+    def adaptive(self, stream, first_frame=0, nframes=None, iters=8, want=("psd", "dof"), out=None):
+        """stream: 1-D torch tensor on this GPU, of the plan's sample dtype; the plan is a multitaper one with 2 .. 8 tapers.
+        Returns Adaptive(psd, dof) with None for what `want` does not name, float32 [nframes][n/2+1]: Thomson's adaptively
+        weighted estimate after exactly `iters` sweeps -- a weighted MEAN of the eigenspectra, where run() gives a weighted
+        sum -- and its degrees of freedom, 2 .. 2 K.  One launch on torch's current stream (glfer_hip_mtm_adaptive_device)."""
+        torch = _torch()
+        assert stream.is_cuda and stream.dim() == 1 and stream.is_contiguous()
+        assert stream.dtype == self._sample_dtype(), (stream.dtype, self._sample_dtype())
+        if nframes is None:
+            nframes = self.num_frames(stream.numel()) - first_frame
+        ts, pitch = self._adaptive_outs(want, out, (), nframes, stream.device)
+        st = C.c_void_p(torch.cuda.current_stream(stream.device).cuda_stream)
+        _check(lib().glfer_hip_mtm_adaptive_device(self._h, C.c_void_p(stream.data_ptr()), stream.numel(), first_frame, nframes,
+                                                   self._cross_ptr(ts, "psd"), self._cross_ptr(ts, "dof"), pitch, iters, st),
+               "glfer_hip_mtm_adaptive_device")
+        return Adaptive(*(ts.get(k) for k in ADAPTIVE_FIELDS))
+
+    def adaptive_batch(self, streams, first_frame=0, nframes=None, iters=8, want=("psd", "dof"), out=None):
+        """streams: 2-D torch tensor [B, T] as run_batch takes it.  Returns Adaptive of [B][nframes][n/2+1] tensors: entry b is
+        what adaptive(streams[b]) gives (glfer_hip_mtm_adaptive_batch_device)."""
+        torch = _torch()
+        assert streams.is_cuda and streams.dim() == 2 and (streams.stride(1) == 1 or streams.size(1) <= 1)
+        assert streams.dtype == self._sample_dtype(), (streams.dtype, self._sample_dtype())
+        nb, total = streams.size(0), streams.size(1)
+        if nframes is None:
+            nframes = self.num_frames(total) - first_frame
+        ts, pitch = self._adaptive_outs(want, out, (nb,), nframes, streams.device)
+        st = C.c_void_p(torch.cuda.current_stream(streams.device).cuda_stream)
+        _check(lib().glfer_hip_mtm_adaptive_batch_device(self._h, C.c_void_p(streams.data_ptr()), nb, streams.stride(0), total,
+                                                         first_frame, nframes, self._cross_ptr(ts, "psd"), self._cross_ptr(ts, "dof"),
+                                                         pitch, iters, st), "glfer_hip_mtm_adaptive_batch_device")
+        return Adaptive(*(ts.get(k) for k in ADAPTIVE_FIELDS))
 
     def welch_rows(self, nsamples, segments, step=None, first_frame=0):
         """Rows cross_welch gives for a stream of nsamples pairs: (frames - first_frame - segments) // step + 1, or 0."""

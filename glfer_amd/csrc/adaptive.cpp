@@ -1,0 +1,119 @@
+// adaptive.cpp -- the adaptive-weight entries of include/glfer_hip.h: Thomson's adaptively weighted multitaper rows of one real
+// channel and their degrees of freedom in one pass (spectro16a.hip).  The checks follow cross.cpp's cross_rows in order and
+// wording; the kernel reads the plan's unscaled taper table (made with the plan) and twiddles, and the weights ride in its
+// argument block.
+#include "plan.h"
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "frame_cuts.h"
+#include "host_tables.h"
+#include "spectro_adaptive_params.h"
+#include "spectro_params.h"
+
+using glfer::DeviceGuard;
+using glfer::hip_fail;
+
+static_assert(GLFER_FMT_F32 == GLFER_SAMPLES_F32 && GLFER_FMT_S16 == GLFER_SAMPLES_S16 && GLFER_FMT_U8 == GLFER_SAMPLES_U8, "AdaptiveParams::fmt");
+
+// The floats the kernel gets from a plan's sig_j (lambda_j = 1 + sig_j, g-l_dpss.c:343): beta_j = max(-sig_j, 0) formed in double
+// and rounded, lambda_j = 1 - beta_j formed in double from the unrounded beta_j and rounded.  false: the lambda are not
+// non-increasing in j (u_j <= 1 rests on that), or not in (0, 1].
+static bool adaptive_weights_of(const double *sig, int k, float *lam, float *beta) {
+  double prev = 1.0;
+  for (int j = 0; j < k; j++) {
+    const double b = std::max(-sig[j], 0.0), l = 1.0 - b;
+    if (!(l > 0.0) || !(l <= prev)) return false;
+    prev = l;
+    if (lam) lam[j] = (float)l;
+    if (beta) beta[j] = (float)b;
+  }
+  return true;
+}
+
+static int adaptive_rows(glfer_hip_plan *p, const void *d_stream, size_t nstreams, size_t stream_pitch, size_t nsamples, size_t first,
+                         size_t nframes, float *d_psd, float *d_dof, size_t row_pitch, int iters, void *hip_stream) {
+  if (!p || !p->d_ataps || glfer_hip_adaptive_supported(&p->cfg) != GLFER_OK) return GLFER_E_ARG;
+  const size_t bins = (size_t)p->n / 2 + 1, pitch = row_pitch ? row_pitch : bins;
+  if (pitch < bins) return GLFER_E_ARG;
+  if (iters < 1 || iters > GLFER_ADAPTIVE_ITERS_MAX) return GLFER_E_ARG;
+  AdaptiveParams q;
+  memset(&q, 0, sizeof q);
+  if (!adaptive_weights_of(p->sig.data(), p->ntapers, q.lam, q.beta)) return GLFER_E_ARG;
+  if (nstreams == 0 || nframes == 0) return GLFER_OK;
+  if (!d_stream || (!d_psd && !d_dof)) return GLFER_E_ARG;
+  const size_t csz = glfer_sample_size(p->cfg.sample_format);
+  if (reinterpret_cast<uintptr_t>(d_stream) & (csz - 1)) return GLFER_E_ARG;
+  const size_t F = nsamples / (size_t)p->hop;
+  if (first + nframes < first || (first + nframes) > F) return GLFER_E_ARG;   // wraps, or a frame past the stream
+  if (nframes > 0x7fffffffu) return GLFER_E_ARG;
+  if (nsamples > SIZE_MAX / csz || stream_pitch > (SIZE_MAX / csz) / nstreams) return GLFER_E_ARG;
+  if (pitch > SIZE_MAX / sizeof(float) / nframes || nframes * pitch > (SIZE_MAX / sizeof(float)) / nstreams) return GLFER_E_ARG;
+  hipStream_t st = (hipStream_t)hip_stream;
+  DeviceGuard guard(p->cfg.device);
+  HIP_TRY(guard.error());
+  size_t ymax = 1;
+  if (nstreams > 1) {
+    int dev = 0, y = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&y, hipDeviceAttributeMaxGridDimY, dev));
+    ymax = (size_t)std::max(1, std::min(y, 65535));
+  }
+  q.frame0 = (long long)first;
+  q.nframes = (int)nframes;
+  q.H = p->hop;
+  q.R = p->keep;
+  q.ntap = p->ntapers;
+  q.history_mode = p->cfg.history_mode ? 1 : 0;
+  q.fmt = p->cfg.sample_format;
+  q.iters = iters;
+  q.inv_n = 1.0f / (float)p->n;
+  q.taps = p->d_ataps;
+  q.tw = p->d_tw;
+  q.row_pitch = (long long)pitch;
+  q.batch_stride = (long long)(stream_pitch * csz);
+  q.row_batch_stride = (long long)(nframes * pitch);
+  const auto launcher = launcher16_adaptive(glfer_logn(p->n));
+  for (size_t c0 = 0; c0 < nstreams; c0 += ymax) {      // batches above the grid's y limit: chunks of it
+    const size_t nb = std::min(nstreams - c0, ymax);
+    q.stream = static_cast<const char *>(d_stream) + c0 * stream_pitch * csz;
+    q.psd = d_psd ? d_psd + c0 * nframes * pitch : nullptr;
+    q.dof = d_dof ? d_dof + c0 * nframes * pitch : nullptr;
+    q.nbatch = (int)nb;
+    const hipError_t e = launcher ? launcher(&q, st) : hipErrorInvalidValue;
+    if (e != hipSuccess) return hip_fail(e, "estimator launch (adaptive)");
+  }
+  return GLFER_OK;
+}
+
+extern "C" {
+
+int glfer_hip_adaptive_supported(const glfer_hip_config *cfg) {
+  if (!cfg) return GLFER_E_ARG;
+  if (cfg->mode != GLFER_MODE_MTM || cfg->mtm_k < 1 || cfg->mtm_k + 1 > GLFER_ADAPTIVE_KMAX) return GLFER_E_ARG;   // K = 2 .. 8 tapers
+  if (cfg->n < 256 || cfg->n > 4096 || (cfg->n & (cfg->n - 1))) return GLFER_E_ARG;
+  return glfer_hip_iq_supported(cfg);                                          // mean removal, limiter, RA9MB, the sample format
+}
+
+int glfer_hip_adaptive_weights(const glfer_hip_config *cfg, float *lambda_out, float *beta_out) {
+  if (glfer_hip_adaptive_supported(cfg) != GLFER_OK || !(cfg->mtm_w > 0.0f)) return GLFER_E_ARG;
+  const int nt = cfg->mtm_k + 1;
+  std::vector<double> tapers((size_t)nt * cfg->n), sig(nt);
+  if (!glfer::make_dpss(cfg->n, cfg->mtm_k, (double)cfg->mtm_w, tapers.data(), sig.data())) return GLFER_E_NUMERIC;
+  return adaptive_weights_of(sig.data(), nt, lambda_out, beta_out) ? nt : GLFER_E_ARG;
+}
+
+int glfer_hip_mtm_adaptive_batch_device(glfer_hip_plan *p, const void *d_stream, size_t nstreams, size_t stream_pitch, size_t nsamples,
+                                        size_t first, size_t nframes, float *d_psd, float *d_dof, size_t row_pitch, int iters,
+                                        void *hip_stream) {
+  return adaptive_rows(p, d_stream, nstreams, stream_pitch, nsamples, first, nframes, d_psd, d_dof, row_pitch, iters, hip_stream);
+}
+
+int glfer_hip_mtm_adaptive_device(glfer_hip_plan *p, const void *d_stream, size_t nsamples, size_t first, size_t nframes, float *d_psd,
+                                  float *d_dof, size_t row_pitch, int iters, void *hip_stream) {
+  return adaptive_rows(p, d_stream, 1, 0, nsamples, first, nframes, d_psd, d_dof, row_pitch, iters, hip_stream);
+}
+
+}  // extern "C"

@@ -483,6 +483,19 @@ int glfer_hip_plan_create(const glfer_hip_config *cfg, glfer_hip_plan **out) {
       }
   }
 
+  // --- adaptive weights (spectro16a.hip): the tapers themselves, float(v_j) with nothing folded in, in the I/Q table's order; two
+  // rows a round, so an odd count ends with a row of zeros.  Made with the plan: the entries allocate and copy nothing
+  std::vector<float> ataps;
+  if (glfer_hip_adaptive_supported(&p->cfg) == GLFER_OK) {
+    const int T = n / 16, rows = 2 * ((p->ntapers + 1) / 2);
+    ataps.assign((size_t)rows * n, 0.0f);
+    for (int j = 0; j < p->ntapers; j++)
+      for (int i = 0; i < n; i++) {
+        const int t = i % T, m = i / T;
+        ataps[(size_t)j * n + ((size_t)(m / 4) * T + t) * 4 + (size_t)(m & 3)] = (float)p->tapers[(size_t)j * n + i];
+      }
+  }
+
   // --- HP-ARMA tables: which lag each cell of the t x (p_e+1) matrix holds after the
   // reference's fill (hparma.c:89-102).  r_xx is matrix(0,t,0,p_e) (hparma.c:64): its rows
   // are contiguous (util.c:153-160), lags 0..t-1 are written into row 0 past its p_e+1
@@ -606,6 +619,10 @@ int glfer_hip_plan_create(const glfer_hip_config *cfg, glfer_hip_plan **out) {
     e = hipMalloc((void **)&p->d_iqtaps, iqtaps.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(p->d_iqtaps, iqtaps.data(), iqtaps.size() * sizeof(float), hipMemcpyHostToDevice);
   }
+  if (e == hipSuccess && !ataps.empty()) {
+    e = hipMalloc((void **)&p->d_ataps, ataps.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(p->d_ataps, ataps.data(), ataps.size() * sizeof(float), hipMemcpyHostToDevice);
+  }
   if (e == hipSuccess && !xtaps.empty() && n == 4096) {
     p->yq = new glfer_yqueue;
     const size_t bytes = (size_t)glfer_yqueue::SLOTS * glfer_yqueue::PITCH * sizeof(unsigned);
@@ -656,6 +673,7 @@ void glfer_hip_plan_destroy(glfer_hip_plan *p) {
   if (p->d_ltaps) (void)hipFree(p->d_ltaps);
   if (p->d_ytaps) (void)hipFree(p->d_ytaps);
   if (p->d_iqtaps) (void)hipFree(p->d_iqtaps);
+  if (p->d_ataps) (void)hipFree(p->d_ataps);
   if (p->yq) {
     if (p->yq->d_counters) (void)hipFree(p->yq->d_counters);
     delete p->yq;

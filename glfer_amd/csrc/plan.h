@@ -147,6 +147,7 @@ struct glfer_hip_plan {
   float *d_ltaps = nullptr;         // odd taper counts, LDS-resident half tables (spectro16xl.hip)
   float *d_ytaps = nullptr;         // five tapers at N = 4096, register-resident half tables (spectro16y.hip); NULL: not exactly symmetric
   float *d_iqtaps = nullptr;        // complex I/Q rows (spectro16c.hip): [ntapers][4][n/16][4] one scaled float per sample and taper; NULL: not supported
+  float *d_ataps = nullptr;         // adaptive weights (spectro16a.hip): [2 ceil(ntapers/2)][4][n/16][4] the tapers UNSCALED, an odd count's last row zeros; NULL: not supported
   glfer_yqueue *yq = nullptr;       // spectro16y.hip's queue form: the plan's ticket counters (N = 4096, odd taper counts)
   uint16_t *d_lagmap = nullptr;     // HP-ARMA: [t][p_e+1] lag held by each matrix cell
   int *d_rot_sched = nullptr;       // HP-ARMA: [rot_steps][8] the Jacobi sweep as steps of up to eight column-disjoint rotations (j | k << 8, -1 = none)

@@ -731,6 +731,60 @@ int glfer_hip_welch_cross_batch_device(glfer_hip_plan *plan, const void *d_xy, s
                                        size_t first_frame, size_t segments, size_t step, size_t nrows, float *d_sxx, float *d_syy,
                                        float *d_coh, size_t row_pitch, void *d_sxy, size_t sxy_pitch, void *hip_stream);
 
+/* ---- Adaptive multitaper weights: leakage-resistant rows and their degrees of freedom in one pass ------------------------------
+ * The multitaper row of glfer_hip_spectrogram_device is the reference's fixed-weight sum, as leaky as its leakiest taper: beside a
+ * strong carrier the last taper's sidelobes, not the data, set the floor.  Thomson's adaptive weighting (1982, section V; Percival
+ * & Walden eq. 368a / 370a) gives every bin its own weights: where the spectrum lies far below the frame's power the leaky
+ * high-order tapers are weighted down to nothing, where it is flat all K tapers count.  Input: one real channel as
+ * glfer_hip_spectrogram_device takes it (cfg.sample_format, both history modes, the virtual base, frame ranges).  With
+ * K = kmax + 1, v_j the plan's unit-energy tapers, x_f the N values the transform sees (zeroed history INCLUDED), for k = 0 .. N/2:
+ *   E_j[k] = |FFT(v_j x_f)[k]|^2 / N         the eigenspectra; there is NO 1 / (1 + sig_j) in them
+ *   sigma2 = sum_n x_f[n]^2 / N              the frame's power
+ *   beta_j = max(-sig_j, 0) formed in double and rounded to float; lambda_j = 1 - beta_j likewise (glfer_hip_adaptive_weights
+ *            returns the floats the kernel gets); B_j = beta_j sigma2 / N bounds taper j's broadband leakage
+ *   S      = (E_0 + E_1) / 2, then exactly `iters` sweeps of
+ *              u_j = (lambda_0 S + B_0) / (lambda_j S + B_j)    u_0 = 1; a quotient whose denominator is 0 counts as 1
+ *              w_j = lambda_j u_j^2
+ *              S   = sum_j w_j E_j / sum_j w_j
+ *   d_psd  = S after the last sweep.  It is a weighted MEAN of the eigenspectra; the row of glfer_hip_spectrogram_device is a
+ *            weighted SUM, about K times larger on a flat spectrum.
+ *   d_dof  = 2 (sum_j w_j)^2 / sum_j w_j^2 from the weights that formed the last sweep: between 2 and 2 K, what a detector
+ *            needs to set a threshold.
+ * w_j is the textbook d_j^2 = lambda_j S^2 / (lambda_j S + B_j)^2 with the factor common to all j cancelled, so u_j <= 1 and
+ * sum w >= lambda_0: nothing underflows to 0 / 0 and silence gives exact zero rows and a finite dof, never NaN.
+ * THE RESULT IS DEFINED BY THE SWEEP COUNT, NOT BY CONVERGENCE, and deliberately so.  After 8 sweeps every bin of a noise frame
+ * is within 0.06 dB of the iteration's limit and all but a few tens of bins of a frame with a strong carrier within 0.1 dB, but
+ * on the carrier's skirts the fixed-point equation has 3 - 5 roots and a handful of bins need 35 - 200 sweeps; an accelerated
+ * iteration lands on another root.  All sums run in the fixed order j = 0, 1, ...: a row is a function of its own frame alone,
+ * and sweep m's bits do not depend on how many sweeps follow.
+ * Outputs, any subset (NULL: not wanted; both NULL is refused): [nframes][row_pitch] floats, row_pitch 0 means P = N/2 + 1, any
+ * other value must be >= P; a batch: row i of stream b at + (b * nframes + i) rows, stream b's sample 0 at d_stream + b *
+ * stream_pitch samples.  cfg.psd_pitch is NOT read here.
+ * One kernel per call (spectro16a.hip: tapers 2r and 2r + 1 of a frame ride one packed transform and are taken apart through the
+ * mirror bins; the K eigenspectra of a lane's bins stay in its registers until the frame's last taper, then the sweeps run
+ * there; a batch above the grid's y limit: one per chunk of streams), no allocation, no host synchronisation: legal on a
+ * hip_stream that is being captured.  ACCURACY: two tapers ride one transform, so an eigenspectrum carries the rounding of its
+ * PAIR (some 2^-24 of the frame's amplitude per bin) -- far below the leakage the weighting removes.
+ * Supported (glfer_hip_adaptive_supported, host only: GLFER_OK or GLFER_E_ARG): MTM mode, 1 <= kmax <= 7 (K = 2 .. 8),
+ * N = 256 .. 4096, every overlap, both history modes, the three sample formats; sub_mean must be 0, the limiter and RA9MB off.
+ * A plan whose lambda_j are not non-increasing in j is refused by the entries and by glfer_hip_adaptive_weights.
+ * glfer_hip_adaptive_weights (host only): the K floats lambda_j and beta_j (either pointer may be NULL); returns K, or
+ * GLFER_E_ARG / GLFER_E_NUMERIC.
+ * Arguments, nothing on the device touched before they pass: GLFER_E_ARG for a NULL plan or one that is not supported, a pitch
+ * below P, iters outside 1 .. 64; then GLFER_OK with nothing launched for nframes == 0 (nstreams == 0); then GLFER_E_ARG for a
+ * NULL d_stream or both outputs NULL, a misaligned d_stream, first_frame + nframes wrapping or reaching past the stream,
+ * nframes > 0x7fffffff, sizes that overflow size_t.  Asynchronous on hip_stream.
+ * Not built: mean removal, N = 8192 (its instantiations spill ten registers) and N = 16384, more than 8 tapers (the
+ * eigenspectra of 16 would take 144 registers a lane), ragged / host / WAV / workers forms, adaptive weights on I/Q or
+ * cross-spectra, jackknife intervals, sweeps to a tolerance. */
+int glfer_hip_adaptive_supported(const glfer_hip_config *cfg);
+int glfer_hip_adaptive_weights(const glfer_hip_config *cfg, float *lambda_out, float *beta_out);
+int glfer_hip_mtm_adaptive_device(glfer_hip_plan *plan, const void *d_stream, size_t nsamples, size_t first_frame, size_t nframes,
+                                  float *d_psd, float *d_dof, size_t row_pitch, int iters, void *hip_stream);
+int glfer_hip_mtm_adaptive_batch_device(glfer_hip_plan *plan, const void *d_stream, size_t nstreams, size_t stream_pitch,
+                                        size_t nsamples, size_t first_frame, size_t nframes, float *d_psd, float *d_dof,
+                                        size_t row_pitch, int iters, void *hip_stream);
+
 /* ---- Zoom: a digital down-converter, and the two-sided rows of its output -------------------------------------------------------
  * A few tens of hertz around one carrier of a 48 kHz recording: instead of a block of a million samples whose transform covers the
  * whole band, the band is moved to 0 Hz, low-passed and decimated by D (a frequency-translating FIR, "DDC"), and the I/Q rows above
