@@ -8,4 +8,5 @@ from .api import (Workers, Phases, AVG_PLAIN, AVG_SUMAVG, AVG_SUMEXTREME, HISTOR
                   update_avg, update_avg_batch, update_avg_ragged, version, waterfall_ragged, wav_probe, deinterleave,
                   IQ_CENTERED, IQ_SWAP, iq_supported, iq_tables, Cross, cross_supported, welch_cross_supported,
                   Adaptive, adaptive_supported, adaptive_weights,
+                  Jackknife, jackknife_supported, jackknife_factor, jackknife_interval,
                   Ddc, DdcConfig, ddc_design, ddc_phase_word, ddc_supported, ddc_tables)

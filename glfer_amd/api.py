@@ -26,6 +26,8 @@ CROSS_FIELDS = ("sxx", "syy", "sxy", "coh")
 Cross = collections.namedtuple("Cross", CROSS_FIELDS)  # what Spectrogram.cross returns: None for what was not asked
 ADAPTIVE_FIELDS = ("psd", "dof")
 Adaptive = collections.namedtuple("Adaptive", ADAPTIVE_FIELDS)  # what Spectrogram.adaptive returns: None for what was not asked
+JACKKNIFE_FIELDS = ("psd", "dof", "logvar")
+Jackknife = collections.namedtuple("Jackknife", JACKKNIFE_FIELDS)  # what Spectrogram.jackknife returns: None for what was not asked
 WINDOWS = {"hanning": 0, "blackman": 1, "gaussian": 2, "welch": 3,
            "bartlett": 4, "rectangular": 5, "hamming": 6, "kaiser": 7}
 SAMPLES_F32, SAMPLES_S16, SAMPLES_U8 = 0, 1, 2
@@ -83,6 +85,9 @@ EXPORTS = [
     "glfer_hip_welch_cross_supported", "glfer_hip_welch_rows", "glfer_hip_welch_cross_device", "glfer_hip_welch_cross_batch_device",
     # adaptive multitaper weights: leakage-resistant rows and their degrees of freedom in one pass
     "glfer_hip_adaptive_supported", "glfer_hip_adaptive_weights", "glfer_hip_mtm_adaptive_device", "glfer_hip_mtm_adaptive_batch_device",
+    # jackknife confidence intervals for multitaper rows in the same pass
+    "glfer_hip_jackknife_supported", "glfer_hip_jackknife_factor", "glfer_hip_mtm_jackknife_device",
+    "glfer_hip_mtm_jackknife_batch_device",
 ]
 
 
@@ -245,6 +250,11 @@ def lib():
         L.glfer_hip_adaptive_weights.argtypes = [C.POINTER(Config), vp, vp]
         L.glfer_hip_mtm_adaptive_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, sz, C.c_int, vp]
         L.glfer_hip_mtm_adaptive_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, sz, C.c_int, vp]
+    if hasattr(L, "glfer_hip_mtm_jackknife_device"):
+        L.glfer_hip_jackknife_supported.argtypes = [C.POINTER(Config)]
+        L.glfer_hip_jackknife_factor.argtypes = [C.POINTER(Config), C.c_double, C.POINTER(C.c_double)]
+        L.glfer_hip_mtm_jackknife_device.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, sz, C.c_int, vp]
+        L.glfer_hip_mtm_jackknife_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, sz, C.c_int, vp]
     if hasattr(L, "glfer_hip_ddc_device"):
         L.glfer_hip_ddc_phase_word.argtypes = [C.c_double]
         L.glfer_hip_ddc_phase_word.restype = C.c_ulonglong
@@ -357,6 +367,30 @@ def adaptive_supported(params):
     """Whether a plan of these parameters gives adaptively weighted rows (glfer_hip_adaptive_supported; host only)."""
     cfg = make_config(params)
     return lib().glfer_hip_adaptive_supported(C.byref(cfg)) == 0
+
+
+def jackknife_supported(params):
+    """Whether a plan of these parameters gives jackknife rows (glfer_hip_jackknife_supported; host only)."""
+    cfg = make_config(params)
+    return lib().glfer_hip_jackknife_supported(C.byref(cfg)) == 0
+
+
+def jackknife_factor(params, level=0.95):
+    """Student's quantile t_{K-1}((1 + level) / 2), what sqrt(logvar) is multiplied by for the interval at `level`
+    (glfer_hip_jackknife_factor; host only)."""
+    cfg = make_config(params)
+    t = C.c_double()
+    _check(lib().glfer_hip_jackknife_factor(C.byref(cfg), float(level), C.byref(t)), "glfer_hip_jackknife_factor")
+    return t.value
+
+
+def jackknife_interval(jk, params, level=0.95):
+    """(lower, upper) of the interval at `level` around jk.psd: psd exp(-/+ t sqrt(logvar)), t = jackknife_factor(params, level);
+    torch tensors on the rows' device.  No bias correction.  logvar = +inf gives (0, +inf) where psd > 0."""
+    torch = _torch()
+    half = jackknife_factor(params, level) * torch.sqrt(jk.logvar)
+    # (psd = 0 has logvar = 0: the interval is the point 0, never 0 * inf)
+    return jk.psd * torch.exp(-half), jk.psd * torch.exp(half)
 
 
 def adaptive_weights(params):
@@ -800,12 +834,13 @@ class Spectrogram:
                                                       pitch, self._cross_ptr(ts, "sxy"), xpitch, st), "glfer_hip_mtm_cross_batch_device")
         return Cross(*(ts.get(k) for k in CROSS_FIELDS))
 
-    def _adaptive_outs(self, want, out, lead, nframes, device):
-        """The outputs of an adaptive call as (tensors by name, row pitch): made here, or the caller's (out: a mapping or an
-        Adaptive tuple of float32 tensors [lead..., nframes, n/2+1] whose row stride may be larger; they share one)."""
+    def _adaptive_outs(self, want, out, lead, nframes, device, fields=ADAPTIVE_FIELDS):
+        """The outputs of an adaptive (fields: a jackknife) call as (tensors by name, row pitch): made here, or the caller's (out:
+        a mapping or an Adaptive tuple of float32 tensors [lead..., nframes, n/2+1] whose row stride may be larger; they share
+        one)."""
         torch = _torch()
         want = tuple(want)
-        assert want and all(w in ADAPTIVE_FIELDS for w in want), want
+        assert want and all(w in fields for w in want), want
         bins = self.n // 2 + 1
         shape = tuple(lead) + (nframes, bins)
         if out is not None and not isinstance(out, dict):
@@ -860,6 +895,43 @@ class Spectrogram:
                                                          first_frame, nframes, self._cross_ptr(ts, "psd"), self._cross_ptr(ts, "dof"),
                                                          pitch, iters, st), "glfer_hip_mtm_adaptive_batch_device")
         return Adaptive(*(ts.get(k) for k in ADAPTIVE_FIELDS))
+
+    def jackknife(self, stream, first_frame=0, nframes=None, iters=8, want=JACKKNIFE_FIELDS, out=None):
+        """stream and plan as adaptive() takes them.  Returns Jackknife(psd, dof, logvar) with None for what `want` does not name,
+        float32 [nframes][n/2+1]: logvar is the delete-one jackknife variance of ln psd over the K tapers with the weights of
+        the last sweep held fixed (0 on a silent frame, +inf where a delete-one estimate is 0, never NaN); psd and dof are the
+        bits of adaptive() at the same `iters`.  iters = 0: no sweeps, the eigenvalue-weighted mean and its interval at close to
+        run()'s cost.  jackknife_interval turns a result into bounds.  One launch on torch's current stream
+        (glfer_hip_mtm_jackknife_device)."""
+        torch = _torch()
+        assert stream.is_cuda and stream.dim() == 1 and stream.is_contiguous()
+        assert stream.dtype == self._sample_dtype(), (stream.dtype, self._sample_dtype())
+        if nframes is None:
+            nframes = self.num_frames(stream.numel()) - first_frame
+        ts, pitch = self._adaptive_outs(want, out, (), nframes, stream.device, JACKKNIFE_FIELDS)
+        st = C.c_void_p(torch.cuda.current_stream(stream.device).cuda_stream)
+        _check(lib().glfer_hip_mtm_jackknife_device(self._h, C.c_void_p(stream.data_ptr()), stream.numel(), first_frame, nframes,
+                                                    self._cross_ptr(ts, "psd"), self._cross_ptr(ts, "dof"),
+                                                    self._cross_ptr(ts, "logvar"), pitch, iters, st),
+               "glfer_hip_mtm_jackknife_device")
+        return Jackknife(*(ts.get(k) for k in JACKKNIFE_FIELDS))
+
+    def jackknife_batch(self, streams, first_frame=0, nframes=None, iters=8, want=JACKKNIFE_FIELDS, out=None):
+        """streams: 2-D torch tensor [B, T] as run_batch takes it.  Returns Jackknife of [B][nframes][n/2+1] tensors: entry b is
+        what jackknife(streams[b]) gives (glfer_hip_mtm_jackknife_batch_device)."""
+        torch = _torch()
+        assert streams.is_cuda and streams.dim() == 2 and (streams.stride(1) == 1 or streams.size(1) <= 1)
+        assert streams.dtype == self._sample_dtype(), (streams.dtype, self._sample_dtype())
+        nb, total = streams.size(0), streams.size(1)
+        if nframes is None:
+            nframes = self.num_frames(total) - first_frame
+        ts, pitch = self._adaptive_outs(want, out, (nb,), nframes, streams.device, JACKKNIFE_FIELDS)
+        st = C.c_void_p(torch.cuda.current_stream(streams.device).cuda_stream)
+        _check(lib().glfer_hip_mtm_jackknife_batch_device(self._h, C.c_void_p(streams.data_ptr()), nb, streams.stride(0), total,
+                                                          first_frame, nframes, self._cross_ptr(ts, "psd"),
+                                                          self._cross_ptr(ts, "dof"), self._cross_ptr(ts, "logvar"), pitch, iters,
+                                                          st), "glfer_hip_mtm_jackknife_batch_device")
+        return Jackknife(*(ts.get(k) for k in JACKKNIFE_FIELDS))
 
     def welch_rows(self, nsamples, segments, step=None, first_frame=0):
         """Rows cross_welch gives for a stream of nsamples pairs: (frames - first_frame - segments) // step + 1, or 0."""

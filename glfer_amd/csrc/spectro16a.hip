@@ -1,5 +1,5 @@
 // spectro16a.hip -- Thomson's adaptively weighted multitaper rows of one real channel, and their degrees of freedom, in one pass
-// (gfx950).  Rows of N/2+1 bins.
+// (gfx950).  Rows of N/2+1 bins.  The JK instantiations add a third row, the jackknife variance of ln psd (the epilogue's end).
 //
 // For frame f and bin k = 0 .. N/2, with v_j the plan's K unit-energy tapers, lambda_j = 1 - beta_j their concentrations
 // (beta_j = max(-sig_j, 0)) and x_f the N values the transform sees (zeroed history included):
@@ -64,8 +64,8 @@ __device__ __forceinline__ const __attribute__((address_space(4))) AdaptiveParam
   return kp;
 }
 
-// BAT: the instantiations a batch launches -- blockIdx.y is the stream
-template <int LOGN, int FMT, int BAT, int WPS = GLFER16A_WAVES_PER_SIMD, int STG = GLFER16_STAGGER>
+// BAT: the instantiations a batch launches -- blockIdx.y is the stream.  JK: the jackknife form (the epilogue's second half)
+template <int LOGN, int FMT, int BAT, int JK = 0, int WPS = GLFER16A_WAVES_PER_SIMD, int STG = GLFER16_STAGGER>
 __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16a_kernel(AdaptiveParams p) {
   using C = Plan16<LOGN>;
   using L = Launch16<LOGN>;
@@ -356,19 +356,98 @@ __global__ __launch_bounds__(Launch16<LOGN>::BLOCK, WPS) void spectro16a_kernel(
           dofv[r] = 0.0f;
         });
         for (int it = 1; it < iters; it++) sweep(std::false_type{});
-        sweep(std::true_type{});
+        if constexpr (JK == 0) {
+          sweep(std::true_type{});
 
-        static_for<0, 16>([&](auto rc) {
-          constexpr int rho = decltype(rc)::value;
-          constexpr int c = rho % B + B * brev(rho / B, R);
-          if constexpr (c <= 8) {
-            if (c < 8 || tl == 0) {
-              const unsigned k = tl + (unsigned)(T * c);
-              if (o_psd) o_psd[f * (size_t)rpitch + k] = S[rho];
-              if (o_dof) o_dof[f * (size_t)rpitch + k] = dofv[rho];
+          static_for<0, 16>([&](auto rc) {
+            constexpr int rho = decltype(rc)::value;
+            constexpr int c = rho % B + B * brev(rho / B, R);
+            if constexpr (c <= 8) {
+              if (c < 8 || tl == 0) {
+                const unsigned k = tl + (unsigned)(T * c);
+                if (o_psd) o_psd[f * (size_t)rpitch + k] = S[rho];
+                if (o_dof) o_dof[f * (size_t)rpitch + k] = dofv[rho];
+              }
             }
-          }
-        });
+          });
+        } else {
+          // ---- THE JACKKNIFE FORM: bin by bin, the last sweep with its K weights kept, the delete-one estimates over them, the
+          // three stores -- no array of dof or logvar, and one bin's weights live at a time.  The last sweep is sweep(LAST)'s
+          // arithmetic operation for operation, so psd and dof are the bits of the JK = 0 form at the same sweep count;
+          // iters = 0: no sweep, w_j = lambda_j (the eigenvalue-weighted mean).  With the weights HELD FIXED
+          //     S_(i) = sum_{j != i} w_j E_j / sum_{j != i} w_j      summed in the order j = 0, 1, ... without i, never as
+          //                                                          total - term (one dominant taper would lose every bit)
+          //     l_i   = ln(S_(i) / S)                                of the ratio, which lies near 1: a row 200 dB down does not
+          //                                                          carry |ln S| ulps into differences of a few 1e-3
+          //     logvar = ((K - 1) / K) sum_i (l_i - mean l)^2
+          // S == 0 gives 0; S > 0 with a delete-one estimate of 0 (or a ratio that leaves the float range) gives +inf; never NaN.
+          float *const o_lv = kp->logvar ? kp->logvar + roff : nullptr;
+          const float kf = (float)K;
+          static_for<0, 16>([&](auto rc) {
+#pragma clang fp contract(off)
+            constexpr int rho = decltype(rc)::value;
+            constexpr int c = rho % B + B * brev(rho / B, R);
+            if constexpr (c <= 8) {
+              const float s = S[rho];
+              const float num = __builtin_fmaf(lam[0], s, bj[0]);
+              float w[KMAX];
+              w[0] = lam[0];
+              float sw = lam[0], sw2 = lam[0] * lam[0], acc = lam[0] * es[0][rho];
+              static_for<1, KMAX>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                float wj = 0.0f;                                   // a taper the plan does not have: weight 0, its terms add 0
+                if (j < K) {
+                  const float den = __builtin_fmaf(lam[j], s, bj[j]);
+                  const float u = den == 0.0f ? 1.0f : num / den;
+                  wj = iters == 0 ? lam[j] : (lam[j] * u) * u;
+                  sw = sw + wj;
+                  sw2 = __builtin_fmaf(wj, wj, sw2);
+                  acc = __builtin_fmaf(wj, es[j][rho], acc);
+                }
+                w[j] = wj;
+              });
+              const float psd = acc / sw;
+              const float dof = (2.0f * sw) * sw / sw2;
+              float l[KMAX], lsum = 0.0f;
+              float pn = 0.0f, pd = 0.0f;          // the terms j < i, summed once: every delete-one sum begins with the same ones
+              bool unbounded = false;
+              static_for<0, KMAX>([&](auto ic) {
+                constexpr int i = decltype(ic)::value;
+                float li = 0.0f;
+                if (i < K) {
+                  float ni = pn, di = pd;
+                  static_for<i + 1, KMAX>([&](auto jc) {
+                    constexpr int j = decltype(jc)::value;
+                    ni = __builtin_fmaf(w[j], es[j][rho], ni);
+                    di = di + w[j];
+                  });
+                  li = ni == 0.0f ? -__builtin_inff() : __builtin_logf((ni / di) / psd);
+                  unbounded = unbounded || !(__builtin_fabsf(li) < __builtin_inff());
+                  lsum = lsum + li;
+                  pn = __builtin_fmaf(w[i], es[i][rho], pn);
+                  pd = pd + w[i];
+                }
+                l[i] = li;
+              });
+              const float lbar = lsum / kf;
+              float ss = 0.0f;
+              static_for<0, KMAX>([&](auto ic) {
+                constexpr int i = decltype(ic)::value;
+                const float d = i < K ? l[i] - lbar : 0.0f;
+                ss = __builtin_fmaf(d, d, ss);
+              });
+              float lv = ((kf - 1.0f) / kf) * ss;
+              lv = unbounded || !(lv >= 0.0f) ? __builtin_inff() : lv;
+              lv = psd == 0.0f ? 0.0f : lv;
+              if (c < 8 || tl == 0) {
+                const unsigned k = tl + (unsigned)(T * c);
+                if (o_psd) o_psd[f * (size_t)rpitch + k] = psd;
+                if (o_dof) o_dof[f * (size_t)rpitch + k] = dof;
+                if (o_lv) o_lv[f * (size_t)rpitch + k] = lv;
+              }
+            }
+          });
+        }
       }
     }
     if (!has_next) break;
@@ -390,19 +469,27 @@ using namespace glfer;
 #define GLFER_CAT2(a, b) a##b
 #define GLFER_CAT(a, b) GLFER_CAT2(a, b)
 
-template <int FMT, int BAT>
+// JK: the jackknife instantiations; they take iters = 0 as well (no sweep, w_j = lambda_j)
+template <int FMT, int BAT, int JK = 0>
 static hipError_t launch16a_fmt(const AdaptiveParams &p, hipStream_t st) {
   constexpr int L = GLFER_LOGN;
   using LC = Launch16<L>;
   // persistent blocks, spectro16cx.hip's shape: enough to fill every CU at the kernel's occupancy, never more than the work
   const long long work = ((long long)p.nframes + LC::FPB - 1) / LC::FPB;
   if (work <= 0) return hipSuccess;
-  if (p.ntap < 2 || p.ntap > GLFER_ADAPTIVE_KMAX || p.iters < 1 || p.iters > GLFER_ADAPTIVE_ITERS_MAX) return hipErrorInvalidValue;
+  if (p.ntap < 2 || p.ntap > GLFER_ADAPTIVE_KMAX || p.iters < (JK != 0 ? 0 : 1) || p.iters > GLFER_ADAPTIVE_ITERS_MAX) return hipErrorInvalidValue;
   const long long resident = resident_workgroups(GLFER16A_WAVES_PER_SIMD, LC::BLOCK);
   const unsigned grid = persistent_grid(work, glfer_batch_cap(4 * resident, p.nbatch));
-  return launch(spectro16a_kernel<L, FMT, BAT>, batch_grid(grid, p), dim3(LC::BLOCK), 0, st, p);
+  return launch(spectro16a_kernel<L, FMT, BAT, JK>, batch_grid(grid, p), dim3(LC::BLOCK), 0, st, p);
 }
 
 extern "C" hipError_t GLFER_CAT(glfer_launch_adaptive16_n, GLFER_LOGN)(const AdaptiveParams *p, hipStream_t st) {
   return with_fmt(p->fmt, [&](auto F) { return p->nbatch > 1 ? launch16a_fmt<F(), 1>(*p, st) : launch16a_fmt<F(), 0>(*p, st); });
 }
+
+// the jackknife launcher of this size, where the Makefile's JLOGNS list names it (spectro_adaptive_params.h's GLFER_LAUNCHERS16J)
+#ifdef GLFER_JACKKNIFE
+extern "C" hipError_t GLFER_CAT(glfer_launch_jackknife16_n, GLFER_LOGN)(const AdaptiveParams *p, hipStream_t st) {
+  return with_fmt(p->fmt, [&](auto F) { return p->nbatch > 1 ? launch16a_fmt<F(), 1, 1>(*p, st) : launch16a_fmt<F(), 0, 1>(*p, st); });
+}
+#endif

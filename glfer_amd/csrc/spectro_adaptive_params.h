@@ -19,7 +19,7 @@ struct AdaptiveParams {
   int ntap;                /* K tapers, 2 .. GLFER_ADAPTIVE_KMAX: ceil(K / 2) packed transforms a frame                        */
   int history_mode;        /* 0: zeros before sample 0 only; 1: history zeroed every frame                                    */
   int fmt;                 /* GLFER_FMT_*                                                                                     */
-  int iters;               /* sweeps, 1 .. GLFER_ADAPTIVE_ITERS_MAX                                                           */
+  int iters;               /* sweeps, 1 .. GLFER_ADAPTIVE_ITERS_MAX (the jackknife form: 0 as well, w_j = lambda_j)            */
   float inv_n;             /* 1 / N, a power of two                                                                           */
   const float *taps;       /* device: the plan's unit-energy tapers UNSCALED, one float per sample: [2 ceil(K/2)][4][N/16][4];
                               an odd K's last row is zeros (the lone taper's partner)                                         */
@@ -31,6 +31,8 @@ struct AdaptiveParams {
   long long row_batch_stride;   /* floats from one stream's first row to the next one's                                       */
   float lam[GLFER_ADAPTIVE_KMAX];    /* lambda_j = 1 - beta_j, rounded to float (glfer_hip_adaptive_weights)                   */
   float beta[GLFER_ADAPTIVE_KMAX];   /* beta_j = max(-sig_j, 0) formed in double, rounded to float                             */
+  float *logvar;           /* device, the jackknife form alone (appended: no field above moves): the jackknife variance of
+                              ln psd, rows as psd's; NULL: not wanted                                                         */
 };
 
 /* THE TABLE OF BUILT ADAPTIVE LAUNCHERS: X(logn), one entry per launcher glfer_launch_adaptive16_n<logn> (spectro16a.hip compiled
@@ -38,18 +40,32 @@ struct AdaptiveParams {
    symbols against one another, as tests/test_launch_table_host.py does for spectro_params.h's table.
    N = 8192 is not in it: its instantiations spill (10 vector registers, profiles/adaptive_kernel_resources.txt). */
 #define GLFER_LAUNCHERS16A(X) X(8) X(9) X(10) X(11) X(12)
+/* THE TABLE OF BUILT JACKKNIFE LAUNCHERS: X(logn), one entry per launcher glfer_launch_jackknife16_n<logn> -- the JK
+   instantiations of the same kernel, built in spectro16a.hip's translation units of the Makefile's JLOGNS list (-DGLFER_JACKKNIFE).
+   tests/test_jackknife_host.py holds the list, this table and the library's symbols against one another.  A size whose JK
+   instantiations do not fit two wavefronts per SIMD without a spill is left out of both (profiles/jackknife_kernel_resources.txt). */
+#define GLFER_LAUNCHERS16J(X) X(8) X(9) X(10) X(11) X(12)
 
 #ifdef __cplusplus
 extern "C" {
 #define GLFER_PROTO16A(l) hipError_t glfer_launch_adaptive16_n##l(const struct AdaptiveParams *p, hipStream_t st);
 GLFER_LAUNCHERS16A(GLFER_PROTO16A)
 #undef GLFER_PROTO16A
+#define GLFER_PROTO16J(l) hipError_t glfer_launch_jackknife16_n##l(const struct AdaptiveParams *p, hipStream_t st);
+GLFER_LAUNCHERS16J(GLFER_PROTO16J)
+#undef GLFER_PROTO16J
 }
 /* the launcher built for a block size, or nullptr */
 static inline hipError_t (*launcher16_adaptive(int logn))(const AdaptiveParams *, hipStream_t) {
 #define GLFER_LOOKUP16A(l) if (logn == l) return glfer_launch_adaptive16_n##l;
   GLFER_LAUNCHERS16A(GLFER_LOOKUP16A)
 #undef GLFER_LOOKUP16A
+  return nullptr;
+}
+static inline hipError_t (*launcher16_jackknife(int logn))(const AdaptiveParams *, hipStream_t) {
+#define GLFER_LOOKUP16J(l) if (logn == l) return glfer_launch_jackknife16_n##l;
+  GLFER_LAUNCHERS16J(GLFER_LOOKUP16J)
+#undef GLFER_LOOKUP16J
   return nullptr;
 }
 #endif

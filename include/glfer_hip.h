@@ -776,7 +776,7 @@ int glfer_hip_welch_cross_batch_device(glfer_hip_plan *plan, const void *d_xy, s
  * nframes > 0x7fffffff, sizes that overflow size_t.  Asynchronous on hip_stream.
  * Not built: mean removal, N = 8192 (its instantiations spill ten registers) and N = 16384, more than 8 tapers (the
  * eigenspectra of 16 would take 144 registers a lane), ragged / host / WAV / workers forms, adaptive weights on I/Q or
- * cross-spectra, jackknife intervals, sweeps to a tolerance. */
+ * cross-spectra, sweeps to a tolerance.  (Jackknife intervals: the section after this one.) */
 int glfer_hip_adaptive_supported(const glfer_hip_config *cfg);
 int glfer_hip_adaptive_weights(const glfer_hip_config *cfg, float *lambda_out, float *beta_out);
 int glfer_hip_mtm_adaptive_device(glfer_hip_plan *plan, const void *d_stream, size_t nsamples, size_t first_frame, size_t nframes,
@@ -784,6 +784,52 @@ int glfer_hip_mtm_adaptive_device(glfer_hip_plan *plan, const void *d_stream, si
 int glfer_hip_mtm_adaptive_batch_device(glfer_hip_plan *plan, const void *d_stream, size_t nstreams, size_t stream_pitch,
                                         size_t nsamples, size_t first_frame, size_t nframes, float *d_psd, float *d_dof,
                                         size_t row_pitch, int iters, void *hip_stream);
+
+/* ---- Jackknife confidence intervals for multitaper rows, in the same pass ---------------------------------------------------------
+ * Whether a bump of 2 dB is real needs an interval.  The one derived from d_dof (a chi-square with dof degrees of freedom) assumes
+ * Gaussian, locally white data, which is what fails on a carrier's skirts and on keyed signals; the delete-one jackknife over
+ * tapers in the log domain (Thomson & Chave 1991; Percival & Walden section 7) does not.  The same kernel as the adaptive entries,
+ * one launch: after a frame's last taper the lane that holds a bin's K eigenspectra and ran its sweeps also forms the statistic.
+ * For a frame and a bin, with E_j the eigenspectra above, j = 0 .. K-1, w_j the final weights and S = sum w_j E_j / sum w_j:
+ *   S_(i)  = sum_{j != i} w_j E_j / sum_{j != i} w_j      i = 0 .. K-1   (weights held fixed; K-1 non-negative terms summed in
+ *                                                                         the order j = 0, 1, ..., skipping i)
+ *   l_i    = ln( S_(i) / S )
+ *   lbar   = (1/K) sum_i l_i
+ *   logvar = ((K-1)/K) sum_i (l_i - lbar)^2                the jackknife variance of ln S
+ * S_(i) is never formed as total - term: with one dominant taper that loses every bit.  The logarithm is taken of the ratio to S,
+ * which lies near 1, and not of S_(i) itself: rows 200 dB down then do not carry |ln S| ulps into differences of a few 1e-3;
+ * centring removes the reference point in exact arithmetic.
+ * Degenerate cases, decided in the kernel: S == 0 (a silent frame) gives logvar = 0; S > 0 with some S_(i) == 0 (or a ratio
+ * S_(i) / S that leaves the float range) gives logvar = +inf, the interval is unbounded; no logvar value is ever NaN.  For K = 2,
+ * S_(i) is the other eigenspectrum, so logvar = 1/4 (ln E_1 - ln E_0)^2.
+ * The weights, by `iters`:
+ *   iters = 1 .. 64   the adaptive weights of the last sweep, the ones d_dof is computed from; d_psd and d_dof are then the bits
+ *                     of glfer_hip_mtm_adaptive_device at the same iters.
+ *   iters = 0         no sweeps, w_j = lambda_j: the eigenvalue-weighted mean (Percival & Walden 369a), intervals at close to the
+ *                     fixed-weight row's cost.  d_psd = sum lambda_j E_j / sum lambda_j, d_dof = 2 (sum lambda)^2 / sum lambda^2.
+ *                     (The adaptive entries above keep refusing iters = 0.)
+ * THE INTERVAL at level p is  d_psd * exp(-/+ t sqrt(logvar)),  t = Student's quantile t_{K-1}((1 + p) / 2), which
+ * glfer_hip_jackknife_factor returns (host only; 0 < level < 1; the closed-form distribution function for 1 .. 7 degrees of
+ * freedom inverted by bisection; GLFER_E_ARG for a NULL pointer, a plan that is not supported, a level outside (0, 1)).
+ * THERE IS NO BIAS CORRECTION: the interval is centred on ln d_psd, not on the jackknife's bias-corrected estimate
+ * K ln S - (K-1) (ln S + lbar).  On independent unit-exponential eigenspectra with equal weights the interval at 0.95 covers the
+ * true level in 0.94 of draws (K = 5 and K = 8; tests/test_jackknife_criterion.py).
+ * Outputs, any subset of the three (NULL: not wanted; all three NULL is refused), rows and pitch as the adaptive entries'; one
+ * launch a call (a batch above the grid's y limit: one per chunk of streams), no allocation, no host synchronisation: legal on a
+ * hip_stream that is being captured.
+ * Supported (glfer_hip_jackknife_supported, host only): what glfer_hip_adaptive_supported takes, at the sizes whose jackknife
+ * instantiations are built -- all of them, N = 256 .. 4096 (profiles/jackknife_kernel_resources.txt).
+ * Arguments: the adaptive entries' checks in their order, with iters outside 0 .. 64 refused.
+ * Not built: the jackknife of coherence and of the cross-spectrum's phase (the cross kernel has no room for per-taper values at two
+ * wavefronts per SIMD), bias correction, N >= 8192, ragged / host / WAV / workers forms, mean removal, intervals for the
+ * fixed-weight row's 1 / (1 + sig_j) sum. */
+int glfer_hip_jackknife_supported(const glfer_hip_config *cfg);
+int glfer_hip_jackknife_factor(const glfer_hip_config *cfg, double level, double *t_out);
+int glfer_hip_mtm_jackknife_device(glfer_hip_plan *plan, const void *d_stream, size_t nsamples, size_t first_frame, size_t nframes,
+                                   float *d_psd, float *d_dof, float *d_logvar, size_t row_pitch, int iters, void *hip_stream);
+int glfer_hip_mtm_jackknife_batch_device(glfer_hip_plan *plan, const void *d_stream, size_t nstreams, size_t stream_pitch,
+                                         size_t nsamples, size_t first_frame, size_t nframes, float *d_psd, float *d_dof,
+                                         float *d_logvar, size_t row_pitch, int iters, void *hip_stream);
 
 /* ---- Zoom: a digital down-converter, and the two-sided rows of its output -------------------------------------------------------
  * A few tens of hertz around one carrier of a 48 kHz recording: instead of a block of a million samples whose transform covers the
