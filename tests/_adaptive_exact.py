@@ -97,10 +97,13 @@ def sweep32(S, E, lam, beta, sigma2, n, no_over_n=False, drop_lambda=False):
     return (acc / sw).astype(f), (f(2.0) * sw * sw / sw2).astype(f)
 
 
-def adaptive32(x32, n, overlap, tapers, lam, beta, iters, history_mode=0, mutate=None, sig=None):
-    """The float32 stand-in after `iters` sweeps: (psd, dof, E32).  mutate: one of MUTATIONS (the criterion test)."""
+def adaptive32(x32, n, overlap, tapers, lam, beta, iters, history_mode=0, mutate=None, sig=None, s2_stride=None):
+    """The float32 stand-in after `iters` sweeps: (psd, dof, E32).  mutate: one of MUTATIONS (the criterion test).  s2_stride:
+    sigma2 of the frame that many frames earlier (one_pass_earlier: the criterion test's stale carried state)."""
     f = np.float32
     E, s2 = eigen32(x32, n, overlap, tapers, history_mode, sig=sig if mutate == "sig_in_eigen" else None)
+    if s2_stride is not None:
+        s2 = one_pass_earlier(s2, s2_stride)
     lam, beta = np.asarray(lam, f), np.asarray(beta, f)
     if mutate == "beta_from_float_lambda":
         beta = (f(1.0) - lam).astype(f)
@@ -149,6 +152,35 @@ def line_bin(n, w):
 
 def make_input(name, n, nsamples, seed, fmt_name="f32", w=2.5, line_db=None):
     """line_db: another level for the weak line than LINE_DB's (the criterion test's record of why u8 is not at 30 dB)."""
+    x = _values(name, n, nsamples, seed, fmt_name, w, line_db)
+    return to_float32(quantise(np.clip(x, -0.999, 0.999).astype(np.float32), fmt_name), fmt_name)
+
+
+# ---- inputs keyed to the passes of a persistent grid (tests/_grid_passes.py): `noise` or `line` times a level that changes where
+# a block goes from one frame group to its next, so that sigma2 -- the state a block's lanes carry through a frame -- differs by
+# 60 dB or by everything between the frame a block handles and the one it handled a pass earlier.  A sample belongs to the frame
+# whose fresh hop it lies in, a frame to pass frame // stride; the pass's level is LEVEL_ORDERS[order][pass % 3].  With two
+# passes: down 1 -> 1e-3, up 0 -> 1e-3, gap 1 -> 0; with three, gap has digital silence between sound and `up` / `down` end / begin
+# with it.  u8 holds neither base at 1e-3 (0.2e-3 and 0.7e-3 of full scale round to the zero code): there that level IS silence.
+LEVEL_ORDERS = {"down": (1.0, 1e-3, 0.0), "up": (0.0, 1e-3, 1.0), "gap": (1.0, 0.0, 1e-3)}
+PASS_INPUTS = tuple("%s_%s" % (b, o) for b in ("noise", "line") for o in ("down", "up", "gap"))
+
+
+def level_by_pass(name, n, hop, nsamples, seed, stride, fmt_name="f32", w=2.5, levels=None):
+    """name: one of PASS_INPUTS.  levels: another level triple than LEVEL_ORDERS' (a case that drops the 1e-3 level)."""
+    base, order = name.split("_")
+    lv = np.asarray(LEVEL_ORDERS[order] if levels is None else levels)
+    x = _values(base, n, nsamples, seed, fmt_name, w, None) * lv[((np.arange(nsamples) // hop) // stride) % 3]
+    return to_float32(quantise(np.clip(x, -0.999, 0.999).astype(np.float32), fmt_name), fmt_name)
+
+
+def one_pass_earlier(a, stride):
+    """Per-frame state as a block that never renewed it would hold it: that of the frame stride earlier."""
+    a = np.asarray(a)
+    return np.concatenate([a[:stride], a[:len(a) - stride]]) if len(a) > stride else a
+
+
+def _values(name, n, nsamples, seed, fmt_name, w, line_db):
     line_db = LINE_DB[fmt_name] if line_db is None else line_db
     rng = np.random.default_rng([seed, n, INPUTS.index(name)])
     t = np.arange(nsamples, dtype=np.float64)
@@ -182,4 +214,4 @@ def make_input(name, n, nsamples, seed, fmt_name="f32", w=2.5, line_db=None):
         x[nsamples // 3:nsamples // 3 + 2 * n + 17] = 0.0
     else:
         raise ValueError(name)
-    return to_float32(quantise(np.clip(x, -0.999, 0.999).astype(np.float32), fmt_name), fmt_name)
+    return x

@@ -135,3 +135,87 @@ def make_input(name, n, nsamples, seed):
     else:
         raise ValueError(name)
     return np.clip(np.stack([x, y], axis=1), -0.999, 0.999).astype(np.float32)
+
+
+# ---- inputs keyed to the passes of a persistent grid (tests/_grid_passes.py): equal-level noise cannot show state that a block
+# carries from one of its frame groups into the next, these can.  `stride` is the frames (Welch: rows) one pass of the grid
+# covers; a sample belongs to the frame whose fresh hop it lies in, a frame to row frame // step, a row to pass row // stride.
+#   x_late         independent noise; x exactly zero from the first sample of frame c on, c = stride * step (+ 1 when segments
+#                  > 1: the first row of pass 1 then has x in its segment 0 alone).  Every frame of the later passes past c
+#                  is silent in x; the frames before c that overlap into it keep the samples they have
+#   x_early        x exactly zero up to the last sample of frame c = stride * step + segments - 2 (segments = 1: the last
+#                  frame of pass 0): pass 0 is silent in x, and the first row of pass 1 has x in its LAST segment alone
+#   apart_by_pass  the channels' levels are 1 and 1e-3 in the even passes and exchanged in the odd ones (two passes: 1 and 1e-3
+#                  in pass 0, exchanged in the later one)
+PASS_INPUTS = ("x_late", "x_early", "apart_by_pass")
+
+
+def make_pass_input(name, n, hop, nframes, seed, stride, segments=1, step=1):
+    nsamples = nframes * hop
+    rng = np.random.default_rng([seed, n, 100 + PASS_INPUTS.index(name)])
+    x, y = 0.2 * rng.standard_normal(nsamples), 0.2 * rng.standard_normal(nsamples)
+    if name == "x_late":
+        c = stride * step + (1 if segments > 1 else 0)
+        x[max(c * hop - (n - hop), 0):] = 0.0
+    elif name == "x_early":
+        c = stride * step + segments - 2
+        x[:(c + 1) * hop] = 0.0
+    elif name == "apart_by_pass":
+        odd = ((np.arange(nsamples) // hop) // step // stride) % 2 == 1
+        x *= np.where(odd, 1e-3, 1.0)
+        y *= np.where(odd, 1.0, 1e-3)
+    else:
+        raise ValueError(name)
+    return np.clip(np.stack([x, y], axis=1), -0.999, 0.999).astype(np.float32)
+
+
+def silence_bits(xy32, n, overlap, history_mode=0):
+    """Per frame: bit 0 / bit 1 set where the frame's x / y samples are not all zero (what the kernel's epilogue decides by)."""
+    xy32 = np.asarray(xy32, np.float32)
+    fr = frames64(xy32[:, 0] + 1j * xy32[:, 1].astype(np.complex64), n, overlap, history_mode)
+    return (fr.real != 0).any(axis=1) * 1 + (fr.imag != 0).any(axis=1) * 2
+
+
+def _packed32(fx, fy, tapers, sig, n):
+    """The float32 sums of frames through ONE packed transform per taper, Z = FFT(v (x + i y)), separated through the mirror
+    bins as the kernel separates them: a silent channel's spectrum is then rounding, not zero.  Returns (sxx, syy, sre, sim)."""
+    from _iq_exact import _fft32
+    half = n // 2 + 1
+    k = np.arange(half)
+    out = [np.zeros((fx.shape[0], half), np.float32) for _ in range(4)]
+    for j in range(len(sig)):
+        c = np.float32(0.25 / (n * (1.0 + sig[j])))
+        v = np.asarray(tapers[j], np.float32)
+        Z = _fft32((fx * v) + 1j * (fy * v))
+        Zk, Zm = Z[:, k], Z[:, (n - k) % n]
+        ar, ai = Zk.real + Zm.real, Zk.imag - Zm.imag
+        br, bi = Zk.imag + Zm.imag, Zm.real - Zk.real
+        out[0] += c * (ar * ar + ai * ai)
+        out[1] += c * (br * br + bi * bi)
+        out[2] += c * (ar * br + ai * bi)
+        out[3] += c * (ai * br - ar * bi)
+    return out
+
+
+def cross32_packed(xy32, n, overlap, tapers, sig, history_mode=0, bits=None):
+    """A float32 stand-in that works as the kernel does: one packed transform per frame and taper, and the rows of a channel
+    whose bit is clear stored as zeros.  bits: the per-frame silence bits it decides by (None: the frames' own) -- the criterion
+    tests hand it the bits of another frame."""
+    xy32 = np.asarray(xy32, np.float32)
+    fr = frames64(xy32[:, 0] + 1j * xy32[:, 1].astype(np.complex64), n, overlap, history_mode)
+    sxx, syy, sre, sim = _packed32(fr.real.astype(np.float32), fr.imag.astype(np.float32), tapers, sig, n)
+    bits = silence_bits(xy32, n, overlap, history_mode) if bits is None else np.asarray(bits)
+    sxx[(bits & 1) == 0] = 0
+    syy[(bits & 2) == 0] = 0
+    sre[bits != 3] = 0
+    sim[bits != 3] = 0
+    sxy = (sre + 1j * sim).astype(np.complex64)
+    return Cross(sxx, syy, sxy, _coh(sxx, syy, sxy))
+
+
+def one_pass_earlier(a, stride):
+    """Per-frame (per-row) state a as a block that never refreshed it would hold it: that of the frame stride earlier."""
+    a = np.asarray(a)
+    out = a.copy()
+    out[stride:] = a[:len(a) - stride]
+    return out

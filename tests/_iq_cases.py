@@ -56,6 +56,9 @@ CASES = [
     mtm(16384, 0.0, 4.5, 8, 5, "noise"),
     # more workgroups than one XCD slice rule keeps (67 -> a grid of 64): the persistent loop's second frame
     fft(4096, 0.75, "hanning", 67, "noise"),
+    # the same where a workgroup holds several frames (16 and 4): 71 units of work on a grid of 64, the last frame group partly
+    # filled (5 and 1 frames) and the second of its workgroup, so that the clamp runs in a later pass (tests/_grid_passes.py)
+    fft(256, 0.5, "hanning", 1125, "noise"), mtm(1024, 0.75, 2.5, 4, 281, "weak", "s16"),
     # silence: exactly zero rows
     fft(1024, 0.5, "hanning", 9, "zero"), mtm(4096, 0.0, 2.5, 4, 5, "zero", "u8"), fft(256, 0.75, "hanning", 37, "zero", "s16"),
 ]

@@ -14,7 +14,7 @@ the statistic in float32, operation for operation as the kernel does.  Its `muta
 """
 import numpy as np
 
-from _adaptive_exact import eigen32, sweep32
+from _adaptive_exact import eigen32, one_pass_earlier, sweep32
 
 MUTATIONS = ("factor_dropped", "factor_one_over_k", "about_ln_s", "weights_recomputed", "previous_sweep_weights", "equal_weights",
              "zero_partner_counted", "total_minus_term")
@@ -91,10 +91,13 @@ def _mean32(w, E):
         return (acc / sw).astype(f), (f(2.0) * sw * sw / sw2).astype(f), acc, sw
 
 
-def jackknife32(x32, n, overlap, tapers, lam, beta, iters, history_mode=0, mutate=None):
-    """The float32 stand-in: (psd, dof, logvar, E32).  iters = 0: w_j = lambda_j.  mutate: one of MUTATIONS."""
+def jackknife32(x32, n, overlap, tapers, lam, beta, iters, history_mode=0, mutate=None, s2_stride=None):
+    """The float32 stand-in: (psd, dof, logvar, E32).  iters = 0: w_j = lambda_j.  mutate: one of MUTATIONS.  s2_stride: sigma2
+    of the frame that many frames earlier (_adaptive_exact.one_pass_earlier)."""
     f = np.float32
     E, s2 = eigen32(x32, n, overlap, tapers, history_mode)
+    if s2_stride is not None:
+        s2 = one_pass_earlier(s2, s2_stride)
     lam, beta = np.asarray(lam, f), np.asarray(beta, f)
     K = E.shape[1]
     S = (f(0.5) * (E[:, 0, :] + E[:, 1, :])).astype(f)

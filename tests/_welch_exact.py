@@ -14,6 +14,7 @@ import collections
 import numpy as np
 
 import _cross_exact as E
+import _grid_passes as G
 from _exact import hop_len
 
 LINE10_DB = -10.0
@@ -161,18 +162,66 @@ def frames_of(c):
 _inputs, _refs = {}, {}
 
 
-def case_input(c, seed=0):
-    """(the stream in the plan's format, its float32 values), made once per case and left unchanged."""
-    key = (c.n, c.ovl, c.fmt, frames_of(c), c.name, seed)
+def case_input(c, seed=0, nbatch=1):
+    """(the stream in the plan's format, its float32 values), made once per case and left unchanged.  The inputs of
+    _cross_exact.PASS_INPUTS are laid out for the passes of the call's grid over the case's rows (a batch of nbatch streams
+    shares the grid: other boundaries)."""
+    key = (c.n, c.ovl, c.fmt, frames_of(c), c.name, seed) + ((c.segments, c.step, nbatch) if c.name in E.PASS_INPUTS else ())
     if key not in _inputs:
-        raw = E.quantise(make_input(c.name, c.n, frames_of(c) * hop_len(c.n, c.ovl), seed), c.fmt)
+        if c.name in E.PASS_INPUTS:
+            stride = G.passes("spectro16cx", c.n, c.rows, nbatch).stride
+            xy = E.make_pass_input(c.name, c.n, hop_len(c.n, c.ovl), frames_of(c), seed, stride, c.segments, c.step)
+        else:
+            xy = make_input(c.name, c.n, frames_of(c) * hop_len(c.n, c.ovl), seed)
+        raw = E.quantise(xy, c.fmt)
         _inputs[key] = (raw, E.to_float32(raw, c.fmt))
     return _inputs[key]
 
 
+# ---- rows past one pass of the grid: 71 units of work, the rows of tests/_grid_passes.py's table (rows, not frames, are the work)
+PASS_SIZES = (256, 2048, 8192)
+PASS_PLANS = ((KINDS[2], 3, 1), (KINDS[2], 3, 5), (KINDS[3], 2, 2))           # Hanning (L, step) = (3, 1), (3, 5); two tapers (2, 2)
+PASS_NAMES = ("noise",) + E.PASS_INPUTS
+
+
+def pass_cases():
+    """Every size with every plan; two of the four inputs each, so that every input is seen at every size and with every plan;
+    overlaps and formats in turn (apart_by_pass never in u8: its quiet channel would be digital silence), one history_mode = 1."""
+    out = []
+    for s, n in enumerate(PASS_SIZES):
+        for pl, (kind, seg, step) in enumerate(PASS_PLANS):
+            i = 3 * s + pl
+            for name in (PASS_NAMES[i % 4], PASS_NAMES[(i + 2) % 4]):
+                fmt = FMTS[i % 3]
+                out.append(Case(n, kind, OVERLAPS[i % 4], "s16" if fmt == "u8" and name == "apart_by_pass" else fmt, int(i == 4),
+                                seg, step, G.TWO_PASS_FRAMES[n], name))
+    return out
+
+
+def row_bits(frame_bits, segments, step, rows):
+    """A row's silence bits: those of its segments OR-ed."""
+    frame_bits = np.asarray(frame_bits)
+    out = np.zeros(rows, np.int64)
+    for s in range(segments):
+        out |= frame_bits[s:s + (rows - 1) * step + 1:step]
+    return out
+
+
+def welch32_packed(packed, segments, step, bits):
+    """packed: _cross_exact.cross32_packed's per-frame rows with every bit set (nothing zeroed).  The float32 average over the
+    segments, then the rows of a channel whose ROW bit is clear stored as zeros -- as the kernel does it."""
+    w = welch32(packed, segments, step)
+    sxx, syy, sxy = w.sxx.copy(), w.syy.copy(), w.sxy.copy()
+    bits = np.asarray(bits)
+    sxx[(bits & 1) == 0] = 0
+    syy[(bits & 2) == 0] = 0
+    sxy[bits != 3] = 0
+    return E.Cross(sxx, syy, sxy, E._coh(sxx, syy, sxy))
+
+
 def case_per_frame(lib, c, seed=0):
     """(cross64's, cross32's) per-frame rows of the case's stream, computed once and shared."""
-    key = (c.n, c.kind, c.ovl, c.fmt, c.hist, frames_of(c), c.name, seed)
+    key = (c.n, c.kind, c.ovl, c.fmt, c.hist, frames_of(c), c.name, seed) + ((c.segments, c.step) if c.name in E.PASS_INPUTS else ())
     if key not in _refs:
         tapers, sig = tables_of(lib, c.n, c.kind)
         xy32 = case_input(c, seed)[1]

@@ -117,6 +117,73 @@ def test_rules_reject_mutation(lib, mutation):
         _chain(bad, STEPS, E64, lam, beta, s2, n, tau, rel=1.0, widen=widen)
 
 
+# ---- inputs keyed to the grid's passes (tests/_grid_passes.py).  PASS_GRID is the GPU module's: every built size, K = 2 / 5 / 8 in
+# turn (an odd count at N = 512 and at N = 4096: 32 and 256 lanes a frame), overlaps, history modes and formats in turn
+PASS_TAPERS = ((1, 2.0), (4, 2.5), (7, 4.5))
+PASS_GRID = tuple((n, PASS_TAPERS[i % 3][0], PASS_TAPERS[i % 3][1], (0.0, 0.5, 0.75, 0.3)[i % 4], int(i == 2), ("f32", "s16", "u8", "f32", "s16")[i])
+                  for i, n in enumerate((256, 512, 1024, 2048, 4096)))
+
+
+def pass_inputs_of(i):
+    """Two of _adaptive_exact.PASS_INPUTS for case i of PASS_GRID: one on noise and one on the line, orders in turn."""
+    orders = ("down", "up", "gap")
+    return "noise_" + orders[i % 3], "line_" + orders[(i + 1) % 3]
+
+
+def pass_stream(case, name, nbatch=1, seed=11, kernel="spectro16a"):
+    """(x, the passes of its call): a stream of the two-pass frame count of its size, the levels laid out for the grid of a call
+    over all its frames (as one of nbatch streams)."""
+    import _grid_passes as G
+    n, kmax, w, overlap, hm, fmt = case
+    frames = G.TWO_PASS_FRAMES[n]
+    p = G.passes(kernel, n, frames, nbatch)
+    hop = int(n * (1.0 - overlap))
+    nsamples = frames * hop + 3
+    if name in X.PASS_INPUTS:
+        return X.level_by_pass(name, n, hop, nsamples, seed, p.stride, fmt, w), p
+    return X.make_input(name, n, nsamples, seed, fmt, w), p
+
+
+# the criterion's cases: every case of the grid with the two inputs the GPU module gives it, and all six at N = 2048 and 4096
+# (2 and 1 frames a block, 141 and 71 frames)
+PASS_CRITERION = [(PASS_GRID[i], name) for i in (0, 1, 2) for name in pass_inputs_of(i)] + \
+                 [(PASS_GRID[i], name) for i in (3, 4) for name in X.PASS_INPUTS]
+
+
+@pytest.mark.parametrize("case,name", PASS_CRITERION, ids=lambda v: v if isinstance(v, str) else "n%d_k%d_%s" % (v[0], v[1] + 1, v[5]))
+def test_sigma2_of_the_frame_one_pass_earlier_is_rejected(lib, case, name):
+    """level_by_pass: the stand-in passes the chained rule (within a quarter of the relative terms, as on every other input); the
+    stand-in that takes sigma2 -- what a block's lanes carry from a frame's first round to its epilogue -- from the frame one grid
+    pass earlier is rejected: its weights are those of a frame 60 dB louder or quieter, or of silence (dof term), and where the
+    stale frame was loud and this one is silent the silent frame's dof is not the one of sigma2 = 0."""
+    n, kmax, w, overlap, hm, fmt = case
+    x, p = pass_stream(case, name)
+    assert p.npasses == 2
+    tapers, sig = lib.make_dpss(n, kmax, w)
+    lam, beta = lib.adaptive_weights(lib.MtmParams(n=n, w=w, kmax=kmax, overlap=overlap))
+    E64, s2 = X.eigen64(x, n, overlap, tapers, hm)
+    assert len(s2) == len(p.pass_of)
+    # the levels do what the input is for: sigma2 of a frame and of the one a pass earlier differ by 10^5 or one of them is 0
+    late = np.arange(p.stride + n // int(n * (1.0 - overlap)), len(s2))
+    a, b = s2[late], s2[late - p.stride]
+    assert ((a == 0) != (b == 0)).all() or (np.maximum(a, b) > 1e5 * np.minimum(a, b)).all(), name
+    memo = {}
+
+    def device(iters, stride=None):
+        if (iters, stride) not in memo:
+            memo[iters, stride] = X.adaptive32(x, n, overlap, tapers, lam, beta, iters, hm, s2_stride=stride)
+        return memo[iters, stride][:2]
+    _, dof32_1, E32 = X.adaptive32(x, n, overlap, tapers, lam, beta, 1, hm)
+    tau = K.eigen_tau(E32, E64)
+    widen = K.start_dof_widen(dof32_1, E64, lam, beta, s2, n)
+    fa, fd = _chain(device, STEPS, E64, lam, beta, s2, n, tau, rel=0.25, widen=1.0, start_dof=False)
+    print("%-10s n=%d K=%d %s: tau %.3g, chained fractions of the QUARTER terms: amp %.3f, dof %.3f" % (name, n, kmax + 1, fmt, tau, fa, fd))
+    quiet = np.flatnonzero(s2 == 0)
+    assert (device(8)[0][quiet] == 0).all() and np.isfinite(device(8)[1]).all()
+    with pytest.raises(AssertionError):
+        _chain(lambda it: device(it, p.stride), STEPS, E64, lam, beta, s2, n, tau, rel=1.0, widen=widen)
+
+
 LINE_SIZES = (256, 512, 1024, 2048, 4096)
 LINE_KMAX, LINE_W = 7, 4.5
 

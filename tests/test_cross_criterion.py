@@ -75,6 +75,76 @@ def test_line_premise_in_float64(lib, n, kmax, nw, overlap):
     assert (settled[:, kl] < 0.9).any() and (settled.max(axis=1) > settled[:, kl]).any()
 
 
+# ---- inputs keyed to the grid's passes (tests/_grid_passes.py): the GPU module's two-pass cases at three sizes
+# (n, kmax, nw, overlap): 16, 2 and 1 frames a block
+PASS_CASES = [(256, 1, 2.0, 0.5), (2048, 4, 2.5, 0.0), (4096, 1, 2.0, 0.75)]
+
+
+def _pass_case(lib, n, kmax, nw, overlap, name):
+    import _grid_passes as G
+    key = ("pass", n, kmax, overlap, name)
+    if key not in _memo:
+        frames = G.TWO_PASS_FRAMES[n]
+        p = G.passes("spectro16cx", n, frames)
+        tapers, sig = lib.make_dpss(n, kmax, nw)
+        xy = E.make_pass_input(name, n, _hop(n, overlap), frames, 0, p.stride)
+        _memo[key] = (xy, tapers, sig, E.cross64(xy, n, overlap, tapers, sig), p)
+    return _memo[key]
+
+
+def silent_x_frames(xy, n, overlap, hist=0):
+    return np.flatnonzero((E.silence_bits(xy, n, overlap, hist) & 1) == 0)
+
+
+def exact_zeros_hold(got, frames):
+    return all((np.asarray(a)[frames] == 0).all() for a in (got.sxx, got.coh, got.sxy.real, got.sxy.imag))
+
+
+@pytest.mark.parametrize("n,kmax,nw,overlap", PASS_CASES)
+@pytest.mark.parametrize("name", E.PASS_INPUTS)
+def test_state_of_the_frame_one_pass_earlier_is_rejected(lib, n, kmax, nw, overlap, name):
+    """On the inputs keyed to the passes: the float32 stand-ins (the module's, and the packed one that separates the channels as
+    the kernel does) pass the rule with the module's tau and keep the exact zeros; a stand-in that decides by the SILENCE BITS of
+    the frame one grid pass earlier does not.  x_early: it zeroes Sxx of frames that hold x (line 1 of the rule, every bin).
+    x_late: it stores the packed transform's rounding where x is silent, so coh != 0 on bins with a b = 0 (fraction inf) and the
+    exact zeros are gone.  apart_by_pass has both bits set in every frame, so stale bits change nothing there; what it is for is
+    the rest of the carried state -- sums that run on from the frame one pass earlier (a missing reset), or that frame's samples
+    (a prefetch that was not renewed): either puts the loud channel's level on a channel 60 dB down."""
+    xy, tapers, sig, ref, p = _pass_case(lib, n, kmax, nw, overlap, name)
+    assert p.npasses == 2
+    tau = K.tau_of(E.cross32(xy, n, overlap, tapers, sig), ref)
+    assert K.FLOOR * K.MARGIN <= tau < 1e-5, tau
+    honest = E.cross32_packed(xy, n, overlap, tapers, sig)
+    K.check(honest, ref, tau, "%s n=%d packed stand-in" % (name, n))
+    quiet = silent_x_frames(xy, n, overlap)
+    assert exact_zeros_hold(honest, quiet) and exact_zeros_hold(ref, quiet)
+    bits = E.silence_bits(xy, n, overlap)
+    if name == "apart_by_pass":
+        assert (bits == 3).all() and len(quiet) == 0
+        run_on = [np.concatenate([a[:p.stride], a[p.stride:] + a[:len(a) - p.stride]]) for a in honest[:3]]
+        for what, got in (("sums that run on", E.Cross(*run_on, E._coh(*run_on))),
+                          ("samples not renewed", E.Cross(*(E.one_pass_earlier(a, p.stride) for a in honest)))):
+            f = K.fraction(got, ref, tau)
+            print("stale %-20s %s n=%d fraction of the bound %.3g" % (what, name, n, f))
+            assert f > 100.0, (what, f)
+        # the levels do what the input is for: the frames of pass 1 have the channels the other way round, 60 dB apart
+        px, py = ref.sxx.sum(axis=1), ref.syy.sum(axis=1)
+        inner = lambda a, b: slice(a + n // _hop(n, overlap), b)           # (past the frames that overlap into the other pass)
+        assert (px[inner(0, p.stride)] > 1e5 * py[inner(0, p.stride)]).all() and (py[inner(p.stride, None)] > 1e5 * px[inner(p.stride, None)]).all()
+        return
+    assert len(quiet) >= p.fpb and ((bits & 1) != 0).sum() >= p.fpb
+    assert len(set(p.pass_of[quiet])) == 1                                  # silence is one pass's; the other holds x
+    stale = E.cross32_packed(xy, n, overlap, tapers, sig, bits=E.one_pass_earlier(bits, p.stride))
+    f = K.fraction(stale, ref, tau)
+    print("stale silence bits %s n=%d fraction of the bound %.3g, exact zeros %s" % (name, n, f, exact_zeros_hold(stale, quiet)))
+    assert f > 1.0, f
+    if name == "x_late":
+        assert not exact_zeros_hold(stale, quiet)
+    else:
+        miss = np.abs(np.sqrt(stale.sxx) - np.sqrt(ref.sxx)) > tau * np.sqrt((ref.sxx + ref.syy).sum(axis=1, keepdims=True))
+        assert miss[p.stride + n // _hop(n, overlap):].mean() > 0.9          # nearly every bin of the frames that hold x
+
+
 def _replace(ref, **kw):
     return ref._replace(**kw)
 

@@ -4,7 +4,12 @@ equalities of the entry's forms, its refusals, and the weak line beside a carrie
 The smallest shapes where the kernel can go wrong: every supported N with 2, 5 and 8 tapers (an odd count ends with a lone taper),
 overlaps 0, 0.5, 0.75 and an odd hop, the three sample formats at an odd sample offset, both history modes, and enough frames that
 a block's frame groups end with a partly filled one and the first frames reach into history.  Every case's fraction of its bound
-goes to the file GLFER_ADAPTIVE_ROWS_OUT names (profiles/adaptive_rows.txt is such a run)."""
+goes to the file GLFER_ADAPTIVE_ROWS_OUT names (profiles/adaptive_rows.txt is such a run).
+
+Past one pass of the persistent grid (tests/_grid_passes.py): every size once more with 71 units of work on a grid of 64, on noise
+and on level_by_pass streams (tests/_adaptive_exact.py: sigma2 steps by 60 dB, or to and from silence, where a block goes from one
+frame group to its next), then 64 and 40 streams sharing the grid over three and two passes, bit for bit.  Their record lines begin
+with 'past-one-pass' (profiles/rows_past_one_pass.txt)."""
 import os
 
 import numpy as np
@@ -12,7 +17,8 @@ import pytest
 
 import _adaptive_check as K
 import _adaptive_exact as X
-from test_adaptive_criterion import LINE_KMAX, LINE_SIZES, LINE_W, full_frames, line_found
+import _grid_passes as G
+from test_adaptive_criterion import LINE_KMAX, LINE_SIZES, LINE_W, PASS_GRID, full_frames, line_found, pass_inputs_of, pass_stream
 from test_adaptive_host import device_entry_refusals
 
 pytestmark = pytest.mark.gpu
@@ -101,6 +107,90 @@ def test_rows_under_both_rules(lib, case):
             assert len(quiet) >= 1 and (device(8)[0][quiet] == 0).all() and np.isfinite(device(8)[1][quiet]).all()
         print(rec)
         RECORDS.append(rec)
+    sp.close()
+
+
+# ---- past one pass of the grid: 71 units of work on a grid of 64, seven blocks run a second frame group (tests/_grid_passes.py)
+def _pass_params():
+    return [(i, name) for i in range(len(PASS_GRID)) for name in ("noise",) + pass_inputs_of(i)]
+
+
+@pytest.mark.parametrize("i,name", _pass_params(), ids=lambda v: v if isinstance(v, str) else "n%d_k%d" % (PASS_GRID[v][0], PASS_GRID[v][1] + 1))
+def test_rows_past_one_pass_under_both_rules(lib, i, name):
+    """Every bin of every frame of both passes: the chained rule at m = 0, 1, 7 on noise and on two level_by_pass streams per
+    size (sigma2 of a frame and of the one its block handled a pass earlier differ by 60 dB, or one of them is silence), the
+    end-to-end rule on noise; psd == 0 and a finite dof in the silent frames."""
+    case = PASS_GRID[i]
+    n, kmax, w, overlap, hm, fmt = case
+    x, p = pass_stream(case, name)
+    assert p.grid == 64 and p.npasses == 2
+    tapers, sig = lib.make_dpss(n, kmax, w)
+    lam, beta = lib.adaptive_weights(_params(lib, *case))
+    E64, s2 = X.eigen64(x, n, overlap, tapers, hm)
+    assert E64.shape[0] == len(p.pass_of)
+    _, dof32_1, E32 = X.adaptive32(x, n, overlap, tapers, lam, beta, 1, hm)
+    tau = K.eigen_tau(E32, E64)
+    widen = K.start_dof_widen(dof32_1, E64, lam, beta, s2, n)
+    sp = lib.Spectrogram(_params(lib, *case))
+    xd = _to_device(x, fmt)
+    memo = {}
+
+    def device(iters):
+        if iters not in memo:
+            r = sp.adaptive(xd, iters=iters)
+            memo[iters] = (r.psd.cpu().numpy(), r.dof.cpu().numpy())
+        return memo[iters]
+    fa = fd = 0.0
+    for m in (0, 1, 7):
+        a, d = K.chained(None if m == 0 else device(m)[0], device(m + 1)[0], device(m + 1)[1], E64, lam, beta, s2, n, tau, dof_widen=widen)
+        fa, fd = max(fa, a), max(fd, d)
+    rec = "past-one-pass n=%-5d K=%d w=%.1f ov=%-4g hm=%d %-3s %-13s tau %.3g  chained: amp %.3f dof %.3f (m=0 dof term x %.2f)" % (
+        n, kmax + 1, w, overlap, hm, fmt, name, tau, fa, fd, widen)
+    if name == "noise":
+        psd32 = X.adaptive32(x, n, overlap, tapers, lam, beta, 8, hm)[0]
+        taup, want = K.end_to_end_tau(psd32, E32, E64, lam, beta, s2, n, 8)
+        rec += "  end-to-end: tau' %.3g, %.3f" % (taup, K.end_to_end(device(8)[0], want, E64, taup))
+    else:
+        quiet = np.flatnonzero(s2 == 0)
+        assert len(quiet) >= p.fpb or "gap" not in name
+        for it in (1, 8):
+            assert (device(it)[0][quiet] == 0).all() and np.isfinite(device(it)[1]).all()
+    sp.close()
+    print(rec)
+    RECORDS.append(rec)
+
+
+@pytest.mark.parametrize("nb", [G.BATCH_MULTIPLE_OF_8, G.BATCH_OTHER])
+@pytest.mark.parametrize("i", (0, 3, 4))
+def test_batch_past_one_pass_bit_for_bit(lib, i, nb):
+    """N = 256 (16 frames a block), 2048 (128 lanes a frame) and 4096: 64 streams share the grid at 32 workgroups each, a multiple
+    of 8, and make three passes; 40 streams at 52, no multiple of 8, make two.  The streams lie one pass apart in one level_by_pass
+    buffer laid out for the BATCH's pass boundaries, so that stream b begins with level b mod 3 of its order and all of
+    1 -> 1e-3 -> 0, 1e-3 -> 0 -> 1 and 0 -> 1 -> 1e-3 appear.  Every stream's rows are the bits of the single-stream call (the
+    two-pass launch held to float64 above), and the first, the middle and the last stream's the bits of range calls of at most 60
+    units of work, each a single pass."""
+    import torch
+    case = PASS_GRID[i]
+    n, kmax, w, overlap, hm, fmt = case
+    frames = G.TWO_PASS_FRAMES[n]
+    p = G.passes("spectro16a", n, frames, nb)
+    assert p.npasses >= (3 if nb == G.BATCH_MULTIPLE_OF_8 else 2) and (p.grid % 8 == 0) == (nb == G.BATCH_MULTIPLE_OF_8)
+    sp = lib.Spectrogram(_params(lib, *case))
+    S = frames * sp.hop + 3
+    name = pass_inputs_of(i)[nb % 2]
+    x = X.level_by_pass(name, n, sp.hop, (nb - 1) * p.stride * sp.hop + S, 17, p.stride, fmt, w)
+    big = _to_device(x, fmt)
+    v = big.as_strided((nb, S), (p.stride * sp.hop, 1), big.storage_offset())
+    got = sp.adaptive_batch(v, iters=8)
+    assert got.psd.shape == (nb, frames, n // 2 + 1)
+    for b in range(nb):
+        one = sp.adaptive(v[b], iters=8)
+        assert _same(got.psd[b], one.psd) and _same(got.dof[b], one.dof), b
+    for b in (0, nb // 2, nb - 1):
+        for first in range(0, frames, 60 * p.fpb):
+            cnt = min(60 * p.fpb, frames - first)
+            part = sp.adaptive(v[b], first_frame=first, nframes=cnt, iters=8)
+            assert _same(part.psd, got.psd[b, first:first + cnt]) and _same(part.dof, got.dof[b, first:first + cnt]), (b, first)
     sp.close()
 
 

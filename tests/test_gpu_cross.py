@@ -8,8 +8,17 @@ and replay.
 The 'line' input (a common line 40 dB under each channel's own noise) is held to the rule like the others; nothing is asserted about
 where its coherence peaks, because in float64 it does not peak at the line (tests/test_cross_criterion.py::test_line_premise_in_float64).
 
-Lines starting with 'cross-rows' (run with -s) are the record kept in profiles/cross_rows.txt."""
+Past one pass of the persistent grid (tests/_grid_passes.py): every size once more with 71 units of work on a grid of 64 -- seven
+blocks run a second frame group, the last one partly filled -- on noise and on the inputs keyed to the pass boundaries
+(tests/_cross_exact.py: x_late, x_early, apart_by_pass), bin by bin against float64 with exact zeros where x has no sample; then 64
+and 40 streams sharing the grid over three and two passes and more, bit for bit against those two-pass calls and against range
+calls of a single pass.  What a kernel that kept a frame group's state for its next would fail there is shown without a GPU in
+tests/test_cross_criterion.py::test_state_of_the_frame_one_pass_earlier_is_rejected.
+
+Lines starting with 'cross-rows' (run with -s) are the record kept in profiles/cross_rows.txt; those that go on with 'past-one-pass',
+in profiles/rows_past_one_pass.txt."""
 import collections
+import functools
 import itertools
 
 import numpy as np
@@ -17,6 +26,7 @@ import pytest
 
 import _cross_check as K
 import _cross_exact as E
+import _grid_passes as G
 from _exact import hop_len
 from test_cross_host import device_entry_refusals
 
@@ -122,6 +132,111 @@ def test_rows_bin_by_bin(lib, torch_cuda, c):
         k = c.n // 16                                    # mid-band: 2 pi k 3 / N = 3 pi / 8
         for f in range(2, c.frames):                     # settled frames
             assert np.angle(ref.sxy[f, k]) > 0 and np.angle(got.sxy[f, k]) > 0, (f, np.angle(ref.sxy[f, k]), np.angle(got.sxy[f, k]))
+
+
+# ---- past one pass of the grid ------------------------------------------------------------------------------------------
+# 71 units of work on a grid of 64 (tests/_grid_passes.py): seven blocks run a second frame group, the last one partly filled
+# where a block holds several frames.  Every size with noise and the three inputs keyed to the passes; taper counts, overlaps and
+# formats in turn; history_mode = 1 once per size.
+PASS_NAMES = ("noise",) + E.PASS_INPUTS
+
+
+def _pass_cases():
+    out = []
+    for s, n in enumerate(SIZES):
+        for i, name in enumerate(PASS_NAMES):
+            kmax, nw = TAPERS[(i + s) % 3]
+            fmt = (("f32", "s16", "u8")[s % 3], "f32", ("u8", "f32", "s16")[s % 3], ("f32", "s16")[s % 2])[i]
+            out.append(Case(n, kmax, nw, OVERLAPS[(i + 2 * s) % 4], fmt, int(i == s % 3), G.TWO_PASS_FRAMES[n], name))
+    return out
+
+
+PASS_CASES = _pass_cases()
+
+
+@functools.lru_cache(maxsize=None)
+def _pass_reference(lib, c):
+    """(raw stream, float64 rows, tau, the frames silent in x) of a case past one pass: computed once, on the CPU alone."""
+    hop = hop_len(c.n, c.ovl)
+    stride = G.passes("spectro16cx", c.n, c.frames).stride
+    xy = E.make_pass_input(c.name, c.n, hop, c.frames, 0, stride) if c.name in E.PASS_INPUTS else E.make_input(c.name, c.n, c.frames * hop, 0)
+    raw = E.quantise(xy, c.fmt)
+    xy32 = E.to_float32(raw, c.fmt)
+    tapers, sig = lib.make_dpss(c.n, c.kmax, c.nw)
+    ref = E.cross64(xy32, c.n, c.ovl, tapers, sig, c.hist)
+    tau = K.tau_of(E.cross32(xy32, c.n, c.ovl, tapers, sig, c.hist), ref)
+    return raw, ref, tau, np.flatnonzero((E.silence_bits(xy32, c.n, c.ovl, c.hist) & 1) == 0)
+
+
+def _check_pass_rows(got, ref, tau, quiet, what):
+    assert (got.sxy.imag[:, 0] == 0).all() and (got.sxy.imag[:, -1] == 0).all()
+    K.check(got, ref, tau, what)
+    for a in (got.sxx, got.coh, got.sxy.real, got.sxy.imag):                       # exact zeros where x has no sample
+        assert (a[quiet] == 0).all(), what
+    loud = np.setdiff1d(np.arange(len(got.sxx)), quiet)
+    assert (got.sxx[loud] > 0).any(axis=1).all(), what
+
+
+def test_the_pass_cases_cover_the_grid():
+    assert {(c.n, c.name) for c in PASS_CASES} == {(n, name) for n in SIZES for name in PASS_NAMES}
+    assert {c.kmax for c in PASS_CASES} == {1, 4, 7} and {c.ovl for c in PASS_CASES} == set(OVERLAPS)
+    assert {c.fmt for c in PASS_CASES} == {"f32", "s16", "u8"} and {c.hist for c in PASS_CASES} == {0, 1}
+    assert not any(c.fmt == "u8" and c.name == "apart_by_pass" for c in PASS_CASES)
+    for c in PASS_CASES:
+        p = G.passes("spectro16cx", c.n, c.frames)
+        assert p.grid == 64 and p.npasses == 2 and G.passes("spectro16cx", c.n, c.frames - 3).npasses == 2
+
+
+@pytest.mark.parametrize("c", PASS_CASES, ids=_id)
+def test_rows_past_one_pass_bin_by_bin(lib, torch_cuda, c):
+    """Every bin of every frame of both passes against float64; the x_early case of every size once more from first_frame = 3, so
+    that the second pass runs with frame0 != 0, against the same float64 rows."""
+    torch = torch_cuda
+    raw, ref, tau, quiet = _pass_reference(lib, c)
+    sp = _plan(lib, c)
+    d = torch.from_numpy(raw).cuda()
+    got = _host(sp.cross(d, want=ALL))
+    assert got.sxx.shape == (c.frames, c.n // 2 + 1)
+    _check_pass_rows(got, ref, tau, quiet, "past-one-pass " + _id(c))
+    if c.name == "x_early":
+        part = _host(sp.cross(d, first_frame=3, want=ALL))
+        assert part.sxx.shape == (c.frames - 3, c.n // 2 + 1)
+        _check_pass_rows(part, E.Cross(*(a[3:] for a in ref)), tau, quiet[quiet >= 3] - 3, "past-one-pass first_frame=3 " + _id(c))
+    sp.close()
+
+
+def _chunks(total, size):
+    return [(a, min(size, total - a)) for a in range(0, total, size)]
+
+
+@pytest.mark.parametrize("nb", [G.BATCH_MULTIPLE_OF_8, G.BATCH_OTHER])
+@pytest.mark.parametrize("n,kmax,nw,ovl,fmt", [(256, 4, 2.5, 0.5, "f32"), (2048, 1, 2.0, 0.75, "s16"), (8192, 7, 4.0, 0.5, "f32")])
+def test_batch_past_one_pass_bit_for_bit(lib, torch_cuda, n, kmax, nw, ovl, fmt, nb):
+    """64 streams share the grid at 32 (N = 8192: 16) workgroups each, a multiple of 8, and make three (five) passes; 40 streams at
+    52 (26), no multiple of 8, make two (three).  The streams are cut from one apart_by_pass buffer laid out for the BATCH's pass
+    boundaries, one pass apart: neighbours begin with the levels the other way round.  Every stream's rows are the bits of the
+    single-stream call (the two-pass launch test_rows_past_one_pass_bin_by_bin holds to float64), and for the first, the middle and
+    the last stream the bits of range calls of at most 60 units of work, each a single pass."""
+    torch = torch_cuda
+    c = Case(n, kmax, nw, ovl, fmt, 0, G.TWO_PASS_FRAMES[n], "apart_by_pass")
+    p = G.passes("spectro16cx", n, c.frames, nb)
+    assert p.npasses >= (3 if nb == G.BATCH_MULTIPLE_OF_8 else 2) and (p.grid % 8 == 0) == (nb == G.BATCH_MULTIPLE_OF_8)
+    hop = hop_len(n, ovl)
+    total = (nb - 1) * p.stride + c.frames
+    big = torch.from_numpy(E.quantise(E.make_pass_input(c.name, n, hop, total, 5, p.stride), fmt)).cuda()
+    S = c.frames * hop
+    v = big.as_strided((nb, S, 2), (p.stride * hop * 2, 2, 1))
+    sp = _plan(lib, c)
+    got = sp.cross_batch(v, want=ALL)
+    assert got.coh.shape == (nb, c.frames, n // 2 + 1)
+    for b in range(nb):
+        assert _same_all([t[b] for t in got], sp.cross(v[b], want=ALL)), b
+    for b in (0, nb // 2, nb - 1):
+        for first, cnt in _chunks(c.frames, 60 * p.fpb):
+            assert G.passes("spectro16cx", n, cnt).npasses == 1
+            part = sp.cross(v[b], first_frame=first, nframes=cnt, want=ALL)
+            assert _same_all(part, [t[b, first:first + cnt] for t in got]), (b, first, cnt)
+    sp.close()
 
 
 # ---- bit for bit ------------------------------------------------------------------------------------------------------

@@ -5,14 +5,19 @@ interval helper.
 The grid: every built N -- 256 (16 lanes a frame, 16 frames a block) to 2048 and 4096 (a frame spans 2 and 4 wavefronts) -- with
 2, 5 (odd: the lone taper) and 8 tapers, 37 frames (a partly filled last frame group), overlaps 0 and 75 %, f32 / s16 / u8 at an odd
 sample offset, both history modes, sweep counts 0, 2 and 8 (1 and 7 for the chain), seven inputs.  Every case's fraction of its
-bound and its excluded share go to the file GLFER_JACKKNIFE_ROWS_OUT names (profiles/jackknife_rows.txt is such a run)."""
+bound and its excluded share go to the file GLFER_JACKKNIFE_ROWS_OUT names (profiles/jackknife_rows.txt is such a run).
+
+Past one pass of the persistent grid: tests/test_gpu_adaptive.py's two-pass cases and shared-grid batches for this entry; their
+record lines begin with 'past-one-pass' (profiles/rows_past_one_pass.txt)."""
 import os
 
 import numpy as np
 import pytest
 
 import _adaptive_exact as X
-from test_jackknife_criterion import CASE_ID, GRID, INPUTS, Case, check_case
+import _grid_passes as G
+from test_adaptive_criterion import PASS_GRID, pass_inputs_of
+from test_jackknife_criterion import CASE_ID, GRID, INPUTS, Case, check_case, pass_case
 from test_jackknife_host import device_entry_refusals
 
 pytestmark = pytest.mark.gpu
@@ -70,6 +75,75 @@ def test_rows_under_the_rule(lib, case):
         rec = check_case(c, device)
         print(rec)
         RECORDS.append(rec)
+    sp.close()
+
+
+# ---- past one pass of the grid: tests/test_gpu_adaptive.py's cases through check_case
+def _pass_params():
+    return [(i, name) for i in range(len(PASS_GRID)) for name in ("noise",) + pass_inputs_of(i)]
+
+
+@pytest.mark.parametrize("i,name", _pass_params(), ids=lambda v: v if isinstance(v, str) else CASE_ID(PASS_GRID[v]))
+def test_rows_past_one_pass_under_the_rule(lib, i, name):
+    """71 units of work on a grid of 64: every bin of every frame of both passes under the rule at iters 0, 2 and 8 (and 0 and 8
+    are the sweep counts the issue names), psd and dof the bits of adaptive() -- whose rows tests/test_gpu_adaptive.py holds to the
+    chained rule on the same streams: with two tapers, and in silent frames, that equality is what sees a stale sigma2
+    (tests/test_jackknife_criterion.py)."""
+    case = PASS_GRID[i]
+    assert lib.jackknife_supported(_params(lib, *case))
+    if name in X.PASS_INPUTS:
+        c, p = pass_case(lib, case, name)
+    else:
+        c, p = Case(lib, case, name, frames=G.TWO_PASS_FRAMES[case[0]]), G.passes("spectro16a", case[0], G.TWO_PASS_FRAMES[case[0]])
+    assert p.grid == 64 and p.npasses == 2
+    sp = lib.Spectrogram(_params(lib, *case))
+    xd = _to_device(c.x, case[5])
+    memo = {}
+
+    def device(iters):
+        if iters not in memo:
+            r = sp.jackknife(xd, iters=iters)
+            memo[iters] = (r.psd.cpu().numpy(), r.dof.cpu().numpy(), r.logvar.cpu().numpy())
+            if iters >= 1:
+                a = sp.adaptive(xd, iters=iters)
+                assert _same(r.psd, a.psd) and _same(r.dof, a.dof), (name, iters)
+        return memo[iters]
+    rec = "past-one-pass " + check_case(c, device)
+    quiet = np.flatnonzero(c.s2 == 0)
+    for it in (0, 8):
+        assert (device(it)[0][quiet] == 0).all() and (device(it)[2][quiet] == 0).all() and np.isfinite(device(it)[1]).all()
+    sp.close()
+    print(rec)
+    RECORDS.append(rec)
+
+
+@pytest.mark.parametrize("nb", [G.BATCH_MULTIPLE_OF_8, G.BATCH_OTHER])
+@pytest.mark.parametrize("i", (0, 3, 4))
+def test_batch_past_one_pass_bit_for_bit(lib, i, nb):
+    """tests/test_gpu_adaptive.py::test_batch_past_one_pass_bit_for_bit for the jackknife entry, iters 0 and 8: three passes on
+    grids of 32 (a multiple of 8) with 64 streams, two on grids of 52 with 40; streams one pass apart in one level_by_pass buffer;
+    every stream against the single-stream two-pass call, three streams against range calls of a single pass each."""
+    import torch  # noqa: F401
+    case = PASS_GRID[i]
+    n, kmax, w, overlap, hm, fmt = case
+    frames = G.TWO_PASS_FRAMES[n]
+    p = G.passes("spectro16a", n, frames, nb)
+    assert p.npasses >= (3 if nb == G.BATCH_MULTIPLE_OF_8 else 2) and (p.grid % 8 == 0) == (nb == G.BATCH_MULTIPLE_OF_8)
+    sp = lib.Spectrogram(_params(lib, *case))
+    S = frames * sp.hop + 3
+    name = pass_inputs_of(i)[(nb + 1) % 2]
+    big = _to_device(X.level_by_pass(name, n, sp.hop, (nb - 1) * p.stride * sp.hop + S, 19, p.stride, fmt, w), fmt)
+    v = big.as_strided((nb, S), (p.stride * sp.hop, 1), big.storage_offset())
+    for iters in (0, 8):
+        got = sp.jackknife_batch(v, iters=iters)
+        assert got.logvar.shape == (nb, frames, n // 2 + 1)
+        for b in range(nb):
+            assert _all_same(lib.Jackknife(*(t[b] for t in got)), sp.jackknife(v[b], iters=iters)), (iters, b)
+        for b in (0, nb // 2, nb - 1):
+            for first in range(0, frames, 60 * p.fpb):
+                cnt = min(60 * p.fpb, frames - first)
+                part = sp.jackknife(v[b], first_frame=first, nframes=cnt, iters=iters)
+                assert _all_same(part, lib.Jackknife(*(t[b, first:first + cnt].contiguous() for t in got))), (iters, b, first)
     sp.close()
 
 

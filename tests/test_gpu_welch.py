@@ -6,7 +6,13 @@ the exact zeros of silent channels; what the rows mean (a delay's phase, a weak 
 against Spectrogram.cross, row ranges, moving rows against block rows, batches against the loop, pitched outputs between
 sentinels, every subset of outputs, the complex view, one capture and replay; and the refusals with real plans.
 
-Lines starting with 'cross-rows' (run with -s) are the record kept in profiles/welch_cross_rows.txt."""
+Past one pass of the persistent grid (tests/_grid_passes.py; rows are the work here): N = 256, 2048 and 8192 with 71 units of rows
+on a grid of 64, Hanning plans with (L, step) = (3, 1) and (3, 5) and a two-taper plan with (2, 2), on noise and on the inputs keyed
+to the pass boundaries -- x_late / x_early leave a row of pass 1 with x in one segment alone --; then 64 and 40 streams sharing the
+grid, bit for bit against those calls and against row ranges of a single pass.
+
+Lines starting with 'cross-rows' (run with -s) are the record kept in profiles/welch_cross_rows.txt; those that go on with
+'past-one-pass', in profiles/rows_past_one_pass.txt."""
 import itertools
 
 import numpy as np
@@ -14,6 +20,7 @@ import pytest
 
 import _cross_check as K
 import _cross_exact as E
+import _grid_passes as G
 import _welch_exact as W
 from _exact import hop_len
 from test_welch_host import check_welch_rows, device_entry_refusals
@@ -119,6 +126,73 @@ def test_a_channel_silent_in_one_segment_only_is_not_zeroed(lib, torch_cuda, n):
     sp.close()
     K.check(got, ref, tau, "x silent in segment 0 n=%d" % n)
     assert (got.sxx > 0).all() and (got.coh > 0).any() and (np.abs(got.sxy) > 0).any()
+
+
+# ---- past one pass of the grid ------------------------------------------------------------------------------------------
+PASS_CASES = W.pass_cases()
+
+
+@pytest.mark.parametrize("c", PASS_CASES, ids=W.case_id)
+def test_rows_past_one_pass_bin_by_bin(lib, torch_cuda, c):
+    """71 units of ROWS on a grid of 64: seven blocks run a second row group.  x_late / x_early put a row into pass 1 that holds
+    x in one of its segments alone (tests/test_welch_criterion.py), so the OR over a row's segments is taken in a later pass."""
+    from test_welch_criterion import pass_case_bits
+    torch = torch_cuda
+    assert G.passes("spectro16cx", c.n, c.rows).npasses == 2
+    raw, xy32 = W.case_input(c)
+    p64, p32 = W.case_per_frame(lib, c)
+    ref = W.welch64(p64, c.segments, c.step)
+    tau = K.tau_of(W.welch32(p32, c.segments, c.step), ref)                       # from the CPU alone
+    sp = _plan(lib, c)
+    d = torch.from_numpy(raw).cuda()
+    got = _host(sp.cross_welch(d, c.segments, c.step, want=ALL))
+    assert got.sxx.shape == (c.rows, c.n // 2 + 1)
+    bits, quiet = pass_case_bits(c, xy32)
+
+    def held(got, ref, bits, quiet, what):
+        assert (got.sxy.imag[:, 0] == 0).all() and (got.sxy.imag[:, -1] == 0).all()
+        K.check(got, ref, tau, what)
+        for a in (got.sxx, got.coh, got.sxy.real, got.sxy.imag):                   # exact zeros where x has no sample in any segment
+            assert (a[quiet] == 0).all(), what
+        assert (got.sxx[(bits & 1) != 0] > 0).any(axis=1).all(), what
+    held(got, ref, bits, quiet, "past-one-pass " + W.case_id(c))
+    if c.name == "x_early":
+        # once more from row 2 (first_frame = 2 step): frame0 + fblk * step + seg with frame0 != 0 in the second pass, two passes
+        # still, against the same float64 rows
+        assert G.passes("spectro16cx", c.n, c.rows - 2).npasses == 2
+        part = _host(sp.cross_welch(d, c.segments, c.step, first_frame=2 * c.step, want=ALL))
+        assert part.sxx.shape == (c.rows - 2, c.n // 2 + 1)
+        held(part, E.Cross(*(a[2:] for a in ref)), bits[2:], quiet[quiet >= 2] - 2, "past-one-pass first_frame=%d %s" % (2 * c.step, W.case_id(c)))
+    sp.close()
+
+
+@pytest.mark.parametrize("nb", [G.BATCH_MULTIPLE_OF_8, G.BATCH_OTHER])
+@pytest.mark.parametrize("n,kind,ovl,fmt,segments,step", [(256, W.KINDS[2], 0.5, "f32", 3, 1), (2048, W.KINDS[3], 0.75, "s16", 2, 2),
+                                                           (8192, W.KINDS[2], 0.5, "f32", 3, 1)])
+def test_batch_past_one_pass_bit_for_bit(lib, torch_cuda, n, kind, ovl, fmt, segments, step, nb):
+    """tests/test_gpu_cross.py::test_batch_past_one_pass_bit_for_bit for rows: the streams lie one pass of ROWS (stride * step
+    frames) apart in one apart_by_pass buffer; every stream against the single-stream two-pass call, three streams against row
+    ranges of at most 60 units of work."""
+    torch = torch_cuda
+    c = W.Case(n, kind, ovl, fmt, 0, segments, step, G.TWO_PASS_FRAMES[n], "apart_by_pass")
+    p = G.passes("spectro16cx", n, c.rows, nb)
+    assert p.npasses >= (3 if nb == G.BATCH_MULTIPLE_OF_8 else 2) and (p.grid % 8 == 0) == (nb == G.BATCH_MULTIPLE_OF_8)
+    hop = hop_len(n, ovl)
+    total = (nb - 1) * p.stride * step + W.frames_of(c)
+    big = torch.from_numpy(E.quantise(E.make_pass_input(c.name, n, hop, total, 5, p.stride, segments, step), fmt)).cuda()
+    S = W.frames_of(c) * hop
+    v = big.as_strided((nb, S, 2), (p.stride * step * hop * 2, 2, 1))
+    sp = _plan(lib, c)
+    got = sp.cross_welch_batch(v, segments, step, want=ALL)
+    assert got.coh.shape == (nb, c.rows, n // 2 + 1)
+    for b in range(nb):
+        assert _same_all([t[b] for t in got], sp.cross_welch(v[b], segments, step, want=ALL)), b
+    for b in (0, nb // 2, nb - 1):
+        for r0 in range(0, c.rows, 60 * p.fpb):
+            cnt = min(60 * p.fpb, c.rows - r0)
+            part = sp.cross_welch(v[b], segments, step, first_frame=r0 * step, nrows=cnt, want=ALL)
+            assert _same_all(part, [t[b, r0:r0 + cnt] for t in got]), (b, r0, cnt)
+    sp.close()
 
 
 # ---- what the rows mean -----------------------------------------------------------------------------------------------

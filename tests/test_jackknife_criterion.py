@@ -54,25 +54,29 @@ CASE_ID = lambda c: "n%d_k%d_ov%g_hm%d_%s" % (c[0], c[1] + 1, c[3], c[4], c[5]) 
 class Case:
     """One (grid case, input): the stream, its float64 eigenspectra, the stand-in's tau -- computed once, shared by the checks."""
 
-    def __init__(self, lib, case, name, frames=FRAMES, seed=11):
+    def __init__(self, lib, case, name, frames=FRAMES, seed=11, stride=None, levels=None):
+        """stride (and levels): for the inputs of _adaptive_exact.PASS_INPUTS, the frames one pass of the call's grid covers."""
         self.n, self.kmax, self.w, self.overlap, self.hm, self.fmt = case
         self.name = name
         self.tapers, self.sig = lib.make_dpss(self.n, self.kmax, self.w)
         self.lam, self.beta = lib.adaptive_weights(lib.MtmParams(n=self.n, w=self.w, kmax=self.kmax, overlap=self.overlap))
         self.hop = int(self.n * (1.0 - self.overlap))
-        self.x = X.make_input(name, self.n, frames * self.hop + 3, seed, self.fmt, self.w)
+        if name in X.PASS_INPUTS:
+            self.x = X.level_by_pass(name, self.n, self.hop, frames * self.hop + 3, seed, stride, self.fmt, self.w, levels)
+        else:
+            self.x = X.make_input(name, self.n, frames * self.hop + 3, seed, self.fmt, self.w)
         self.E64, self.s2 = X.eigen64(self.x, self.n, self.overlap, self.tapers, self.hm)
         assert self.E64.shape[0] == frames
         self.E32 = X.eigen32(self.x, self.n, self.overlap, self.tapers, self.hm)[0]
         self.tau = AK.eigen_tau(self.E32, self.E64)
 
-    def stand_in(self, mutate=None):
+    def stand_in(self, mutate=None, s2_stride=None):
         memo = {}
 
         def device(iters):
             if iters not in memo:
                 memo[iters] = JX.jackknife32(self.x, self.n, self.overlap, self.tapers, self.lam, self.beta, iters, self.hm,
-                                             mutate=mutate)[:3]
+                                             mutate=mutate, s2_stride=s2_stride)[:3]
             return memo[iters]
         return device
 
@@ -189,6 +193,59 @@ def test_stand_in_passes_the_rule_within_a_quarter(lib, case):
         c = Case(lib, case, name)
         case_conditions(c)
         print(check_case(c, c.stand_in(), rel=0.25))
+
+
+# ---- 3b. inputs keyed to the grid's passes: tests/test_adaptive_criterion.py's PASS_GRID and streams
+def pass_case(lib, case, name, nbatch=1):
+    """(Case, the passes of its call) of a level_by_pass stream of the two-pass frame count of its size."""
+    import _grid_passes as G
+    frames = G.TWO_PASS_FRAMES[case[0]]
+    p = G.passes("spectro16a", case[0], frames, nbatch)
+    return Case(lib, case, name, frames=frames, stride=p.stride), p
+
+
+def _pass_criterion():
+    from test_adaptive_criterion import PASS_CRITERION
+    return PASS_CRITERION
+
+
+@pytest.mark.parametrize("case,name", _pass_criterion(), ids=lambda v: v if isinstance(v, str) else CASE_ID(v))
+def test_sigma2_of_the_frame_one_pass_earlier_is_rejected(lib, case, name):
+    """level_by_pass: from float64 alone the excluded share of the noise-based streams stays within NOISE_SHARE (1e-3 level
+    included, at every size: nothing had to be dropped); the stand-in passes the rule within a quarter of REL_LOG; the stand-in
+    whose weights come from sigma2 of the frame one grid pass earlier is rejected.
+
+    By WHICH assertion of the device test it is rejected depends on the case.  With five and eight tapers and sound in the later
+    pass, by the logvar rule at iters 2 and 8 (iters = 0 has no sigma2 in it).  With TWO tapers logvar is 1/4 (ln E_1 - ln E_0)^2
+    whatever the weights (test_two_tapers_closed_form), and a silent frame's logvar is 0 whatever they are: there the rule on
+    logvar cannot see sigma2, and what rejects the stand-in is the other half of the device test -- psd and dof are the bits of
+    adaptive(), whose rows tests/test_gpu_adaptive.py holds to the chained rule on the same stream.  Both are tried here, and
+    which one fired is printed."""
+    c, p = pass_case(lib, case, name)
+    assert p.npasses == 2
+
+    def chained_rule(device):
+        """The chained rule of tests/_adaptive_check.py on the stand-in's psd and dof rows (m = 1 and 7: given S, no widening)."""
+        for m in (1, 7):
+            AK.chained(device(m)[0], device(m + 1)[0], device(m + 1)[1], c.E64, c.lam, c.beta, c.s2, c.n, c.tau)
+    for iters in ITERS:
+        share, _ = JK.excluded_share(c.E64, c.float64_weights(iters), c.tau)
+        print("%s %s iters %d: excluded share %.2g" % (CASE_ID(case), name, iters, share))
+        if name.startswith("noise"):
+            assert share <= JK.NOISE_SHARE, (name, iters, share)
+    print(check_case(c, c.stand_in(), rel=0.25))
+    quiet = np.flatnonzero(c.s2 == 0)
+    assert all((np.asarray(c.stand_in()(it)[2])[quiet] == 0).all() for it in ITERS)
+    chained_rule(c.stand_in())
+    fired = []
+    for what, rule in (("logvar rule", lambda d: check_case(c, d)), ("chained rule on psd / dof", chained_rule)):
+        try:
+            rule(c.stand_in(s2_stride=p.stride))
+        except AssertionError:
+            fired.append(what)
+    print("stale sigma2 %s %s: rejected by %s" % (CASE_ID(case), name, fired))
+    assert "chained rule on psd / dof" in fired
+    assert "logvar rule" in fired or c.kmax == 1 or name.endswith("gap") or c.fmt == "u8"
 
 
 # ---- 4. mutations

@@ -81,6 +81,68 @@ def test_mutations_are_rejected(lib, c):
         assert f > 1.0, (what, W.case_id(c), f)
 
 
+# ---- inputs keyed to the grid's passes: the GPU module's two-pass cases (the longest stream, N = 256 at step 5, left to the GPU)
+PASS_CASES = [c for c in W.pass_cases() if c.name in E.PASS_INPUTS and not (c.n == 256 and c.step == 5)]
+
+
+def pass_case_bits(c, xy32):
+    """(per-row silence bits, the rows silent in x) of a case's stream."""
+    bits = W.row_bits(E.silence_bits(xy32, c.n, c.ovl, c.hist), c.segments, c.step, c.rows)
+    return bits, np.flatnonzero((bits & 1) == 0)
+
+
+def test_the_pass_cases_cover_their_grid():
+    import _grid_passes as G
+    cs = W.pass_cases()
+    assert {(c.n, c.kind, c.segments, c.step) for c in cs} == {(n,) + pl for n in W.PASS_SIZES for pl in W.PASS_PLANS}
+    for n in W.PASS_SIZES:
+        assert {c.name for c in cs if c.n == n} == set(W.PASS_NAMES)
+    for pl in W.PASS_PLANS:
+        assert {c.name for c in cs if (c.kind, c.segments, c.step) == pl} == set(W.PASS_NAMES)
+    assert {c.fmt for c in cs} == set(W.FMTS) and {c.hist for c in cs} == {0, 1}
+    assert all(G.passes("spectro16cx", c.n, c.rows).npasses == 2 for c in cs)
+
+
+@pytest.mark.parametrize("c", PASS_CASES, ids=W.case_id)
+def test_row_bits_of_the_row_one_pass_earlier_are_rejected(lib, c):
+    """The float32 stand-ins pass the rule on the pass-keyed inputs and keep the exact zeros; a stand-in that stores a row by the
+    silence bits of the row one grid pass earlier does not (tests/test_cross_criterion.py's test of the per-frame entry, with
+    the OR over a row's segments).  x_late and x_early put a row into pass 1 that holds x in ONE of its segments: a stand-in that
+    takes a row's bits from its last segment alone, or its first alone, zeroes or keeps the wrong rows there."""
+    import _grid_passes as G
+    p = G.passes("spectro16cx", c.n, c.rows)
+    raw, xy32 = W.case_input(c)
+    p64, p32 = W.case_per_frame(lib, c)
+    ref = W.welch64(p64, c.segments, c.step)
+    tau = K.tau_of(W.welch32(p32, c.segments, c.step), ref)
+    assert K.FLOOR * K.MARGIN <= tau < 1e-5, tau
+    tapers, sig = W.tables_of(lib, c.n, c.kind)
+    fbits = E.silence_bits(xy32, c.n, c.ovl, c.hist)
+    packed = E.cross32_packed(xy32, c.n, c.ovl, tapers, sig, c.hist, bits=np.full(len(fbits), 3))
+    bits, quiet = pass_case_bits(c, xy32)
+    honest = W.welch32_packed(packed, c.segments, c.step, bits)
+    K.check(honest, ref, tau, W.case_id(c) + " packed stand-in")
+    from test_cross_criterion import exact_zeros_hold
+    assert exact_zeros_hold(honest, quiet) and exact_zeros_hold(ref, quiet)
+    if c.name == "apart_by_pass":
+        assert (bits == 3).all()
+        moved = E.Cross(*(E.one_pass_earlier(a, p.stride) for a in honest))        # the samples of the row one pass earlier
+        assert K.fraction(moved, ref, tau) > 100.0
+        return
+    assert len(quiet) >= p.fpb and len(set(p.pass_of[quiet])) == 1
+    # the row of pass 1 that holds x in one segment only: its bits need the OR, taken in a later pass
+    first = p.stride
+    segs = [int(fbits[first * c.step + s] & 1) for s in range(c.segments)]
+    assert sum(segs) == 1 and segs[0 if c.name == "x_late" else -1] == 1 and bits[first] == 3, segs
+    stale = W.welch32_packed(packed, c.segments, c.step, E.one_pass_earlier(bits, p.stride))
+    f = K.fraction(stale, ref, tau)
+    print("stale row bits %s fraction of the bound %.3g, exact zeros %s" % (W.case_id(c), f, exact_zeros_hold(stale, quiet)))
+    assert f > 1.0, f
+    assert not exact_zeros_hold(stale, quiet) if c.name == "x_late" else (stale.sxx[first:] == 0).all()
+    one_segment = fbits[(c.segments - 1 if c.name == "x_late" else 0):][:(c.rows - 1) * c.step + 1:c.step]
+    assert K.fraction(W.welch32_packed(packed, c.segments, c.step, one_segment), ref, tau) > 1.0
+
+
 def test_float64_products_vanish_for_silence_only(lib):
     """The rule asks for coh == 0 exactly where the float64 Sxx Syy is 0, which a device can owe only where a channel is silent.
     So no accuracy case may have a float64 row with a zero product for any other reason (an exact cancellation in float64, as
