@@ -108,9 +108,12 @@ RANGE_CASES = [(fft(128, 0.5, "hanning", 45), 1), (fft(1024, 0.75, "hanning", 41
 #     spectro16h.hip: the periodogram at N = 2048, 4 096 + 1 009 frames.  launch16_fmt (spectro16.hip) starts at most 4 x
 #     resident blocks: 2048 x 2 = 4 096 frames at N = 2048 (four tapers: packed), 3072 x 16 = 49 152 at N = 256, where the
 #     five-taper plan runs spectro16xl.hip in the same blocks.  spectro16y.hip: 16 384 frames a pass (checked on cuts of the
-#     stream by the GPU module: the float64 rows of 20 000 frames are not kept whole).  Left out: spectro16w.hip and
-#     spectro_big.hip -- a pass of theirs is thousands of frames of 16 384 samples and more, whose float64 rows and oracle
-#     rows cost minutes of CPU per case; tests/test_gpu_round3.py keeps their long launches against the oracle on a few rows
+#     stream by the GPU module: the float64 rows of 20 000 frames are not kept whole).  Covered elsewhere, on 65 ... 71 units of
+#     work (a grid of 64: persistent_grid keeps whole XCD slices) and at the launchers' own thresholds -- tests/_walk_cases.py,
+#     tests/test_gpu_walk.py: spectro16h.hip's SHIFT = 2 / 4 / 8 forms (from work >= 4 x resident on), its multitaper form,
+#     spectro16x.hip, spectro16xl.hip at N = 512 ... 2048, spectro16w.hip in every form, the packed kernel at N = 512 ... 8192, and
+#     spectro_big.hip past subfft_kernel's grid cap and past its first scratch group (cuts); tests/test_gpu_round3.py keeps the
+#     long launches of the large blocks against the oracle on a few rows
 LONG_CASES = [fft(16, 0.0, "hanning", 40001, "noise"), fft(2048, 0.5, "hanning", 4096 + 1009, "noise"),
               mtm(256, 0.75, 2.5, 4, 49152 + 1009, "noise"), mtm(2048, 0.75, 2.0, 3, 4096 + 1009, "noise")]
 LONG_Y = mtm(4096, 0.0, 2.5, 4, 16384 + 4097, "weak")

@@ -25,6 +25,10 @@ Which case reaches which kernel file (glfer_hip.cpp, launch_by_n):
   spectro16y.hip      odd taper counts at N = 4096: five tapers NW 2.5 the half-table form, GLFER_Y_TAPERS=full and 3 / 9 tapers the full
   spectro16w.hip      the multitaper at N = 16384, GLFER_FORM=w from N = 2048, spectrum=True at N = 32768
   spectro_big.hip     the periodogram from N = 32768, the two-level combine from N = 131072
+Past one unit of work per workgroup, and spectro16h.hip's register-walk forms (SHIFT = 2 / 4 / 8: the periodogram at overlap 87.5 / 75 /
+50 % without mean removal from work >= 4 x resident on -- no case here is that long): tests/test_gpu_walk.py, same rule;
+group (f) below covers spectro_small, spectro16h's plain form at N = 2048, the packed kernel at N = 256 / 2048, spectro16xl at
+N = 256 and spectro16y.
 Not here: limiter / RA9MB (non-linear: tests/test_gpu_nonlin.py holds them to the same rule), HP-ARMA, LMP, the F-test (own
 rules), the host / WAV / worker entries (the same kernels).
 

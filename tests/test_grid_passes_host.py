@@ -82,3 +82,101 @@ def test_batch_cases(kernel):
         assert (b.block_of[:b.stride:b.fpb] == np.arange(b.grid)).all()
     assert G.fpb_of(BATCH_SIZES[kernel][0]) == 16 and BATCH_SIZES[kernel][1] // 16 == 128
     assert BATCH_SIZES[kernel][2] == max(G.KERNELS[kernel].sizes)
+
+
+# ---- the single-stream route, spectro16h.hip's register-walk forms and the second units of work (tests/_walk_cases.py) ------------
+def test_the_restated_kernels():
+    import _walk_cases as W
+    h, w = G.KERNELS["spectro16h"], G.KERNELS["spectro16w"]
+    sizes = (512, 1024, 2048, 4096, 8192, 16384)
+    assert [h.fpb(n) for n in sizes] == [16, 8, 4, 2, 1, 1] and [h.block(n) for n in sizes] == [256] * 5 + [512]
+    assert [G.walk_resident(n) for n in sizes] == [768] * 5 + [256]
+    assert [G.walk_threshold_frames(n) for n in sizes] == [49152, 24576, 12288, 6144, 3072, 1024]
+    assert [w.fpb(n) for n in w.sizes] == [4, 2, 1, 1, 1] and [w.block(n) for n in w.sizes] == [256, 256, 256, 512, 1024]
+    assert [G.KERNELS["spectro16xl"].fpb(n) for n in (256, 512, 1024, 2048)] == [32, 16, 8, 4]
+    assert G.KERNELS["spectro16x"].fpb(1024) == 8 and G.cap_of("spectro16xl", 512) == 2048
+    # tests/_rows_cases.py (f): "launch16_fmt (spectro16.hip) starts at most 4 x resident blocks: 2048 x 2 = 4 096 frames at
+    # N = 2048 ..., 3072 x 16 = 49 152 at N = 256"; tests/_pairs_cases.py xl_second_pass_from: "grid of at most 2 048 workgroups"
+    assert G.cap_of("spectro16", 2048) == 2048 and G.cap_of("spectro16", 256) == 3072
+    for kernel in ("spectro16", "spectro16x", "spectro16xl"):
+        assert G.KERNELS[kernel].walk == "strided"
+    for kernel in ("spectro16h", "spectro16h_mt", "spectro16w"):
+        assert G.KERNELS[kernel].walk == "contiguous"
+    # the cut: frame_cuts.h's own examples of tests/c_frame_cuts.c's kind
+    assert G.first_inside(4096, 1024) == 3 and G.first_inside(4096, 512) == 7 and G.first_inside(4096, 4096) == 0
+    assert G.cut_frames(0, 100, 3) == (3, 100) and G.cut_frames(5, 100, 3) == (5, 100) and G.cut_frames(0, 3, 3) == (3, 3)
+    assert G.cut_frames(0, 21, 3, 8) == (8, 16) and G.cut_frames(0, 15, 3, 8) == (15, 15) and G.cut_frames(0, 9, 7, 8) == (9, 9)
+    assert G.hop_sixteenths(4096, 1024) == 4 and G.hop_sixteenths(4096, 409) == 0
+    # tests/_rows_cases.py LONG_CASES: fft(2048, 0.5, ..., 4096 + 1009) stays in the plain form (1 277 units)
+    lw = G.walk(2048, 1024, 4096 + 1009 - 1)
+    assert lw.shift == 0 and lw.work == 1276 and W.head_of(W.WALK_CASES[0]) == 3
+
+
+def test_walk_cases_are_above_the_threshold_and_the_just_below_cases_below():
+    import _walk_cases as W
+    assert len(W.WALK_CASES) == 14
+    seen, pers = set(), set()
+    for c in W.WALK_CASES:
+        b0, w = W.walk_of(c)
+        k16 = G.hop_sixteenths(c.n, W.X.hop_len(c.n, c.ovl))
+        assert b0 == W.head_of(c) and w.shift == k16 and k16 in G.WALK_SHIFTS, W.case_id(c)
+        assert w.work >= 4 * G.walk_resident(c.n) and w.grid == G.walk_resident(c.n) and w.per in (4, 5)
+        assert 0 < w.last_slot_frames < w.per                         # a partly filled last slot
+        assert w.slot[-1] + 1 < w.grid * w.fpb or w.per == 4          # per = 5: whole slots (and workgroups) past the end
+        assert (np.bincount(w.slot)[:-1] == w.per).all() and (np.diff(w.it)[np.diff(w.slot) == 0] == 1).all()
+        assert 8e6 <= c.frames * (c.n // 2 + 1) <= 13e6
+        seen.add((c.n, w.shift, c.fmt))
+        pers.add(w.per)
+    assert pers == {4, 5}                                             # an even and an odd per
+    assert {n for n, _, _ in seen} == {512, 1024, 2048, 4096, 8192, 16384}
+    assert {s for n, s, _ in seen if n == 4096} == {2, 4, 8} and {s for n, s, _ in seen if n <= 1024} == {2, 4, 8}
+    assert {f for _, _, f in seen} == {"f32", "s16", "u8"} and {(4, "s16"), (4, "u8")} <= {(s, f) for _, s, f in seen}
+    assert (4096, 4, "f32") in seen and W.WALK_CASES[6].window == "hanning"   # C2's own shape
+    for c in W.BELOW_CASES:
+        _, w = W.walk_of(c)
+        assert w.shift == 0 and w.work == 4 * G.walk_resident(c.n) - 1, W.case_id(c)
+    # the range calls: still above the threshold, the start off the whole-stream call's slot grid, the end inside a slot of their own
+    assert {G.hop_sixteenths(c.n, W.X.hop_len(c.n, c.ovl)) for c in W.RANGE_CASES} == {2, 4, 8}
+    for c in W.RANGE_CASES:
+        lo, hi = W.range_of(c)
+        b0w, whole = W.walk_of(c)
+        b0, w = W.walk_of(c, lo, hi)
+        assert b0 == lo and w.shift == whole.shift and whole.it[lo - b0w] != 0
+        assert 0 < w.last_slot_frames < w.per
+    # the batch and the ragged call: every stream's body above the threshold on the grid the streams share
+    _, w = W.walk_of(W.BATCH_CASE, nbatch=2)
+    assert w.shift == 8 and w.grid == G.walk_resident(W.BATCH_CASE.n)
+    for more in (0, W.RAGGED_MORE):
+        c = W.RAGGED_CASE._replace(frames=W.RAGGED_CASE.frames + more)
+        _, w = W.walk_of(c, nbatch=2)
+        assert w.shift == 4 and 0 < w.last_slot_frames < w.per
+
+
+def test_second_unit_cases_have_65_to_71_units_on_64_workgroups():
+    import _walk_cases as W
+    kernels = set()
+    for s in W.SECOND_CASES:
+        b0, b1, p = W.second_passes(s)
+        assert 65 <= p.work <= 71 and p.grid == 64 and p.npasses == 2, W.second_id(s)
+        late = p.pass_of >= 1
+        assert late.any() and (p.block_of[p.prev[late]] == p.block_of[late]).all() and (p.pass_of[p.prev[late]] == 0).all()
+        if p.fpb > 1 and not W._shared_odd(s):
+            assert (b1 - b0) % p.fpb != 0                             # the last unit is partly filled
+        if W._shared_odd(s):
+            assert s.c.kmax % 2 == 0 and b1 < s.c.frames and len(W.second_pairs(s)) >= p.fpb // 2
+        if s.key == "pass":                                           # a workgroup's two units differ in level, each level in each pass
+            lv = W.second_levels(s)[b0:b1]
+            assert (lv[late] != lv[p.prev[late]]).all()
+            assert set(lv[~late]) == set(W.LEVELS) and len(set(lv[late])) == min(3, -(-int(late.sum()) // p.fpb))
+        kernels.add((s.kernel, s.c.est, s.c.n, s.form))
+    assert {(k, n) for k, _, n, _ in kernels if k == "spectro16xl"} == {("spectro16xl", 512), ("spectro16xl", 1024), ("spectro16xl", 2048)}
+    assert ("spectro16x", "mtm", 1024, "default") in kernels
+    for est in ("fft", "mtm"):
+        assert {n for k, e, n, f in kernels if k == "spectro16" and e == est and f == "x"} == {512, 1024, 4096, 8192}
+        assert {n for k, e, n, f in kernels if k == "spectro16w" and e == est and f == "w"} == {2048, 4096, 8192}
+    assert len([s for s in W.SECOND_CASES if s.kernel == "spectro16h_mt"]) == 3
+    assert ("spectro16w", "mtm", 16384, "default") in kernels and any(s.spectrum and s.c.n == 32768 for s in W.SECOND_CASES)
+    assert any(s.c.fmt != "f32" and s.offset and s.offset % 2 == 0 for s in W.SECOND_CASES)
+    # spectro_big.hip: the frame at which subfft_kernel's workgroups start over, and the launcher's scratch group
+    assert W.big_wrap_frame(32768) == 1024 < W.BIG_CAP[0].frames and W.big_group_frames(32768) == 4096
+    assert W.big_group_frames(1 << 20) == 128 < W.BIG_GROUP[0].frames == 131
