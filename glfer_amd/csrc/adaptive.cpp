@@ -12,6 +12,7 @@
 
 #include "frame_cuts.h"
 #include "host_tables.h"
+#include "plan_tables.h"
 #include "spectro_adaptive_params.h"
 #include "spectro_params.h"
 
@@ -75,8 +76,8 @@ static int adaptive_rows(glfer_hip_plan *p, const void *d_stream, size_t nstream
   q.fmt = p->cfg.sample_format;
   q.iters = iters;
   q.inv_n = 1.0f / (float)p->n;
-  q.taps = p->d_ataps;
-  q.tw = p->d_tw;
+  q.taps = p->d_ataps.get();
+  q.tw = p->d_tw.as<float2>();
   q.row_pitch = (long long)pitch;
   q.batch_stride = (long long)(stream_pitch * csz);
   q.row_batch_stride = (long long)(nframes * pitch);
@@ -112,12 +113,7 @@ static double student_cdf(double t, int nu) {
 
 extern "C" {
 
-int glfer_hip_adaptive_supported(const glfer_hip_config *cfg) {
-  if (!cfg) return GLFER_E_ARG;
-  if (cfg->mode != GLFER_MODE_MTM || cfg->mtm_k < 1 || cfg->mtm_k + 1 > GLFER_ADAPTIVE_KMAX) return GLFER_E_ARG;   // K = 2 .. 8 tapers
-  if (cfg->n < 256 || cfg->n > 4096 || (cfg->n & (cfg->n - 1))) return GLFER_E_ARG;
-  return glfer_hip_iq_supported(cfg);                                          // mean removal, limiter, RA9MB, the sample format
-}
+int glfer_hip_adaptive_supported(const glfer_hip_config *cfg) { return glfer::adaptive_config_ok(cfg); }   // (plan_tables.cpp: the plan asks the same)
 
 int glfer_hip_adaptive_weights(const glfer_hip_config *cfg, float *lambda_out, float *beta_out) {
   if (glfer_hip_adaptive_supported(cfg) != GLFER_OK || !(cfg->mtm_w > 0.0f)) return GLFER_E_ARG;

@@ -69,8 +69,8 @@ static int cross_rows(glfer_hip_plan *p, bool ok, const void *d_xy, size_t nstre
   q.ntap = p->ntapers;
   q.history_mode = p->cfg.history_mode ? 1 : 0;
   q.fmt = p->cfg.sample_format;
-  q.taps = p->d_iqtaps;
-  q.tw = p->d_tw;
+  q.taps = p->d_iqtaps.get();
+  q.tw = p->d_tw.as<float2>();
   q.row_pitch = (long long)pitch;
   q.sxy_pitch = (long long)xpitch;
   q.batch_stride = (long long)(stream_pitch * csz);

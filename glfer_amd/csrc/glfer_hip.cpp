@@ -1,11 +1,9 @@
-// glfer_hip.cpp -- the C-ABI of include/glfer_hip.h: plans, tables, launches.
+// glfer_hip.cpp -- the C-ABI of include/glfer_hip.h: the launches of a plan's estimators.
 //
-// Host side of the drop-in boundary.  A plan is what fft_init()/mtm_init() build in the
-// reference (fft.c:168-187, mtm.c:88-151): window or DPSS tapers, here also uploaded to
-// HBM with the 1/N normalisation (fft.c:212-216), the eigenvalue weights 1/(1+sig_j)
-// (mtm.c:214-219) and the 1/2 of the re/im packing folded in, so the kernel's epilogue is
-// a single add.  No CPU fallback exists: every compute entry fails with GLFER_E_HIP when
-// HIP cannot run it.
+// Host side of the drop-in boundary.  The plan itself -- what fft_init()/mtm_init() build in the
+// reference (fft.c:168-187, mtm.c:88-151) -- is made by plan.cpp from the tables of plan_tables.cpp;
+// the entries here fill a kernel's argument block from it and launch.  No CPU fallback exists:
+// every compute entry fails with GLFER_E_HIP when HIP cannot run it.
 #include "plan.h"
 
 #include <algorithm>
@@ -21,7 +19,6 @@
 #include "frame_cuts.h"
 #include "channel_cuts.h"
 #include "host_tables.h"
-#include "hparma_frames.h"
 #include "ragged_cols.hpp"
 #include "spectro_params.h"
 #include "spectro_iq_params.h"
@@ -110,65 +107,6 @@ using glfer::data_device;
 using glfer::DeviceGuard;
 using glfer::hip_fail;
 
-static bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
-
-// Device layout of the taper tables, the order the kernel's lanes read them in: sample i of a
-// frame belongs to lane t = i mod T at register m = i / T (T = n/16 lanes per frame); a lane
-// fetches registers m, m+1 of both tapers of a pair with one 16-byte load:
-//   taps[pair][m/2][t][4] = { taper 2p @m, taper 2p+1 @m, taper 2p @m+1, taper 2p+1 @m+1 }
-static size_t tap_slot(int n, int pair, int i, int which) {
-  if (n < 256) return ((size_t)pair * n + i) * 2 + which;       // spectro_small.hip: [pair][i][2]
-  const int T = n / 16, t = i % T, m = i / T;
-  return (size_t)pair * n * 2 + ((size_t)(m / 2) * T + t) * 4 + (size_t)(m & 1) * 2 + which;
-}
-
-// spectro16y.hip's half-table form (five tapers at N = 4096): what a lane keeps in registers, from the tables the plan
-// builds for the full-table form -- taps (the two pairs, tap_slot layout) and xtaps (the last taper, [4][n/16][4]).
-// DPSS tapers are symmetric (even order) or antisymmetric (odd order) about the frame centre; the half table is built only
-// if the SCALED FLOATS have that symmetry exactly (a == b, a == -b as float comparisons: a zero of either sign gives a
-// product that is a zero either way, and no sum or power can tell them apart), because rows from half tables must be the
-// full-table form's rows bit for bit.  Layout: spectro_params.h, glfer_yhalf_residue().  false: `half` is left alone.
-static bool build_y_half_table(int n, const float *taps, const float *xtaps, float *half) {
-  if (n != 4096) return false;
-  const int T = n / 16;
-  auto last = [&](int i) { return xtaps[((size_t)((i / T) / 4) * T + (size_t)(i % T)) * 4 + (size_t)((i / T) & 3)]; };
-  for (int i = 0; i < n / 2; i++) {
-    for (int j = 0; j < 4; j++) {
-      const float a = taps[tap_slot(n, j / 2, i, j & 1)], b = taps[tap_slot(n, j / 2, n - 1 - i, j & 1)];
-      if (!((j & 1) ? b == -a : b == a)) return false;
-    }
-    if (!(last(n - 1 - i) == last(i))) return false;
-  }
-  for (int t = 0; t < T; t++) {
-    const int r = (int)glfer_yhalf_residue((unsigned)t);
-    float *row = half + (size_t)t * GLFER_YHALF_FLOATS;
-    for (int m = 0; m < 8; m++) {
-      for (int j = 0; j < 4; j++) row[16 * (j / 2) + 2 * m + (j & 1)] = taps[tap_slot(n, j / 2, r + T * m, j & 1)];
-      row[32 + m] = last(r + T * m);
-    }
-  }
-  return true;
-}
-
-// The scaled float tables of a multitaper plan with an odd taper count: the pairs (taps, tap_slot layout:
-// psd += |FFT(v_j x)|^2 / N / (1+sig_j), mtm.c:212-219, and the 1/2 of the packing) and the last taper alone (xtaps,
-// [4][n/16][4]; |Y|^2 = |E|^2/4 in the shared transform, so its scale carries 1/4 instead of 1/2).
-static void mtm_pair_tables(int n, int ntapers, const double *tapers, const double *sig, float *taps) {
-  for (int j = 0; j < ntapers; j++) {
-    const double scale = std::sqrt(1.0 / (2.0 * n * (1.0 + sig[j])));
-    for (int i = 0; i < n; i++)
-      taps[tap_slot(n, j / 2, i, j & 1)] = (float)(tapers[(size_t)j * n + i] * scale);
-  }
-}
-static void mtm_last_table(int n, int ntapers, const double *tapers, const double *sig, float *xtaps) {
-  const int T = n / 16, j = ntapers - 1;
-  const double scale = std::sqrt(1.0 / (4.0 * n * (1.0 + sig[j])));
-  for (int i = 0; i < n; i++) {
-    const int t = i % T, m = i / T;
-    xtaps[((size_t)(m / 4) * T + t) * 4 + (size_t)(m & 3)] = (float)(tapers[(size_t)j * n + i] * scale);
-  }
-}
-
 extern "C" {
 
 const char *glfer_hip_version(void) { return "glfer_hip 0.9 (gfx950; 16 points/lane Stockham radix-16 with LDS exchange, inter-pass twiddles folded into the butterflies: packed pairs, real-input and wavefront-private forms, shared odd taper, register reuse across overlapped frames, mean removal in the reference's summation order (cfg.sub_mean = 1) or inside the kernels; N = 8..1048576; periodogram, multitaper + F-test, HP-ARMA with column-disjoint Jacobi rotations side by side and frames from a queue, LMP; rows at a caller's pitch; wavefront floor, fused average, display map with the average taken inside it; chunk ring for ingest with uploads and downloads at once, WAV files and waterfalls over several GPUs, read-ahead behind the per-hop shim, kept scratch blocks with a cap, workers bound to their GPU's NUMA node)"; }
@@ -224,547 +162,6 @@ const char *glfer_hip_strerror(int code) {
 }
 
 const char *glfer_hip_last_hip_error(void) { return g_hip_err.c_str(); }
-
-int glfer_hip_plan_create(const glfer_hip_config *cfg, glfer_hip_plan **out) {
-  if (!cfg || !out) return GLFER_E_ARG;
-  *out = nullptr;
-  const int n = cfg->n;
-  // any power of two the user can type (g_options.c:386-387): 8 .. 128 through spectro_small.hip,
-  // 256 .. 16384 through the 16-points-per-lane kernels, 32768 through spectro16w.hip alone, 65536 .. 1048576
-  // through spectro_big.hip (sub-transforms and combine as two kernels around a scratch in HBM)
-  if (!is_pow2(n) || n < 8 || n > (1 << 20)) return GLFER_E_ARG;
-  // HP-ARMA: the frame, its autocorrelation's zero tail and the matrix live in one wavefront's LDS -- any power of two from 32 up to what
-  // fits 160 KB (N = 32768 with t = 128, p_e = 32: 137 KB, one frame in flight per CU); round 5 (it was 256 .. 16384)
-  if (cfg->mode == GLFER_MODE_HPARMA && (n < 32 || n > 32768)) return GLFER_E_ARG;
-  const bool small = n < 256, huge = n > 16384;
-  if (!(cfg->overlap >= 0.0f) || !(cfg->overlap < 1.0f)) return GLFER_E_ARG;   // g_options.c:1030
-  if (cfg->mode != GLFER_MODE_FFT && cfg->mode != GLFER_MODE_MTM && cfg->mode != GLFER_MODE_HPARMA &&
-      cfg->mode != GLFER_MODE_LMP)
-    return GLFER_E_ARG;
-  if (cfg->mode == GLFER_MODE_LMP && (cfg->lmp_av < 1 || cfg->lmp_av > 4096)) return GLFER_E_ARG;
-  if (cfg->mode == GLFER_MODE_HPARMA) {
-    const int t = cfg->hparma_t, ncol = cfg->hparma_p_e + 1;
-    if (t < 2 || ncol < 2 || ncol > t || t > n || ncol > 256 || t > 65535) return GLFER_E_ARG;   // p_e+1 <= t (hparma.c:107)
-    if (glfer_hparma_lds_bytes(n, t, ncol) > 160 * 1024) return GLFER_E_ARG;   // (hparma_frames.h: the frame's LDS, as its launcher asks for it)
-  }
-  if (cfg->sample_format < 0 || cfg->sample_format > 2) return GLFER_E_ARG;
-  if (cfg->mode == GLFER_MODE_MTM && (cfg->mtm_k < 0 || cfg->mtm_k > 31 || !(cfg->mtm_w > 0.0f)))
-    return GLFER_E_ARG;
-  if (cfg->mode == GLFER_MODE_FFT && (cfg->window_type < 0 || cfg->window_type > 7)) return GLFER_E_ARG;
-
-  glfer_hip_plan *p = new (std::nothrow) glfer_hip_plan();
-  if (!p) return GLFER_E_NOMEM;
-  p->cfg = *cfg;
-  p->n = n;
-  p->hop = (int)(n * (1.0 - cfg->overlap));                        // fft.c:70
-  p->keep = n - p->hop;                                            // fft.c:71
-  p->bins = n / 2 + 1;
-  p->lanes = n / 64;
-  if (p->hop <= 0) { delete p; return GLFER_E_ARG; }
-  // cfg.psd_pitch: floats from one PSD row to the next in the DEVICE entries' d_psd (0 = dense, N/2+1).  The LMP statistic
-  // and the host / file entries (their rows go home through a dense ring) keep dense rows.
-  p->pitch = cfg->psd_pitch ? cfg->psd_pitch : p->bins;
-  if (cfg->psd_pitch < 0 || p->pitch < p->bins || (cfg->psd_pitch && cfg->mode == GLFER_MODE_LMP)) { delete p; return GLFER_E_ARG; }
-
-  // --- host tables
-  p->window.assign(n, 1.0f);
-  std::vector<float> taps;
-  // LMP (lmp.c:101-181): the periodogram of the raw assembled frame -- lmp.c:114-116 overwrites what
-  // prepare_audio left in inbuf_fft, so window (rectangular anyway, source.c:395), a and limiter
-  // have no effect -- followed by the per-bin statistic over the last lmp_av periodograms
-  const bool lmp = cfg->mode == GLFER_MODE_LMP;
-  if (lmp) {
-    p->cfg.window_type = GLFER_WIN_RECTANGULAR;
-    p->cfg.limiter_a = 0.0f;
-    p->cfg.enable_limiter = 0;
-    p->lmp_av = cfg->lmp_av;
-  }
-  if (cfg->mode == GLFER_MODE_FFT || lmp) {
-    p->ntapers = 1;
-    p->npairs = 1;
-    glfer::make_window(p->cfg.window_type, n, p->window.data());
-    p->nonlin = (p->cfg.limiter_a > 0.0f) || (p->cfg.enable_limiter == 1);
-    // psd = |X|^2/N (fft.c:212-216); the pair packing contributes |Z_k|^2+|Z_{N-k}|^2 = 2|X_k|^2
-    // (N = 32768 runs the real-input form only: its inputs carry sqrt(1/(4N)), see the w tables below)
-    const double scale = std::sqrt(1.0 / ((huge ? 4.0 : 2.0) * n));
-    p->spec_unscale = (float)scale;
-    // device layout: taps[pair][i] = (taper 2*pair, taper 2*pair+1)[i], interleaved
-    taps.assign((size_t)2 * n, 0.0f);
-    const bool rect = (p->cfg.window_type == GLFER_WIN_RECTANGULAR);
-    for (int i = 0; i < n; i++) {
-      const double w = rect ? 1.0 : (double)p->window[i];          // fft.c:132,139: no multiply when rectangular
-      taps[tap_slot(n, 0, i, 0)] = p->nonlin ? (float)w : (float)(w * scale);
-    }
-  } else if (cfg->mode == GLFER_MODE_HPARMA) {
-    p->ntapers = 0;
-    p->npairs = 0;
-    taps.assign(4, 0.0f);
-  } else {
-    p->ntapers = cfg->mtm_k + 1;                                   // mtm.c:189: j = 0..kmax inclusive
-    p->npairs = (p->ntapers + 1) / 2;
-    p->tapers.resize((size_t)p->ntapers * n);
-    p->sig.resize(p->ntapers);
-    // gl_dpss (g-l_dpss.c:288-347) is the expensive part of mtm_init -- 0.1-0.3 s at N = 16384 with 9 tapers -- and the
-    // *_multi / *_workers entries make a plan per worker and call: the last few results are kept (same doubles, bit for bit)
-    {
-      struct Kept { int n, kmax; float w; std::vector<double> tapers, sig; };
-      static std::mutex mu;
-      static std::vector<Kept> kept;
-      bool hit = false;
-      {
-        std::lock_guard<std::mutex> lock(mu);
-        for (const Kept &k : kept)
-          if (k.n == n && k.kmax == cfg->mtm_k && k.w == cfg->mtm_w) {
-            p->tapers = k.tapers;
-            p->sig = k.sig;
-            hit = true;
-            break;
-          }
-      }
-      if (!hit) {
-        if (!glfer::make_dpss(n, cfg->mtm_k, (double)cfg->mtm_w, p->tapers.data(), p->sig.data())) {
-          delete p;
-          return GLFER_E_NUMERIC;
-        }
-        std::lock_guard<std::mutex> lock(mu);
-        if (kept.size() >= 4) kept.erase(kept.begin());
-        kept.push_back(Kept{n, cfg->mtm_k, cfg->mtm_w, p->tapers, p->sig});
-      }
-    }
-    taps.assign((size_t)2 * p->npairs * n, 0.0f);
-    if (!huge) mtm_pair_tables(n, p->ntapers, p->tapers.data(), p->sig.data(), taps.data());
-    p->spec_unscale = 1.0f;
-  }
-  int logn = 0;
-  while ((1 << logn) < n) logn++;
-  p->lanes = n / 16;
-  std::vector<float> tw(2, 0.0f);
-  if (!small && !huge) {
-    tw.assign((size_t)2 * glfer::make_twiddles16(logn, nullptr) * p->lanes, 0.0f);
-    glfer::make_twiddles16(logn, tw.data());
-  }
-  if (huge) taps.assign(4, 0.0f);                                  // no packed form at this size
-
-  // --- real-input form of the linear periodogram (spectro16h.hip): z[i] = y[2i] + i*y[2i+1],
-  // lane t of n/32 holds points i = t + (n/32)*m; |X|^2/N needs the inputs scaled by sqrt(1/(4N))
-  std::vector<float> htaps, htw, hrot;
-  // Multitaper at N >= 8192 takes the same form, one taper after the other on the frame held in
-  // registers: the packed N-point form would need the whole N-point exchange buffer (139 KB at
-  // N = 16384: one workgroup per CU), the real-input form half of it.  Each taper carries its weight:
-  // sqrt(1 / (4N (1 + sig_j))).
-  const bool h_periodogram = (cfg->mode == GLFER_MODE_FFT || lmp) && !p->nonlin && n >= 512 && !huge;
-  const bool h_multitaper = cfg->mode == GLFER_MODE_MTM && n >= 8192 && !huge;
-  if (h_periodogram || h_multitaper) {
-    const int th = n / 32;
-    const int nwin = h_multitaper ? p->ntapers : 1;
-    const bool rect = h_periodogram && (p->cfg.window_type == GLFER_WIN_RECTANGULAR);
-    htaps.resize((size_t)nwin * n);
-    for (int j = 0; j < nwin; j++) {
-      const double scale = std::sqrt(1.0 / (4.0 * n * (h_multitaper ? 1.0 + p->sig[j] : 1.0)));
-      for (int m = 0; m < 16; m++)
-        for (int t = 0; t < th; t++)
-          for (int e = 0; e < 2; e++) {
-            const int i = 2 * (t + th * m) + e;
-            const double w = h_multitaper ? p->tapers[(size_t)j * n + i] : (rect ? 1.0 : (double)p->window[i]);
-            htaps[(size_t)j * n + ((size_t)(m / 2) * th + t) * 4 + (size_t)(m & 1) * 2 + e] = (float)(w * scale);
-          }
-    }
-    p->htapers = nwin;
-    htw.resize((size_t)2 * glfer::make_twiddles16(logn - 1, nullptr) * th);
-    glfer::make_twiddles16(logn - 1, htw.data());
-    hrot.resize((size_t)2 * th);
-    for (int t = 0; t < th; t++) {
-      const double ang = 2.0 * 3.14159265358979323846 * t / n;
-      hrot[2 * t] = (float)std::cos(ang);
-      hrot[2 * t + 1] = (float)std::sin(ang);
-    }
-  }
-
-  // --- the same real-input form with wavefront-private 1024-point sub-transforms (spectro16w.hip),
-  // N = 2048 .. 16384: z index n = W*(t + 64 m) + w for wavefront w, lane t, register m
-  std::vector<float> wtaps, wtw, wcomb;
-  const bool w_form = (((cfg->mode == GLFER_MODE_FFT || lmp) && (!p->nonlin || huge)) || cfg->mode == GLFER_MODE_MTM) && n >= 2048;
-  if (w_form) {
-    const int M = n / 2, W = M / 1024, LF = 64 * W, IPL = LF <= 512 ? 512 / LF : 1;
-    const bool mt = cfg->mode == GLFER_MODE_MTM;
-    const int nwin = mt ? p->ntapers : 1;
-    const bool rect = !mt && (p->cfg.window_type == GLFER_WIN_RECTANGULAR);
-    wtaps.resize((size_t)nwin * n);
-    for (int j = 0; j < nwin; j++) {
-      const double scale = std::sqrt(1.0 / (4.0 * n * (mt ? 1.0 + p->sig[j] : 1.0)));
-      for (int w = 0; w < W; w++)
-        for (int m = 0; m < 16; m++)
-          for (int t = 0; t < 64; t++)
-            for (int e = 0; e < 2; e++) {
-              const int i = 2 * (W * (t + 64 * m) + w) + e;
-              const double v = mt ? p->tapers[(size_t)j * n + i] : (rect ? 1.0 : (double)p->window[i]);
-              // (RA9MB / limiter, N = 32768 only: the plain window, the scale follows the limiter as post_scale)
-              wtaps[((((size_t)j * W + w) * 8 + m / 2) * 64 + t) * 4 + (size_t)(m & 1) * 2 + e] = (float)(p->nonlin ? v : v * scale);
-            }
-    }
-    p->wtapers = nwin;
-    wtw.resize((size_t)2 * glfer::make_twiddles16(10, nullptr) * 64);
-    glfer::make_twiddles16(10, wtw.data());
-    wcomb.resize(n <= 32768 ? (size_t)2 * IPL * W * LF : 2);      // (N = 65536 computes its twiddles in the kernels)
-    const double two_pi = 2.0 * 3.14159265358979323846;
-    for (int i = 0; i < IPL && n <= 32768; i++)
-      for (int ww = 0; ww < W; ww++)
-        for (int u = 0; u < LF; u++) {
-          const long long k1 = u + (long long)LF * i;
-          const double ang = ww == 0 ? two_pi * (double)k1 / n : two_pi * (double)((ww * k1) % M) / M;
-          wcomb[2 * ((size_t)(i * W + ww) * LF + u)] = (float)std::cos(ang);
-          wcomb[2 * ((size_t)(i * W + ww) * LF + u) + 1] = (float)std::sin(ang);
-        }
-  }
-
-  // --- odd taper count (spectro16x.hip): the last taper shares a transform with the next frame's;
-  // |Y|^2 = |E|^2/4 there (no mirror-sum doubling), so its scale carries 1/4 instead of 1/2
-  std::vector<float> xtaps;
-  if (cfg->mode == GLFER_MODE_MTM && (p->ntapers & 1) && p->ntapers >= 3 && !small && !huge) {
-    xtaps.resize((size_t)n);
-    mtm_last_table(n, p->ntapers, p->tapers.data(), p->sig.data(), xtaps.data());
-  }
-
-  // --- five tapers at N = 4096 (spectro16y.hip): the half tables a lane keeps in registers, where the float tables are
-  // exactly (anti)symmetric; otherwise (and for every other taper count) the plan keeps the full-table form
-  std::vector<float> ytaps;
-  if (!xtaps.empty() && n == 4096 && p->ntapers == 5) {
-    ytaps.resize((size_t)(n / 16) * GLFER_YHALF_FLOATS);
-    if (!build_y_half_table(n, taps.data(), xtaps.data(), ytaps.data())) ytaps.clear();
-  }
-
-  // --- the same, with half tables that stay in LDS (spectro16xl.hip): DPSS tapers are symmetric
-  // (even order) or antisymmetric (odd order) about the frame centre, so samples n < N/2 suffice.
-  // Built only if the tapers computed above have that symmetry to 1e-7 of their peak and the
-  // tables leave room for two blocks per CU.
-  std::vector<float> ltaps;
-  if (!xtaps.empty() && n <= 4096) {
-    const int T = n / 16, nfull = p->npairs - 1;
-    bool sym = true;
-    for (int j = 0; j < p->ntapers && sym; j++) {
-      const double *v = &p->tapers[(size_t)j * n];
-      double peak = 0.0, dev = 0.0;
-      for (int i = 0; i < n / 2; i++) {
-        peak = std::max(peak, std::fabs(v[i]));
-        dev = std::max(dev, std::fabs(v[n - 1 - i] - ((j & 1) ? -v[i] : v[i])));
-      }
-      sym = dev <= 1e-7 * peak;
-    }
-    const size_t lds = ((size_t)(n + n / 16) * (T >= 256 ? 1 : 256 / T) + 16 * 17 + 8 + (size_t)nfull * 8 * T + 4 * T) * 8;
-    if (sym && lds <= 80 * 1024) {
-      ltaps.resize((size_t)nfull * 8 * T * 2 + (size_t)8 * T);
-      for (int j = 0; j < p->ntapers; j++) {
-        const bool last = j == p->ntapers - 1;
-        const double scale = std::sqrt(1.0 / ((last ? 4.0 : 2.0) * n * (1.0 + p->sig[j])));
-        for (int m = 0; m < 8; m++)
-          for (int t = 0; t < T; t++) {
-            const float val = (float)(p->tapers[(size_t)j * n + t + T * m] * scale);
-            if (last) ltaps[(size_t)nfull * 8 * T * 2 + (size_t)m * T + t] = val;
-            else ltaps[(((size_t)(j / 2) * 8 + m) * T + t) * 2 + (j & 1)] = val;
-          }
-      }
-    }
-  }
-
-  // --- complex I/Q rows (spectro16c.hip): one scaled float per sample and taper, in the order a lane's four 16-byte loads take them
-  // ([taper][m/4][t][4] for sample t + T m); made with the plan so that the entries allocate and copy nothing (stream capture)
-  std::vector<float> iqtaps;
-  if (glfer_hip_iq_supported(&p->cfg) == GLFER_OK) {
-    std::vector<float> flat((size_t)p->ntapers * n);
-    const bool mt = cfg->mode == GLFER_MODE_MTM;
-    glfer::make_iq_table(n, p->ntapers, (mt || p->cfg.window_type == GLFER_WIN_RECTANGULAR) ? nullptr : p->window.data(),
-                         mt ? p->tapers.data() : nullptr, mt ? p->sig.data() : nullptr, flat.data());
-    iqtaps.resize(flat.size());
-    const int T = n / 16;
-    for (int j = 0; j < p->ntapers; j++)
-      for (int i = 0; i < n; i++) {
-        const int t = i % T, m = i / T;
-        iqtaps[(size_t)j * n + ((size_t)(m / 4) * T + t) * 4 + (size_t)(m & 3)] = flat[(size_t)j * n + i];
-      }
-  }
-
-  // --- adaptive weights (spectro16a.hip): the tapers themselves, float(v_j) with nothing folded in, in the I/Q table's order; two
-  // rows a round, so an odd count ends with a row of zeros.  Made with the plan: the entries allocate and copy nothing
-  std::vector<float> ataps;
-  if (glfer_hip_adaptive_supported(&p->cfg) == GLFER_OK) {
-    const int T = n / 16, rows = 2 * ((p->ntapers + 1) / 2);
-    ataps.assign((size_t)rows * n, 0.0f);
-    for (int j = 0; j < p->ntapers; j++)
-      for (int i = 0; i < n; i++) {
-        const int t = i % T, m = i / T;
-        ataps[(size_t)j * n + ((size_t)(m / 4) * T + t) * 4 + (size_t)(m & 3)] = (float)p->tapers[(size_t)j * n + i];
-      }
-  }
-
-  // --- HP-ARMA tables: which lag each cell of the t x (p_e+1) matrix holds after the
-  // reference's fill (hparma.c:89-102).  r_xx is matrix(0,t,0,p_e) (hparma.c:64): its rows
-  // are contiguous (util.c:153-160), lags 0..t-1 are written into row 0 past its p_e+1
-  // columns, and the Toeplitz loop then copies cells that it may already have rewritten.
-  // Simulated here with lag labels instead of values.
-  std::vector<uint16_t> lagmap;
-  std::vector<float> unit;
-  std::vector<int> rot_sched;                                      // [steps][8]: j | k << 8, or -1 (hparma.hip, round 4)
-  if (cfg->mode == GLFER_MODE_HPARMA) {
-    const int t = cfg->hparma_t, ncol = cfg->hparma_p_e + 1;
-    // The Jacobi sweep of compute_svd (util.c:301-355) as a STATIC SCHEDULE of steps of up to eight rotations that share
-    // no column.  Two rotations that share a column must keep the order of the reference's row-cyclic walk -- nothing
-    // else orders them (a rotation touches its two columns only, its skip tests are its own) -- so the walk is a DAG in
-    // which (j, k) waits for the last earlier rotation on column j and the last on column k; list scheduling by longest
-    // remaining path fills steps of eight: 80 steps for 33 columns (66 would be full steps; anti-diagonal by anti-diagonal
-    // it is 94).
-    // GLFER_HPARMA_WIDTH=16: sixteen rotations per step, each over 4 lanes (A/B runs; 63 steps for 33 columns -- the critical path)
-    const int width = [] { const char *e = getenv("GLFER_HPARMA_WIDTH"); return e && atoi(e) == 16 ? 16 : 8; }();
-    p->rot_width = width;
-    if (ncol >= 2 && ncol <= 64) {
-      std::vector<std::pair<int, int>> rots;
-      for (int j = 0; j < ncol - 1; j++)
-        for (int k = j + 1; k < ncol; k++) rots.push_back({j, k});
-      const int R = (int)rots.size();
-      std::vector<std::vector<int>> succ(R);
-      std::vector<int> indeg(R, 0), lastc(ncol, -1), lp(R, 1);
-      for (int i = 0; i < R; i++) {
-        const int cs[2] = {rots[i].first, rots[i].second};
-        int seen = -1;
-        for (int c : cs) {
-          if (lastc[c] >= 0 && lastc[c] != seen) {
-            succ[lastc[c]].push_back(i);
-            indeg[i]++;
-            seen = lastc[c];
-          }
-          lastc[c] = i;
-        }
-      }
-      for (int i = R - 1; i >= 0; i--)
-        for (int s : succ[i]) lp[i] = std::max(lp[i], 1 + lp[s]);
-      std::vector<int> ready;
-      for (int i = 0; i < R; i++)
-        if (!indeg[i]) ready.push_back(i);
-      int done = 0;
-      while (done < R) {
-        std::sort(ready.begin(), ready.end(), [&](int a, int b) { return lp[a] != lp[b] ? lp[a] > lp[b] : a < b; });
-        const int take = std::min<int>(width, (int)ready.size());
-        std::vector<int> cur(ready.begin(), ready.begin() + take);
-        ready.erase(ready.begin(), ready.begin() + take);
-        for (int g = 0; g < width; g++) rot_sched.push_back(g < take ? (rots[cur[g]].first | rots[cur[g]].second << 8) : -1);
-        for (int i : cur) {
-          done++;
-          for (int s : succ[i])
-            if (--indeg[s] == 0) ready.push_back(s);
-        }
-      }
-    }
-    std::vector<int> flat((size_t)(t + 1) * ncol, -1);
-    for (int i = 0; i < t; i++) flat[i] = i;                       // r_xx[0][i] = r(i)
-    for (int i = 1; i < t; i++)
-      for (int j = 0; j < ncol; j++) flat[(size_t)i * ncol + j] = flat[std::abs(j - i)];
-    lagmap.resize((size_t)t * ncol);
-    for (size_t i = 0; i < lagmap.size(); i++) lagmap[i] = (uint16_t)(flat[i] < 0 ? 0 : flat[i]);
-    unit.resize((size_t)2 * (n / 2 + 1));
-    for (int k = 0; k <= n / 2; k++) {
-      const double ang = -2.0 * 3.14159265358979323846 * k / n;
-      unit[2 * k] = (float)std::cos(ang);
-      unit[2 * k + 1] = (float)std::sin(ang);
-    }
-  }
-
-  // --- device tables
-  DeviceGuard guard(cfg->device);
-  hipError_t e = guard.error();
-  if (e == hipSuccess) e = hipMalloc((void **)&p->d_taps, taps.size() * sizeof(float));
-  if (e == hipSuccess && cfg->mode == GLFER_MODE_FFT && cfg->window_type != GLFER_WIN_RECTANGULAR) {
-    e = hipMalloc((void **)&p->d_window, (size_t)n * sizeof(float));            // prepare_audio's multiply, fft.c:139-146
-    if (e == hipSuccess) e = hipMemcpy(p->d_window, p->window.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess) e = hipMalloc((void **)&p->d_tw, tw.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(p->d_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && !htaps.empty()) {
-    e = hipMalloc((void **)&p->d_htaps, htaps.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_htw, htw.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_hrot, hrot.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->d_htaps, htaps.data(), htaps.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_htw, htw.data(), htw.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_hrot, hrot.data(), hrot.size() * sizeof(float), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !wtaps.empty()) {
-    e = hipMalloc((void **)&p->d_wtaps, wtaps.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_wtw, wtw.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_wcomb, wcomb.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->d_wtaps, wtaps.data(), wtaps.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_wtw, wtw.data(), wtw.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_wcomb, wcomb.data(), wcomb.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && huge) {
-      // spectro_big.hip: W_M^(w k1), k1 = t + 64 m, is exp(-2 pi i w t / M) (one sincos per lane) times this table's entry
-      const int M = n / 2, W = M / 1024;
-      std::vector<float> bt((size_t)W * 16 * 2);
-      for (int w = 0; w < W; w++)
-        for (int m = 0; m < 16; m++) {
-          const double ang = -2.0 * 3.14159265358979323846 * (double)(((long long)64 * w * m) % M) / M;
-          bt[2 * ((size_t)w * 16 + m)] = (float)std::cos(ang);
-          bt[2 * ((size_t)w * 16 + m) + 1] = (float)std::sin(ang);
-        }
-      e = hipMalloc((void **)&p->d_bigtw, bt.size() * sizeof(float));
-      if (e == hipSuccess) e = hipMemcpy(p->d_bigtw, bt.data(), bt.size() * sizeof(float), hipMemcpyHostToDevice);
-    }
-  }
-  if (e == hipSuccess && !xtaps.empty()) {
-    e = hipMalloc((void **)&p->d_xtaps, xtaps.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->d_xtaps, xtaps.data(), xtaps.size() * sizeof(float), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !ytaps.empty()) {
-    e = hipMalloc((void **)&p->d_ytaps, ytaps.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->d_ytaps, ytaps.data(), ytaps.size() * sizeof(float), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !iqtaps.empty()) {
-    e = hipMalloc((void **)&p->d_iqtaps, iqtaps.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->d_iqtaps, iqtaps.data(), iqtaps.size() * sizeof(float), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !ataps.empty()) {
-    e = hipMalloc((void **)&p->d_ataps, ataps.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->d_ataps, ataps.data(), ataps.size() * sizeof(float), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !xtaps.empty() && n == 4096) {
-    p->yq = new glfer_yqueue;
-    const size_t bytes = (size_t)glfer_yqueue::SLOTS * glfer_yqueue::PITCH * sizeof(unsigned);
-    e = hipMalloc((void **)&p->yq->d_counters, bytes);
-    if (e == hipSuccess) e = hipMemset(p->yq->d_counters, 0, bytes);
-  }
-  if (e == hipSuccess && !ltaps.empty()) {
-    e = hipMalloc((void **)&p->d_ltaps, ltaps.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->d_ltaps, ltaps.data(), ltaps.size() * sizeof(float), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !lagmap.empty()) {
-    e = hipMalloc((void **)&p->d_lagmap, lagmap.size() * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_unit, unit.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->d_lagmap, lagmap.data(), lagmap.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !rot_sched.empty()) {
-      e = hipMalloc((void **)&p->d_rot_sched, rot_sched.size() * sizeof(int));
-      if (e == hipSuccess) e = hipMemcpy(p->d_rot_sched, rot_sched.data(), rot_sched.size() * sizeof(int), hipMemcpyHostToDevice);
-      p->rot_steps = (int)(rot_sched.size() / p->rot_width);
-    }
-    if (e == hipSuccess) e = hipMemcpy(p->d_unit, unit.data(), unit.size() * sizeof(float), hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) {
-    int rc = hip_fail(e, "plan_create");
-    glfer_hip_plan_destroy(p);
-    return rc;
-  }
-  *out = p;
-  return GLFER_OK;
-}
-
-void glfer_hip_plan_destroy(glfer_hip_plan *p) {
-  if (!p) return;
-  DeviceGuard guard(p->cfg.device);
-  if (p->d_taps) (void)hipFree(p->d_taps);
-  if (p->d_window) (void)hipFree(p->d_window);
-  if (p->d_ftaps_mu_first) (void)hipFree(p->d_ftaps_mu_first);
-  if (p->d_ftaps2) (void)hipFree(p->d_ftaps2);
-  if (p->d_U0) (void)hipFree(p->d_U0);
-  if (p->d_tw) (void)hipFree(p->d_tw);
-  if (p->d_htaps) (void)hipFree(p->d_htaps);
-  if (p->d_htw) (void)hipFree(p->d_htw);
-  if (p->d_hrot) (void)hipFree(p->d_hrot);
-  if (p->d_xtaps) (void)hipFree(p->d_xtaps);
-  if (p->d_wtaps) (void)hipFree(p->d_wtaps);
-  if (p->d_wtw) (void)hipFree(p->d_wtw);
-  if (p->d_wcomb) (void)hipFree(p->d_wcomb);
-  if (p->d_bigtw) (void)hipFree(p->d_bigtw);
-  if (p->d_ltaps) (void)hipFree(p->d_ltaps);
-  if (p->d_ytaps) (void)hipFree(p->d_ytaps);
-  if (p->d_iqtaps) (void)hipFree(p->d_iqtaps);
-  if (p->d_ataps) (void)hipFree(p->d_ataps);
-  if (p->yq) {
-    if (p->yq->d_counters) (void)hipFree(p->yq->d_counters);
-    delete p->yq;
-  }
-  if (p->d_lagmap) (void)hipFree(p->d_lagmap);
-  if (p->d_rot_sched) (void)hipFree(p->d_rot_sched);
-  if (p->d_unit) (void)hipFree(p->d_unit);
-  glfer::ingest_ring_free(p->ring);
-  for (hipStream_t a : p->aux)
-    if (a) (void)hipStreamDestroy(a);
-  for (hipEvent_t ev : p->aux_events) (void)hipEventDestroy(ev);
-  delete p;
-}
-
-int glfer_hip_hop(const glfer_hip_plan *p) { return p ? p->hop : GLFER_E_ARG; }
-int glfer_hip_bins(const glfer_hip_plan *p) { return p ? p->bins : GLFER_E_ARG; }
-int glfer_hip_num_tapers(const glfer_hip_plan *p) { return p ? p->ntapers : GLFER_E_ARG; }
-size_t glfer_hip_num_frames(const glfer_hip_plan *p, size_t nsamples) {
-  return p ? nsamples / (size_t)p->hop : 0;
-}
-
-int glfer_hip_get_window(const glfer_hip_plan *p, float *w) {
-  if (!p || !w) return GLFER_E_ARG;
-  memcpy(w, p->window.data(), (size_t)p->n * sizeof(float));
-  return GLFER_OK;
-}
-
-int glfer_hip_get_tapers(const glfer_hip_plan *p, double *tapers, double *sig) {
-  if (!p || p->cfg.mode != GLFER_MODE_MTM) return GLFER_E_ARG;
-  if (tapers) memcpy(tapers, p->tapers.data(), p->tapers.size() * sizeof(double));
-  if (sig) memcpy(sig, p->sig.data(), p->sig.size() * sizeof(double));
-  return GLFER_OK;
-}
-
-int glfer_hip_make_window(int window_type, int n, float *window) {
-  if (!window || n < 2 || window_type < 0 || window_type > 7) return GLFER_E_ARG;
-  glfer::make_window(window_type, n, window);
-  return GLFER_OK;
-}
-
-int glfer_hip_y_half_tables(int n, int kmax, double nw, float *half, float *pairs, float *last) {
-  if (!half || n != 4096 || kmax != 4 || !(nw > 0.0)) return GLFER_E_ARG;
-  const int nt = kmax + 1;
-  std::vector<double> tapers((size_t)nt * n), sig(nt);
-  if (!glfer::make_dpss(n, kmax, nw, tapers.data(), sig.data())) return GLFER_E_NUMERIC;
-  std::vector<float> taps((size_t)2 * ((nt + 1) / 2) * n, 0.0f), xtaps((size_t)n);
-  mtm_pair_tables(n, nt, tapers.data(), sig.data(), taps.data());
-  mtm_last_table(n, nt, tapers.data(), sig.data(), xtaps.data());
-  if (pairs) memcpy(pairs, taps.data(), (size_t)4 * n * sizeof(float));
-  if (last) memcpy(last, xtaps.data(), (size_t)n * sizeof(float));
-  return build_y_half_table(n, taps.data(), xtaps.data(), half) ? 1 : 0;
-}
-
-int glfer_hip_iq_supported(const glfer_hip_config *cfg) {
-  if (!cfg) return GLFER_E_ARG;
-  if (cfg->mode != GLFER_MODE_FFT && cfg->mode != GLFER_MODE_MTM) return GLFER_E_ARG;
-  if (!is_pow2(cfg->n) || cfg->n < 256 || cfg->n > 16384) return GLFER_E_ARG;
-  if (cfg->sub_mean != 0 || cfg->limiter_a > 0.0f || cfg->enable_limiter != 0) return GLFER_E_ARG;
-  if (cfg->sample_format < 0 || cfg->sample_format > 2) return GLFER_E_ARG;
-  return GLFER_OK;
-}
-
-int glfer_hip_iq_tables(const glfer_hip_config *cfg, float *table) {
-  if (glfer_hip_iq_supported(cfg) != GLFER_OK) return GLFER_E_ARG;
-  const int n = cfg->n;
-  if (cfg->mode == GLFER_MODE_FFT) {
-    if (cfg->window_type < 0 || cfg->window_type > 7) return GLFER_E_ARG;
-    if (!table) return 1;
-    std::vector<float> w(n);
-    glfer::make_window(cfg->window_type, n, w.data());
-    glfer::make_iq_table(n, 1, cfg->window_type == GLFER_WIN_RECTANGULAR ? nullptr : w.data(), nullptr, nullptr, table);
-    return 1;
-  }
-  if (cfg->mtm_k < 0 || cfg->mtm_k > 31 || !(cfg->mtm_w > 0.0f)) return GLFER_E_ARG;
-  const int nt = cfg->mtm_k + 1;
-  if (!table) return nt;
-  std::vector<double> tapers((size_t)nt * n), sig(nt);
-  if (!glfer::make_dpss(n, cfg->mtm_k, (double)cfg->mtm_w, tapers.data(), sig.data())) return GLFER_E_NUMERIC;
-  glfer::make_iq_table(n, nt, nullptr, tapers.data(), sig.data(), table);
-  return nt;
-}
-
-void glfer_hip_y_queue_shape(int *blocks, int *chunk) {
-  if (blocks) *blocks = GLFER_YQ_BLOCKS;
-  if (chunk) *chunk = GLFER_YQ_CHUNK;
-}
-
-int glfer_hip_make_dpss(int n, int kmax, double nw, double *tapers, double *sig) {
-  if (!tapers || !sig || n < 2 || kmax < 0 || kmax > 31 || !(nw > 0.0)) return GLFER_E_ARG;
-  return glfer::make_dpss(n, kmax, nw, tapers, sig) ? GLFER_OK : GLFER_E_NUMERIC;
-}
 
 extern "C" hipError_t glfer_launch_spectro_small(const SpectroParams *p, int n, const float *staps, hipStream_t st);
 extern "C" hipError_t glfer_launch_spectro_big(const SpectroParams *p, int n, hipStream_t st);
@@ -850,7 +247,7 @@ static hipError_t launch_y(SpectroParams &q, hipStream_t st) {
     if (slot == glfer_yqueue::SLOTS) return launch16(GLFER_KIND_spectro16y, q, 4096, st);
     yq->owner[yq->used++] = st;
   }
-  q.yq_counter = yq->d_counters + (size_t)slot * glfer_yqueue::PITCH;
+  q.yq_counter = yq->d_counters.get() + (size_t)slot * glfer_yqueue::PITCH;
   q.yq_base = yq->base[slot];
   q.yq_chunk = y_queue_chunk();
   const hipError_t e = glfer_launch_spectro16y_n12(&q, st);
@@ -988,21 +385,21 @@ static void fill_params(const glfer_hip_plan *p, SpectroParams &sp) {
   sp.a = p->cfg.limiter_a;
   sp.post_scale = p->spec_unscale;
   sp.spec_unscale = p->spec_unscale;
-  sp.taps = p->d_taps;
-  sp.tw = p->d_tw;
-  sp.htaps = p->d_htaps;
+  sp.taps = p->d_taps.get();
+  sp.tw = p->d_tw.as<float2>();
+  sp.htaps = p->d_htaps.get();
   sp.htapers = p->htapers;
-  sp.htw = p->d_htw;
-  sp.hrot = p->d_hrot;
-  sp.xtaps = p->d_xtaps;
-  sp.ltaps = p->d_ltaps;
-  sp.ytaps = p->d_ytaps;
-  sp.yq = p->yq;
-  sp.wtaps = p->d_wtaps;
+  sp.htw = p->d_htw.as<float2>();
+  sp.hrot = p->d_hrot.as<float2>();
+  sp.xtaps = p->d_xtaps.get();
+  sp.ltaps = p->d_ltaps.get();
+  sp.ytaps = p->d_ytaps.get();
+  sp.yq = p->yq.get();
+  sp.wtaps = p->d_wtaps.get();
   sp.wtapers = p->wtapers;
-  sp.wtw = p->d_wtw;
-  sp.wcomb = p->d_wcomb;
-  sp.bigtw = p->d_bigtw;
+  sp.wtw = p->d_wtw.as<float2>();
+  sp.wcomb = p->d_wcomb.as<float2>();
+  sp.bigtw = p->d_bigtw.as<float2>();
 }
 
 // cfg.sub_mean: any non-zero value but GLFER_SUBMEAN_FAST asks for the reference's rows, i.e. the hop means in
@@ -1342,7 +739,7 @@ int glfer_run_device(glfer_hip_plan *p, const void *d_stream, size_t nsamples, s
     if (const int rc = submean_scratch(p, sp, first, nframes, st, copy, tail_fresh); rc != GLFER_OK) return rc;
   if (p->cfg.mode != GLFER_MODE_LMP) {
     const hipError_t e = p->cfg.mode == GLFER_MODE_HPARMA
-                             ? glfer_launch_hparma(&sp, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched, p->rot_steps, p->rot_width, p->d_lagmap, p->d_unit, st)
+                             ? glfer_launch_hparma(&sp, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched.get(), p->rot_steps, p->rot_width, p->d_lagmap.get(), p->d_unit.as<float2>(), st)
                              : launch_by_n(sp, p->n, st);
     return e == hipSuccess ? GLFER_OK : hip_fail(e, "estimator launch");
   }
@@ -1480,8 +877,8 @@ static int batch_rows(glfer_hip_plan *p, const void *d_streams, size_t nstreams,
       glfer::Scratch<float> copy(st);
       if (p->cfg.sub_mean)
         if (const int rc = submean_scratch(p, sp, first - back, nrows, st, copy); rc != GLFER_OK) return rc;
-      const hipError_t e = hparma ? glfer_launch_hparma_batch(&sp, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched, p->rot_steps,
-                                                              p->rot_width, p->d_lagmap, p->d_unit, st)
+      const hipError_t e = hparma ? glfer_launch_hparma_batch(&sp, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched.get(), p->rot_steps,
+                                                              p->rot_width, p->d_lagmap.get(), p->d_unit.as<float2>(), st)
                                   : launch_by_n(sp, p->n, st);
       if (e != hipSuccess) return hip_fail(e, "estimator launch (batch)");
     }
@@ -1532,8 +929,8 @@ int glfer_hip_spectrogram_iq_batch_device(glfer_hip_plan *p, const void *d_iq, s
   q.history_mode = p->cfg.history_mode ? 1 : 0;
   q.fmt = p->cfg.sample_format;
   q.flags = flags;
-  q.taps = p->d_iqtaps;
-  q.tw = p->d_tw;
+  q.taps = p->d_iqtaps.get();
+  q.tw = p->d_tw.as<float2>();
   q.pitch = (long long)pitch;
   q.batch_stride = (long long)(stream_pitch * csz);
   q.psd_batch_stride = (long long)(nframes * pitch);
@@ -1846,8 +1243,8 @@ struct RaggedChunk {
         all[b].frame0 = (long long)from[b];
         all[b].nframes = (int)(to[b] - from[b]);
       }
-      const hipError_t e = glfer_launch_hparma_ragged(&sp, all.data(), nb, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched,
-                                                      p->rot_steps, p->rot_width, p->d_lagmap, p->d_unit, st);
+      const hipError_t e = glfer_launch_hparma_ragged(&sp, all.data(), nb, p->n, p->cfg.hparma_t, p->cfg.hparma_p_e + 1, p->d_rot_sched.get(),
+                                                      p->rot_steps, p->rot_width, p->d_lagmap.get(), p->d_unit.as<float2>(), st);
       return e == hipSuccess ? GLFER_OK : hip_fail(e, "estimator launch (HP-ARMA, ragged)");
     }
     // the route of THESE samples, as launch_by_n reads it: a corrected copy is f32 whatever the raw format, so its frames may
@@ -2152,77 +1549,8 @@ int glfer_hip_prepare_device(glfer_hip_plan *p, const void *d_stream, size_t nsa
   // MTM / HP-ARMA / LMP run prepare_audio with a rectangular window (source.c:344,369,395); a and
   // the limiter still act on inbuf_fft there, but those estimators overwrite it, so the shims ask
   // for this only in FFT mode
-  const hipError_t e = glfer_launch_prepare(&sp, p->n, p->d_window, d_frames, st);
+  const hipError_t e = glfer_launch_prepare(&sp, p->n, p->d_window.get(), d_frames, st);
   return e == hipSuccess ? GLFER_OK : hip_fail(e, "glfer_launch_prepare");
-}
-
-// The F-test's tables, made on the first F call of a plan (either entry) and kept with it.
-static int ftest_tables(glfer_hip_plan *p) {
-  const int n = p->n, T = p->ntapers;
-  if (p->d_ftaps) return GLFER_OK;       // tables of mtm.c:76-83, 124-136, once per plan
-  {
-    p->U0.resize(T);
-    p->hn.resize(n);
-    glfer::make_ftest_tables(n, T - 1, p->tapers.data(), p->U0.data(), p->hn.data(), &p->sum_U0_sqr);
-    // [hn][taper 0..T-1][hn]: the one-launch form starts with hn (mu first), the spectrum-by-spectrum form ends with it
-    std::vector<float> taps((size_t)(T + 2) * 2 * n, 0.0f);
-    for (int j = -1; j <= T; j++)
-      for (int i = 0; i < n; i++)
-        taps[(size_t)(j + 1) * 2 * n + tap_slot(n, 0, i, 0)] = (j >= 0 && j < T) ? (float)p->tapers[(size_t)j * n + i] : p->hn[i];
-    float *d = nullptr;
-    double *du = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, taps.size() * sizeof(float)));
-    // [U0: T doubles][c_j = 1 / (n (1 + sig_j)): T floats], the rows' weights of the rows-and-F entries (the tables above stay unscaled)
-    std::vector<float> cj((size_t)T);
-    for (int j = 0; j < T; j++) cj[j] = (float)(1.0 / ((double)n * (1.0 + p->sig[j])));
-    hipError_t e = hipMalloc((void **)&du, (size_t)T * (sizeof(double) + sizeof(float)));
-    if (e == hipSuccess) e = hipMemcpy(d, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(du, p->U0.data(), (size_t)T * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(du + T, cj.data(), (size_t)T * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(d);
-      (void)hipFree(du);
-      return hip_fail(e, "ftest tables");
-    }
-    p->d_ftaps_mu_first = d;
-    p->d_ftaps = d + (size_t)2 * n;
-    p->d_U0 = du;
-    p->d_rows_cj = reinterpret_cast<float *>(du + T);
-    // the paired form's tables: two real sequences per N-point transform (re / im), each halved (X_a = (Z[k] + conj Z[N-k]) / 2)
-    // hn = sum_j U0_j v_j / sum(U0^2) has the 2-norm 1 / sqrt(sum(U0^2)) against a taper's 1: sharing a transform with taper 0 as it is,
-    // mu would come out of the separation with the rounding of a spectrum ~ sqrt(sum(U0^2)) times its size (up to 128 at N = 16384),
-    // and mu U0_j carries that into every residual.  A power of two brings hn to a taper's size; the kernel takes it out of mu again.
-    {
-      int ex = 0;
-      (void)frexpf(sqrtf(p->sum_U0_sqr), &ex);                     // sqrt(sum U0^2) = m 2^ex, 1/2 <= m < 1
-      p->hn_scale = p->sum_U0_sqr > 0.0f && ex > 0 && ex < 64 ? ldexpf(1.0f, ex - 1) : 1.0f;
-    }
-    const int r_mu = (T + 2) / 2, r_nomu = (T + 1) / 2;
-    std::vector<float> pt((size_t)(r_mu + r_nomu) * 2 * n, 0.0f);
-    auto seq = [&](int s_, int i, bool with_mu) -> float {          // sequence s_ of the call: hn first when mu is live, then the tapers
-      const int j = with_mu ? s_ - 1 : s_;
-      if (j >= T) return 0.0f;
-      return 0.5f * (j < 0 ? p->hn_scale * p->hn[i] : (float)p->tapers[(size_t)j * n + i]);
-    };
-    for (int r = 0; r < r_mu + r_nomu; r++) {
-      const bool with_mu = r < r_mu;
-      const int rr = with_mu ? r : r - r_mu;
-      for (int i = 0; i < n; i++) {
-        pt[(size_t)r * 2 * n + tap_slot(n, 0, i, 0)] = seq(2 * rr, i, with_mu);
-        pt[(size_t)r * 2 * n + tap_slot(n, 0, i, 1)] = seq(2 * rr + 1, i, with_mu);
-      }
-    }
-    float *d2 = nullptr;
-    hipError_t e2 = hipMalloc((void **)&d2, pt.size() * sizeof(float));
-    if (e2 == hipSuccess) e2 = hipMemcpy(d2, pt.data(), pt.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e2 != hipSuccess) {
-      (void)hipFree(d2);
-      return hip_fail(e2, "ftest tables (paired)");
-    }
-    p->d_ftaps2 = d2;
-    p->d_ftaps2_nomu = d2 + (size_t)r_mu * 2 * n;
-  }
-  return GLFER_OK;
 }
 
 // The argument block both F entries start from: the packed kernel (it is the one with the spectrum output), one table per launch.
@@ -2252,11 +1580,11 @@ static SpectroParams ftest_in_launch(const glfer_hip_plan *p, const SpectroParam
   }
   q.spec = nullptr;
   q.ftest = d_ftest;
-  q.ft_U0 = p->d_U0;
+  q.ft_U0 = p->d_U0.get();
   q.ft_sum_U0_sqr = p->sum_U0_sqr;
   q.ft_mu_live = mu_live ? 1 : 0;
   q.npairs = mu_live ? T + 1 : T;                    // rounds: hn first (mu), then the tapers
-  q.taps = mu_live ? p->d_ftaps_mu_first : p->d_ftaps;
+  q.taps = mu_live ? p->d_ftaps_mu_first.get() : p->d_ftaps;
   // round 5: two sequences per transform, separated through the mirror bins (GLFER_FTEST_PAIRED=0: one per transform, for A/B runs and tests)
   // Measured (gpurun_out/r5/ftest_rate.txt): N = 4096, 5 tapers 39.2 against 33.5 M frames/s; N = 1024, 8 tapers 94.3 against 105.9 -- the
   // mirror exchange (two barriers, 16 LDS writes, 9 reads a round) costs a short transform more than it saves: paired from N = 2048.
@@ -2264,7 +1592,7 @@ static SpectroParams ftest_in_launch(const glfer_hip_plan *p, const SpectroParam
   if (pe && *pe ? *pe != '0' : n >= 2048) {
     q.ft_nseq = mu_live ? T + 1 : T;
     q.npairs = (q.ft_nseq + 1) / 2;
-    q.taps = mu_live ? p->d_ftaps2 : p->d_ftaps2_nomu;
+    q.taps = mu_live ? p->d_ftaps2.get() : p->d_ftaps2_nomu;
     q.ft_mu_unscale = 1.0f / p->hn_scale;
   }
   return q;
@@ -2335,10 +1663,10 @@ static int ftest_single(glfer_hip_plan *p, const void *d_stream, size_t first, s
       e = launch_packed(q, n, st);
     }
     if (e == hipSuccess && d_psd)
-      e = glfer_launch_ftest_rows(spec.get(), g, n, T, p->d_U0, p->sum_U0_sqr, mu_live ? 1 : 0, d_ftest + done * (size_t)p->bins,
+      e = glfer_launch_ftest_rows(spec.get(), g, n, T, p->d_U0.get(), p->sum_U0_sqr, mu_live ? 1 : 0, d_ftest + done * (size_t)p->bins,
                                   p->d_rows_cj, d_psd + done * (size_t)p->pitch, p->pitch, st);
     else if (e == hipSuccess)
-      e = glfer_launch_ftest(spec.get(), g, n, T, p->d_U0, p->sum_U0_sqr, mu_live ? 1 : 0, d_ftest + done * (size_t)p->bins, st);
+      e = glfer_launch_ftest(spec.get(), g, n, T, p->d_U0.get(), p->sum_U0_sqr, mu_live ? 1 : 0, d_ftest + done * (size_t)p->bins, st);
     if (e != hipSuccess) return hip_fail(e, "ftest launch");
   }
   return GLFER_OK;

@@ -2,12 +2,14 @@
 // state, fft.c:168-187, mtm.c:88-151), error plumbing and the device guard.  Internal.
 #pragma once
 #include "../../include/glfer_hip.h"
+#include "device_table.hpp"
 #include "ragged_cols.hpp"
 #include "scratch.hpp"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -96,7 +98,7 @@ size_t ingest_ring_spare_bytes(int dev);       // pinned host + device bytes of 
 // the static stride.
 struct glfer_yqueue {
   static constexpr int SLOTS = 8, PITCH = 32;      // a 128-byte line per counter
-  unsigned *d_counters = nullptr;                  // [SLOTS][PITCH]
+  glfer::DeviceTable<unsigned> d_counters;         // [SLOTS][PITCH]
   hipStream_t owner[SLOTS] = {};
   unsigned base[SLOTS] = {};
   int used = 0;
@@ -131,37 +133,37 @@ struct glfer_hip_plan {
   std::vector<float> window;        // [n] as the reference stores it (unit power)
   std::vector<double> tapers;       // [ntapers][n]
   std::vector<double> sig;          // [ntapers]
-  float *d_taps = nullptr;          // [npairs][8][n/16][4] scaled tables (tap_slot)
-  float *d_window = nullptr;        // [n] the window itself (FFT mode, not rectangular): prepare_audio's multiply
-  float2 *d_tw = nullptr;           // [slots][lanes]
-  float *d_htaps = nullptr;         // real-input form (spectro16h.hip): window pairs, [htapers][8][n/32][4]
-  int htapers = 0;                  // 1: periodogram window; > 1: the tapers of the multitaper form (n >= 8192)
-  float2 *d_htw = nullptr;          //   twiddles of the n/2-point transform
-  float2 *d_hrot = nullptr;         //   (cos,sin)(2 pi t/n), t < n/32
-  float *d_wtaps = nullptr;         // wavefront-private real-input form (spectro16w.hip): [wtapers][W][8][64][4]
+  // the device tables (plan_tables.h has a builder for each layout); an empty one: this plan has no such table
+  glfer::DeviceTable<float> d_taps;     // [npairs][8][n/16][4] scaled tables (tap_slot)
+  glfer::DeviceTable<float> d_window;   // [n] the window itself (FFT mode, not rectangular): prepare_audio's multiply
+  glfer::DeviceTable<float> d_tw;       // [slots][lanes] float2
+  glfer::DeviceTable<float> d_htaps;    // real-input form (spectro16h.hip): window pairs, [htapers][8][n/32][4]
+  int htapers = 0;                      // 1: periodogram window; > 1: the tapers of the multitaper form (n >= 8192)
+  glfer::DeviceTable<float> d_htw;      //   twiddles of the n/2-point transform, float2
+  glfer::DeviceTable<float> d_hrot;     //   (cos,sin)(2 pi t/n), t < n/32
+  glfer::DeviceTable<float> d_wtaps;    // wavefront-private real-input form (spectro16w.hip): [wtapers][W][8][64][4]
   int wtapers = 0;
-  float2 *d_wtw = nullptr;          //   [27][64] twiddles of the 1024-point transform
-  float2 *d_wcomb = nullptr;        //   combine / split twiddles per lane
-  float2 *d_bigtw = nullptr;        // spectro_big.hip (N >= 32768): [W][16] the register part of the sub-transforms' twiddles
-  float *d_xtaps = nullptr;         // odd taper counts (spectro16x.hip): the last taper alone, [4][n/16][4]
-  float *d_ltaps = nullptr;         // odd taper counts, LDS-resident half tables (spectro16xl.hip)
-  float *d_ytaps = nullptr;         // five tapers at N = 4096, register-resident half tables (spectro16y.hip); NULL: not exactly symmetric
-  float *d_iqtaps = nullptr;        // complex I/Q rows (spectro16c.hip): [ntapers][4][n/16][4] one scaled float per sample and taper; NULL: not supported
-  float *d_ataps = nullptr;         // adaptive weights (spectro16a.hip): [2 ceil(ntapers/2)][4][n/16][4] the tapers UNSCALED, an odd count's last row zeros; NULL: not supported
-  glfer_yqueue *yq = nullptr;       // spectro16y.hip's queue form: the plan's ticket counters (N = 4096, odd taper counts)
-  uint16_t *d_lagmap = nullptr;     // HP-ARMA: [t][p_e+1] lag held by each matrix cell
-  int *d_rot_sched = nullptr;       // HP-ARMA: [rot_steps][8] the Jacobi sweep as steps of up to eight column-disjoint rotations (j | k << 8, -1 = none)
+  glfer::DeviceTable<float> d_wtw;      //   [27][64] twiddles of the 1024-point transform, float2
+  glfer::DeviceTable<float> d_wcomb;    //   combine / split twiddles per lane, float2
+  glfer::DeviceTable<float> d_bigtw;    // spectro_big.hip (N >= 32768): [W][16] the register part of the sub-transforms' twiddles, float2
+  glfer::DeviceTable<float> d_xtaps;    // odd taper counts (spectro16x.hip): the last taper alone, [4][n/16][4]
+  glfer::DeviceTable<float> d_ltaps;    // odd taper counts, LDS-resident half tables (spectro16xl.hip)
+  glfer::DeviceTable<float> d_ytaps;    // five tapers at N = 4096, register-resident half tables (spectro16y.hip); empty: not exactly symmetric
+  glfer::DeviceTable<float> d_iqtaps;   // complex I/Q rows (spectro16c.hip): [ntapers][4][n/16][4] one scaled float per sample and taper; empty: not supported
+  glfer::DeviceTable<float> d_ataps;    // adaptive weights (spectro16a.hip): [2 ceil(ntapers/2)][4][n/16][4] the tapers UNSCALED, an odd count's last row zeros; empty: not supported
+  std::unique_ptr<glfer_yqueue> yq;     // spectro16y.hip's queue form: the plan's ticket counters (N = 4096, odd taper counts)
+  glfer::DeviceTable<uint16_t> d_lagmap;   // HP-ARMA: [t][p_e+1] lag held by each matrix cell
+  glfer::DeviceTable<int> d_rot_sched;  // HP-ARMA: [rot_steps][8] the Jacobi sweep as steps of up to eight column-disjoint rotations (j | k << 8, -1 = none)
   int rot_steps = 0, rot_width = 8;
-  float2 *d_unit = nullptr;         // HP-ARMA: [n/2+1] exp(-2 pi i k/n)
-  // harmonic F-test (mtm.c:124-136): built on first use
-  float *d_ftaps_mu_first = nullptr;   // the allocation: [hn][taper 0..ntapers-1][hn], each [2n] alone in slot 0 of the packed layout
+  glfer::DeviceTable<float> d_unit;     // HP-ARMA: [n/2+1] exp(-2 pi i k/n), float2
+  // harmonic F-test (mtm.c:124-136): built on first use by ftest_tables, all of it or nothing
+  std::mutex ftest_mu;                  // held while the F tables are looked for and made
+  glfer::DeviceTable<float> d_ftaps_mu_first;   // [hn][taper 0..ntapers-1][hn], each [2n] alone in slot 0 of the packed layout
   float *d_ftaps = nullptr;         // = d_ftaps_mu_first + 2n: [ntapers+1][2n], taper j, then hn
-  float *d_ftaps2 = nullptr;        // the paired form (round 5): [ceil((ntapers+1)/2)][2n] with (hn_scale hn, taper 0), (taper 1, taper 2) ... as (re, im), halved;
+  glfer::DeviceTable<float> d_ftaps2;   // the paired form (round 5): [ceil((ntapers+1)/2)][2n] with (hn_scale hn, taper 0), (taper 1, taper 2) ... as (re, im), halved;
   float *d_ftaps2_nomu = nullptr;   //   then [ceil(ntapers/2)][2n] with (taper 0, taper 1) ... (mu_live = 0); one allocation
-  double *d_U0 = nullptr;           // [ntapers]
+  glfer::DeviceTable<double> d_U0;      // [ntapers]
   float *d_rows_cj = nullptr;       // [ntapers] 1 / (n (1 + sig_j)), in d_U0's allocation behind it: the rows' weights of the rows-and-F entries
-  std::vector<double> U0;           // [ntapers]
-  std::vector<float> hn;            // [n]
   float sum_U0_sqr = 0.0f;
   float hn_scale = 1.0f;            // the power of two hn is multiplied by in d_ftaps2 (see SpectroParams::ft_mu_unscale)
   float spec_unscale = 1.0f;
@@ -173,6 +175,10 @@ struct glfer_hip_plan {
   std::vector<hipEvent_t> aux_events;  // their events, made once (hipEventCreate per piece cost more than a piece's kernels)
   bool aux_busy = false;               // one call at a time forks onto the side streams; a second one meanwhile stays on its own stream
 };
+
+// The F-test's tables, made on the first F call of a plan (any entry) and kept with it.  Safe from several threads; a failed
+// attempt leaves the plan as it was, and the next call tries again.  plan.cpp
+int ftest_tables(glfer_hip_plan *p);
 
 // frames [first, first+nframes) of a device-resident stream (virtual base allowed); psd and/or
 // halfcomplex spectra out.  Asynchronous on `st`.  Defined in glfer_hip.cpp.

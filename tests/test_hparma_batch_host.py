@@ -148,7 +148,7 @@ def test_frame_table_against_its_definition(walked):
 def test_the_launcher_and_the_c_abi_share_the_header():
     """the LDS rule exists once: the kernel's launcher sizes its launch with the header, and plan creation refuses with it"""
     hip = open(os.path.join(CSRC, "hparma.hip")).read()
-    cabi = open(os.path.join(CSRC, "glfer_hip.cpp")).read()
+    cabi = open(os.path.join(CSRC, "plan_tables.cpp")).read()        # (plan_config_ok: plan creation's refusals)
     for text in (hip, cabi):
         assert '#include "hparma_frames.h"' in text and "glfer_hparma_lds_bytes(" in text
     assert "glfer_hparma_resident(" in hip and "glfer_hparma_frame_table(" in hip
