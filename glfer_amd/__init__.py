@@ -9,4 +9,5 @@ from .api import (Workers, Phases, AVG_PLAIN, AVG_SUMAVG, AVG_SUMEXTREME, HISTOR
                   IQ_CENTERED, IQ_SWAP, iq_supported, iq_tables, Cross, cross_supported, welch_cross_supported,
                   Adaptive, adaptive_supported, adaptive_weights,
                   Jackknife, jackknife_supported, jackknife_factor, jackknife_interval,
+                  Drift, drift_blocks, drift_offsets, drift_sums, drift_sums_batch,
                   Ddc, DdcConfig, ddc_design, ddc_phase_word, ddc_supported, ddc_tables)

@@ -28,6 +28,8 @@ ADAPTIVE_FIELDS = ("psd", "dof")
 Adaptive = collections.namedtuple("Adaptive", ADAPTIVE_FIELDS)  # what Spectrogram.adaptive returns: None for what was not asked
 JACKKNIFE_FIELDS = ("psd", "dof", "logvar")
 Jackknife = collections.namedtuple("Jackknife", JACKKNIFE_FIELDS)  # what Spectrogram.jackknife returns: None for what was not asked
+DRIFT_FIELDS = ("sums", "best", "drift")
+Drift = collections.namedtuple("Drift", "sums best drift")  # what drift_sums and Spectrogram.run_drift return: None for what was not asked
 WINDOWS = {"hanning": 0, "blackman": 1, "gaussian": 2, "welch": 3,
            "bartlett": 4, "rectangular": 5, "hamming": 6, "kaiser": 7}
 SAMPLES_F32, SAMPLES_S16, SAMPLES_U8 = 0, 1, 2
@@ -88,6 +90,9 @@ EXPORTS = [
     # jackknife confidence intervals for multitaper rows in the same pass
     "glfer_hip_jackknife_supported", "glfer_hip_jackknife_factor", "glfer_hip_mtm_jackknife_device",
     "glfer_hip_mtm_jackknife_batch_device",
+    # the drift search: rows summed along straight lines of frequency drift
+    "glfer_hip_drift_blocks", "glfer_hip_drift_offsets", "glfer_hip_drift_device", "glfer_hip_drift_batch_device",
+    "glfer_hip_spectrogram_drift_device",
 ]
 
 
@@ -267,6 +272,13 @@ def lib():
         L.glfer_hip_ddc_device.argtypes = [vp, vp, sz, sz, sz, vp, vp]
         L.glfer_hip_ddc_batch_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, sz, vp]
         L.glfer_hip_spectrogram_zoom_device.argtypes = [vp, vp, vp, sz, sz, sz, vp, sz, C.c_uint, vp]
+    if hasattr(L, "glfer_hip_drift_device"):
+        L.glfer_hip_drift_blocks.argtypes = [sz, sz, sz]
+        L.glfer_hip_drift_blocks.restype = sz
+        L.glfer_hip_drift_offsets.argtypes = [sz, C.c_int, C.c_int, vp]
+        L.glfer_hip_drift_device.argtypes = [vp, sz, C.c_int, sz, sz, sz, sz, C.c_int, C.c_int, vp, vp, vp, vp]
+        L.glfer_hip_drift_batch_device.argtypes = [vp, sz, sz, sz, C.c_int, sz, sz, sz, sz, C.c_int, C.c_int, vp, sz, vp, sz, vp, sz, vp]
+        L.glfer_hip_spectrogram_drift_device.argtypes = [vp, vp, sz, sz, sz, sz, sz, C.c_int, C.c_int, vp, vp, vp, vp]
     L.glfer_hip_host_alloc.argtypes = [sz]
     L.glfer_hip_host_alloc.restype = vp
     L.glfer_hip_host_free.argtypes = [vp]
@@ -988,6 +1000,30 @@ class Spectrogram:
                                                        C.c_void_p(out.data_ptr()), pitch, IQ_CENTERED if centered else 0, st),
                "glfer_hip_spectrogram_zoom_device")
         return out
+
+    def run_drift(self, stream, frames, step=None, dmin=None, dmax=None, first_frame=0, nblocks=None, want=("best", "drift"), out=None):
+        """drift_sums over the plan's rows of `stream` (what run takes) without the caller holding them: block b is frames
+        first_frame + b step .. + frames - 1; nblocks defaults to every block that fits behind first_frame.  Returns Drift(sums,
+        best, drift), bit for bit drift_sums(run(stream, first_frame, ...), ...); the rows go through stream-ordered scratch in
+        pieces of whole blocks, so not under graph capture (glfer_hip_spectrogram_drift_device)."""
+        torch = _torch()
+        if not (stream.is_cuda and stream.dim() == 1 and stream.is_contiguous() and stream.dtype == self._sample_dtype()):
+            raise ValueError("stream: a contiguous 1-D tensor of the plan's sample dtype on the GPU")
+        frames, step, dmin, dmax = _drift_args(frames, step, dmin, dmax)
+        first_frame = int(first_frame)
+        total = self.num_frames(stream.numel())
+        if first_frame < 0 or first_frame > total:
+            raise ValueError("first_frame: 0 .. the stream's frames")
+        fit = drift_blocks(total - first_frame, frames, step)
+        nblocks = fit if nblocks is None else int(nblocks)
+        if nblocks < 0 or nblocks > fit:
+            raise ValueError("nblocks: at most the %d blocks behind first_frame" % fit)
+        ts = _drift_outs(want, out, (), nblocks, dmax - dmin + 1, self.bins, stream.device)
+        st = C.c_void_p(torch.cuda.current_stream(stream.device).cuda_stream)
+        _check(lib().glfer_hip_spectrogram_drift_device(self._h, C.c_void_p(stream.data_ptr()), stream.numel(), first_frame, frames, step,
+                                                        nblocks, dmin, dmax, *(_drift_ptr(ts, k) for k in DRIFT_FIELDS), st),
+               "glfer_hip_spectrogram_drift_device")
+        return Drift(*(ts.get(k) for k in DRIFT_FIELDS))
 
     def run_channels(self, samples, channels=None, select=None, first_frame=0, nframes=None, out=None):
         """samples: an interleaved recording on this GPU, of the plan's sample dtype -- a 1-D tensor (`channels` says how many
@@ -1837,6 +1873,128 @@ def lmp_statistic_ragged(rows, row_starts, avg, out=None):
     _check(lib().glfer_hip_lmp_ragged_device(rows.data_ptr(), starts.size - 1, starts.ctypes.data, rows.size(1), int(avg), out.data_ptr(), st),
            "glfer_hip_lmp_ragged_device")
     return out, starts.astype(np.int64)
+
+
+def _drift_args(frames, step, dmin, dmax):
+    """the checks the drift wrappers share: returns (frames, step, dmin, dmax) with the defaults filled in"""
+    frames = int(frames)
+    if not 2 <= frames <= 4096:
+        raise ValueError("frames: 2 .. 4096")
+    step = frames if step is None else int(step)
+    if step < 1:
+        raise ValueError("step: at least 1")
+    reach = min(frames - 1, 127)
+    dmin = -reach if dmin is None else int(dmin)
+    dmax = reach if dmax is None else int(dmax)
+    if not (-(frames - 1) <= dmin <= 0 <= dmax <= frames - 1):
+        raise ValueError("dmin, dmax: -(frames - 1) <= dmin <= 0 <= dmax <= frames - 1")
+    if dmax - dmin + 1 > 255:
+        raise ValueError("dmin, dmax: at most 255 drifts")
+    return frames, step, dmin, dmax
+
+
+def _drift_outs(want, out, lead, nblocks, ndrifts, bins, device):
+    """The outputs of a drift call by name: made here, or the caller's (out: a mapping or a Drift tuple of dense tensors):
+    sums float32 [lead..., nblocks, ndrifts, bins], best float32 and drift int16 [lead..., nblocks, bins]."""
+    torch = _torch()
+    want = tuple(want)
+    if not want or any(w not in DRIFT_FIELDS for w in want):
+        raise ValueError("want: a non-empty subset of %s" % (DRIFT_FIELDS,))
+    if out is not None and not isinstance(out, dict):
+        out = out._asdict()
+    ts = {}
+    for name in want:
+        shape = tuple(lead) + ((nblocks, ndrifts, bins) if name == "sums" else (nblocks, bins))
+        dtype = torch.int16 if name == "drift" else torch.float32
+        o = None if out is None else out.get(name)
+        if o is None:
+            o = torch.empty(shape, dtype=dtype, device=device)
+        elif not (o.is_cuda and o.dtype == dtype and tuple(o.shape) == shape and o.is_contiguous()):
+            raise ValueError("out[%r]: a dense %s tensor of shape %s on the GPU" % (name, dtype, shape))
+        ts[name] = o
+    return ts
+
+
+def _drift_ptr(ts, name):
+    return C.c_void_p(ts[name].data_ptr()) if name in ts and ts[name].numel() else None
+
+
+def _drift_rows(rows, dim):
+    """the checks drift_sums and drift_sums_batch share on the rows: returns (rows held, bins, pitch)"""
+    torch = _torch()
+    if rows.dim() != dim or rows.dtype != torch.float32:
+        raise ValueError("rows: a %d-D float32 tensor" % dim)
+    held, bins = rows.size(dim - 2), rows.size(dim - 1)
+    if bins < 1:
+        raise ValueError("rows: at least one bin")
+    if bins > 1 and rows.stride(dim - 1) != 1:
+        raise ValueError("rows: a row's bins adjacent (stride(-1) == 1)")
+    pitch = rows.stride(dim - 2) if held > 1 else bins
+    if pitch < bins:
+        raise ValueError("rows: the rows at least `bins` floats apart")
+    if not rows.is_cuda:
+        raise ValueError("rows: on the GPU")
+    return held, bins, pitch
+
+
+def drift_blocks(nrows, frames, step=None):
+    """blocks of `frames` rows, `step` (default: frames) rows apart, in a run of nrows rows: (nrows - frames) // step + 1, none in
+    a shorter run (glfer_hip_drift_blocks)"""
+    frames = int(frames)
+    step = frames if step is None else int(step)
+    if nrows < 0 or not 2 <= frames <= 4096 or step < 1:
+        raise ValueError("nrows >= 0, frames 2 .. 4096, step >= 1")
+    return int(lib().glfer_hip_drift_blocks(int(nrows), frames, step))
+
+
+def drift_offsets(frames, dmin, dmax):
+    """o(d, t) = d t / (frames - 1) rounded half away from zero, as the kernel takes it: numpy int32 [dmax - dmin + 1][frames]
+    (glfer_hip_drift_offsets)"""
+    frames, _, dmin, dmax = _drift_args(frames, None, dmin, dmax)
+    offs = np.empty((dmax - dmin + 1, frames), np.int32)
+    _check(lib().glfer_hip_drift_offsets(frames, dmin, dmax, offs.ctypes.data), "glfer_hip_drift_offsets")
+    return offs
+
+
+def drift_sums(rows, frames, step=None, dmin=None, dmax=None, want=("best", "drift"), out=None):
+    """The drift search over rows already on the GPU (glfer_hip_drift_device): rows [F][bins] float32 with stride(1) == 1 and
+    stride(0) >= bins (rows of run / run_batch / update_avg's inputs, a slice of wider rows included).  Block b is rows
+    b step .. b step + frames - 1 (step defaults to frames); along every straight line of drift d = dmin .. dmax bins across the
+    block (defaults -+min(frames - 1, 127)) the rows are summed in float32 in frame order, a bin outside the row adding nothing.
+    Returns Drift(sums [blocks][drifts][bins], best [blocks][bins], drift [blocks][bins] int16) with None for what `want` does
+    not name: best is the largest sum at a bin and drift the d that gave it (ties: the smallest |d|, +d before -d).  One launch
+    on torch's current stream, no allocation inside the library: legal under graph capture with `out` given."""
+    torch = _torch()
+    held, bins, pitch = _drift_rows(rows, 2)
+    frames, step, dmin, dmax = _drift_args(frames, step, dmin, dmax)
+    nblocks = drift_blocks(held, frames, step)
+    ts = _drift_outs(want, out, (), nblocks, dmax - dmin + 1, bins, rows.device)
+    st = C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
+    _check(lib().glfer_hip_drift_device(C.c_void_p(rows.data_ptr()), held, bins, pitch, frames, step, nblocks, dmin, dmax,
+                                        *(_drift_ptr(ts, k) for k in DRIFT_FIELDS), st), "glfer_hip_drift_device")
+    return Drift(*(ts.get(k) for k in DRIFT_FIELDS))
+
+
+def drift_sums_batch(rows, frames, step=None, dmin=None, dmax=None, want=("best", "drift"), out=None):
+    """drift_sums over B independent streams in one launch (glfer_hip_drift_batch_device): rows [B][F][bins] float32 on the GPU,
+    stride(2) == 1, stride(1) >= bins, the streams at least a stream's rows apart (stride(0)).  Returns Drift of
+    [B][blocks][...] tensors; entry b is bit for bit drift_sums(rows[b], ...)."""
+    torch = _torch()
+    held, bins, pitch = _drift_rows(rows, 3)
+    frames, step, dmin, dmax = _drift_args(frames, step, dmin, dmax)
+    nb = rows.size(0)
+    need = (held - 1) * pitch + bins if held else 0
+    stride = rows.stride(0) if nb > 1 else need
+    if stride < need:
+        raise ValueError("rows: the streams at least a stream's rows apart")
+    nblocks = drift_blocks(held, frames, step)
+    D = dmax - dmin + 1
+    ts = _drift_outs(want, out, (nb,), nblocks, D, bins, rows.device)
+    st = C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
+    _check(lib().glfer_hip_drift_batch_device(C.c_void_p(rows.data_ptr()), nb, stride, held, bins, pitch, frames, step, nblocks, dmin, dmax,
+                                              _drift_ptr(ts, "sums"), nblocks * D * bins, _drift_ptr(ts, "best"), nblocks * bins,
+                                              _drift_ptr(ts, "drift"), nblocks * bins, st), "glfer_hip_drift_batch_device")
+    return Drift(*(ts.get(k) for k in DRIFT_FIELDS))
 
 
 def update_avg_batch(mode, psd, depth, minbin, maxbin, max0=0, n_out=None):

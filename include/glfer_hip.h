@@ -1016,6 +1016,65 @@ int glfer_hip_spectrogram_avg_batch_device(glfer_hip_plan *plan, const void *d_s
 int glfer_hip_avg_cum_device(const float *d_psd, size_t nframes, int bins, int n_out, int depth,
                              int minbin, int maxbin, double *d_cum, void *hip_stream);
 
+/* ---- Drift search: rows summed along straight lines of frequency drift ----
+ * Every average above integrates along time at a fixed bin; a carrier that moves a few bins during a long integration (slow-CW
+ * work: oscillator and path drift) is smeared over them.  These entries sum a block of T = `frames` consecutive rows along
+ * every straight line from drift dmin to drift dmax (whole bins across the block's T - 1 steps) and keep, per bin, the largest
+ * sum and the drift that gave it.
+ *   P[f][k]   : float rows, k = 0 .. bins - 1 (bins <= 2^31 - 1025), `pitch` >= bins floats apart (rows of any entry above, as they lie on the device)
+ *   frames    : T, 2 .. 4096
+ *   step      : >= 1, rows from one block to the next (step = T: disjoint blocks; step < T: a moving search)
+ *   dmin,dmax : dmin <= 0 <= dmax, -(T - 1) <= dmin, dmax <= T - 1, D = dmax - dmin + 1 <= 255
+ * The offset of drift d at frame t, in integers, d t / (T - 1) rounded half away from zero:
+ *     o(d, t) = sgn(d) ((2 |d| t + (T - 1)) div (2 (T - 1)))
+ * so o(d, 0) = 0, o(d, T - 1) = d, o(-d, t) = -o(d, t), |o(d, t + 1) - o(d, t)| <= 1.  A run of F rows has
+ * (F - T) / step + 1 blocks (none if F < T); block b starts at row b step.  Outputs, dense, any non-empty subset (NULL: not
+ * written):
+ *   d_sums  [nblocks][D][bins] floats : sums[b][d - dmin][k] = sum over t = 0 .. T - 1 of P[b step + t][k + o(d, t)], added in
+ *             float in increasing t from +0.0f with plain adds; a term whose bin lies outside [0, bins) contributes nothing
+ *             (the padding between bins and pitch and the next row are never read as data).  A block's values depend on its
+ *             own T rows alone.
+ *   d_best  [nblocks][bins] floats    : the largest of the D sums at k
+ *   d_drift [nblocks][bins] shorts    : the d that gave it.  Among equal sums the smallest |d| wins and +d comes before -d: the
+ *             rule is a scan in the order 0, +1, -1, +2, -2, ... that replaces on strict >, so a NaN on the zero-drift line
+ *             gives NaN with drift 0, a NaN elsewhere never wins, and silence gives best = 0, drift = 0.
+ * The waterfall and compute_floor entries take d_best rows as they are.
+ * glfer_hip_drift_blocks and glfer_hip_drift_offsets touch no device: the block count (0 for frames outside 2 .. 4096 or
+ * step == 0), and the check of frames / dmin / dmax (GLFER_OK or GLFER_E_ARG) with, where `offsets` is not NULL, o(d, t) at
+ * offsets[(d - dmin) * frames + t].
+ * glfer_hip_drift_device: blocks 0 .. nblocks - 1 of the nrows rows at d_rows.  One kernel (drift.hip): a workgroup streams a
+ * block's rows through LDS, a tile of 256 bins and a halo of max(-dmin, dmax) each side, and a lane keeps up to 64 drifts'
+ * sums in registers; more drifts are further passes over the block's rows inside the launch.  65 535 blocks a launch.
+ * glfer_hip_drift_batch_device: the same over nstreams streams that share every size; stream b's rows at
+ * d_rows + b * row_stride floats, its outputs at d_sums + b * sums_stride, d_best + b * best_stride, d_drift + b * drift_stride
+ * elements (strides at least a stream's rows / outputs; ignored for one stream).  Stream b's outputs are bit for bit the single
+ * entry's; one launch per 65 535 streams (per 65 535 blocks), the kernel's blockIdx.z the stream.
+ * Neither entry allocates, uploads a table or waits for the device (the offsets are integer arithmetic in the kernel): both are
+ * legal on a hip_stream that is being captured into a graph.
+ * glfer_hip_spectrogram_drift_device: the rows are the plan's, for frames first_frame .. first_frame + (nblocks - 1) step + T - 1
+ * of the stream, computed by glfer_hip_spectrogram_device into stream-ordered scratch (cfg.psd_pitch floats apart) and never
+ * stored for the caller.  Every plan that entry takes.  The blocks go in pieces of whole blocks whose rows take at most half of
+ * glfer_hip_scratch_limit's cap (one block at least); a piece's rows are computed from the multiple of GLFER_FRAME_ALIGN at or
+ * below its first frame to the one at or above its last (inside the call's frames), so by rule (1) of "Cutting a stream" the
+ * outputs are bit for bit those of the rows entry over the call's frames followed by glfer_hip_drift_device, whatever the cut.
+ * It refuses a hip_stream that is being captured (scratch is taken per piece).
+ * Arguments, in this order: GLFER_E_ARG for frames, step, dmin, dmax, bins or pitch out of range (and a NULL plan); GLFER_OK with
+ * nothing launched for nblocks == 0 or no stream; GLFER_E_ARG for NULL rows, all three outputs NULL, nblocks above
+ * glfer_hip_drift_blocks of the rows (frames past the stream), strides shorter than a stream, sizes that overflow size_t.
+ * Not built: ragged, host, WAV and workers forms; a mean normalised by the count of in-range terms; fractional or curved
+ * drifts (and no Taylor tree under this name: its paths are not these lines); drift sums of update_avg's double rows; more
+ * than 255 drifts a call.  Asynchronous on hip_stream. */
+size_t glfer_hip_drift_blocks(size_t nrows, size_t frames, size_t step);
+int glfer_hip_drift_offsets(size_t frames, int dmin, int dmax, int *offsets /* [D][frames] */);
+int glfer_hip_drift_device(const float *d_rows, size_t nrows, int bins, size_t pitch, size_t frames, size_t step, size_t nblocks,
+                           int dmin, int dmax, float *d_sums, float *d_best, short *d_drift, void *hip_stream);
+int glfer_hip_drift_batch_device(const float *d_rows, size_t nstreams, size_t row_stride, size_t nrows, int bins, size_t pitch,
+                                 size_t frames, size_t step, size_t nblocks, int dmin, int dmax, float *d_sums, size_t sums_stride,
+                                 float *d_best, size_t best_stride, short *d_drift, size_t drift_stride, void *hip_stream);
+int glfer_hip_spectrogram_drift_device(glfer_hip_plan *plan, const void *d_stream, size_t nsamples, size_t first_frame, size_t frames,
+                                       size_t step, size_t nblocks, int dmin, int dmax, float *d_sums, float *d_best, short *d_drift,
+                                       void *hip_stream);
+
 /* ---- display mapping: main_window_draw's column loop (g_main.c:1099-1236) over a batch ---- */
 enum { GLFER_SCALE_LIN = 0, GLFER_SCALE_LIN_MAX0, GLFER_SCALE_LOG, GLFER_SCALE_LOG_MAX0 };   /* glfer.h:43 */
 enum { GLFER_PAL_HSV = 0, GLFER_PAL_THRESH, GLFER_PAL_COOL, GLFER_PAL_HOT, GLFER_PAL_BW,
